@@ -25,18 +25,22 @@ stream is an HBM stream from the first timed launch on.
 
 Also in the same JSON line:
   roofline      the fused kernel against the HBM peak, from HIP events on the launch stream
+  repetitions   the K-launch timed region (`--reps` > 1: that many regions; `value` / `ms_per_step` are then the MEDIAN
+                region -- each region is exactly K launches between barrier + synchronize -- and all regions are listed)
+  outputs_dump  (`--dump-outputs DIR`) what was written: the last timed launch's transitions for a seeded sample of lanes
+
+A run launches W + K x reps times and nothing else, so that its length follows --steps.  `--extended` adds the side
+records below, each measured after the timed region with launches of its own (most of them K per workload):
   cpu_baseline  the reference-style scalar Python loop on the host cores (kind "port":
                 gymnasium / brax are not installable here, the reference cannot be timed)
   per_call      the one-launch-per-env-step path (`carl_step`, eager and hipGraph-replayed)
   also          the same launch train for north_star's target env (CARLCartPole x 65 536) and
                 BASELINE configs 3-5 (Acrobot+MountainCar mixed batch, Ant, Halfcheetah+Humanoid)
-
+  roofline.launch_us  min / median / max launch time from one further region with an event between every two launches
   sustained     the same launch train for >= 0.3 s (the K-launch region of the driver's command is ~1.5 ms: burst
                 clocks; sustained runs clock ~8 % lower)
   weak          (N > 1) 65 536 contexts PER GPU, same launch train -- `value` itself is the strong-scaling run
                 (BASELINE's "at 65k parallel contexts (whole node)": 65 536 / N contexts per GPU); `--weak` swaps them
-  repetitions   the K-launch timed region is run `--reps` (5) times; `value` / `ms_per_step` are the MEDIAN region
-                (each region is exactly K launches between barrier + synchronize), all regions are listed
   clocks        sclk / mclk of this GPU sampled from sysfs while the sustained train runs (a 12 % swing between two
                 runs of one binary can then be told from a regression)
   shard8        (N = 1) the 8-GPU operating point of BASELINE's configs measured on this ONE GPU: CARLCartPole /
@@ -83,6 +87,7 @@ PER_LAUNCH = {"pendulum": 8 + 4 + 16 + 4 + 4 + 8 + 4 + 4, "cartpole": 16 + 4 + 2
               "humanoid": 2 * 20 * 11 * 4 + 4 + 15 * 4 + 4 + 4 + 4 + 4}
 
 BRAX_ENVS = ("ant", "halfcheetah", "humanoid")
+DUMP_BUDGET = 60 * 10**6  # --dump-outputs: bytes of array data in all (the .npy headers stay well inside 64 MB)
 # env steps per fused launch: SURVEY.md 8(d)'s K = 1 000 measured steps for the classic families (actions pre-generated
 # on the device as [K, N]) -- one launch carries all of them (r02 / r03 used 250: `also.cartpole_T250` keeps that figure
 # comparable); Brax: 20 env steps (= 200-320 pipeline substeps) per launch
@@ -140,7 +145,16 @@ def parse():
                    help="headline value = weak scaling (--lanes contexts PER GPU).  Default: strong -- --lanes is the TOTAL "
                         "number of contexts (BASELINE: 65 536 over the whole node), split over the GPUs; for N > 1 the other "
                         "mode is reported in the same line (under 'weak' / 'strong') either way")
-    p.add_argument("--reps", type=int, default=5, help="repetitions of the K-launch timed region (value = the median region)")
+    p.add_argument("--reps", type=int, default=1,
+                   help="repetitions of the K-launch timed region (value = the median region); the default times exactly "
+                        "--steps launches")
+    p.add_argument("--extended", action="store_true",
+                   help="after the timed region, also run the side records (sustained, launch_us, per_call, cpu_baseline, "
+                        "also, shard8, the other scaling mode, uneven shards); each launches further steps, most of them "
+                        "--steps per workload")
+    p.add_argument("--dump-outputs", metavar="DIR", default=None,
+                   help="write what the last timed launch computed to DIR/<name>.npy (float32; a fixed, seeded sample of "
+                        "lanes, every env step of the launch, %d MB at most)" % (DUMP_BUDGET // 10**6))
     p.add_argument("--no-shard8", action="store_true")
     p.add_argument("--lanes-per-env", default="",
                    help="Brax launch shape pinned instead of autotuned, e.g. 'ant=9,halfcheetah=7,humanoid=11' (counter passes: "
@@ -159,6 +173,9 @@ def parse():
     p.add_argument("--cpu-steps-per-env", type=int, default=1000)
     a = p.parse_args()
     a.strong = not a.weak
+    if not a.extended:
+        a.no_per_call = a.no_cpu_baseline = a.no_shard8 = True
+        a.also = "none"
     Workload.pinned_lanes_per_env = {k: int(v) for k, v in (kv.split("=") for kv in a.lanes_per_env.split(",") if kv)}
     a.families = tuple(a.env.split("+"))
     for f in a.families:
@@ -373,6 +390,37 @@ class SplitWorkload(Workload):
 
     def __init__(self, family, lanes_each, T, sets, rank, world, device):
         super().__init__((family, family), lanes_each, T, sets, rank, world, device)
+
+
+def dump_outputs(wl, path, rank, world):
+    """--dump-outputs: the output buffers of the LAST timed launch -- what `rollout` hands its caller: obs [T, N, D],
+    reward / terminated / truncated [T, N] per family -- as float32 DIR/<name>.npy, for comparing two builds output for
+    output.  A full launch writes far more than DUMP_BUDGET (CartPole x 65 536 x 1 000 steps: 1.8 GB), so every array
+    keeps all T env steps of a sample of lanes: drawn with seed 0, sorted, as many as the budget allows -- the same lanes
+    for every run with the same arguments.  Mixed batches prefix the names with the family; ranks > 1 of a multi-GPU run
+    add `.rank<r>`.  Returns the record the JSON line carries."""
+    import numpy as np
+    import torch
+
+    outs = wl.outs[(wl._i - 1) % len(wl.outs)]
+    parts = wl.eng.parts if wl.mixed else [wl.eng]
+    prefixes = [f"{f}_" if wl.mixed else "" for f in wl.families]
+    if len(set(prefixes)) < len(prefixes):
+        prefixes = [f"{f}{k}_" for k, f in enumerate(wl.families)]
+    suffix = f".rank{rank}" if world > 1 else ""
+    os.makedirs(path, exist_ok=True)
+    rec = {"dir": path, "lanes": {}, "bytes": 0}
+    for prefix, p, out in zip(prefixes, parts, outs):
+        lane_bytes = sum(4 * t[:, 0].numel() for t in out.values())  # one lane's column of every array, as float32
+        m = max(1, min(p.n, DUMP_BUDGET // len(parts) // lane_bytes))
+        lanes = np.sort(np.random.default_rng(0).choice(p.n, m, replace=False))
+        idx = torch.as_tensor(lanes, device=p.device)
+        for name, t in out.items():
+            a = t.index_select(1, idx).to(torch.float32).cpu().numpy()
+            np.save(os.path.join(path, f"{prefix}{name}{suffix}.npy"), a)
+            rec["bytes"] += a.nbytes
+        rec["lanes"][prefix.rstrip("_") or wl.families[0]] = f"{m} of {p.n} (numpy default_rng(0), sorted)"
+    return rec
 
 
 def traffic_record(key):
@@ -1069,7 +1117,11 @@ def main():
     # ---- timed region: exactly K fused launches (K x T env steps of every lane), repeated --reps times ----
     regions, med = timed_regions(wl, K, W, args.reps, barrier, max_over_ranks)
     elapsed, avg_launch_s = regions[med]
-    roofline = launch_stats(wl, roofline_of(wl, avg_launch_s), K, barrier)
+    # (before anything launches again: the side records below step the same engine into the same buffers)
+    dump = dump_outputs(wl, args.dump_outputs, rank, world) if args.dump_outputs else None
+    roofline = roofline_of(wl, avg_launch_s)
+    if args.extended:
+        roofline = launch_stats(wl, roofline, K, barrier)
     per_rank_launch_ms = gather_over_ranks(avg_launch_s * 1e3)
     repetitions = {"n": len(regions), "median_index": med, "steps_each": K,
                    "ms_per_step": [w / K * 1e3 for w, _ in regions], "launch_period_ms": [p_ * 1e3 for _, p_ in regions],
@@ -1080,13 +1132,15 @@ def main():
     # ---- the same launch train, sustained: the K-launch region above is ~1-2 ms (burst clocks) ----
     import math
 
-    Ks = max(K, int(math.ceil(args.sustained_seconds / max(avg_launch_s, 1e-6))))
-    with ClockSampler(device) as clk:
-        wall_s, avg_s = wl.train(Ks, 0, barrier)
-    el_s = max_over_ranks(wall_s)
-    sustained = {"steps": Ks, "seconds": el_s, "value": n * world * T * Ks / el_s, "unit": "env-steps/s",
-                 "ms_per_step": el_s / Ks * 1e3, "avg_launch_ms": avg_s * 1e3, "frac": roofline_of(wl, avg_s)["frac"]}
-    clocks = clk.record()
+    sustained = clocks = None
+    if args.extended:
+        Ks = max(K, int(math.ceil(args.sustained_seconds / max(avg_launch_s, 1e-6))))
+        with ClockSampler(device) as clk:
+            wall_s, avg_s = wl.train(Ks, 0, barrier)
+        el_s = max_over_ranks(wall_s)
+        sustained = {"steps": Ks, "seconds": el_s, "value": n * world * T * Ks / el_s, "unit": "env-steps/s",
+                     "ms_per_step": el_s / Ks * 1e3, "avg_launch_ms": avg_s * 1e3, "frac": roofline_of(wl, avg_s)["frac"]}
+        clocks = clk.record()
 
     # ---- reporting collective: episodic returns all-gathered over RCCL ------------
     gather_ms, rccl_ranks = None, None
@@ -1114,7 +1168,7 @@ def main():
     # total % world ranks one lane more; every shard takes the staged kernel whatever its lane count (row pitch, ABI 9)
     # and the return all-gather runs in its uneven-counts form (VERDICT r05 "Next" #5 / #6)
     uneven = None
-    if dist is not None and world > 1:
+    if dist is not None and world > 1 and args.extended:
         try:
             uneven = uneven_shard_record(args.families[0], args.lanes + 5, rank, world, device, backend, barrier, gather_over_ranks)
         except Exception as e:  # a plumbing side record: it must not take the scaling measurement with it
@@ -1285,7 +1339,7 @@ def main():
 
     # ---- N > 1: the OTHER scaling mode of the headline workload, same launch train ----
     other = None
-    if world > 1:
+    if world > 1 and args.extended:
         lanes3 = args.lanes if args.strong else args.lanes // world  # headline strong -> weak run; headline weak -> strong run
         w3 = Workload(args.families, lanes3, T, args.buffer_sets, rank, world, device, narrow_actions=args.narrow_actions)
         regs3, m3 = timed_regions(w3, K, W, args.reps, barrier, max_over_ranks)
@@ -1321,7 +1375,7 @@ def main():
             ("weak" if args.strong else "strong"): other, "per_call": per_call, "also": also,
             "mean_last_episode_return": mean_return, "return_allgather_ms": gather_ms, "rccl_ranks": rccl_ranks,
             "collective_backend": (backend if dist is not None else None),
-            "per_rank_avg_launch_ms": per_rank_launch_ms, "uneven_shards": uneven,
+            "per_rank_avg_launch_ms": per_rank_launch_ms, "uneven_shards": uneven, "outputs_dump": dump,
         }
         print(json.dumps(line), flush=True)
     _close_pool()

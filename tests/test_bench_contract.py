@@ -139,3 +139,74 @@ def test_committed_profiler_records_come_from_one_run():
         block = summary.split(f"== {k}\n")[1].split("\n== ")[0]
         avgs = [float(x) for x in re.findall(r"avg ([0-9.]+) us", block)]
         assert abs(sum(avgs) - kt[k]["kernel_avg_us"]) < 0.02 * len(avgs), (k, avgs, kt[k]["kernel_avg_us"])
+
+
+def test_plain_run_times_exactly_the_steps_asked_for(monkeypatch):
+    """`--steps K --warmup W` launches W + K times: one timed region, and none of the side records that launch more
+    unless `--extended` asks for them (a caller sizes later runs by the line's ms_per_step)."""
+    monkeypatch.setattr(bench.sys, "argv", ["bench.py", "--gpus", "1", "--steps", "7", "--warmup", "2"])
+    a = bench.parse()
+    assert (a.steps, a.warmup, a.reps, a.extended, a.dump_outputs) == (7, 2, 1, False, None)
+    assert a.no_per_call and a.no_cpu_baseline and a.no_shard8 and a.also == "none"
+    monkeypatch.setattr(bench.sys, "argv", ["bench.py", "--extended", "--dump-outputs", "d"])
+    a = bench.parse()
+    assert not (a.no_per_call or a.no_cpu_baseline or a.no_shard8) and "config5" in a.also.split(",")
+    assert a.dump_outputs == "d"
+
+
+def _fake_workload(families, n, T, dims, sets=2, launches=5, full=False):
+    """A Workload's output side only: per buffer set, one `alloc_rollout`-shaped dict per family (CPU tensors; `full`:
+    expanded views, so that the headline's 1.8 GB launch costs no memory)"""
+    import types
+
+    import torch
+
+    wl = bench.Workload.__new__(bench.Workload)
+    wl.families, wl.mixed, wl._i = tuple(families), len(families) > 1, launches
+    parts = [types.SimpleNamespace(n=n, device=torch.device("cpu")) for _ in families]
+    wl.eng = types.SimpleNamespace(parts=parts) if wl.mixed else parts[0]
+    g = torch.Generator().manual_seed(1)
+
+    def arr(shape, dtype=torch.float32):
+        if full:
+            return torch.ones((), dtype=dtype).expand(shape)
+        if dtype == torch.uint8:
+            return torch.randint(0, 2, shape, dtype=dtype, generator=g)
+        return torch.rand(shape, generator=g)
+
+    wl.outs = [[{"obs": arr((T, n, D)), "reward": arr((T, n)), "terminated": arr((T, n), torch.uint8),
+                 "truncated": arr((T, n), torch.uint8)} for D in dims] for _ in range(sets)]
+    return wl
+
+
+def test_dump_outputs_writes_the_last_launch_for_a_seeded_lane_sample(tmp_path, monkeypatch):
+    import numpy as np
+
+    monkeypatch.setattr(bench, "DUMP_BUDGET", 200_000)
+    wl = _fake_workload(["cartpole"], 4096, 50, [4])
+    rec = bench.dump_outputs(wl, str(tmp_path / "a"), 0, 1)
+    m = 200_000 // (50 * (4 + 3) * 4)
+    assert rec["lanes"] == {"cartpole": f"{m} of 4096 (numpy default_rng(0), sorted)"} and rec["bytes"] <= 200_000
+    lanes = np.sort(np.random.default_rng(0).choice(4096, m, replace=False))
+    last = wl.outs[(5 - 1) % 2][0]  # five launches over two buffer sets: the last one wrote set 0
+    for name, t in last.items():
+        a = np.load(tmp_path / "a" / f"{name}.npy")
+        assert a.dtype == np.float32 and a.shape == (50, m) + tuple(t.shape[2:])
+        np.testing.assert_array_equal(a, t.numpy()[:, lanes].astype(np.float32))
+    bench.dump_outputs(wl, str(tmp_path / "b"), 0, 1)  # same arguments -> same files
+    for f in os.listdir(tmp_path / "a"):
+        assert (tmp_path / "a" / f).read_bytes() == (tmp_path / "b" / f).read_bytes()
+    # a mixed batch: one set of files per family, the budget shared; ranks of a multi-GPU run keep theirs apart
+    mixed = _fake_workload(["acrobot", "mountaincar"], 1024, 20, [6, 2])
+    rec = bench.dump_outputs(mixed, str(tmp_path / "c"), 1, 2)
+    assert sorted(os.listdir(tmp_path / "c")) == sorted(f"{f}_{k}.rank1.npy" for f in ("acrobot", "mountaincar")
+                                                       for k in ("obs", "reward", "terminated", "truncated"))
+    assert rec["bytes"] <= 200_000
+
+
+def test_dump_of_the_headline_launch_stays_within_64_mb(tmp_path):
+    wl = _fake_workload(["cartpole"], 65536, 1000, [4], full=True)
+    rec = bench.dump_outputs(wl, str(tmp_path), 0, 1)
+    on_disk = sum(os.path.getsize(tmp_path / f) for f in os.listdir(tmp_path))
+    assert rec["bytes"] <= bench.DUMP_BUDGET and on_disk <= 64 * 10**6
+    assert rec["lanes"]["cartpole"].startswith(f"{bench.DUMP_BUDGET // (1000 * 7 * 4)} of 65536")

@@ -84,6 +84,11 @@ def test_sample(cs):
     assert len(ctxs) == 10 and all(bounded.verify_context(c) for c in ctxs)
     with pytest.raises(ValueError):
         cs.sample_contexts(["false_feature"], size=0)
+    # the reference's own calls, on the space with the unbounded gravity feature: still valid contexts
+    assert cs.verify_context(cs.sample_contexts(["gravity"], size=1))
+    for names in (["gravity"], None):
+        ctxs = cs.sample_contexts(names, size=10)
+        assert len(ctxs) == 10 and all(cs.verify_context(c) for c in ctxs)
 
 
 def test_context_bounds():

@@ -5,7 +5,7 @@
 # 2/4/8-GPU runs are the driver's).
 export CARL_AMD_NO_BUILD=1 CARL_BENCH_SHARE_GPU=1 CARL_BENCH_BACKEND=gloo
 timeout 300 python -m torch.distributed.run --nnodes=1 --nproc-per-node 2 --master-addr 127.0.0.1 --master-port 29517 \
-  bench.py --gpus 2 --steps 10 --warmup 3 2>&1 | grep "^{" | python -c "
+  bench.py --gpus 2 --steps 10 --warmup 3 --extended 2>&1 | grep "^{" | python -c "
 import json, sys
 d = json.loads(sys.stdin.read().strip().splitlines()[-1])
 print('n_gpus', d['n_gpus'], 'value %.3e' % d['value'], 'total_lanes', d['config']['total_lanes'], 'rccl_ranks', d['rccl_ranks'],

@@ -7,10 +7,10 @@
 K=${1:-20}; W=${2:-5}
 O=gpurun_out/scale; mkdir -p $O
 export HSA_ENABLE_IPC_MODE_LEGACY=0
-python bench.py --gpus 1 --steps $K --warmup $W > $O/bench_N1.json
+python bench.py --gpus 1 --steps $K --warmup $W --extended > $O/bench_N1.json
 for N in 2 4 8; do
   python -m torch.distributed.run --nnodes=1 --nproc-per-node $N --master-addr 127.0.0.1 --master-port $((29500 + N)) \
-    bench.py --gpus $N --steps $K --warmup $W > $O/bench_N$N.json
+    bench.py --gpus $N --steps $K --warmup $W --extended > $O/bench_N$N.json
 done
 python - <<'PY'
 import json
