@@ -124,30 +124,119 @@ bool use_lds_ctx(const carl_batch_t* b) {
 }
 
 // lanes per row of the action / output arrays of a rollout (carl_step_io_t::row_pitch; 0 = dense rows)
-int row_pitch_of(const carl_batch_t* b, const carl_step_io_t* io) {
-  return (io != nullptr && io->row_pitch > 0) ? io->row_pitch : b->n_lanes;
+int row_pitch_of(const carl_batch_t* b, const carl_step_io_t* io) { return io->row_pitch > 0 ? io->row_pitch : b->n_lanes; }
+
+// Which kernel a rollout of this batch launches: launch_step, launch_pair, carl_rollout_variant(_io) and the
+// narrow-format refusal all read it from here.  Pure host logic: no HIP call, no allocation.
+struct RolloutPlan {
+  int variant = CARL_ROLLOUT_STAGED;  // CARL_ROLLOUT_*
+  bool lean = false;         // the lean staged configuration: staged, static / host selector, no finished-episode log,
+                             // no final_obs
+  bool unsupported = false;  // a narrow action format (uint8 / float16 / bfloat16) outside the lean staged configuration
+  // rollout_staged_kernel's template arguments (variant == CARL_ROLLOUT_STAGED) and its dynamic LDS
+  int ak = 0;  // action kind: 0 int32 / float32, 1 int64, carl::kActU8 / kActF16 / kActBF16
+  bool plain = false, ldsctx = false, moves = false, fin = false, ar = false, deep = false;
+  size_t lds_bytes = 0;
+};
+
+template <class Fam>
+RolloutPlan plan_rollout(const carl_batch_t* b, const carl_step_io_t* io) {
+  // (every family opts in to the predrawn done path, whose lean specialisations follow)
+  static_assert(carl::predraw_of<Fam>::value, "the staged kernels below are instantiated for predrawing families");
+  RolloutPlan p;
+  const int dt = io->action_dtype;
+  p.ak = dt == CARL_ACTION_I64 ? 1 : dt == CARL_ACTION_U8 ? carl::kActU8 : dt == CARL_ACTION_F16 ? carl::kActF16
+         : dt == CARL_ACTION_BF16 ? carl::kActBF16 : 0;
+  // The staged kernel writes 16-byte pieces of every row: rows must start on 16-byte boundaries (pitch % 16 == 0) and
+  // the columns [n_lanes, n_lanes rounded up to 16) must be the caller's to lose -- they are when the lane count is a
+  // multiple of 16 (there are none) or when the pitch IS that rounded-up count (the padded layout of carl_rollout_pitch).
+  // A wider pitch with an odd lane count is a view into an array whose neighbouring columns belong to someone else:
+  // direct stores.  ... and every array must START on a 16-byte boundary (fresh allocations do; a column view
+  // `array[:, k:]` need not).  The loader wave reads a lane-row of four actions per load: 16 bytes (int32 / float32;
+  // int64: two of them), 4 (uint8), 8 (float16 / bfloat16).
+  const int pitch = row_pitch_of(b, io), n16 = (b->n_lanes + 15) / 16 * 16;
+  const uintptr_t bits = reinterpret_cast<uintptr_t>(io->obs) | reinterpret_cast<uintptr_t>(io->reward) |
+                         reinterpret_cast<uintptr_t>(io->terminated) | reinterpret_cast<uintptr_t>(io->truncated) |
+                         reinterpret_cast<uintptr_t>(io->final_obs);
+  const uintptr_t amask = p.ak == carl::kActU8 ? 3u : p.ak > carl::kActU8 ? 7u : 15u;
+  const bool aligned = (bits & 15) == 0 && (reinterpret_cast<uintptr_t>(io->action) & amask) == 0;
+  if (b->flags & CARL_FLAG_ROLLOUT_DIRECT)
+    p.variant = CARL_ROLLOUT_DIRECT_FLAG;
+  else if (!(aligned && pitch % 16 == 0 && (b->n_lanes % 16 == 0 || pitch == n16)))
+    p.variant = CARL_ROLLOUT_DIRECT_SHAPE;
+  const bool keeps_context = b->selector == CARL_SEL_STATIC || b->selector == CARL_SEL_HOST;
+  p.lean = p.variant == CARL_ROLLOUT_STAGED && keeps_context && b->fin_count == nullptr && io->final_obs == nullptr;
+  // the narrow formats are read by the lean staged rollout only (include/carl_amd.h: CARL_ACTION_U8)
+  p.unsupported = p.ak >= carl::kActU8 && !p.lean;
+  if (p.variant != CARL_ROLLOUT_STAGED) return p;
+
+  p.lds_bytes = carl::rollout_staged_lds_bytes<Fam>();
+  // (also for tables small enough for LDS: a fused rollout gathers parameters once per launch and on resets, so the
+  // global table costs nothing there; the LDS copy pays off when lanes change contexts on reset, below)
+  const size_t table_bytes = (size_t)Fam::F * b->n_contexts * sizeof(float);
+  // static LDS of the kernel (Acrobot's fp64 kernels carry the 8 KiB sin/cos table) counts against the 160 KiB too
+  constexpr size_t static_lds = carl::has_tables<Fam>::value ? sizeof(double) * 2 * CARL_SINCOS_TAB_N : 0;
+  const bool table_fits = use_lds_ctx<Fam>(b) && p.lds_bytes + table_bytes + static_lds <= 160 * 1024;
+  if (p.lean) {
+    // two specialisations of the done path (made for CartPole, whose done path runs on nearly every step; every family
+    // opts in: the leaner code also helps the step loop's register allocation): none of the optional features is on,
+    // the done path compiled without them ...
+    p.plain = true;
+    // ... and, for the short-episode family, with auto-reset a compile-time fact (step_dense: AR)
+    p.ar = carl::dense_done_of<Fam>::value && (b->flags & CARL_FLAG_AUTORESET);
+    // a batch that leaves compute units empty: two chunks of int32 / float32 actions in flight (same results)
+    p.deep = p.ak == 0 && b->n_lanes < carl::deep_below_lanes_of<Fam>::value;
+  } else if (carl::dense_done_of<Fam>::value && b->fin_count == nullptr) {
+    // short-episode family: the dense done handling also covers lanes that change contexts on reset (round robin --
+    // the reference's default selector -- or random; the next context's parameters are gathered per chunk) and
+    // terminal observations; only the finished-episode log still takes the generic path
+    p.plain = true;
+    p.moves = !keeps_context;
+    p.fin = io->final_obs != nullptr;
+    p.ldsctx = p.moves && table_fits;
+  } else {
+    // lanes change contexts on reset and the table is small: re-gather from LDS, not from HBM
+    p.ldsctx = !keeps_context && table_fits;
+  }
+  if (p.ldsctx) p.lds_bytes += table_bytes;
+  return p;
 }
 
-// The staged kernel writes 16-byte pieces of every row: rows must start on 16-byte boundaries (pitch % 16 == 0) and the
-// columns [n_lanes, n_lanes rounded up to 16) must be the caller's to lose -- they are when the lane count is a multiple
-// of 16 (there are none) or when the pitch IS that rounded-up count (the padded layout of carl_rollout_pitch).  A wider
-// pitch with an odd lane count is a view into an array whose neighbouring columns belong to someone else: direct stores.
-int rollout_variant(const carl_batch_t* b, const carl_step_io_t* io = nullptr) {
-  if (b->flags & CARL_FLAG_ROLLOUT_DIRECT) return CARL_ROLLOUT_DIRECT_FLAG;
-  const int pitch = row_pitch_of(b, io), n16 = (b->n_lanes + 15) / 16 * 16;
-  // ... and every array must START on a 16-byte boundary (fresh allocations do; a column view `array[:, k:]` need not)
-  bool aligned = true;
-  if (io != nullptr) {
-    const uintptr_t bits = reinterpret_cast<uintptr_t>(io->obs) | reinterpret_cast<uintptr_t>(io->reward) |
-                           reinterpret_cast<uintptr_t>(io->terminated) | reinterpret_cast<uintptr_t>(io->truncated) |
-                           reinterpret_cast<uintptr_t>(io->final_obs);
-    // the loader wave reads a lane-row of four actions per load: 16 bytes (int32 / float32; int64: two of them), 4 (uint8), 8
-    const uintptr_t amask = io->action_dtype == CARL_ACTION_U8 ? 3u
-                            : (io->action_dtype == CARL_ACTION_F16 || io->action_dtype == CARL_ACTION_BF16) ? 7u : 15u;
-    aligned = (bits & 15) == 0 && (reinterpret_cast<uintptr_t>(io->action) & amask) == 0;
+using staged_kern_t = void (*)(carl_batch_t, carl_step_io_t, int);
+
+// The rollout_staged_kernel instances that exist, and the one a plan names (nullptr: none).
+template <class Fam>
+staged_kern_t staged_kernel(const RolloutPlan& p) {
+#define CARL_STAGED(AK, PLAIN, LDSCTX, MOVES, FIN, AR, DEEP)                                                         \
+  if (p.ak == AK && p.plain == PLAIN && p.ldsctx == LDSCTX && p.moves == MOVES && p.fin == FIN && p.ar == AR &&    \
+      p.deep == DEEP)                                                                                              \
+    return carl::rollout_staged_kernel<Fam, AK, bool(PLAIN), bool(LDSCTX), bool(MOVES), bool(FIN), bool(AR), bool(DEEP)>;
+#define CARL_STAGED_01(...) CARL_STAGED(0, __VA_ARGS__) CARL_STAGED(1, __VA_ARGS__)  // int32 / float32 and int64 actions
+  constexpr bool dense = carl::dense_done_of<Fam>::value, deep = carl::deep_below_lanes_of<Fam>::value > 0;
+  //             PLAIN LDSCTX MOVES FIN AR DEEP
+  CARL_STAGED_01(    0,     0,    0,  0, 0,   0)  // generic
+  CARL_STAGED_01(    0,     1,    0,  0, 0,   0)  // generic, table in LDS
+  CARL_STAGED_01(    1,     0,    0,  0, 0,   0)  // lean
+  if constexpr (std::is_same_v<typename Fam::Action, int>) {
+    CARL_STAGED(carl::kActU8, 1, 0, 0, 0, 0, 0)
+  } else {
+    CARL_STAGED(carl::kActF16, 1, 0, 0, 0, 0, 0)
+    CARL_STAGED(carl::kActBF16, 1, 0, 0, 0, 0, 0)
   }
-  return (aligned && pitch % 16 == 0 && (b->n_lanes % 16 == 0 || pitch == n16)) ? CARL_ROLLOUT_STAGED
-                                                                                : CARL_ROLLOUT_DIRECT_SHAPE;
+  if constexpr (deep) CARL_STAGED(0, 1, 0, 0, 0, 0, 1)  // lean, two chunks of actions in flight
+  if constexpr (dense) {
+    CARL_STAGED_01(  1,     0,    0,  0, 1,   0)  // lean with auto-reset
+    CARL_STAGED(carl::kActU8, 1, 0, 0, 0, 1, 0)
+    if constexpr (deep) CARL_STAGED(0, 1, 0, 0, 0, 1, 1)
+    CARL_STAGED_01(  1,     0,    0,  1, 0,   0)  // the dense done path: terminal observations, moving lanes
+    CARL_STAGED_01(  1,     0,    1,  0, 0,   0)
+    CARL_STAGED_01(  1,     0,    1,  1, 0,   0)
+    CARL_STAGED_01(  1,     1,    1,  0, 0,   0)
+    CARL_STAGED_01(  1,     1,    1,  1, 0,   0)
+  }
+#undef CARL_STAGED_01
+#undef CARL_STAGED
+  return nullptr;
 }
 
 // 64-thread workgroups spread a small batch over all 256 CUs x 4 SIMDs (65 536
@@ -174,28 +263,34 @@ int launch_reset(const carl_batch_t* b, const uint8_t* mask, const int32_t* idx,
 template <class Fam>
 int launch_step(const carl_batch_t* b, const carl_step_io_t* io, int n_steps, hipStream_t s) {
   if (b->n_lanes == 0 || n_steps == 0) return 0;
-  const bool lds = use_lds_ctx<Fam>(b);
   const bool rollout = n_steps >= 0;
-  // rollout: 256 compute lanes + one loader wave per workgroup, actions double-buffered
-  // in LDS; per-call step: plain lane-per-thread workgroups
+  const RolloutPlan plan = plan_rollout<Fam>(b, io);
+  if (plan.unsupported || (!rollout && plan.ak >= carl::kActU8))
+    return fail(CARL_ERR_UNSUPPORTED,
+                "uint8 / float16 / bfloat16 actions: carl_rollout in its lean staged configuration only (row pitch %% 16 == 0, "
+                "static / host selector, no finished-episode log, no final_obs); pass int32 / int64 / float32 actions");
+  carl_step_io_t io_resolved = *io;  // the kernels read the pitch as given: never 0
+  io_resolved.row_pitch = row_pitch_of(b, io);
+  // row pitch % 16 == 0 (dense rows: n_lanes % 16 == 0): records are staged in LDS and written out by the workgroup's
+  // storer waves with 16-byte stores (rollout_staged_kernel).  Other shapes -- and CARL_FLAG_ROLLOUT_DIRECT, the A/B
+  // switch -- take rollout_kernel (per-lane stores, ~50 % slower); carl_rollout_variant() tells a caller which one it gets.
+  if (rollout && plan.variant == CARL_ROLLOUT_STAGED) {
+    const staged_kern_t kern = staged_kernel<Fam>(plan);
+    if (kern == nullptr) return fail(CARL_ERR_UNSUPPORTED, "carl_rollout: no staged kernel for this configuration");
+    if (int e = carl_host::ensure_dynamic_lds(reinterpret_cast<const void*>(kern), plan.lds_bytes, "carl_rollout")) return e;
+    const int grid = (b->n_lanes + carl::kRolloutLanes - 1) / carl::kRolloutLanes;
+    // 4 compute waves + loader wave + storer waves
+    hipLaunchKernelGGL(kern, dim3(grid), dim3(carl::kStagedThreads), plan.lds_bytes, s, *b, io_resolved, n_steps);
+    return check_launch("carl_rollout");
+  }
+  // rollout_kernel: 256 compute lanes + one loader wave per workgroup, actions double-buffered in LDS; per-call step:
+  // plain lane-per-thread workgroups
+  const bool lds = use_lds_ctx<Fam>(b), a64 = io->action_dtype == CARL_ACTION_I64;
   const int block = rollout ? carl::kRolloutThreads : pick_block(b->n_lanes, lds);
   const int lanes_per_block = rollout ? carl::kRolloutLanes : block;
-  const int grid = (b->n_lanes + lanes_per_block - 1) / lanes_per_block;
+  const dim3 g((b->n_lanes + lanes_per_block - 1) / lanes_per_block), t(block);
   const size_t sh = (lds ? (size_t)Fam::F * b->n_contexts * sizeof(float) : 0) +
                     (rollout ? carl::rollout_action_lds_bytes() : 0);
-  const bool a64 = io->action_dtype == CARL_ACTION_I64;
-  // the narrow formats (uint8 / float16 / bfloat16): the lean staged rollout only (include/carl_amd.h: CARL_ACTION_U8)
-  const bool au8 = io->action_dtype == CARL_ACTION_U8;
-  const bool af16 = io->action_dtype == CARL_ACTION_F16, abf16 = io->action_dtype == CARL_ACTION_BF16;
-  if (au8 || af16 || abf16) {
-    const bool keeps_context = b->selector == CARL_SEL_STATIC || b->selector == CARL_SEL_HOST;
-    const bool lean = b->fin_count == nullptr && io->final_obs == nullptr;
-    if (!rollout || rollout_variant(b, io) != CARL_ROLLOUT_STAGED || !keeps_context || !lean || !carl::predraw_of<Fam>::value)
-      return fail(CARL_ERR_UNSUPPORTED,
-                  "uint8 / float16 / bfloat16 actions: carl_rollout in its lean staged configuration only (row pitch %% 16 == 0, "
-                  "static / host selector, no finished-episode log, no final_obs); pass int32 / int64 / float32 actions");
-  }
-  const dim3 g(grid), t(block);
 #define CARL_LAUNCH(KERNEL, ...)                                                                    \
   do {                                                                                              \
     if (lds && a64) hipLaunchKernelGGL((carl::KERNEL<Fam, true, true>), g, t, sh, s, __VA_ARGS__);   \
@@ -203,118 +298,31 @@ int launch_step(const carl_batch_t* b, const carl_step_io_t* io, int n_steps, hi
     else if (a64) hipLaunchKernelGGL((carl::KERNEL<Fam, false, true>), g, t, sh, s, __VA_ARGS__);    \
     else hipLaunchKernelGGL((carl::KERNEL<Fam, false, false>), g, t, sh, s, __VA_ARGS__);            \
   } while (0)
-  if (n_steps < 0) {  // per-call step
+  if (!rollout) {
     CARL_LAUNCH(step_kernel, *b, *io);
     return check_launch("carl_step");
   }
-  carl_step_io_t io_resolved = *io;  // the kernels read the pitch as given: never 0
-  io_resolved.row_pitch = row_pitch_of(b, io);
-  io = &io_resolved;
-  // row pitch % 16 == 0 (dense rows: n_lanes % 16 == 0): records are staged in LDS and written out by the workgroup's
-  // storer waves with 16-byte stores (rollout_staged_kernel).  Other shapes -- and CARL_FLAG_ROLLOUT_DIRECT, the A/B switch -- take
-  // rollout_kernel (per-lane stores, ~50 % slower); carl_rollout_variant() tells a caller which one it gets.
-  // (also for tables small enough for LDS: a fused rollout gathers parameters once per launch and on
-  // resets, so the global table costs nothing there; the LDS copy pays off in the per-call kernel)
-  if (rollout_variant(b, io) == CARL_ROLLOUT_STAGED) {  // 16-byte pieces of every output row stay inside the row
-    size_t sh_staged = carl::rollout_staged_lds_bytes<Fam>();
-    using kern_t = void (*)(carl_batch_t, carl_step_io_t, int);
-    kern_t kern = a64 ? static_cast<kern_t>(carl::rollout_staged_kernel<Fam, true>)
-                      : static_cast<kern_t>(carl::rollout_staged_kernel<Fam, false>);
-    if constexpr (carl::predraw_of<Fam>::value) {
-      // two specialisations of the done path (made for CartPole, whose done path runs on nearly every step;
-      // every family opts in: the leaner code also helps the step loop's register allocation)
-      const bool keeps_context = b->selector == CARL_SEL_STATIC || b->selector == CARL_SEL_HOST;
-      const size_t table_bytes = (size_t)Fam::F * b->n_contexts * sizeof(float);
-      const bool lean = b->fin_count == nullptr && io->final_obs == nullptr;
-      // static LDS of the kernel (Acrobot's fp64 kernels carry the 8 KiB sin/cos table) counts against the 160 KiB too
-      constexpr size_t static_lds = carl::has_tables<Fam>::value ? sizeof(double) * 2 * CARL_SINCOS_TAB_N : 0;
-      const bool table_fits = lds && sh_staged + table_bytes + static_lds <= 160 * 1024;
-      bool picked = false;
-      if (keeps_context && lean) {
-        // none of the optional features is on: the done path compiled without them
-        kern = a64 ? static_cast<kern_t>(carl::rollout_staged_kernel<Fam, true, true>)
-                   : static_cast<kern_t>(carl::rollout_staged_kernel<Fam, false, true>);
-        if constexpr (carl::dense_done_of<Fam>::value) {
-          // ... and, for the short-episode family, with auto-reset a compile-time fact (step_dense: AR)
-          if (b->flags & CARL_FLAG_AUTORESET)
-            kern = a64 ? static_cast<kern_t>(carl::rollout_staged_kernel<Fam, true, true, false, false, false, true>)
-                       : static_cast<kern_t>(carl::rollout_staged_kernel<Fam, false, true, false, false, false, true>);
-        }
-        if constexpr (carl::deep_below_lanes_of<Fam>::value > 0) {
-          // a batch that leaves compute units empty: two chunks of actions in flight (same results)
-          if (!a64 && !au8 && !af16 && !abf16 && b->n_lanes < carl::deep_below_lanes_of<Fam>::value) {
-            kern = static_cast<kern_t>(carl::rollout_staged_kernel<Fam, 0, true, false, false, false, false, true>);
-            if constexpr (carl::dense_done_of<Fam>::value) {
-              if (b->flags & CARL_FLAG_AUTORESET)
-                kern = static_cast<kern_t>(carl::rollout_staged_kernel<Fam, 0, true, false, false, false, true, true>);
-            }
-          }
-        }
-        if constexpr (std::is_same_v<typename Fam::Action, float>) {
-          if (af16) kern = static_cast<kern_t>(carl::rollout_staged_kernel<Fam, carl::kActF16, true>);
-          if (abf16) kern = static_cast<kern_t>(carl::rollout_staged_kernel<Fam, carl::kActBF16, true>);
-        }
-        if constexpr (std::is_same_v<typename Fam::Action, int>) {
-          if (au8) {  // the same two kernels reading one byte per action
-            kern = static_cast<kern_t>(carl::rollout_staged_kernel<Fam, carl::kActU8, true>);
-            if constexpr (carl::dense_done_of<Fam>::value) {
-              if (b->flags & CARL_FLAG_AUTORESET)
-                kern = static_cast<kern_t>(carl::rollout_staged_kernel<Fam, carl::kActU8, true, false, false, false, true>);
-            }
-          }
-        }
-        picked = true;
-      }
-      if constexpr (carl::dense_done_of<Fam>::value) {
-        // short-episode family: the dense done handling also covers lanes that change contexts on reset (round
-        // robin -- the reference's default selector -- or random; the next context's parameters are gathered per
-        // chunk) and terminal observations; only the finished-episode log still takes the generic path
-        if (!picked && b->fin_count == nullptr) {
-          const bool moves = !keeps_context, fin = io->final_obs != nullptr, tl = moves && table_fits;
-          using carl::rollout_staged_kernel;
-#define CARL_DENSE(A, L, M, F) static_cast<kern_t>(rollout_staged_kernel<Fam, A, true, L, M, F>)
-          if (a64) {
-            kern = tl ? (fin ? CARL_DENSE(true, true, true, true) : CARL_DENSE(true, true, true, false))
-                      : moves ? (fin ? CARL_DENSE(true, false, true, true) : CARL_DENSE(true, false, true, false))
-                              : CARL_DENSE(true, false, false, true);
-          } else {
-            kern = tl ? (fin ? CARL_DENSE(false, true, true, true) : CARL_DENSE(false, true, true, false))
-                      : moves ? (fin ? CARL_DENSE(false, false, true, true) : CARL_DENSE(false, false, true, false))
-                              : CARL_DENSE(false, false, false, true);
-          }
-#undef CARL_DENSE
-          if (tl) sh_staged += table_bytes;
-          picked = true;
-        }
-      }
-      if (!picked && !keeps_context && table_fits) {
-        // lanes change contexts on reset and the table is small: re-gather from LDS, not from HBM
-        kern = a64 ? static_cast<kern_t>(carl::rollout_staged_kernel<Fam, true, false, true>)
-                   : static_cast<kern_t>(carl::rollout_staged_kernel<Fam, false, false, true>);
-        sh_staged += table_bytes;
-      }
-    }
-    if (int e = carl_host::ensure_dynamic_lds(reinterpret_cast<const void*>(kern), sh_staged, "carl_rollout")) return e;
-    const dim3 ts(carl::kStagedThreads);  // 4 compute waves + loader wave + storer wave
-    hipLaunchKernelGGL(kern, g, ts, sh_staged, s, *b, *io, n_steps);
-    return check_launch("carl_rollout");
-  }
-  CARL_LAUNCH(rollout_kernel, *b, *io, n_steps);
+  CARL_LAUNCH(rollout_kernel, *b, io_resolved, n_steps);
 #undef CARL_LAUNCH
   return check_launch("carl_rollout");
 }
 
 // One launch for a mixed batch of two classic families (engine_kernels.hip.h: rollout_staged_pair_kernel).  A is the
 // float64 Acrobot -- the family whose single wavefront per SIMD leaves issue slots for another family's wavefronts;
-// pairing two memory-bound float32 families would gain nothing.
+// pairing two memory-bound float32 families would gain nothing.  Both parts must be what launch_step would run as
+// rollout_staged_kernel<Fam, 0, PLAIN = true>: the lean staged configuration with int32 / float32 actions.
 template <class FamB>
 int launch_pair(const carl_batch_t* a, const carl_step_io_t* ioa, const carl_batch_t* b, const carl_step_io_t* iob,
                 int n_steps, hipStream_t s) {
   using FamA = carl::Acrobot;
+  const RolloutPlan pa = plan_rollout<FamA>(a, ioa), pb = plan_rollout<FamB>(b, iob);
+  if (a->n_lanes == 0 || b->n_lanes == 0 || !pa.lean || !pb.lean || pa.ak != 0 || pb.ak != 0)
+    return fail(CARL_ERR_UNSUPPORTED, "carl_rollout_pair: both parts must be lean staged rollouts (row pitch %% 16 == 0, static / host "
+                "selector, no finished-episode log, no terminal observations, int32 / float32 actions)");
   using kern_t = void (*)(carl_batch_t, carl_step_io_t, carl_batch_t, carl_step_io_t, int, int);
   kern_t kern = static_cast<kern_t>(carl::rollout_staged_pair_kernel<FamA, FamB, false, false>);
   if constexpr (carl::dense_done_of<FamB>::value) {
-    if (b->flags & CARL_FLAG_AUTORESET) kern = static_cast<kern_t>(carl::rollout_staged_pair_kernel<FamA, FamB, false, true>);
+    if (pb.ar) kern = static_cast<kern_t>(carl::rollout_staged_pair_kernel<FamA, FamB, false, true>);
   }
   const size_t sh = carl::rollout_pair_lds_bytes<FamA, FamB>();
   if (int e = carl_host::ensure_dynamic_lds(reinterpret_cast<const void*>(kern), sh, "carl_rollout_pair")) return e;
@@ -325,14 +333,6 @@ int launch_pair(const carl_batch_t* a, const carl_step_io_t* ioa, const carl_bat
   rb.row_pitch = row_pitch_of(b, iob);
   hipLaunchKernelGGL(kern, dim3(grid_a + grid_b), dim3(carl::kStagedThreads), sh, s, *a, ra, *b, rb, n_steps, grid_a);
   return check_launch("carl_rollout_pair");
-}
-
-// the lean staged configuration of one part of a pair launch (what launch_step would run as
-// rollout_staged_kernel<Fam, false, PLAIN = true>)
-bool pair_part_ok(const carl_batch_t* b, const carl_step_io_t* io) {
-  const bool keeps_context = b->selector == CARL_SEL_STATIC || b->selector == CARL_SEL_HOST;
-  return b->n_lanes > 0 && rollout_variant(b, io) == CARL_ROLLOUT_STAGED && keeps_context && b->fin_count == nullptr &&
-         io->final_obs == nullptr && (io->action_dtype == CARL_ACTION_I32 || io->action_dtype == CARL_ACTION_F32);
 }
 
 #define CARL_DISPATCH(family, CALL)                                   \
@@ -443,9 +443,6 @@ int carl_rollout_pair(const carl_batch_t* batch_a, const carl_step_io_t* io_a, c
   }
   if (batch_b->family == CARL_ACROBOT)
     return fail(CARL_ERR_UNSUPPORTED, "carl_rollout_pair: the second family cannot be Acrobot");
-  if (!pair_part_ok(batch_a, io_a) || !pair_part_ok(batch_b, io_b))
-    return fail(CARL_ERR_UNSUPPORTED, "carl_rollout_pair: both parts must be lean staged rollouts (row pitch %% 16 == 0, static / host "
-                "selector, no finished-episode log, no terminal observations, int32 / float32 actions)");
   hipStream_t s = (hipStream_t)stream;
   switch (batch_b->family) {
     case CARL_CARTPOLE: return launch_pair<carl::CartPole>(batch_a, io_a, batch_b, io_b, n_steps, s);
@@ -456,7 +453,9 @@ int carl_rollout_pair(const carl_batch_t* batch_a, const carl_step_io_t* io_a, c
   }
 }
 
-int carl_rollout_variant(const carl_batch_t* batch) {
+int carl_rollout_variant(const carl_batch_t* batch) { return carl_rollout_variant_io(batch, nullptr); }
+
+int carl_rollout_variant_io(const carl_batch_t* batch, const carl_step_io_t* io) {
   if (batch == nullptr) {
     fail(CARL_ERR_INVALID_ARGUMENT, "carl_rollout_variant: batch is NULL");
     return CARL_ERR_INVALID_ARGUMENT;
@@ -465,17 +464,14 @@ int carl_rollout_variant(const carl_batch_t* batch) {
     fail(CARL_ERR_INVALID_ARGUMENT, "carl_rollout_variant: family %d is not a classic-control family", batch->family);
     return CARL_ERR_INVALID_ARGUMENT;
   }
-  return rollout_variant(batch);
-}
-
-int carl_rollout_variant_io(const carl_batch_t* batch, const carl_step_io_t* io) {
-  const int dense = carl_rollout_variant(batch);
-  if (dense == CARL_ERR_INVALID_ARGUMENT || io == nullptr) return dense;
-  if (io->row_pitch != 0 && io->row_pitch < batch->n_lanes) {
+  if (io != nullptr && io->row_pitch != 0 && io->row_pitch < batch->n_lanes) {
     fail(CARL_ERR_INVALID_ARGUMENT, "carl_rollout_variant_io: io.row_pitch %d < n_lanes %d", io->row_pitch, batch->n_lanes);
     return CARL_ERR_INVALID_ARGUMENT;
   }
-  return rollout_variant(batch, io);
+  const carl_step_io_t dense{};  // no io: dense rows, arrays on 16-byte boundaries
+#define CALL(F) plan_rollout<F>(batch, io != nullptr ? io : &dense).variant
+  CARL_DISPATCH(batch->family, CALL)
+#undef CALL
 }
 
 int32_t carl_rollout_pitch(int32_t n_lanes) { return n_lanes <= 0 ? 0 : (n_lanes + 15) / 16 * 16; }

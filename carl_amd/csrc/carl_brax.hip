@@ -102,17 +102,6 @@ int validate_brax(const carl_batch_t* b, const carl_brax_sys_t* sd, const carl_b
   return 0;
 }
 
-// Lanes per env (the kernels' kSub).  The Brax kernel is bound by the instruction stream a
-// wavefront issues (~4.3 cycles per wavefront instruction with two resident waves per SIMD,
-// profiles/r01g), so a joint or body round with one busy lane per env costs as much as a full one:
-// the width is the number of links (every phase = one round), rounded up to an instantiated
-// (width, MULTI) pair, and widened for small batches so that the launch has at least two
-// wavefronts per SIMD.  carl_brax_sys_t::lanes_per_env pins it (autotune, tests).
-constexpr int kBraxWidths[] = {2, 4, 7, 8, 9, 11, 16};
-constexpr bool brax_instantiated(int k, bool multi, bool task) {
-  if (task) return k == 4 || k == 8 || k == 16;  // reacher: 3 links, pusher: 8
-  return multi ? (k == 2 || k == 11 || k == 16) : (k == 4 || k == 7 || k == 8 || k == 9 || k == 16);
-}
 // The GENERAL kernels (template parameter TASK of brax_kernel): the reach / push task models -- and every model with a link
 // whose principal moments of inertia differ.  Every shipped locomotion model has isotropic effective inertia
 // (spring_inertia_scale = 1), so the rotated-inertia code R diag(1 / I) R^T lives in the general kernels only: the lean and
@@ -171,7 +160,71 @@ bool brax_is_planar(const carl_brax_sys_t* sh) {
   return true;
 }
 
-int brax_lanes_per_env(int n_links, bool multi, bool task, int n_lanes, int hint) {
+// The kernel class a launch of this model takes: reset (MODE 0) never takes the planar substep or float32 pose algebra.
+struct BraxClass {
+  bool multi, task, planar, f32;
+};
+BraxClass brax_class(const carl_brax_sys_t* sh, uint32_t flags, bool step) {
+  const bool task = brax_is_task(sh), planar_model = brax_is_planar(sh);
+  const bool planar = step && !(flags & CARL_FLAG_BRAX_GENERIC) && planar_model;
+  // task models run the multi-hinge general kernels; a planar model stepped by the general substep
+  // (CARL_FLAG_BRAX_GENERIC): its root's slides need the multi-hinge kernels
+  const bool multi = task || brax_is_multi(sh) || (step && planar_model && !planar);
+  return {multi, task, planar, step && (flags & CARL_FLAG_BRAX_FP32) != 0};
+}
+
+// Every instantiated brax_kernel<MODE, MULTI, K, TASK, PLANAR, F32>: (class, K) -> its reset and step kernels.
+using brax_kern_t = void (*)(carl_batch_t, const carl_brax_sys_t*, carl::brax::Prepared, carl_step_io_t, const uint8_t*,
+                             float*, int);
+struct BraxKernel {
+  BraxClass c;
+  int k;
+  brax_kern_t reset, step;
+};
+#define CARL_BRAX(MULTI, K, TASK) \
+  {{MULTI, TASK, false, false}, K, carl::brax::brax_kernel<0, MULTI, K, TASK>, carl::brax::brax_kernel<1, MULTI, K, TASK>}
+#define CARL_BRAX_STEP(MULTI, K, PLANAR, F32) \
+  {{MULTI, false, PLANAR, F32}, K, nullptr, carl::brax::brax_kernel<1, MULTI, K, false, PLANAR, F32>}
+const BraxKernel kBraxKernels[] = {
+    // lean (a free root and single hinges: Ant)
+    CARL_BRAX(false, 4, false), CARL_BRAX(false, 7, false), CARL_BRAX(false, 8, false), CARL_BRAX(false, 9, false),
+    CARL_BRAX(false, 16, false),
+    // multi-hinge
+    CARL_BRAX(true, 2, false), CARL_BRAX(true, 11, false), CARL_BRAX(true, 16, false),
+    // general: reach / push task models (reacher: 3 links, pusher: 8) and anisotropic inertia
+    CARL_BRAX(true, 4, true), CARL_BRAX(true, 8, true), CARL_BRAX(true, 16, true),
+    // planar
+    CARL_BRAX_STEP(false, 4, true, false), CARL_BRAX_STEP(false, 7, true, false), CARL_BRAX_STEP(false, 8, true, false),
+    CARL_BRAX_STEP(false, 9, true, false), CARL_BRAX_STEP(false, 16, true, false),
+    // CARL_FLAG_BRAX_FP32 (opt-in): the same kernels with the substeps' pose algebra in float32
+    CARL_BRAX_STEP(false, 4, false, true), CARL_BRAX_STEP(false, 7, false, true), CARL_BRAX_STEP(false, 8, false, true),
+    CARL_BRAX_STEP(false, 9, false, true), CARL_BRAX_STEP(false, 16, false, true),
+    CARL_BRAX_STEP(true, 2, false, true), CARL_BRAX_STEP(true, 11, false, true), CARL_BRAX_STEP(true, 16, false, true),
+    CARL_BRAX_STEP(false, 4, true, true), CARL_BRAX_STEP(false, 7, true, true), CARL_BRAX_STEP(false, 8, true, true),
+    CARL_BRAX_STEP(false, 9, true, true), CARL_BRAX_STEP(false, 16, true, true),
+};
+#undef CARL_BRAX
+#undef CARL_BRAX_STEP
+
+bool same_class(const BraxClass& a, const BraxClass& b) {
+  return a.multi == b.multi && a.task == b.task && a.planar == b.planar && a.f32 == b.f32;
+}
+
+// the narrowest instantiated width >= w of the class; 0 if there is none
+int brax_width_from(const BraxClass& c, int w) {
+  int k = 0;
+  for (const BraxKernel& e : kBraxKernels)
+    if (same_class(e.c, c) && e.k >= w && (k == 0 || e.k < k)) k = e.k;
+  return k;
+}
+
+// Lanes per env (the kernels' kSub).  The Brax kernel is bound by the instruction stream a
+// wavefront issues (~4.3 cycles per wavefront instruction with two resident waves per SIMD,
+// profiles/r01g), so a joint or body round with one busy lane per env costs as much as a full one:
+// the width is the number of links (every phase = one round), rounded up to an instantiated
+// width of the class, and widened for small batches so that the launch has at least two
+// wavefronts per SIMD.  carl_brax_sys_t::lanes_per_env pins it (autotune, tests).
+int brax_lanes_per_env(int n_links, const BraxClass& c, int n_lanes, int hint) {
   int want = n_links;
   bool pinned = false;
   if (hint > 0) {  // sys.lanes_per_env (autotuned by the caller); never narrower than one lane per link (the kernels'
@@ -179,21 +232,12 @@ int brax_lanes_per_env(int n_links, bool multi, bool task, int n_lanes, int hint
     want = hint > n_links ? hint : n_links;
     pinned = true;
   }
-  int k = 16;
-  for (int w : kBraxWidths)
-    if (w >= want && brax_instantiated(w, multi, task)) {
-      k = w;
-      break;
-    }
+  int k = brax_width_from(c, want);
+  if (k == 0) k = 16;
   if (!pinned)
     while (k < 16 && ((long long)n_lanes + 64 / k - 1) / (64 / k) < 2048) {
-      int next = 16;
-      for (int w : kBraxWidths)
-        if (w > k && brax_instantiated(w, multi, task)) {
-          next = w;
-          break;
-        }
-      k = next;
+      const int next = brax_width_from(c, k + 1);
+      k = next == 0 ? 16 : next;
     }
   return k;
 }
@@ -203,12 +247,10 @@ int launch_brax(const carl_batch_t* b, const carl_brax_sys_t* sd, const carl_bra
                        const carl_step_io_t* io, const uint8_t* mask, float* reset_obs, int n_steps, hipStream_t st,
                        const char* who) {
   if (b->n_lanes == 0 || (MODE == 1 && n_steps == 0)) return 0;
-  const bool task = brax_is_task(sh);  // task models have a hinge-less last link: multi
-  const bool planar_model = brax_is_planar(sh);
-  const bool planar = MODE == 1 && !(b->flags & CARL_FLAG_BRAX_GENERIC) && planar_model;
-  // a planar model stepped by the general substep (CARL_FLAG_BRAX_GENERIC): its root's slides need the general kernels
-  const bool multi = brax_is_multi(sh) || (MODE == 1 && planar_model && !planar);
-  const int K = brax_lanes_per_env(sh->n_links, multi, task, b->n_lanes, sh->lanes_per_env);
+  const BraxClass c = brax_class(sh, b->flags, MODE == 1);
+  if (c.f32 && c.task)
+    return fail(CARL_ERR_UNSUPPORTED, "%s: CARL_FLAG_BRAX_FP32 is not built for the reach / push task models or anisotropic inertia", who);
+  const int K = brax_lanes_per_env(sh->n_links, c, b->n_lanes, sh->lanes_per_env);
   const int envs = carl::brax::kLanes / K;  // one wavefront = envs x K lanes; LDS rows are `envs` floats wide
   const carl::brax::Layout lay = carl::brax::layout_of(*sh);
   // independent wavefronts per workgroup, sharing the LDS copy of the static tables: as many (<= kMaxWavesPerWg) as fit
@@ -235,7 +277,7 @@ int launch_brax(const carl_batch_t* b, const carl_brax_sys_t* sd, const carl_bra
     if (hipGetDevice(&dev) == hipSuccess && hipDeviceGetAttribute(&v, hipDeviceAttributeMultiprocessorCount, dev) == hipSuccess && v > 0)
       n_cu = v;
   }
-  const int max_w = carl::brax::max_waves_per_wg(task);
+  const int max_w = carl::brax::max_waves_per_wg(c.task);
   const int n_groups = (b->n_lanes + envs - 1) / envs;
   int per_cu_of[16] = {0};
   int W = 1, best = 0;
@@ -244,8 +286,7 @@ int launch_brax(const carl_batch_t* b, const carl_brax_sys_t* sd, const carl_bra
     if (wg > 160 * 1024) break;
     if (w > 1 && (long long)(w - 1) * envs >= b->n_lanes) break;  // a small batch: no empty wavefronts
     int per_cu = (int)((160 * 1024) / wg) * w;                     // resident wavefronts per CU, LDS-wise
-    const int waves_per_eu = (MODE == 1 && (b->flags & CARL_FLAG_BRAX_FP32)) ? CARL_BRAX_WAVES_PER_EU_F32(task)
-                                                                              : CARL_BRAX_WAVES_PER_EU(task);
+    const int waves_per_eu = c.f32 ? CARL_BRAX_WAVES_PER_EU_F32(c.task) : CARL_BRAX_WAVES_PER_EU(c.task);
     if (per_cu > 4 * waves_per_eu) per_cu = 4 * waves_per_eu;
     per_cu -= per_cu % w;  // whole workgroups
     per_cu_of[w] = per_cu;
@@ -272,60 +313,9 @@ int launch_brax(const carl_batch_t* b, const carl_brax_sys_t* sd, const carl_bra
     }
   }
   const size_t sh_bytes = (size_t)W * wave_bytes;
-  using kern_t = void (*)(carl_batch_t, const carl_brax_sys_t*, carl::brax::Prepared, carl_step_io_t, const uint8_t*,
-                          float*, int);
-  kern_t kern = nullptr;
-#define CARL_PICK(KK, MM) \
-  if (!task && K == KK && multi == MM) kern = static_cast<kern_t>(carl::brax::brax_kernel<MODE, MM, KK>)
-#define CARL_PICK_TASK(KK) \
-  if (task && K == KK) kern = static_cast<kern_t>(carl::brax::brax_kernel<MODE, true, KK, true>)
-  CARL_PICK_TASK(4);
-  CARL_PICK_TASK(8);
-  CARL_PICK_TASK(16);
-  CARL_PICK(2, true);
-  CARL_PICK(11, true);
-  CARL_PICK(16, true);
-  CARL_PICK(4, false);
-  CARL_PICK(7, false);
-  CARL_PICK(8, false);
-  CARL_PICK(9, false);
-  CARL_PICK(16, false);
-  if constexpr (MODE == 1) {
-#define CARL_PICK_PLANAR(KK) \
-  if (planar && K == KK) kern = static_cast<kern_t>(carl::brax::brax_kernel<1, false, KK, false, true>)
-    CARL_PICK_PLANAR(4);
-    CARL_PICK_PLANAR(7);
-    CARL_PICK_PLANAR(8);
-    CARL_PICK_PLANAR(9);
-    CARL_PICK_PLANAR(16);
-#undef CARL_PICK_PLANAR
-    // CARL_FLAG_BRAX_FP32 (opt-in): the same kernels with the substeps' pose algebra in float32
-    if (b->flags & CARL_FLAG_BRAX_FP32) {
-      if (task) return fail(CARL_ERR_UNSUPPORTED, "%s: CARL_FLAG_BRAX_FP32 is not built for the reach / push task models or anisotropic inertia", who);
-      kern = nullptr;
-#define CARL_PICK_F32(KK, MM) \
-  if (!planar && K == KK && multi == MM) kern = static_cast<kern_t>(carl::brax::brax_kernel<1, MM, KK, false, false, true>)
-#define CARL_PICK_F32_PLANAR(KK) \
-  if (planar && K == KK) kern = static_cast<kern_t>(carl::brax::brax_kernel<1, false, KK, false, true, true>)
-      CARL_PICK_F32(2, true);
-      CARL_PICK_F32(11, true);
-      CARL_PICK_F32(16, true);
-      CARL_PICK_F32(4, false);
-      CARL_PICK_F32(7, false);
-      CARL_PICK_F32(8, false);
-      CARL_PICK_F32(9, false);
-      CARL_PICK_F32(16, false);
-      CARL_PICK_F32_PLANAR(4);
-      CARL_PICK_F32_PLANAR(7);
-      CARL_PICK_F32_PLANAR(8);
-      CARL_PICK_F32_PLANAR(9);
-      CARL_PICK_F32_PLANAR(16);
-#undef CARL_PICK_F32
-#undef CARL_PICK_F32_PLANAR
-    }
-  }
-#undef CARL_PICK
-#undef CARL_PICK_TASK
+  brax_kern_t kern = nullptr;
+  for (const BraxKernel& e : kBraxKernels)
+    if (same_class(e.c, c) && e.k == K) kern = MODE == 0 ? e.reset : e.step;
   if (kern == nullptr) return fail(CARL_ERR_UNSUPPORTED, "%s: no kernel for %d lanes per env", who, K);
   if (sh_bytes > 48 * 1024) {
     if (int e = carl_host::ensure_dynamic_lds(reinterpret_cast<const void*>(kern), sh_bytes, who)) return e;
@@ -421,10 +411,10 @@ int carl_brax_lane_widths(const carl_brax_sys_t* sys_host, uint32_t batch_flags,
   }
   // the kernels a STEP / ROLLOUT launch of such a batch takes (launch_brax<1>): a planar model stepped by the general
   // substep (CARL_FLAG_BRAX_GENERIC) runs the multi-hinge kernels, whose widths differ from the planar ones
-  const bool multi = brax_is_multi(sys_host) || (brax_is_planar(sys_host) && (batch_flags & CARL_FLAG_BRAX_GENERIC));
+  const BraxClass c = brax_class(sys_host, batch_flags, true);
   int n = 0;
-  for (int w : kBraxWidths)  // one lane per link or wider
-    if (w >= sys_host->n_links && brax_instantiated(w, multi, brax_is_task(sys_host)) && n < cap) widths_out[n++] = w;
+  for (int w = brax_width_from(c, sys_host->n_links); w != 0 && n < cap; w = brax_width_from(c, w + 1))
+    widths_out[n++] = w;  // one lane per link or wider
   return n;
 }
 

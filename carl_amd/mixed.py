@@ -205,24 +205,26 @@ class MixedVecEngine:
             return None
         if any(torch.is_tensor(a) and a.dtype in (torch.uint8, torch.float16, torch.bfloat16) for a in actions[:2]):
             return None  # the pair kernel reads int32 / float32 actions; narrow-format parts take their own launches
-        # What carl_rollout_pair declines (carl_amd.hip: pair_part_ok) is decided HERE, before any tensor is touched: an
-        # eligible family pair in a non-lean configuration (round-robin / random selector, int64 actions, terminal
-        # observations, a finished-episode log, rows whose pitch is not a multiple of 16 lanes) used to convert both action
-        # tensors and allocate full [T, N, ...] outputs on every call only to hear UNSUPPORTED and do it all again in the
-        # per-part path.
+        # What carl_rollout_pair declines is decided HERE, before any tensor is touched: an eligible family pair in a
+        # non-lean configuration (round-robin / random selector, int64 actions, terminal observations, a finished-episode
+        # log, rows that do not take the staged kernel) used to convert both action tensors and allocate full [T, N, ...]
+        # outputs on every call only to hear UNSUPPORTED and do it all again in the per-part path.  Which
+        # kernel the rows take is the library's answer for a probe of the launch's pitch and output arrays.
         fams = {pa.family, pb.family}
         if fams - set(range(_lib.CARL_N_FAMILIES)) or _lib.ACROBOT not in fams or pa.family == pb.family or \
                 any(p.family == _lib.ACROBOT and (p.b.flags & _lib.FLAG_ACROBOT_FP32) for p in self.parts):
             self._pair_ok = False  # never eligible: stop asking
             return None
         for k, p in enumerate(self.parts):
-            a = actions[k]
-            pitch = p._row_pitch() if outs is None else max(p.n, int(outs[k]["reward"].stride(0)))  # (engine.py: _rollout_io)
-            lean = (p.b.selector in (_lib.SEL_STATIC, _lib.SEL_HOST) and not p._takes_direct_kernel(pitch) and p.fin_capacity == 0
-                    and not (p.b.flags & _lib.FLAG_ROLLOUT_DIRECT)
-                    and not (torch.is_tensor(a) and a.dtype == torch.int64)
-                    and not (outs is not None and outs[k].get("final_obs") is not None))
-            if not lean:
+            a, out = actions[k], None if outs is None else outs[k]
+            probe = _lib.StepIO()
+            probe.row_pitch = p._row_pitch() if out is None else max(p.n, int(out["reward"].stride(0)))  # (engine.py: _rollout_io)
+            for name in () if out is None else ("obs", "reward", "terminated", "truncated"):
+                setattr(probe, name, out[name].data_ptr())
+            if (p.b.selector not in (_lib.SEL_STATIC, _lib.SEL_HOST) or p.fin_capacity != 0
+                    or (torch.is_tensor(a) and a.dtype == torch.int64)
+                    or (out is not None and out.get("final_obs") is not None)
+                    or p.lib.carl_rollout_variant_io(C.byref(p.b), C.byref(probe)) != _lib.ROLLOUT_STAGED):
                 return None
         aa, dta = pa._action_tensor(actions[0], (T,))
         ab, dtb = pb._action_tensor(actions[1], (T,))

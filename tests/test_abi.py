@@ -183,6 +183,15 @@ def test_brax_and_sampler_entry_points_validate_arguments():
     cb.flags = _lib.FLAG_ROLLOUT_DIRECT
     io.row_pitch = 65552
     assert lib.carl_rollout_variant_io(C.byref(cb), C.byref(io)) == _lib.ROLLOUT_DIRECT_FLAG
+    # every array must start on a 16-byte boundary (a column view one lane in does not); the actions on the boundary of
+    # one load of the loader wave: 16 bytes (int32 / int64 / float32), 4 (uint8)
+    cb.flags, cb.n_lanes, io.row_pitch = 0, 1024, 1040
+    io.reward = 4096 + 4
+    assert lib.carl_rollout_variant_io(C.byref(cb), C.byref(io)) == _lib.ROLLOUT_DIRECT_SHAPE
+    io.reward, io.action = 4096, 8192 + 4
+    assert lib.carl_rollout_variant_io(C.byref(cb), C.byref(io)) == _lib.ROLLOUT_DIRECT_SHAPE
+    io.action_dtype = _lib.ACTION_U8
+    assert lib.carl_rollout_variant_io(C.byref(cb), C.byref(io)) == _lib.ROLLOUT_STAGED
     spec = (_lib.FeatureSpec * 1)()
     spec[0].kind = 99
     assert lib.carl_sample_contexts(C.addressof(spec), spec, 1, 4, 4, 0, 0, 1, None) == -1  # table "pointer" 1, kind 99

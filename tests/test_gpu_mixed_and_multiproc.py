@@ -548,6 +548,42 @@ def test_small_brax_parts_side_by_side_equal_back_to_back(device):
     assert float(after) == float(o2[0]["reward"].sum() + o2[1]["reward"].sum())
 
 
+def test_mixed_batch_with_a_misaligned_output_view_takes_separate_launches_same_results(device):
+    """An output array that does not start on a 16-byte boundary (a column view one lane in) takes the direct-store kernel,
+    which the pair launch does not have: the pair pre-check asks the library (carl_rollout_variant_io) for the caller's
+    arrays and launches the parts one after the other, with one warning and the transitions of the pair launch."""
+    from carl_amd.engine import VecEngine
+    from carl_amd.mixed import MixedVecEngine
+
+    dev = device
+    rng = np.random.default_rng(9)
+    n, T, P = 1024, 19, 1040
+
+    def build():
+        parts = []
+        for fam in (O.ACROBOT, O.MOUNTAINCAR):
+            t = np.tile(O.default_row(fam), (n, 1))
+            parts.append(VecEngine(fam, t, n, dev, selector=O.SEL_STATIC, seed=2, ctx_idx0=np.arange(n)))
+        m = MixedVecEngine(parts)
+        m.reset()
+        return m
+
+    def view(p, shift):
+        return {"obs": torch.zeros((T, P, p.D), device=dev)[:, :n], "reward": torch.zeros((T, P), device=dev)[:, shift:n + shift],
+                "terminated": torch.zeros((T, P), dtype=torch.uint8, device=dev)[:, :n],
+                "truncated": torch.zeros((T, P), dtype=torch.uint8, device=dev)[:, :n]}
+
+    mv, ma = build(), build()
+    acts = [torch.as_tensor(rng.integers(0, 3, (T, n)).astype(np.int32), device=dev) for _ in range(2)]
+    with pytest.warns(RuntimeWarning, match="16-byte boundary"):
+        ov = mv.rollout(acts, [view(mv.parts[0], 0), view(mv.parts[1], 1)])
+    oa = ma.rollout(acts)
+    assert mv.pair_launches == 0 and ma.pair_launches == 1
+    for pv, pa in zip(ov, oa):
+        for k in ("obs", "reward", "terminated", "truncated"):
+            assert torch.equal(pv[k], pa[k]), k
+
+
 def test_mixed_batch_with_uint8_actions_takes_separate_launches_same_results(device):
     """uint8 actions (ABI 7) are read by the single-family lean rollout; the heterogeneous pair kernel reads int32 --
     a mixed batch fed uint8 launches its parts one after the other, with the transitions of the int32 pair launch."""

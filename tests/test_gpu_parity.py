@@ -922,6 +922,26 @@ def test_rollout_variant_is_visible_and_odd_lane_counts_take_the_staged_kernel(d
         want_a, want_b = ra.rollout(acts_a), rb.rollout(acts_b)
         for k in ("obs", "reward", "terminated", "truncated"):
             assert torch.equal(wide[k][:, :n_a], want_a[k]) and torch.equal(wide[k][:, n_a:], want_b[k]), (n_a, k)
+    # a reward array that does not start on a 16-byte boundary (a column view one lane in; rows of 1 040 lanes) takes the
+    # direct-store kernel: one warning over two launches, the aligned launches' results
+    fam, n, P = O.PENDULUM, 1024, 1040
+    tab = random_table(fam, rng, n)
+    acts_u = torch.as_tensor(random_actions(fam, rng, (2, T, n)), device=device)
+    u = _engine(fam, tab, n, device, selector=O.SEL_STATIC, seed=4, ctx_idx0=np.arange(n))
+    r = _engine(fam, tab, n, device, selector=O.SEL_STATIC, seed=4, ctx_idx0=np.arange(n))
+    u.reset()
+    r.reset()
+    view = {"obs": torch.zeros((T, P, 3), device=device)[:, :n], "reward": torch.zeros((T, P), device=device)[:, 1:n + 1],
+            "terminated": torch.zeros((T, P), dtype=torch.uint8, device=device)[:, :n],
+            "truncated": torch.zeros((T, P), dtype=torch.uint8, device=device)[:, :n]}
+    for q in range(2):
+        with warnings.catch_warnings(record=True) as caught:
+            warnings.simplefilter("always")
+            u.rollout(acts_u[q], view)
+        assert [w.category for w in caught] == ([RuntimeWarning] if q == 0 else []), caught
+        want = r.rollout(acts_u[q])
+        for k in ("obs", "reward", "terminated", "truncated"):
+            assert torch.equal(view[k], want[k]), (q, k)
     # buffers whose arrays disagree about the pitch are refused
     bad = e.alloc_rollout(T)
     bad["reward"] = torch.empty((T, n), device=device)
