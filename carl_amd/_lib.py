@@ -236,3 +236,29 @@ EXPORTS.update({
                                        C.c_uint64, _vp, _vp]),
     "carl_verify_contexts": (C.c_int, [_vp, C.POINTER(FeatureSpec), C.c_int32, C.c_int32, C.c_int32, _vp, _vp, _vp]),
 })
+
+
+# ---- closed-loop rollout: a policy network on the device (include/carl_amd.h: carl_policy_t) ------------------
+POLICY_MAX_IN, POLICY_MAX_HIDDEN, POLICY_MAX_WIDTH = 32, 2, 64
+POLICY_IDENTITY, POLICY_TANH, POLICY_RELU = range(3)
+POLICY_HEAD_ARGMAX, POLICY_HEAD_BOX = range(2)
+
+
+class Policy(C.Structure):
+    _fields_ = [
+        ("n_in", _i), ("n_ctx", _i), ("ctx_rows", _i * POLICY_MAX_IN), ("n_hidden", _i),
+        ("width", _i * POLICY_MAX_HIDDEN), ("n_out", _i), ("activation", _i), ("head", _i), ("n_sets", _i),
+        ("lanes_per_set", _i), ("reserved", _i), ("params", _vp),
+    ]
+
+
+class PolicySummary(C.Structure):
+    _fields_ = [("episodes", _vp), ("return_sum", _vp), ("length_sum", _vp)]
+
+
+EXPORTS.update({
+    "carl_rollout_policy": (C.c_int, [C.POINTER(Batch), C.POINTER(Policy), C.POINTER(StepIO), C.c_int32,
+                                      C.POINTER(PolicySummary), _vp]),
+    "carl_policy_lane_quantum": (C.c_int32, []),
+    "carl_policy_set_floats": (C.c_int32, [C.POINTER(Policy)]),
+})

@@ -29,6 +29,7 @@ class _BraxInfo:
 
 class BraxVecEngine(VecEngine):
     _narrow_actions = False  # carl_brax_step / carl_brax_rollout read float32 actions: narrower dtypes are widened here
+    _policy_rollout = False  # the closed-loop rollout (VecEngine.rollout_policy) is classic-control only
 
     def __init__(self, sys_table: _lib.BraxSys, n_features: int, ctx_table, n_lanes: int, device="cuda", *,
                  autoreset_mode: str = "redraw", **kw):

@@ -1,0 +1,196 @@
+// carl_policy.hip -- C-ABI entry points of the closed-loop rollout (include/carl_amd.h: carl_rollout_policy) and their
+// kernel dispatch.  A translation unit of its own: the kernels (policy_kernels.hip.h) instantiate the engine's device
+// templates anew, and the open-loop kernels of carl_amd.hip compile exactly as they did without them.
+#include <hip/hip_runtime.h>
+
+#include <cstdint>
+
+#include "../../include/carl_amd.h"
+#include "classic_control.hip.h"
+#include "host_common.hpp"
+#include "policy_kernels.hip.h"
+
+namespace {
+
+using carl_host::check_launch;
+using carl_host::fail;
+
+// floats of one packed weight set (include/carl_amd.h), or -1 for a shape outside the limits
+int set_floats_of(const carl_policy_t* p) {
+  if (p->n_in < 1 || p->n_in > CARL_POLICY_MAX_IN || p->n_out < 1 || p->n_out > 4 || p->n_hidden < 0 ||
+      p->n_hidden > CARL_POLICY_MAX_HIDDEN)
+    return -1;
+  int64_t total = 0, prev = p->n_in;
+  for (int l = 0; l <= p->n_hidden; ++l) {
+    const int64_t w = l < p->n_hidden ? p->width[l] : p->n_out;
+    if (l < p->n_hidden && (w < 1 || w > CARL_POLICY_MAX_WIDTH)) return -1;
+    total += w * prev + w;
+    prev = w;
+  }
+  total += 2 * (int64_t)p->n_in + 1;
+  return (int)((total + 3) / 4 * 4);
+}
+
+int validate_policy(const carl_batch_t* b, const carl_policy_t* p, const carl_family_info_t& fi) {
+  const char* who = "carl_rollout_policy";
+  if (p->n_hidden < 0 || p->n_hidden > CARL_POLICY_MAX_HIDDEN)
+    return fail(CARL_ERR_INVALID_ARGUMENT, "%s: n_hidden %d outside [0, %d]", who, p->n_hidden, CARL_POLICY_MAX_HIDDEN);
+  for (int l = 0; l < p->n_hidden; ++l)
+    if (p->width[l] < 1 || p->width[l] > CARL_POLICY_MAX_WIDTH)
+      return fail(CARL_ERR_INVALID_ARGUMENT, "%s: hidden width[%d] = %d outside [1, %d]", who, l, p->width[l],
+                  CARL_POLICY_MAX_WIDTH);
+  if (p->n_ctx < 0 || p->n_ctx > fi.n_features)
+    return fail(CARL_ERR_INVALID_ARGUMENT, "%s: n_ctx %d outside [0, F = %d]", who, p->n_ctx, fi.n_features);
+  for (int k = 0; k < p->n_ctx; ++k)
+    if (p->ctx_rows[k] < 0 || p->ctx_rows[k] >= fi.n_features)
+      return fail(CARL_ERR_INVALID_ARGUMENT, "%s: ctx_rows[%d] = %d is not a context-table row (F = %d)", who, k,
+                  p->ctx_rows[k], fi.n_features);
+  if (p->n_in != p->n_ctx + fi.obs_dim)
+    return fail(CARL_ERR_INVALID_ARGUMENT, "%s: n_in %d != n_ctx %d + obs_dim %d", who, p->n_in, p->n_ctx, fi.obs_dim);
+  const int want_out = fi.action_is_discrete ? fi.n_actions : 1;
+  if (p->n_out != want_out)
+    return fail(CARL_ERR_INVALID_ARGUMENT, "%s: head width %d, the family needs %d (%s)", who, p->n_out, want_out,
+                fi.action_is_discrete ? "n_actions" : "one Box value");
+  if (p->head != (fi.action_is_discrete ? CARL_POLICY_HEAD_ARGMAX : CARL_POLICY_HEAD_BOX))
+    return fail(CARL_ERR_INVALID_ARGUMENT, "%s: head kind %d does not match the family's action space", who, p->head);
+  if (p->activation < CARL_POLICY_IDENTITY || p->activation > CARL_POLICY_RELU)
+    return fail(CARL_ERR_INVALID_ARGUMENT, "%s: unknown activation %d", who, p->activation);
+  if (p->n_sets < 1) return fail(CARL_ERR_INVALID_ARGUMENT, "%s: n_sets %d < 1", who, p->n_sets);
+  if (p->lanes_per_set < carl::kPolicyLanes || p->lanes_per_set % carl::kPolicyLanes != 0)
+    return fail(CARL_ERR_INVALID_ARGUMENT, "%s: lanes_per_set %d is not a positive multiple of %d (carl_policy_lane_quantum)",
+                who, p->lanes_per_set, carl::kPolicyLanes);
+  if ((int64_t)p->n_sets * p->lanes_per_set < b->n_lanes)
+    return fail(CARL_ERR_INVALID_ARGUMENT, "%s: %d sets x %d lanes do not cover %d lanes", who, p->n_sets,
+                p->lanes_per_set, b->n_lanes);
+  if (p->params == nullptr) return fail(CARL_ERR_INVALID_ARGUMENT, "%s: params is NULL", who);
+  return 0;
+}
+
+int validate_batch(const carl_batch_t* b) {
+  const char* who = "carl_rollout_policy";
+  if (b->n_lanes < 0) return fail(CARL_ERR_INVALID_ARGUMENT, "%s: n_lanes %d < 0", who, b->n_lanes);
+  if (b->n_contexts <= 0 || b->ctx_stride < b->n_contexts)
+    return fail(CARL_ERR_INVALID_ARGUMENT, "%s: n_contexts %d / ctx_stride %d invalid", who, b->n_contexts, b->ctx_stride);
+  if (b->selector < CARL_SEL_STATIC || b->selector > CARL_SEL_HOST)
+    return fail(CARL_ERR_INVALID_ARGUMENT, "%s: unknown selector %d", who, b->selector);
+  if (!b->state || !b->elapsed || !b->ctx_idx || !b->episode || !b->n_calls || !b->ep_return || !b->ctx_table)
+    return fail(CARL_ERR_INVALID_ARGUMENT, "%s: a required batch pointer is NULL", who);
+  if (b->n_ctx_obs < 0 || b->n_ctx_obs > CARL_MAX_CTX_OBS || (b->n_ctx_obs > 0 && b->ctx_obs == nullptr))
+    return fail(CARL_ERR_INVALID_ARGUMENT, "%s: n_ctx_obs %d / ctx_obs invalid", who, b->n_ctx_obs);
+  if (b->fin_count != nullptr && (b->fin_capacity <= 0 || !b->fin_lane || !b->fin_return || !b->fin_length))
+    return fail(CARL_ERR_INVALID_ARGUMENT, "%s: finished-episode log is incomplete", who);
+  return 0;
+}
+
+// transitions mode: the staged layout of carl_rollout (see include/carl_amd.h: carl_step_io_t::row_pitch)
+int validate_io(const carl_batch_t* b, const carl_step_io_t* io, const carl_family_info_t& fi) {
+  const char* who = "carl_rollout_policy";
+  if (!io->action || !io->obs || !io->reward || !io->terminated || !io->truncated)
+    return fail(CARL_ERR_INVALID_ARGUMENT, "%s: a required io pointer is NULL", who);
+  const int want = fi.action_is_discrete ? CARL_ACTION_I32 : CARL_ACTION_F32;
+  if (io->action_dtype != want)
+    return fail(CARL_ERR_INVALID_ARGUMENT, "%s: the action column is %s for this family", who,
+                fi.action_is_discrete ? "int32 (CARL_ACTION_I32)" : "float32 (CARL_ACTION_F32)");
+  if (io->row_pitch != 0 && io->row_pitch < b->n_lanes)
+    return fail(CARL_ERR_INVALID_ARGUMENT, "%s: io.row_pitch %d < n_lanes %d", who, io->row_pitch, b->n_lanes);
+  const int pitch = io->row_pitch > 0 ? io->row_pitch : b->n_lanes, n16 = (b->n_lanes + 15) / 16 * 16;
+  const uintptr_t bits = reinterpret_cast<uintptr_t>(io->obs) | reinterpret_cast<uintptr_t>(io->reward) |
+                         reinterpret_cast<uintptr_t>(io->terminated) | reinterpret_cast<uintptr_t>(io->truncated) |
+                         reinterpret_cast<uintptr_t>(io->final_obs) | reinterpret_cast<uintptr_t>(io->action);
+  if ((bits & 15) != 0 || pitch % 16 != 0 || !(b->n_lanes % 16 == 0 || pitch == n16))
+    return fail(CARL_ERR_UNSUPPORTED, "%s: rows of %d lanes for %d lanes: the closed-loop rollout writes the staged layout "
+                "only (pitch %% 16 == 0 and n_lanes %% 16 == 0 or pitch == carl_rollout_pitch(n_lanes), arrays on 16-byte "
+                "boundaries)", who, pitch, b->n_lanes);
+  return 0;
+}
+
+using policy_kern_t = void (*)(carl_batch_t, carl_step_io_t, carl_policy_t, int, carl_policy_summary_t, int);
+
+template <class Fam, int H>
+policy_kern_t pick(bool summary) {
+  return summary ? carl::policy_rollout_kernel<Fam, H, true> : carl::policy_rollout_kernel<Fam, H, false>;
+}
+
+template <class Fam>
+int launch_policy(const carl_batch_t* b, const carl_policy_t* p, const carl_step_io_t* io, int n_steps,
+                  const carl_policy_summary_t* sum, hipStream_t s) {
+  const bool summary = io == nullptr;
+  int wmax = 0;
+  for (int l = 0; l < p->n_hidden; ++l) wmax = wmax > p->width[l] ? wmax : p->width[l];
+  // the hidden width is padded to an instantiated class: 0 (a linear policy), 32, 64
+  const int H = p->n_hidden == 0 ? 0 : wmax <= 32 ? 32 : 64;
+  policy_kern_t kern = H == 0 ? pick<Fam, 0>(summary) : H == 32 ? pick<Fam, 32>(summary) : pick<Fam, 64>(summary);
+  const size_t lds = H == 0 ? (summary ? carl::policy_lds_bytes<Fam, 0, true>() : carl::policy_lds_bytes<Fam, 0, false>())
+                     : H == 32 ? (summary ? carl::policy_lds_bytes<Fam, 32, true>() : carl::policy_lds_bytes<Fam, 32, false>())
+                               : (summary ? carl::policy_lds_bytes<Fam, 64, true>() : carl::policy_lds_bytes<Fam, 64, false>());
+  static_assert(carl::policy_lds_bytes<Fam, 64, false>() + carl::policy_static_lds<Fam>() <= 160 * 1024,
+                "the closed-loop rollout's LDS does not fit a compute unit");
+  if (int e = carl_host::ensure_dynamic_lds(reinterpret_cast<const void*>(kern), lds, "carl_rollout_policy")) return e;
+  carl_step_io_t io_r{};
+  if (!summary) {
+    io_r = *io;
+    io_r.row_pitch = io->row_pitch > 0 ? io->row_pitch : b->n_lanes;  // the kernel reads the pitch as given: never 0
+  }
+  const carl_policy_summary_t sum_r = sum != nullptr ? *sum : carl_policy_summary_t{nullptr, nullptr, nullptr};
+  const int grid = (b->n_lanes + carl::kPolicyLanes - 1) / carl::kPolicyLanes;
+  const int threads = summary ? carl::kPolicyThreadsSummary : carl::kPolicyThreadsTransitions;
+  hipLaunchKernelGGL(kern, dim3(grid), dim3(threads), lds, s, *b, io_r, *p, set_floats_of(p), sum_r, n_steps);
+  return check_launch("carl_rollout_policy");
+}
+
+}  // namespace
+
+extern "C" {
+
+int32_t carl_policy_lane_quantum(void) { return carl::kPolicyLanes; }
+
+int32_t carl_policy_set_floats(const carl_policy_t* policy_host) {
+  if (policy_host == nullptr) return -1;
+  return set_floats_of(policy_host);
+}
+
+int carl_rollout_policy(const carl_batch_t* batch, const carl_policy_t* policy_host, const carl_step_io_t* io,
+                        int32_t n_steps, const carl_policy_summary_t* summary_out, void* stream) {
+  if (batch == nullptr || policy_host == nullptr)
+    return fail(CARL_ERR_INVALID_ARGUMENT, "carl_rollout_policy: batch / policy is NULL");
+  if (batch->family >= CARL_N_FAMILIES)
+    return fail(CARL_ERR_INVALID_ARGUMENT, "carl_rollout_policy: family %d is a Brax family -- the closed-loop rollout "
+                "covers the classic-control families only", batch->family);
+  carl_family_info_t fi;
+  if (int e = carl_family_info(batch->family, &fi)) return e;
+  if (int e = validate_batch(batch)) return e;
+  if (int e = validate_policy(batch, policy_host, fi)) return e;
+  if (n_steps < 0) return fail(CARL_ERR_INVALID_ARGUMENT, "carl_rollout_policy: n_steps %d < 0", n_steps);
+  if (io == nullptr) {
+    if (summary_out == nullptr || !summary_out->episodes || !summary_out->return_sum || !summary_out->length_sum)
+      return fail(CARL_ERR_INVALID_ARGUMENT, "carl_rollout_policy: summary mode (io NULL) needs all three summary arrays");
+  } else {
+    if (int e = validate_io(batch, io, fi)) return e;
+    if (summary_out != nullptr && (!summary_out->episodes || !summary_out->return_sum || !summary_out->length_sum))
+      return fail(CARL_ERR_INVALID_ARGUMENT, "carl_rollout_policy: a summary needs all three arrays");
+  }
+  if (batch->n_lanes == 0 || n_steps == 0) {
+    if (summary_out == nullptr || batch->n_lanes == 0) return 0;
+    // no step: every total is zero
+    hipStream_t s = (hipStream_t)stream;
+    const size_t bytes = (size_t)batch->n_lanes * 4;
+    for (void* p : {(void*)summary_out->episodes, (void*)summary_out->return_sum, (void*)summary_out->length_sum})
+      if (const hipError_t e = hipMemsetAsync(p, 0, bytes, s); e != hipSuccess)
+        return fail((int)e, "carl_rollout_policy: hipMemsetAsync: %s", hipGetErrorString(e));
+    return 0;
+  }
+  hipStream_t s = (hipStream_t)stream;
+  switch (batch->family) {
+    case CARL_CARTPOLE: return launch_policy<carl::CartPole>(batch, policy_host, io, n_steps, summary_out, s);
+    case CARL_PENDULUM: return launch_policy<carl::Pendulum>(batch, policy_host, io, n_steps, summary_out, s);
+    case CARL_ACROBOT:
+      return (batch->flags & CARL_FLAG_ACROBOT_FP32)
+                 ? launch_policy<carl::AcrobotFast>(batch, policy_host, io, n_steps, summary_out, s)
+                 : launch_policy<carl::Acrobot>(batch, policy_host, io, n_steps, summary_out, s);
+    case CARL_MOUNTAINCAR: return launch_policy<carl::MountainCar>(batch, policy_host, io, n_steps, summary_out, s);
+    case CARL_MOUNTAINCAR_CONT: return launch_policy<carl::MountainCarCont>(batch, policy_host, io, n_steps, summary_out, s);
+    default: return fail(CARL_ERR_INVALID_ARGUMENT, "carl_rollout_policy: unknown family %d", batch->family);
+  }
+}
+
+}  // extern "C"

@@ -589,6 +589,89 @@ class VecEngine:
         buf[:, self.n:] = rows[:, self.n - 1:]
         return buf
 
+    # ------------------------------------------------------------------ closed loop (carl_amd/policy.py)
+    _policy_rollout = True  # (the classic-control families; BraxVecEngine turns it off)
+
+    def alloc_policy_summary(self) -> dict:
+        """Per-lane totals of a summary-mode ``rollout_policy``: ``episodes`` / ``length_sum`` int32, ``return_sum``
+        float32, ``[N]`` each."""
+        z = lambda dt: torch.zeros(self.n, dtype=dt, device=self.device)  # noqa: E731
+        return {"episodes": z(torch.int32), "return_sum": z(torch.float32), "length_sum": z(torch.int32)}
+
+    def rollout_policy(self, policy, n_steps: int, out: dict | None = None, mode: str = "transitions",
+                       final_obs: bool = False) -> dict:
+        """``n_steps`` steps in ONE launch, each lane's action chosen on the device by ``policy`` (``carl_amd.policy.
+        MLPPolicy``) from the lane's current context and observation -- closed loop, where ``rollout`` replays actions
+        written beforehand.
+        ``mode="transitions"``: ``rollout``'s dict (``alloc_rollout`` layout; ``final_obs=True`` adds the terminal
+        observations) plus ``"action"`` ``[T, N]`` (int32 / float32): the action each step took -- ``rollout`` of those
+        actions from the same engine state gives the same bits.  ``mode="summary"``: no per-step output at all; returns
+        ``{"episodes", "return_sum", "length_sum"}`` per lane (episodes finished in the launch, the float32 sum of their
+        returns in step order, the sum of their lengths).  Either way the engine state advances exactly as in
+        ``rollout``.  No host synchronisation (the policy's parameters are uploaded on its first use on a device)."""
+        if not self._policy_rollout:
+            raise NotImplementedError(f"{type(self).__name__}: the closed-loop rollout covers the classic-control "
+                                      "families only")
+        if policy.family != self.family or policy.obs_dim != self.D:
+            raise ValueError(f"the policy was built for family {policy.family}, this engine runs family {self.family}")
+        T = int(n_steps)
+        params = policy.device_params(self.device)
+        pol = policy.struct(self.n, params.data_ptr())
+        if mode == "summary":
+            if final_obs:
+                raise ValueError("final_obs: transitions mode only (a summary launch stores nothing per step)")
+            res = self.alloc_policy_summary() if out is None else out
+            for k in ("episodes", "return_sum", "length_sum"):
+                t = res[k]
+                if t.device != self.device or not t.is_contiguous() or t.numel() != self.n or t.element_size() != 4:
+                    raise ValueError(f"summary output '{k}' must be a contiguous 4-byte [{self.n}] tensor on {self.device}")
+            summ = _lib.PolicySummary(_ptr(res["episodes"]), _ptr(res["return_sum"]), _ptr(res["length_sum"]))
+            with torch.cuda.device(self.device):
+                _lib.check(self.lib.carl_rollout_policy(self._b_ref, C.byref(pol), None, T, C.byref(summ), self._stream()))
+            return res
+        if mode != "transitions":
+            raise ValueError(f"mode {mode!r}: 'transitions' or 'summary'")
+        if out is None:
+            out = self.alloc_rollout(T, final_obs=final_obs)
+            P = int(out["reward"].stride(0)) if out["reward"].dim() == 2 else self.n
+            adt = torch.int32 if self.info.action_is_discrete else torch.float32
+            full = torch.empty((T, max(P, self.n)), dtype=adt, device=self.device)
+            out["action"] = full if full.shape[1] == self.n else full[:, : self.n]
+        io = self._policy_io(out, T)
+        with torch.cuda.device(self.device):
+            _lib.check(self.lib.carl_rollout_policy(self._b_ref, C.byref(pol), C.byref(io), T, None, self._stream()))
+        return out
+
+    def _policy_io(self, out: dict, T: int) -> "_lib.StepIO":
+        """``carl_step_io_t`` of a transitions-mode ``rollout_policy``: every ``[T, N(, D)]`` array, the action column
+        included, must be rows of one common pitch (``alloc_rollout``'s layout)."""
+        if "action" not in out:
+            raise ValueError("rollout_policy output needs an 'action' [T, N] buffer")
+        n, D = self.n, self.D
+        P = max(n, int(out["reward"].stride(0))) if out["reward"].dim() == 2 else n
+        adt = torch.int32 if self.info.action_is_discrete else torch.float32
+        if out["action"].dtype != adt:
+            raise ValueError(f"rollout_policy 'action' buffer must be {adt} for this family")
+        for k, tail in (("obs", (D,)), ("reward", ()), ("terminated", ()), ("truncated", ()), ("final_obs", (D,)),
+                        ("action", ())):
+            t = out.get(k)
+            if t is None:
+                continue
+            inner = int(np.prod(tail, dtype=np.int64)) if tail else 1
+            want = (P * inner, inner, 1) if tail else (P, 1)
+            if t.shape[0] < T or tuple(t.shape[1:]) != (n,) + tail or t.device != self.device or any(
+                    sz > 1 and st != w for sz, st, w in zip(t.shape, t.stride(), want)):
+                raise ValueError(f"rollout_policy output '{k}': shape {tuple(t.shape)} / strides {tuple(t.stride())} do "
+                                 f"not form [>= {T}, {n}{', ' + str(D) if tail else ''}] rows of one common pitch ({P} lanes)")
+        io = _lib.StepIO()
+        io.row_pitch = P if P != n else 0
+        io.action = _ptr(out["action"])
+        io.action_dtype = _lib.ACTION_I32 if self.info.action_is_discrete else _lib.ACTION_F32
+        io.obs, io.reward = _ptr(out["obs"]), _ptr(out["reward"])
+        io.terminated, io.truncated = _ptr(out["terminated"]), _ptr(out["truncated"])
+        io.final_obs = _ptr(out.get("final_obs"))
+        return io
+
     def rollout_variant(self) -> int:
         """Which kernel ``rollout`` launches for this batch into ``alloc_rollout``'s buffers: ``_lib.ROLLOUT_STAGED``
         (fast path: rows of a pitch that is a multiple of 16 -- any lane count since round 6), ``ROLLOUT_DIRECT_FLAG``

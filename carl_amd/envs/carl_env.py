@@ -312,6 +312,13 @@ class CARLEnv(abc.ABC):
         obs = {"obs": c["obs"]["obs"], "context": dict(ctx) if isinstance(ctx, dict) else ctx}
         return obs, reward, c["term"], c["trunc"], info
 
+    def rollout_policy(self, policy, n_steps: int, out: dict | None = None, mode: str = "transitions",
+                       final_obs: bool = False) -> dict:
+        """``n_steps`` closed-loop steps of every lane in one launch, actions chosen on the device by ``policy``
+        (``carl_amd.policy.MLPPolicy.for_env(self, ...)``): ``VecEngine.rollout_policy`` of this env's engine.  The
+        engine's outputs (``step``'s views) are not touched; the host selector object is not consulted."""
+        return self.env.rollout_policy(policy, n_steps, out=out, mode=mode, final_obs=final_obs)
+
     def _views(self) -> dict:
         eng = self.env
         key = (eng.obs.data_ptr(), eng.ctx_obs.data_ptr(), eng.ctx_idx.data_ptr(), eng.terminated.data_ptr(),

@@ -126,6 +126,11 @@ class MixedVecEngine:
     def _small_brax_parts(self) -> bool:
         return len(self.parts) > 1 and all(hasattr(p, "sys") and p.n <= self.SMALL_BRAX_PART for p in self.parts)
 
+    def rollout_policy(self, *args, **kwargs):
+        """Out of scope: run ``VecEngine.rollout_policy`` on each part's engine instead (one launch per family)."""
+        raise NotImplementedError("MixedVecEngine: the closed-loop rollout has no pair launch; call rollout_policy on "
+                                  "each part's engine")
+
     def rollout(self, actions: Sequence, outs: Sequence[dict] | None = None, *, free_running: bool = False,
                 overlap: bool | None = None) -> list[dict]:
         """T fused steps of every family; ``actions[k]`` is part k's ``[T, n_k(, A_k)]``.

@@ -1,0 +1,221 @@
+"""A small fp32 MLP evaluated on the device inside the fused rollout (include/carl_amd.h: carl_rollout_policy).
+
+``MLPPolicy`` holds the weights of one policy -- or of several with the same shape (``stack``) -- in the packed layout
+the kernel reads, plus the context rows its input starts with.  Its input is what ``FlattenObservation(env)`` gives a
+trained agent (the reference's examples/carl_with_sb3.py): gymnasium's ``Dict`` space orders its keys, so "context"
+comes before "obs", and inside the context part the feature names are sorted when ``obs_context_as_dict`` is set and
+in ``obs_context_features`` order otherwise.  ``VecEngine.rollout_policy`` / ``CARLEnv.rollout_policy`` run it.
+
+Packed layout of one weight set (float32): for every layer in order -- the hidden layers, then the head -- ``W[out][in]``
+row-major followed by ``b[out]``; then ``shift[n_in]``, ``scale[n_in]`` and one ``clip``; zero padding to a multiple of
+four floats.  The kernel computes ``x = clip((x - shift) * scale, -clip, clip)`` (SB3's ``VecNormalize`` with
+``scale = 1 / sqrt(var + eps)``), ``h = act(W h + b)`` per hidden layer and a linear head; discrete families take the
+first index of the largest head output, Box families the head output itself (the env clips it as usual).
+
+Out of scope: the Brax families, ``MixedVecEngine`` pairs, the gymnasium drop-in (``carl_amd.dropin``) and the
+multi-process helpers (``carl_amd.distributed``).
+"""
+from __future__ import annotations
+
+import ctypes as C
+from typing import Sequence
+
+import numpy as np
+import torch
+
+from carl_amd import _lib
+
+_ACTIVATIONS = {"identity": _lib.POLICY_IDENTITY, "tanh": _lib.POLICY_TANH, "relu": _lib.POLICY_RELU}
+
+
+def _engine_of(env):
+    """(VecEngine, CARLEnv or None) of what the caller passes; refuses the out-of-scope engines."""
+    from carl_amd.engine import VecEngine
+
+    carl_env = None
+    eng = env
+    if not isinstance(env, VecEngine) and isinstance(getattr(env, "env", None), VecEngine):
+        carl_env, eng = env, env.env
+    if not isinstance(eng, VecEngine):
+        raise TypeError(f"MLPPolicy: {type(env).__name__} is not a classic-control CARLEnv or VecEngine (MixedVecEngine "
+                        "pairs, the gymnasium drop-in and the distributed helpers are out of scope of the closed-loop rollout)")
+    if not getattr(eng, "_policy_rollout", False):
+        raise TypeError(f"MLPPolicy: the closed-loop rollout covers the classic-control families only, not "
+                        f"{type(eng).__name__}")
+    return eng, carl_env
+
+
+def flattened_context_rows(env, features: Sequence | None = None) -> tuple[list[int], list]:
+    """Context-table rows (and their names, or rows for a bare engine) of the context part of ``FlattenObservation(env)``,
+    in its order.  ``features``: a subset to use instead (names for a ``CARLEnv``, table rows for a ``VecEngine``), each of
+    which must be a context value the engine makes visible; ``[]``: the policy sees the observation only."""
+    eng, cenv = _engine_of(env)
+    visible = list(eng.ctx_obs_rows)
+    if cenv is None:
+        rows = visible if features is None else [int(f) for f in features]
+        for r in rows:
+            if r not in visible:
+                raise ValueError(f"context row {r} is not one of the engine's visible context rows {visible}")
+        return rows, list(rows)
+    names = list(cenv._table.names)
+    vis_names = [names[r] for r in visible]
+    if features is None:
+        order = sorted(vis_names) if cenv.obs_context_as_dict else vis_names  # (vis_names: obs_context_features order)
+    else:
+        order = [str(f) for f in features]
+        for f in order:
+            if f not in vis_names:
+                raise ValueError(f"context feature {f!r} is not a visible context row of this env (visible: {vis_names})")
+    return [names.index(f) for f in order], order
+
+
+class MLPPolicy:
+    """One or more weight sets of one MLP shape, for one env family (see the module docstring)."""
+
+    def __init__(self, family: int, obs_dim: int, ctx_rows: Sequence[int], layers: Sequence, activation: str = "tanh",
+                 input_shift=None, input_scale=None, input_clip: float | None = None, context_names: Sequence | None = None):
+        info = _lib.family_info(int(family))
+        self.family, self.obs_dim = int(family), int(obs_dim)
+        self.ctx_rows = [int(r) for r in ctx_rows]
+        self.context_names = list(context_names) if context_names is not None else list(self.ctx_rows)
+        if activation not in _ACTIVATIONS:
+            raise ValueError(f"activation {activation!r}: one of {sorted(_ACTIVATIONS)}")
+        self.activation = activation
+        self.discrete = bool(info.action_is_discrete)
+        self.n_in = len(self.ctx_rows) + self.obs_dim
+        if len(self.ctx_rows) > _lib.POLICY_MAX_IN or self.n_in > _lib.POLICY_MAX_IN:
+            raise ValueError(f"{self.n_in} inputs: at most {_lib.POLICY_MAX_IN}")
+        for r in self.ctx_rows:
+            if not 0 <= r < info.n_features:
+                raise ValueError(f"context row {r} outside the family's table (F = {info.n_features})")
+        self.layers = []
+        prev = self.n_in
+        for k, (W, b) in enumerate(layers):
+            W = np.asarray(W, dtype=np.float32)
+            b = np.zeros(W.shape[0], np.float32) if b is None else np.asarray(b, dtype=np.float32).reshape(-1)
+            if W.ndim != 2 or W.shape[1] != prev or b.shape != (W.shape[0],):
+                raise ValueError(f"layer {k}: W {W.shape} / b {b.shape} do not continue from {prev} inputs")
+            self.layers.append((W, b))
+            prev = W.shape[0]
+        if not self.layers:
+            raise ValueError("a policy needs at least its head layer")
+        self.widths = [W.shape[0] for W, _ in self.layers[:-1]]
+        if len(self.widths) > _lib.POLICY_MAX_HIDDEN or any(not 1 <= w <= _lib.POLICY_MAX_WIDTH for w in self.widths):
+            raise ValueError(f"hidden widths {self.widths}: at most {_lib.POLICY_MAX_HIDDEN} layers of width <= "
+                             f"{_lib.POLICY_MAX_WIDTH}")
+        self.n_out = self.layers[-1][0].shape[0]
+        want = int(info.n_actions) if self.discrete else 1
+        if self.n_out != want:
+            raise ValueError(f"head width {self.n_out}: this family needs {want} ({'n_actions' if self.discrete else 'Box'})")
+        self.shift = np.zeros(self.n_in, np.float32) if input_shift is None else np.asarray(input_shift, np.float32).reshape(-1)
+        self.scale = np.ones(self.n_in, np.float32) if input_scale is None else np.asarray(input_scale, np.float32).reshape(-1)
+        if self.shift.shape != (self.n_in,) or self.scale.shape != (self.n_in,):
+            raise ValueError(f"input_shift / input_scale need {self.n_in} values")
+        self.clip = np.float32(np.inf if input_clip is None else input_clip)
+        self.params = self._pack()[None]  # [n_sets, set_floats]
+        self.lanes_per_set = None  # one set: every lane
+        self._dev = {}
+
+    # ------------------------------------------------------------------ construction
+    @classmethod
+    def for_env(cls, env, layers: Sequence, activation: str = "tanh", input_shift=None, input_scale=None,
+                input_clip: float | None = None, context_features: Sequence | None = None) -> "MLPPolicy":
+        """A policy for ``env`` (a classic-control ``CARLEnv`` or ``VecEngine``) from explicit ``(W [out, in], b [out])``
+        arrays, hidden layers first, the head last.  The input is ``FlattenObservation(env)``'s vector (module docstring);
+        ``context_features`` narrows its context part (``[]``: observation only)."""
+        eng, _ = _engine_of(env)
+        rows, names = flattened_context_rows(env, context_features)
+        return cls(eng.family, eng.D, rows, layers, activation, input_shift, input_scale, input_clip, names)
+
+    @classmethod
+    def from_sequential(cls, env, seq: torch.nn.Sequential, **kw) -> "MLPPolicy":
+        """The same from a ``torch.nn.Sequential`` of ``Linear`` layers with ``Tanh`` / ``ReLU`` / ``Identity`` between
+        them (one activation kind for every hidden layer; nothing after the head but ``Identity``)."""
+        linears, acts = [], []
+        for m in seq:
+            if isinstance(m, torch.nn.Linear):
+                linears.append(m)
+                acts.append(None)
+            elif isinstance(m, (torch.nn.Tanh, torch.nn.ReLU)):
+                if not linears or acts[-1] is not None:
+                    raise ValueError(f"{type(m).__name__} must follow a Linear layer (one activation per layer)")
+                acts[-1] = "tanh" if isinstance(m, torch.nn.Tanh) else "relu"
+            elif isinstance(m, torch.nn.Identity):
+                continue
+            else:
+                raise TypeError(f"{type(m).__name__}: the device policy takes Linear / Tanh / ReLU / Identity only")
+        if not linears:
+            raise ValueError("the Sequential holds no Linear layer")
+        if acts[-1] is not None:
+            raise ValueError("the head (the last Linear) must be linear: no activation after it")
+        kinds = {a or "identity" for a in acts[:-1]}
+        if len(kinds) > 1:
+            raise ValueError(f"hidden activations {sorted(kinds)}: the device policy applies one kind to every hidden layer")
+        layers = [(m.weight.detach().cpu().numpy(), None if m.bias is None else m.bias.detach().cpu().numpy())
+                  for m in linears]
+        return cls.for_env(env, layers, activation=kinds.pop() if kinds else "tanh", **kw)
+
+    @staticmethod
+    def stack(policies: Sequence["MLPPolicy"], lanes_per_set: int) -> "MLPPolicy":
+        """Several weight sets of one shape: lane ``l`` uses set ``l // lanes_per_set`` (a multiple of
+        ``carl_policy_lane_quantum()``, 256 -- the lanes of one workgroup)."""
+        if not policies:
+            raise ValueError("stack() needs at least one policy")
+        p0 = policies[0]
+        key = lambda p: (p.family, p.ctx_rows, p.obs_dim, [W.shape for W, _ in p.layers], p.activation)  # noqa: E731
+        for p in policies[1:]:
+            if key(p) != key(p0):
+                raise ValueError("stack(): every weight set must have the same family, inputs, shape and activation")
+        q = _lib.load().carl_policy_lane_quantum()
+        if lanes_per_set <= 0 or lanes_per_set % q:
+            raise ValueError(f"lanes_per_set {lanes_per_set} is not a positive multiple of {q}")
+        out = object.__new__(MLPPolicy)
+        out.__dict__.update(p0.__dict__)
+        out.params = np.concatenate([p.params for p in policies], axis=0)
+        out.lanes_per_set = int(lanes_per_set)
+        out._dev = {}
+        return out
+
+    @property
+    def n_sets(self) -> int:
+        return int(self.params.shape[0])
+
+    def _pack(self) -> np.ndarray:
+        parts = []
+        for W, b in self.layers:
+            parts += [W.reshape(-1), b]
+        parts += [self.shift, self.scale, np.array([self.clip], np.float32)]
+        flat = np.concatenate(parts).astype(np.float32)
+        pad = (-flat.size) % 4
+        return np.concatenate([flat, np.zeros(pad, np.float32)])
+
+    # ------------------------------------------------------------------ C ABI
+    def struct(self, n_lanes: int, params_ptr: int | None = None) -> "_lib.Policy":
+        """The ``carl_policy_t`` of this policy for a batch of ``n_lanes`` (one set: every lane uses it)."""
+        p = _lib.Policy()
+        p.n_in, p.n_ctx = self.n_in, len(self.ctx_rows)
+        for k, r in enumerate(self.ctx_rows):
+            p.ctx_rows[k] = r
+        p.n_hidden = len(self.widths)
+        for k, w in enumerate(self.widths):
+            p.width[k] = w
+        p.n_out = self.n_out
+        p.activation = _ACTIVATIONS[self.activation]
+        p.head = _lib.POLICY_HEAD_ARGMAX if self.discrete else _lib.POLICY_HEAD_BOX
+        p.n_sets = self.n_sets
+        if self.lanes_per_set is None:
+            q = int(_lib.load().carl_policy_lane_quantum())
+            p.lanes_per_set = max(q, (int(n_lanes) + q - 1) // q * q)
+        else:
+            p.lanes_per_set = self.lanes_per_set
+        p.params = params_ptr
+        return p
+
+    def device_params(self, device) -> torch.Tensor:
+        """The packed parameters on ``device`` (uploaded once per device)."""
+        dev = torch.device(device)
+        t = self._dev.get(dev)
+        if t is None:
+            t = torch.as_tensor(self.params).to(dev).contiguous()
+            self._dev[dev] = t
+        return t

@@ -297,6 +297,81 @@ int carl_done_compact(const uint8_t* terminated, const uint8_t* truncated, int32
                       int32_t* idx_out, int32_t* count_out, int32_t* scratch, void* stream);
 int32_t carl_done_compact_scratch_elems(int32_t n);
 
+/* ======================= closed-loop rollout: a policy network on the device (ABI 9, additive) =======================
+ * carl_rollout takes actions written before the launch (open loop).  carl_rollout_policy evaluates a small fp32 MLP
+ * for every lane at every step instead, and that step takes the action it yields: the workload of evaluating a
+ * trained agent over a context set (the reference's examples/carl_with_sb3.py trains a policy on
+ * FlattenObservation(env); carl/envs/carl_env.py:276-305 builds what it sees).  Classic-control families only: a
+ * Brax batch (family >= CARL_N_FAMILIES) is refused, and so are the pair launch (carl_rollout_pair) and the
+ * narrow action formats -- the kernel writes the actions it takes, it reads none.
+ *
+ * The policy's input is what FlattenObservation(env) yields for a lane:
+ *   x = [ctx_table[ctx_rows[0]][c], ..., ctx_table[ctx_rows[n_ctx - 1]][c], obs_0, ..., obs_{D-1}]
+ * with c the lane's CURRENT context (after any auto-reset of the previous step) and obs the lane's current
+ * observation (before the step).  n_in = n_ctx + D.  Then
+ *   x = min(max((x - shift) * scale, -clip), clip)          (SB3 VecNormalize; shift 0, scale 1, clip inf: identity)
+ *   h = act(W_l h + b_l)  for each of the n_hidden layers     (act: CARL_POLICY_* below, the same for every layer)
+ *   y = W_head h + b_head                                    (n_out values)
+ * Discrete families: the action is the index of the largest y (the first one on ties: `>` comparisons); n_out must
+ * be carl_family_info().n_actions.  Box families: the action is y[0] as it comes (n_out = 1), and the env clips it
+ * exactly as it clips an action given to carl_rollout.  Every product is an explicit fma (in input order, bias
+ * first); tanh is evaluated as 1 - 2 / (exp(2 v) + 1) with the hardware exponential (~1e-7 absolute).
+ *
+ * Packed parameters, float32, one block of carl_policy_set_floats() floats per weight set (set k at params +
+ * k * carl_policy_set_floats(p)), each block: for every layer in order (hidden layers, then the head) W[out][in]
+ * row-major followed by b[out]; then shift[n_in], scale[n_in], clip (one value for every input); zero padding up to a
+ * multiple of 4 floats.  Lane l uses weight set l / lanes_per_set; lanes_per_set is a positive multiple of
+ * carl_policy_lane_quantum() (the lanes of one workgroup: it stages one set in LDS) and n_sets * lanes_per_set must
+ * cover n_lanes. */
+#define CARL_POLICY_MAX_IN 32
+#define CARL_POLICY_MAX_HIDDEN 2
+#define CARL_POLICY_MAX_WIDTH 64
+enum { CARL_POLICY_IDENTITY = 0, CARL_POLICY_TANH = 1, CARL_POLICY_RELU = 2 };  /* hidden-layer activation */
+enum { CARL_POLICY_HEAD_ARGMAX = 0, CARL_POLICY_HEAD_BOX = 1 };               /* discrete / Box families */
+
+typedef struct carl_policy {
+  int32_t n_in;                          /* n_ctx + obs_dim */
+  int32_t n_ctx;                         /* leading inputs that are context values */
+  int32_t ctx_rows[CARL_POLICY_MAX_IN];  /* [n_ctx] context-table row of each, in FlattenObservation order; < F */
+  int32_t n_hidden;                      /* 0 (a linear policy) .. CARL_POLICY_MAX_HIDDEN */
+  int32_t width[CARL_POLICY_MAX_HIDDEN]; /* [n_hidden] 1 .. CARL_POLICY_MAX_WIDTH */
+  int32_t n_out;                         /* head width */
+  int32_t activation;                    /* CARL_POLICY_IDENTITY / TANH / RELU */
+  int32_t head;                          /* CARL_POLICY_HEAD_ARGMAX (discrete) / CARL_POLICY_HEAD_BOX */
+  int32_t n_sets;                        /* >= 1 */
+  int32_t lanes_per_set;                 /* multiple of carl_policy_lane_quantum(); n_sets * lanes_per_set >= n_lanes */
+  int32_t reserved;
+  const float* params;                   /* DEVICE [n_sets][carl_policy_set_floats()] */
+} carl_policy_t;
+
+/* per-lane totals of one launch (summary mode; optional in transitions mode) */
+typedef struct carl_policy_summary {
+  int32_t* episodes;   /* [n_lanes] episodes finished in the launch */
+  float* return_sum;   /* [n_lanes] fp32 sum of their returns, added in step order */
+  int32_t* length_sum; /* [n_lanes] sum of their lengths */
+} carl_policy_summary_t;
+
+/* T steps of every lane in ONE launch, each step's action chosen by `policy_host` (a HOST pointer; its `params` are on
+ * the device).  No reference counterpart on this path: the reference steps one env object per Python call and its
+ * caller runs the policy between the calls (carl/envs/carl_env.py:321-342).
+ *  - transitions mode (io != NULL): everything carl_rollout writes (obs / reward / terminated / truncated per step,
+ *    io->final_obs when not NULL, the engine state at the end), plus the action taken at step t in row t of
+ *    io->action -- an OUTPUT here: int32 (CARL_ACTION_I32) for discrete families, float32 (CARL_ACTION_F32) for Box
+ *    ones.  Row layout as carl_rollout's staged kernel: (io->row_pitch ? io->row_pitch : n_lanes) % 16 == 0 and
+ *    either n_lanes % 16 == 0 or the pitch is carl_rollout_pitch(n_lanes) (the padding columns receive the padding
+ *    lanes' records), every array on a 16-byte boundary; other layouts return CARL_ERR_UNSUPPORTED.
+ *    Replaying the recorded actions with carl_rollout from the same engine state gives the same bits.
+ *  - summary mode (io == NULL): no per-step stores; summary_out (required) receives each lane's totals, and the
+ *    engine state ends exactly as after a transitions-mode launch.
+ * summary_out is optional in transitions mode (then both are written).  Bad arguments -- widths over their limits, a
+ * head width that is not n_actions (discrete) or 1 (Box), a Brax family, a bad lanes_per_set, a context row >= F --
+ * return CARL_ERR_INVALID_ARGUMENT before anything is enqueued. */
+int carl_rollout_policy(const carl_batch_t* batch, const carl_policy_t* policy_host, const carl_step_io_t* io,
+                        int32_t n_steps, const carl_policy_summary_t* summary_out, void* stream);
+int32_t carl_policy_lane_quantum(void); /* lanes_per_set must be a positive multiple of this (256) */
+/* floats per weight set of the packed parameters (see above) for this policy's shape; -1 for an invalid shape */
+int32_t carl_policy_set_floats(const carl_policy_t* policy_host);
+
 /* ======================= Brax-locomotion families (spring backend) =======================
  * Replaces CARLBraxEnv + BraxGymWrapper/VectorGymWrapper + brax.spring.pipeline.step x
  * n_frames + brax.envs.<env>.step/reset (carl/envs/brax/carl_brax_env.py:115-336,

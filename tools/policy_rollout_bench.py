@@ -1,0 +1,135 @@
+"""Closed-loop rollout throughput: CartPole x 65 536 lanes x 1 000 steps per launch, env-steps/s of
+
+  policy_rollout   VecEngine.rollout_policy (transitions / summary) with a linear policy, a 2x32 and a 2x64 tanh MLP
+                   (each seeing the eight context features and the observation);
+  open_loop        VecEngine.rollout of pre-written int32 actions (the staged kernel), same T;
+  graph_step_mlp   what a caller has without the feature: a captured hipGraph of `step` + a torch forward of the same
+                   MLP + argmax per env step (100 steps per graph, replayed to 1 000).
+
+Host timing with torch.cuda events around `--reps` launches after one warm-up launch; the median per launch is
+reported.  Kernel times belong to a separate `rocprofv3 --kernel-trace --stats` run of this script.
+
+  python tools/policy_rollout_bench.py [--lanes 65536] [--steps 1000] [--reps 5] [--out FILE]
+"""
+from __future__ import annotations
+
+import argparse
+import json
+import os
+import sys
+
+import numpy as np
+import torch
+
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+
+from carl_amd import _lib  # noqa: E402
+from carl_amd.engine import VecEngine  # noqa: E402
+from carl_amd.envs import CARLCartPole  # noqa: E402
+from carl_amd.policy import MLPPolicy  # noqa: E402
+
+
+def make_engine(n, seed=0):
+    rng = np.random.default_rng(seed)
+    names = list(CARLCartPole.get_context_features())
+    t = np.tile([float(f.default_value) for f in CARLCartPole.get_context_features().values()], (n, 1))
+    t[:, names.index("gravity")] = rng.uniform(5, 15, n)
+    t[:, names.index("length")] = rng.uniform(0.3, 1.0, n)
+    eng = VecEngine(_lib.CARTPOLE, t, n, "cuda", selector=_lib.SEL_STATIC, auto_reset=True, seed=seed)
+    eng.reset()
+    return eng
+
+
+def make_mlp(widths, n_in, seed=0):
+    torch.manual_seed(seed)
+    mods, prev = [], n_in
+    for w in widths:
+        mods += [torch.nn.Linear(prev, w), torch.nn.Tanh()]
+        prev = w
+    mods.append(torch.nn.Linear(prev, 2))
+    return torch.nn.Sequential(*mods)
+
+
+def time_launches(fn, reps):
+    fn()  # warm-up (code object load, first-touch of the buffers)
+    torch.cuda.synchronize()
+    ts = []
+    for _ in range(reps):
+        a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        a.record()
+        fn()
+        b.record()
+        b.synchronize()
+        ts.append(a.elapsed_time(b) * 1e-3)
+    return float(np.median(ts)), ts
+
+
+def graph_step_mlp(eng, mlp, T, per_graph=100):
+    """a hipGraph of `per_graph` x (torch forward of mlp on [ctx_obs, obs] -> argmax -> step)"""
+    dev = eng.device
+    act = torch.zeros(eng.n, dtype=torch.int32, device=dev)
+
+    def one():
+        x = torch.cat([eng.ctx_obs.t(), eng.obs], dim=1)
+        act.copy_(mlp(x).argmax(dim=1).to(torch.int32))
+        eng.step(act)
+
+    side = torch.cuda.Stream(device=dev)
+    side.wait_stream(torch.cuda.current_stream(dev))
+    g = torch.cuda.CUDAGraph()
+    with torch.cuda.stream(side), torch.no_grad():
+        for _ in range(3):
+            one()
+        with torch.cuda.graph(g, stream=side):
+            for _ in range(per_graph):
+                one()
+    torch.cuda.current_stream(dev).wait_stream(side)
+
+    def run():
+        for _ in range(T // per_graph):
+            g.replay()
+
+    return run
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--lanes", type=int, default=65536)
+    ap.add_argument("--steps", type=int, default=1000)
+    ap.add_argument("--reps", type=int, default=5)
+    ap.add_argument("--out", default=None)
+    args = ap.parse_args()
+    n, T = args.lanes, args.steps
+    eng = make_engine(n)
+    n_in = len(eng.ctx_obs_rows) + eng.D
+    rows = []
+
+    def record(name, sec, ts):
+        r = {"config": name, "lanes": n, "steps": T, "sec_per_launch": sec, "env_steps_per_s": n * T / sec,
+             "ns_per_step": sec / T * 1e9, "reps_sec": ts}
+        rows.append(r)
+        print(json.dumps(r), flush=True)
+
+    acts = torch.randint(0, 2, (T, n), dtype=torch.int32, device=eng.device)
+    out = eng.alloc_rollout(T)
+    record("open_loop_rollout_int32", *time_launches(lambda: eng.rollout(acts, out=out), args.reps))
+
+    policies = {"linear": [], "mlp_2x32_tanh": [32, 32], "mlp_2x64_tanh": [64, 64]}
+    for name, widths in policies.items():
+        mlp = make_mlp(widths, n_in)
+        pol = MLPPolicy.from_sequential(eng, mlp)
+        pout = eng.rollout_policy(pol, T)  # buffers reused by every timed launch
+        record(f"policy_transitions_{name}", *time_launches(lambda: eng.rollout_policy(pol, T, out=pout), args.reps))
+        s = eng.alloc_policy_summary()
+        record(f"policy_summary_{name}", *time_launches(lambda: eng.rollout_policy(pol, T, out=s, mode="summary"),
+                                                       args.reps))
+        with torch.no_grad():
+            run = graph_step_mlp(eng, mlp.to(eng.device), T)
+            record(f"graph_step_torch_{name}", *time_launches(run, max(1, args.reps // 2)))
+    if args.out:
+        with open(args.out, "w") as f:
+            json.dump({"device": torch.cuda.get_device_name(0), "results": rows}, f, indent=1)
+
+
+if __name__ == "__main__":
+    main()
