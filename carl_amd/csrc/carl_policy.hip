@@ -169,6 +169,11 @@ int carl_rollout_policy(const carl_batch_t* batch, const carl_policy_t* policy_h
     if (summary_out != nullptr && (!summary_out->episodes || !summary_out->return_sum || !summary_out->length_sum))
       return fail(CARL_ERR_INVALID_ARGUMENT, "carl_rollout_policy: a summary needs all three arrays");
   }
+  // Without auto-reset a finished lane stays done and reports done again on every later step (its return and length
+  // still growing): the per-lane totals would count one episode many times.  A summary needs CARL_FLAG_AUTORESET.
+  if (summary_out != nullptr && !(batch->flags & CARL_FLAG_AUTORESET))
+    return fail(CARL_ERR_UNSUPPORTED, "carl_rollout_policy: a summary needs CARL_FLAG_AUTORESET (without auto-reset a "
+                "finished lane reports done on every later step, and its episode would be counted on each of them)");
   if (batch->n_lanes == 0 || n_steps == 0) {
     if (summary_out == nullptr || batch->n_lanes == 0) return 0;
     // no step: every total is zero

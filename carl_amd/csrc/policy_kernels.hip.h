@@ -19,8 +19,10 @@
 // padded hidden width of the instantiation (0: a linear policy, else 32 or 64):
 //   W1 [H][K] | b1 [H] | W2 [H][H] | b2 [H] | Wh^T [HI][4] | bh [4] | shift [K] | scale [K] | clip [4]
 // HI = K when H == 0, else H.  Input slot of context input k: k (k < n_ctx); of observation entry d: F + d.  Every
-// slot, row and column the policy does not use holds 0: a padded hidden unit computes act(0) = 0 and feeds zero
-// weights, a padded input is clamp((0 - 0) * 0) = 0 -- the padding changes no result, only the instruction count.
+// slot, row and column the policy does not use holds 0, a padded input slot is never written (0), and a padded hidden
+// unit is forced to exact 0 after its activation (activate): its zero weights would turn an infinite input into NaN
+// (fma(0, inf, y)), and the zero head weights would carry that NaN into every output.  So the padding changes no
+// result, only the instruction count (up to the sign of a zero sum: fma(0, 0, -0) = +0).
 #pragma once
 
 // engine_kernels.hip.h also DEFINES the two non-template done-compaction kernels, which carl_amd.hip owns: in this
@@ -149,14 +151,19 @@ __device__ __forceinline__ float tanh_fast(float v) {
   return 1.0f - __fdividef(2.0f, e + 1.0f);
 }
 
+// h = act(h) on the `width` real units; the padded units [width, N) become exact 0 (one select each)
 template <int N>
-__device__ __forceinline__ void activate(float (&h)[N], int act) {
+__device__ __forceinline__ void activate(float (&h)[N], int act, int width) {
   if (act == CARL_POLICY_TANH) {
 #pragma unroll
     for (int j = 0; j < N; ++j) h[j] = tanh_fast(h[j]);
   } else if (act == CARL_POLICY_RELU) {
 #pragma unroll
     for (int j = 0; j < N; ++j) h[j] = fmaxf(h[j], 0.0f);
+  }
+  if (width < N) {  // (wave-uniform: a full-width layer pays nothing)
+#pragma unroll
+    for (int j = 0; j < N; ++j) h[j] = j < width ? h[j] : 0.0f;
   }
 }
 
@@ -199,7 +206,8 @@ __device__ __forceinline__ void head_layer(const float* wt, const float* b, cons
   }
 }
 
-// x_slot = min(max((v - shift) * scale, -clip), clip)
+// x_slot = min(max((v - shift) * scale, -clip), clip); a NaN (a NaN input, or 0 * inf) becomes -clip: fmaxf returns
+// the operand that is not NaN
 __device__ __forceinline__ float normalize_input(float v, float shift, float scale, float clip) {
 #pragma clang fp contract(off)
   return fminf(fmaxf((v - shift) * scale, -clip), clip);
@@ -208,7 +216,7 @@ __device__ __forceinline__ float normalize_input(float v, float shift, float sca
 // The policy's action for input slots x (LDS layout above)
 template <class Fam, int H>
 __device__ __forceinline__ typename Fam::Action policy_action(const float* w, const float (&x)[PolicyLayout<Fam, H>::K],
-                                                              int n_hidden, int act) {
+                                                              int n_hidden, int act, int w0, int w1) {
   using L = PolicyLayout<Fam, H>;
   float y[4];
   if constexpr (H == 0) {
@@ -216,11 +224,11 @@ __device__ __forceinline__ typename Fam::Action policy_action(const float* w, co
   } else {
     float h1[H];
     dense_layer<H, L::K>(w + L::kW1, w + L::kB1, x, h1);
-    activate(h1, act);
+    activate(h1, act, w0);
     if (n_hidden > 1) {  // (wave-uniform)
       float h2[H];
       dense_layer<H, H>(w + L::kW2, w + L::kB2, h1, h2);
-      activate(h2, act);
+      activate(h2, act, w1);
       head_layer<H>(w + L::kWh, w + L::kBh, h2, y);
     } else {
       head_layer<H>(w + L::kWh, w + L::kBh, h1, y);
@@ -305,6 +313,7 @@ __global__ void __launch_bounds__(SUMMARY ? kPolicyThreadsSummary : kPolicyThrea
     r.valid = active;
     float* const final_base = (!SUMMARY && io.final_obs != nullptr && active) ? io.final_obs + (size_t)lane * Fam::D : nullptr;
     const int n_ctx = pol.n_ctx, n_hidden = pol.n_hidden, act = pol.activation;
+    const int w0 = pol.width[0], w1 = pol.width[1];  // (w1: read only when n_hidden == 2)
     const float clip = wts[L::kClip];
     float x[L::K];
 #pragma unroll
@@ -333,7 +342,7 @@ __global__ void __launch_bounds__(SUMMARY ? kPolicyThreadsSummary : kPolicyThrea
 #pragma unroll
         for (int d = 0; d < Fam::D; ++d)
           x[Fam::F + d] = normalize_input(o[d], wts[L::kShift + Fam::F + d], wts[L::kScale + Fam::F + d], clip);
-        const Action a = policy_action<Fam, H>(wts, x, n_hidden, act);
+        const Action a = policy_action<Fam, H>(wts, x, n_hidden, act, w0, w1);
         const int before = r.n_new_episodes;
         if constexpr (SUMMARY) {
           step_lane<Fam, GlobalCtx, true, NullSink<Fam>>(b, ctx, NullSink<Fam>{}, b.max_episode_steps, true, lane, glane,

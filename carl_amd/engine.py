@@ -608,12 +608,16 @@ class VecEngine:
         actions from the same engine state gives the same bits.  ``mode="summary"``: no per-step output at all; returns
         ``{"episodes", "return_sum", "length_sum"}`` per lane (episodes finished in the launch, the float32 sum of their
         returns in step order, the sum of their lengths).  Either way the engine state advances exactly as in
-        ``rollout``.  No host synchronisation (the policy's parameters are uploaded on its first use on a device)."""
+        ``rollout``; a summary needs ``auto_reset`` (ValueError otherwise).  No host synchronisation (the policy's parameters
+        are uploaded on its first use on a device)."""
         if not self._policy_rollout:
             raise NotImplementedError(f"{type(self).__name__}: the closed-loop rollout covers the classic-control "
                                       "families only")
         if policy.family != self.family or policy.obs_dim != self.D:
             raise ValueError(f"the policy was built for family {policy.family}, this engine runs family {self.family}")
+        if mode == "summary" and not self.auto_reset:
+            raise ValueError("mode='summary' needs auto_reset=True: without it a finished lane reports done on every later "
+                             "step, and the totals would count its episode on each of them")
         T = int(n_steps)
         params = policy.device_params(self.device)
         pol = policy.struct(self.n, params.data_ptr())

@@ -47,7 +47,7 @@ class FlattenObservation:
     def _flat(self, obs):
         ctx, o = obs["context"], obs["obs"]
         if torch.is_tensor(o):
-            c = torch.stack([ctx[k] for k in sorted(ctx)], dim=1) if isinstance(ctx, dict) else ctx
+            c = self._ctx_matrix(ctx) if isinstance(ctx, dict) else ctx
             return torch.cat([c, o], dim=1)
         c = [ctx[k] for k in sorted(ctx)] if isinstance(ctx, dict) else list(ctx)
         return np.concatenate([np.asarray(c, dtype=np.float32), np.asarray(o, dtype=np.float32).reshape(-1)])
@@ -57,7 +57,11 @@ class FlattenObservation:
         return self._flat(obs), info
 
     def _ctx_matrix(self, ctx):
-        return torch.stack([ctx[k] for k in sorted(ctx)], dim=1) if isinstance(ctx, dict) else ctx
+        if not isinstance(ctx, dict):
+            return ctx
+        if not ctx:  # obs_context_features=[]: a [N, 0] context part (torch.stack refuses an empty list)
+            return torch.zeros((self.env.num_envs, 0), dtype=torch.float32, device=self.env.env.device)
+        return torch.stack([ctx[k] for k in sorted(ctx)], dim=1)
 
     def step(self, action):
         # (ctx_obs aliases a live engine buffer that the step rewrites for lanes that reset onto another context)

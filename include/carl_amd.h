@@ -309,13 +309,16 @@ int32_t carl_done_compact_scratch_elems(int32_t n);
  *   x = [ctx_table[ctx_rows[0]][c], ..., ctx_table[ctx_rows[n_ctx - 1]][c], obs_0, ..., obs_{D-1}]
  * with c the lane's CURRENT context (after any auto-reset of the previous step) and obs the lane's current
  * observation (before the step).  n_in = n_ctx + D.  Then
- *   x = min(max((x - shift) * scale, -clip), clip)          (SB3 VecNormalize; shift 0, scale 1, clip inf: identity)
+ *   x = min(max((x - shift) * scale, -clip), clip)          (SB3 VecNormalize; shift 0, scale 1, clip inf: identity;
+ *                                                            a NaN -- a NaN input, or 0 * inf -- becomes -clip)
  *   h = act(W_l h + b_l)  for each of the n_hidden layers     (act: CARL_POLICY_* below, the same for every layer)
  *   y = W_head h + b_head                                    (n_out values)
  * Discrete families: the action is the index of the largest y (the first one on ties: `>` comparisons); n_out must
  * be carl_family_info().n_actions.  Box families: the action is y[0] as it comes (n_out = 1), and the env clips it
  * exactly as it clips an action given to carl_rollout.  Every product is an explicit fma (in input order, bias
- * first); tanh is evaluated as 1 - 2 / (exp(2 v) + 1) with the hardware exponential (~1e-7 absolute).
+ * first); tanh is evaluated as 1 - 2 / (exp(2 v) + 1) with the hardware exponential and reciprocal (within 6 * 2^-24
+ * absolute; exactly +-1 once exp(2 v) overflows or underflows).  The kernel pads the network to a fixed width with
+ * zero weights and forces padded hidden units to 0: the padding changes no result, infinite inputs included.
  *
  * Packed parameters, float32, one block of carl_policy_set_floats() floats per weight set (set k at params +
  * k * carl_policy_set_floats(p)), each block: for every layer in order (hidden layers, then the head) W[out][in]
@@ -362,7 +365,9 @@ typedef struct carl_policy_summary {
  *    lanes' records), every array on a 16-byte boundary; other layouts return CARL_ERR_UNSUPPORTED.
  *    Replaying the recorded actions with carl_rollout from the same engine state gives the same bits.
  *  - summary mode (io == NULL): no per-step stores; summary_out (required) receives each lane's totals, and the
- *    engine state ends exactly as after a transitions-mode launch.
+ *    engine state ends exactly as after a transitions-mode launch.  A summary (in either mode) needs
+ *    CARL_FLAG_AUTORESET, else CARL_ERR_UNSUPPORTED: without auto-reset a finished lane reports done on every later
+ *    step, and its one episode would be counted on each of them.
  * summary_out is optional in transitions mode (then both are written).  Bad arguments -- widths over their limits, a
  * head width that is not n_actions (discrete) or 1 (Box), a Brax family, a bad lanes_per_set, a context row >= F --
  * return CARL_ERR_INVALID_ARGUMENT before anything is enqueued. */

@@ -243,3 +243,53 @@ def verify_contexts(specs, table: np.ndarray) -> int:
     fn.restype = C.c_int
     fn.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p]
     return int(fn(C.addressof(specs), table.shape[0], table.shape[1], table.shape[1], _p(table)))
+
+
+# ---- closed-loop policy restatement (oracle/carl_oracle.c: oracle_policy_forward) ----------------------------------
+POLICY_IDENTITY, POLICY_TANH, POLICY_RELU = range(3)
+_POLICY_ACT = {"identity": POLICY_IDENTITY, "tanh": POLICY_TANH, "relu": POLICY_RELU}
+
+
+def tanh_abs() -> float:
+    """Absolute error allowance of one device tanh (derivation: carl_oracle.c, ORACLE_TANH_ABS)."""
+    fn = lib().oracle_tanh_abs
+    fn.restype = C.c_double
+    return float(fn())
+
+
+def fmaf(a, b, c) -> np.ndarray:
+    """Correctly rounded float32 fma, elementwise (libm fmaf through the oracle)."""
+    a, b, c = (np.ascontiguousarray(np.broadcast_to(v, np.broadcast(a, b, c).shape), dtype=np.float32).reshape(-1)
+               for v in (a, b, c))
+    out = np.empty_like(a)
+    lib().oracle_fmaf_n(C.c_int(a.size), _p(a), _p(b), _p(c), _p(out))
+    return out
+
+
+@dataclass
+class PolicyOut:
+    y32: np.ndarray     # [N, n_out] float32: the documented fp32 forward pass
+    y64: np.ndarray     # [N, n_out] float64 forward pass of the same network
+    bound: np.ndarray   # [N, n_out] bound on |fp32 forward - exact| (tanh: with the device tanh's allowance)
+    action: np.ndarray  # [N] int32: the first maximal index of y32
+
+
+def policy_forward(params, n_in: int, widths, n_out: int, activation: str, x, sets=None) -> PolicyOut:
+    """Evaluate packed weight sets ``params`` ([n_sets, set_floats] float32, include/carl_amd.h layout) on raw inputs
+    ``x`` ([N, n_in]: context values, then the observation); row r uses set ``sets[r]`` (default 0)."""
+    params = np.ascontiguousarray(np.atleast_2d(params), dtype=np.float32)
+    x = np.ascontiguousarray(x, dtype=np.float32).reshape(-1, n_in)
+    n = x.shape[0]
+    sets = np.zeros(n, np.int32) if sets is None else np.ascontiguousarray(sets, dtype=np.int32).reshape(n)
+    assert sets.size == 0 or (sets.min() >= 0 and sets.max() < params.shape[0])
+    w = np.zeros(2, np.int32)
+    w[: len(widths)] = widths
+    y32 = np.empty((n, n_out), np.float32)
+    y64 = np.empty((n, n_out), np.float64)
+    bound = np.empty((n, n_out), np.float64)
+    act = np.empty(n, np.int32)
+    rc = lib().oracle_policy_forward(C.c_int(n), C.c_int(n_in), C.c_int(len(widths)), _p(w), C.c_int(n_out),
+                                     C.c_int(_POLICY_ACT[activation]), _p(params), C.c_int(params.shape[1]), _p(sets),
+                                     _p(x), _p(y32), _p(y64), _p(bound), _p(act))
+    assert rc == 0, "policy shape outside the limits"
+    return PolicyOut(y32, y64, bound, act)
