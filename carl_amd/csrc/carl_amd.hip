@@ -55,13 +55,6 @@ int ensure_dynamic_lds(const void* kernel, size_t bytes, const char* who) {
   return 0;
 }
 
-}  // namespace carl_host
-
-namespace {
-
-using carl_host::check_launch;
-using carl_host::fail;
-
 const carl_family_info_t kInfo[CARL_N_FAMILIES] = {
     /* state obs feat adim disc nact max_steps rsv lo hi */
     {4, 4, 8, 1, 1, 2, 500, 0, 0.0f, 1.0f},     // CartPole-v1
@@ -94,6 +87,97 @@ int validate_batch(const carl_batch_t* b, const char* who) {
     return fail(CARL_ERR_INVALID_ARGUMENT, "%s: finished-episode log is incomplete", who);
   return 0;
 }
+
+// The staged kernels write 16-byte pieces of every row: rows must start on 16-byte boundaries (pitch % 16 == 0) and
+// the columns [n_lanes, n_lanes rounded up to 16) must be the caller's to lose -- they are when the lane count is a
+// multiple of 16 (there are none) or when the pitch IS that rounded-up count (the padded layout of carl_rollout_pitch).
+// A wider pitch with an odd lane count is a view into an array whose neighbouring columns belong to someone else.
+// ... and every array must START on a 16-byte boundary (fresh allocations do; a column view `array[:, k:]` need not),
+// the action array on the boundary of its loads (action_align_mask + 1 bytes).
+bool staged_rows(const carl_batch_t* b, const carl_step_io_t* io, uintptr_t action_align_mask) {
+  const int pitch = io->row_pitch > 0 ? io->row_pitch : b->n_lanes, n16 = (b->n_lanes + 15) / 16 * 16;
+  const uintptr_t bits = reinterpret_cast<uintptr_t>(io->obs) | reinterpret_cast<uintptr_t>(io->reward) |
+                         reinterpret_cast<uintptr_t>(io->terminated) | reinterpret_cast<uintptr_t>(io->truncated) |
+                         reinterpret_cast<uintptr_t>(io->final_obs);
+  const bool aligned = (bits & 15) == 0 && (reinterpret_cast<uintptr_t>(io->action) & action_align_mask) == 0;
+  return aligned && pitch % 16 == 0 && (b->n_lanes % 16 == 0 || pitch == n16);
+}
+
+}  // namespace carl_host
+
+namespace carl {
+
+// -------------------------------- done-mask compaction ------------------------------
+// Ordered (ascending lane id) compaction of terminated|truncated in two launches:
+//   count: per-block popcount of wave ballots            -> block_counts[nb]
+//   write: block offset = sum of lower blocks' counts; within the block each wave's
+//          offset = sum of lower waves' popcounts, each lane's rank = mbcnt(ballot).
+constexpr int kCompactBlock = 1024;  // 16 waves
+
+__global__ void __launch_bounds__(kCompactBlock) done_count_kernel(const uint8_t* __restrict__ term,
+                                                                    const uint8_t* __restrict__ trunc, int n,
+                                                                    int32_t* __restrict__ block_counts) {
+  __shared__ int wave_counts[kCompactBlock / kWave];
+  const int i = blockIdx.x * kCompactBlock + threadIdx.x;
+  const bool done = (i < n) && ((term[i] | trunc[i]) != 0);
+  const unsigned long long m = ballot(done);
+  if (lane_id() == 0) wave_counts[threadIdx.x / kWave] = __popcll(m);
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    int c = 0;
+#pragma unroll
+    for (int w = 0; w < kCompactBlock / kWave; ++w) c += wave_counts[w];
+    block_counts[blockIdx.x] = c;
+  }
+}
+
+__global__ void __launch_bounds__(kCompactBlock) done_write_kernel(const uint8_t* __restrict__ term,
+                                                                    const uint8_t* __restrict__ trunc, int n,
+                                                                    const int32_t* __restrict__ block_counts,
+                                                                    int32_t* __restrict__ idx_out,
+                                                                    int32_t* __restrict__ count_out) {
+  __shared__ int wave_counts[kCompactBlock / kWave];
+  __shared__ int partial[kCompactBlock / kWave];
+  __shared__ int block_base;
+  // offset of this block = sum of the counts of all lower blocks
+  int acc = 0;
+  for (int k = threadIdx.x; k < (int)blockIdx.x; k += kCompactBlock) acc += block_counts[k];
+#pragma unroll
+  for (int off = kWave / 2; off > 0; off >>= 1) acc += __shfl_down(acc, off);
+  if (lane_id() == 0) partial[threadIdx.x / kWave] = acc;
+  const int i = blockIdx.x * kCompactBlock + threadIdx.x;
+  const bool done = (i < n) && ((term[i] | trunc[i]) != 0);
+  const unsigned long long m = ballot(done);
+  if (lane_id() == 0) wave_counts[threadIdx.x / kWave] = __popcll(m);
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    int base = 0;
+#pragma unroll
+    for (int w = 0; w < kCompactBlock / kWave; ++w) base += partial[w];
+    block_base = base;
+  }
+  __syncthreads();
+  int wave_off = 0;
+  const int wave = threadIdx.x / kWave;
+  for (int w = 0; w < wave; ++w) wave_off += wave_counts[w];
+  if (done) idx_out[block_base + wave_off + prefix_popc(m)] = i;
+  if (blockIdx.x == gridDim.x - 1 && threadIdx.x == 0) {
+    int total = block_base;
+#pragma unroll
+    for (int w = 0; w < kCompactBlock / kWave; ++w) total += wave_counts[w];
+    *count_out = total;
+  }
+}
+
+}  // namespace carl
+
+namespace {
+
+using carl_host::check_launch;
+using carl_host::fail;
+using carl_host::kInfo;
+using carl_host::validate_batch;
+using carl_host::with_classic_family;
 
 int validate_io(const carl_batch_t* b, const carl_step_io_t* io, const char* who) {
   if (io == nullptr) return fail(CARL_ERR_INVALID_ARGUMENT, "%s: io is NULL", who);
@@ -147,22 +231,12 @@ RolloutPlan plan_rollout(const carl_batch_t* b, const carl_step_io_t* io) {
   const int dt = io->action_dtype;
   p.ak = dt == CARL_ACTION_I64 ? 1 : dt == CARL_ACTION_U8 ? carl::kActU8 : dt == CARL_ACTION_F16 ? carl::kActF16
          : dt == CARL_ACTION_BF16 ? carl::kActBF16 : 0;
-  // The staged kernel writes 16-byte pieces of every row: rows must start on 16-byte boundaries (pitch % 16 == 0) and
-  // the columns [n_lanes, n_lanes rounded up to 16) must be the caller's to lose -- they are when the lane count is a
-  // multiple of 16 (there are none) or when the pitch IS that rounded-up count (the padded layout of carl_rollout_pitch).
-  // A wider pitch with an odd lane count is a view into an array whose neighbouring columns belong to someone else:
-  // direct stores.  ... and every array must START on a 16-byte boundary (fresh allocations do; a column view
-  // `array[:, k:]` need not).  The loader wave reads a lane-row of four actions per load: 16 bytes (int32 / float32;
-  // int64: two of them), 4 (uint8), 8 (float16 / bfloat16).
-  const int pitch = row_pitch_of(b, io), n16 = (b->n_lanes + 15) / 16 * 16;
-  const uintptr_t bits = reinterpret_cast<uintptr_t>(io->obs) | reinterpret_cast<uintptr_t>(io->reward) |
-                         reinterpret_cast<uintptr_t>(io->terminated) | reinterpret_cast<uintptr_t>(io->truncated) |
-                         reinterpret_cast<uintptr_t>(io->final_obs);
+  // Other row layouts take direct stores (carl_host::staged_rows).  The loader wave reads a lane-row of four actions per
+  // load: 16 bytes (int32 / float32; int64: two of them), 4 (uint8), 8 (float16 / bfloat16).
   const uintptr_t amask = p.ak == carl::kActU8 ? 3u : p.ak > carl::kActU8 ? 7u : 15u;
-  const bool aligned = (bits & 15) == 0 && (reinterpret_cast<uintptr_t>(io->action) & amask) == 0;
   if (b->flags & CARL_FLAG_ROLLOUT_DIRECT)
     p.variant = CARL_ROLLOUT_DIRECT_FLAG;
-  else if (!(aligned && pitch % 16 == 0 && (b->n_lanes % 16 == 0 || pitch == n16)))
+  else if (!carl_host::staged_rows(b, io, amask))
     p.variant = CARL_ROLLOUT_DIRECT_SHAPE;
   const bool keeps_context = b->selector == CARL_SEL_STATIC || b->selector == CARL_SEL_HOST;
   p.lean = p.variant == CARL_ROLLOUT_STAGED && keeps_context && b->fin_count == nullptr && io->final_obs == nullptr;
@@ -174,9 +248,8 @@ RolloutPlan plan_rollout(const carl_batch_t* b, const carl_step_io_t* io) {
   // (also for tables small enough for LDS: a fused rollout gathers parameters once per launch and on resets, so the
   // global table costs nothing there; the LDS copy pays off when lanes change contexts on reset, below)
   const size_t table_bytes = (size_t)Fam::F * b->n_contexts * sizeof(float);
-  // static LDS of the kernel (Acrobot's fp64 kernels carry the 8 KiB sin/cos table) counts against the 160 KiB too
-  constexpr size_t static_lds = carl::has_tables<Fam>::value ? sizeof(double) * 2 * CARL_SINCOS_TAB_N : 0;
-  const bool table_fits = use_lds_ctx<Fam>(b) && p.lds_bytes + table_bytes + static_lds <= 160 * 1024;
+  const bool table_fits =
+      use_lds_ctx<Fam>(b) && p.lds_bytes + table_bytes + carl::static_lds_bytes<Fam>() <= carl::kCuLdsBytes;
   if (p.lean) {
     // two specialisations of the done path (made for CartPole, whose done path runs on nearly every step; every family
     // opts in: the leaner code also helps the step loop's register allocation): none of the optional features is on,
@@ -335,17 +408,6 @@ int launch_pair(const carl_batch_t* a, const carl_step_io_t* ioa, const carl_bat
   return check_launch("carl_rollout_pair");
 }
 
-#define CARL_DISPATCH(family, CALL)                                   \
-  switch (family) {                                                   \
-    case CARL_CARTPOLE: return CALL(carl::CartPole);                  \
-    case CARL_PENDULUM: return CALL(carl::Pendulum);                  \
-    case CARL_ACROBOT:                                                \
-      return (batch->flags & CARL_FLAG_ACROBOT_FP32) ? CALL(carl::AcrobotFast) : CALL(carl::Acrobot); \
-    case CARL_MOUNTAINCAR: return CALL(carl::MountainCar);            \
-    case CARL_MOUNTAINCAR_CONT: return CALL(carl::MountainCarCont);   \
-    default: return fail(CARL_ERR_INVALID_ARGUMENT, "unknown family %d", family); \
-  }
-
 // ---------------------------- Brax-locomotion families -----------------------------------
 int validate_specs(const carl_feature_spec_t* sd, const carl_feature_spec_t* sh, int n_features, int n_contexts,
                    int ctx_stride, const void* table, const char* who) {
@@ -392,9 +454,9 @@ int carl_family_info(int family, carl_family_info_t* out) {
 
 int carl_reset(const carl_batch_t* batch, const uint8_t* mask, float* obs, void* stream) {
   if (int e = validate_batch(batch, "carl_reset")) return e;
-#define CALL(F) launch_reset<F>(batch, mask, nullptr, nullptr, obs, (hipStream_t)stream)
-  CARL_DISPATCH(batch->family, CALL)
-#undef CALL
+  return with_classic_family(batch, [&](auto fam) {
+    return launch_reset<decltype(fam)>(batch, mask, nullptr, nullptr, obs, (hipStream_t)stream);
+  });
 }
 
 int carl_reset_indexed(const carl_batch_t* batch, const int32_t* idx, const int32_t* count, float* obs,
@@ -402,26 +464,24 @@ int carl_reset_indexed(const carl_batch_t* batch, const int32_t* idx, const int3
   if (int e = validate_batch(batch, "carl_reset_indexed")) return e;
   if (idx == nullptr || count == nullptr)
     return fail(CARL_ERR_INVALID_ARGUMENT, "carl_reset_indexed: idx/count is NULL");
-#define CALL(F) launch_reset<F>(batch, nullptr, idx, count, obs, (hipStream_t)stream)
-  CARL_DISPATCH(batch->family, CALL)
-#undef CALL
+  return with_classic_family(batch, [&](auto fam) {
+    return launch_reset<decltype(fam)>(batch, nullptr, idx, count, obs, (hipStream_t)stream);
+  });
 }
 
 int carl_step(const carl_batch_t* batch, const carl_step_io_t* io, void* stream) {
   if (int e = validate_batch(batch, "carl_step")) return e;
   if (int e = validate_io(batch, io, "carl_step")) return e;
-#define CALL(F) launch_step<F>(batch, io, -1, (hipStream_t)stream)
-  CARL_DISPATCH(batch->family, CALL)
-#undef CALL
+  return with_classic_family(batch,
+                             [&](auto fam) { return launch_step<decltype(fam)>(batch, io, -1, (hipStream_t)stream); });
 }
 
 int carl_rollout(const carl_batch_t* batch, const carl_step_io_t* io, int32_t n_steps, void* stream) {
   if (int e = validate_batch(batch, "carl_rollout")) return e;
   if (int e = validate_io(batch, io, "carl_rollout")) return e;
   if (n_steps < 0) return fail(CARL_ERR_INVALID_ARGUMENT, "carl_rollout: n_steps %d < 0", n_steps);
-#define CALL(F) launch_step<F>(batch, io, n_steps, (hipStream_t)stream)
-  CARL_DISPATCH(batch->family, CALL)
-#undef CALL
+  return with_classic_family(batch,
+                             [&](auto fam) { return launch_step<decltype(fam)>(batch, io, n_steps, (hipStream_t)stream); });
 }
 
 int carl_rollout_pair(const carl_batch_t* batch_a, const carl_step_io_t* io_a, const carl_batch_t* batch_b,
@@ -469,9 +529,7 @@ int carl_rollout_variant_io(const carl_batch_t* batch, const carl_step_io_t* io)
     return CARL_ERR_INVALID_ARGUMENT;
   }
   const carl_step_io_t dense{};  // no io: dense rows, arrays on 16-byte boundaries
-#define CALL(F) plan_rollout<F>(batch, io != nullptr ? io : &dense).variant
-  CARL_DISPATCH(batch->family, CALL)
-#undef CALL
+  return with_classic_family(batch, [&](auto fam) { return plan_rollout<decltype(fam)>(batch, io != nullptr ? io : &dense).variant; });
 }
 
 int32_t carl_rollout_pitch(int32_t n_lanes) { return n_lanes <= 0 ? 0 : (n_lanes + 15) / 16 * 16; }

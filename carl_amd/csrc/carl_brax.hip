@@ -260,7 +260,7 @@ int launch_brax(const carl_batch_t* b, const carl_brax_sys_t* sd, const carl_bra
                             (size_t)carl::brax::kSphRecBytes * (CARL_BRAX_MAX_COLL + 1) +
                             sizeof(int) * carl::brax::kMaxWavesPerWg3;
   const size_t wave_bytes = lay.bytes(envs);
-  if (wave_bytes + static_lds > 160 * 1024)
+  if (wave_bytes + static_lds > carl::kCuLdsBytes)
     return fail(CARL_ERR_UNSUPPORTED, "%s: model needs %zu B of LDS per wavefront", who, wave_bytes);
   // Registers allow 2 (multi-hinge / task models) or 3 wavefronts per SIMD = 8 / 12 per CU (brax_kernels.hip.h:
   // CARL_BRAX_WAVES_PER_EU): take the SMALLEST
@@ -283,9 +283,9 @@ int launch_brax(const carl_batch_t* b, const carl_brax_sys_t* sd, const carl_bra
   int W = 1, best = 0;
   for (int w = 1; w <= max_w; ++w) {
     const size_t wg = (size_t)w * wave_bytes + static_lds;
-    if (wg > 160 * 1024) break;
+    if (wg > carl::kCuLdsBytes) break;
     if (w > 1 && (long long)(w - 1) * envs >= b->n_lanes) break;  // a small batch: no empty wavefronts
-    int per_cu = (int)((160 * 1024) / wg) * w;                     // resident wavefronts per CU, LDS-wise
+    int per_cu = (int)(carl::kCuLdsBytes / wg) * w;                    // resident wavefronts per CU, LDS-wise
     const int waves_per_eu = c.f32 ? CARL_BRAX_WAVES_PER_EU_F32(c.task) : CARL_BRAX_WAVES_PER_EU(c.task);
     if (per_cu > 4 * waves_per_eu) per_cu = 4 * waves_per_eu;
     per_cu -= per_cu % w;  // whole workgroups

@@ -10,6 +10,7 @@
 namespace carl {
 
 constexpr int kWave = 64;
+constexpr size_t kCuLdsBytes = 160 * 1024;  // LDS of one compute unit: a workgroup's static + dynamic LDS must fit it
 
 // ---- Philox4x32-10 (Salmon et al. SC'11, Random123 constants) ------------------
 // Counter-based: a lane's draw is a pure function of (seed, global lane id,

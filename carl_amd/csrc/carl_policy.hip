@@ -66,22 +66,6 @@ int validate_policy(const carl_batch_t* b, const carl_policy_t* p, const carl_fa
   return 0;
 }
 
-int validate_batch(const carl_batch_t* b) {
-  const char* who = "carl_rollout_policy";
-  if (b->n_lanes < 0) return fail(CARL_ERR_INVALID_ARGUMENT, "%s: n_lanes %d < 0", who, b->n_lanes);
-  if (b->n_contexts <= 0 || b->ctx_stride < b->n_contexts)
-    return fail(CARL_ERR_INVALID_ARGUMENT, "%s: n_contexts %d / ctx_stride %d invalid", who, b->n_contexts, b->ctx_stride);
-  if (b->selector < CARL_SEL_STATIC || b->selector > CARL_SEL_HOST)
-    return fail(CARL_ERR_INVALID_ARGUMENT, "%s: unknown selector %d", who, b->selector);
-  if (!b->state || !b->elapsed || !b->ctx_idx || !b->episode || !b->n_calls || !b->ep_return || !b->ctx_table)
-    return fail(CARL_ERR_INVALID_ARGUMENT, "%s: a required batch pointer is NULL", who);
-  if (b->n_ctx_obs < 0 || b->n_ctx_obs > CARL_MAX_CTX_OBS || (b->n_ctx_obs > 0 && b->ctx_obs == nullptr))
-    return fail(CARL_ERR_INVALID_ARGUMENT, "%s: n_ctx_obs %d / ctx_obs invalid", who, b->n_ctx_obs);
-  if (b->fin_count != nullptr && (b->fin_capacity <= 0 || !b->fin_lane || !b->fin_return || !b->fin_length))
-    return fail(CARL_ERR_INVALID_ARGUMENT, "%s: finished-episode log is incomplete", who);
-  return 0;
-}
-
 // transitions mode: the staged layout of carl_rollout (see include/carl_amd.h: carl_step_io_t::row_pitch)
 int validate_io(const carl_batch_t* b, const carl_step_io_t* io, const carl_family_info_t& fi) {
   const char* who = "carl_rollout_policy";
@@ -93,22 +77,23 @@ int validate_io(const carl_batch_t* b, const carl_step_io_t* io, const carl_fami
                 fi.action_is_discrete ? "int32 (CARL_ACTION_I32)" : "float32 (CARL_ACTION_F32)");
   if (io->row_pitch != 0 && io->row_pitch < b->n_lanes)
     return fail(CARL_ERR_INVALID_ARGUMENT, "%s: io.row_pitch %d < n_lanes %d", who, io->row_pitch, b->n_lanes);
-  const int pitch = io->row_pitch > 0 ? io->row_pitch : b->n_lanes, n16 = (b->n_lanes + 15) / 16 * 16;
-  const uintptr_t bits = reinterpret_cast<uintptr_t>(io->obs) | reinterpret_cast<uintptr_t>(io->reward) |
-                         reinterpret_cast<uintptr_t>(io->terminated) | reinterpret_cast<uintptr_t>(io->truncated) |
-                         reinterpret_cast<uintptr_t>(io->final_obs) | reinterpret_cast<uintptr_t>(io->action);
-  if ((bits & 15) != 0 || pitch % 16 != 0 || !(b->n_lanes % 16 == 0 || pitch == n16))
+  if (!carl_host::staged_rows(b, io, 15))
     return fail(CARL_ERR_UNSUPPORTED, "%s: rows of %d lanes for %d lanes: the closed-loop rollout writes the staged layout "
                 "only (pitch %% 16 == 0 and n_lanes %% 16 == 0 or pitch == carl_rollout_pitch(n_lanes), arrays on 16-byte "
-                "boundaries)", who, pitch, b->n_lanes);
+                "boundaries)", who, io->row_pitch > 0 ? io->row_pitch : b->n_lanes, b->n_lanes);
   return 0;
 }
 
-using policy_kern_t = void (*)(carl_batch_t, carl_step_io_t, carl_policy_t, int, carl_policy_summary_t, int);
+// a policy_rollout_kernel instance and the dynamic LDS it takes
+struct PolicyKernel {
+  void (*fn)(carl_batch_t, carl_step_io_t, carl_policy_t, int, carl_policy_summary_t, int);
+  size_t lds;
+};
 
 template <class Fam, int H>
-policy_kern_t pick(bool summary) {
-  return summary ? carl::policy_rollout_kernel<Fam, H, true> : carl::policy_rollout_kernel<Fam, H, false>;
+PolicyKernel policy_kernel(bool summary) {
+  if (summary) return {carl::policy_rollout_kernel<Fam, H, true>, carl::policy_lds_bytes<Fam, H, true>()};
+  return {carl::policy_rollout_kernel<Fam, H, false>, carl::policy_lds_bytes<Fam, H, false>()};
 }
 
 template <class Fam>
@@ -119,13 +104,11 @@ int launch_policy(const carl_batch_t* b, const carl_policy_t* p, const carl_step
   for (int l = 0; l < p->n_hidden; ++l) wmax = wmax > p->width[l] ? wmax : p->width[l];
   // the hidden width is padded to an instantiated class: 0 (a linear policy), 32, 64
   const int H = p->n_hidden == 0 ? 0 : wmax <= 32 ? 32 : 64;
-  policy_kern_t kern = H == 0 ? pick<Fam, 0>(summary) : H == 32 ? pick<Fam, 32>(summary) : pick<Fam, 64>(summary);
-  const size_t lds = H == 0 ? (summary ? carl::policy_lds_bytes<Fam, 0, true>() : carl::policy_lds_bytes<Fam, 0, false>())
-                     : H == 32 ? (summary ? carl::policy_lds_bytes<Fam, 32, true>() : carl::policy_lds_bytes<Fam, 32, false>())
-                               : (summary ? carl::policy_lds_bytes<Fam, 64, true>() : carl::policy_lds_bytes<Fam, 64, false>());
-  static_assert(carl::policy_lds_bytes<Fam, 64, false>() + carl::policy_static_lds<Fam>() <= 160 * 1024,
+  const PolicyKernel k = H == 0 ? policy_kernel<Fam, 0>(summary) : H == 32 ? policy_kernel<Fam, 32>(summary)
+                                                                  : policy_kernel<Fam, 64>(summary);
+  static_assert(carl::policy_lds_bytes<Fam, 64, false>() + carl::static_lds_bytes<Fam>() <= carl::kCuLdsBytes,
                 "the closed-loop rollout's LDS does not fit a compute unit");
-  if (int e = carl_host::ensure_dynamic_lds(reinterpret_cast<const void*>(kern), lds, "carl_rollout_policy")) return e;
+  if (int e = carl_host::ensure_dynamic_lds(reinterpret_cast<const void*>(k.fn), k.lds, "carl_rollout_policy")) return e;
   carl_step_io_t io_r{};
   if (!summary) {
     io_r = *io;
@@ -134,7 +117,7 @@ int launch_policy(const carl_batch_t* b, const carl_policy_t* p, const carl_step
   const carl_policy_summary_t sum_r = sum != nullptr ? *sum : carl_policy_summary_t{nullptr, nullptr, nullptr};
   const int grid = (b->n_lanes + carl::kPolicyLanes - 1) / carl::kPolicyLanes;
   const int threads = summary ? carl::kPolicyThreadsSummary : carl::kPolicyThreadsTransitions;
-  hipLaunchKernelGGL(kern, dim3(grid), dim3(threads), lds, s, *b, io_r, *p, set_floats_of(p), sum_r, n_steps);
+  hipLaunchKernelGGL(k.fn, dim3(grid), dim3(threads), k.lds, s, *b, io_r, *p, set_floats_of(p), sum_r, n_steps);
   return check_launch("carl_rollout_policy");
 }
 
@@ -156,9 +139,9 @@ int carl_rollout_policy(const carl_batch_t* batch, const carl_policy_t* policy_h
   if (batch->family >= CARL_N_FAMILIES)
     return fail(CARL_ERR_INVALID_ARGUMENT, "carl_rollout_policy: family %d is a Brax family -- the closed-loop rollout "
                 "covers the classic-control families only", batch->family);
+  if (int e = carl_host::validate_batch(batch, "carl_rollout_policy")) return e;
   carl_family_info_t fi;
   if (int e = carl_family_info(batch->family, &fi)) return e;
-  if (int e = validate_batch(batch)) return e;
   if (int e = validate_policy(batch, policy_host, fi)) return e;
   if (n_steps < 0) return fail(CARL_ERR_INVALID_ARGUMENT, "carl_rollout_policy: n_steps %d < 0", n_steps);
   if (io == nullptr) {
@@ -184,18 +167,9 @@ int carl_rollout_policy(const carl_batch_t* batch, const carl_policy_t* policy_h
         return fail((int)e, "carl_rollout_policy: hipMemsetAsync: %s", hipGetErrorString(e));
     return 0;
   }
-  hipStream_t s = (hipStream_t)stream;
-  switch (batch->family) {
-    case CARL_CARTPOLE: return launch_policy<carl::CartPole>(batch, policy_host, io, n_steps, summary_out, s);
-    case CARL_PENDULUM: return launch_policy<carl::Pendulum>(batch, policy_host, io, n_steps, summary_out, s);
-    case CARL_ACROBOT:
-      return (batch->flags & CARL_FLAG_ACROBOT_FP32)
-                 ? launch_policy<carl::AcrobotFast>(batch, policy_host, io, n_steps, summary_out, s)
-                 : launch_policy<carl::Acrobot>(batch, policy_host, io, n_steps, summary_out, s);
-    case CARL_MOUNTAINCAR: return launch_policy<carl::MountainCar>(batch, policy_host, io, n_steps, summary_out, s);
-    case CARL_MOUNTAINCAR_CONT: return launch_policy<carl::MountainCarCont>(batch, policy_host, io, n_steps, summary_out, s);
-    default: return fail(CARL_ERR_INVALID_ARGUMENT, "carl_rollout_policy: unknown family %d", batch->family);
-  }
+  return carl_host::with_classic_family(batch, [&](auto fam) {
+    return launch_policy<decltype(fam)>(batch, policy_host, io, n_steps, summary_out, (hipStream_t)stream);
+  });
 }
 
 }  // extern "C"

@@ -27,6 +27,7 @@
 
 #include "carl_device.hip.h"
 #include "fast_math.hip.h"
+#include "host_common.hpp"
 
 namespace carl {
 
@@ -711,3 +712,21 @@ struct MountainCarCont {
 };
 
 }  // namespace carl
+
+namespace carl_host {
+
+// The family -> traits dispatch of the classic-control entry points: fn(Fam{}) for the batch's family (Acrobot: the
+// float32 AcrobotFast under CARL_FLAG_ACROBOT_FP32, else the float64 one).
+template <class Fn>
+int with_classic_family(const carl_batch_t* b, Fn&& fn) {
+  switch (b->family) {
+    case CARL_CARTPOLE: return fn(carl::CartPole{});
+    case CARL_PENDULUM: return fn(carl::Pendulum{});
+    case CARL_ACROBOT: return (b->flags & CARL_FLAG_ACROBOT_FP32) ? fn(carl::AcrobotFast{}) : fn(carl::Acrobot{});
+    case CARL_MOUNTAINCAR: return fn(carl::MountainCar{});
+    case CARL_MOUNTAINCAR_CONT: return fn(carl::MountainCarCont{});
+    default: return fail(CARL_ERR_INVALID_ARGUMENT, "unknown family %d", b->family);
+  }
+}
+
+}  // namespace carl_host

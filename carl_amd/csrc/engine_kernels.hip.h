@@ -37,6 +37,12 @@ __device__ __forceinline__ void stage_family_tables() {
   }
 }
 
+// the static LDS those tables take (Acrobot's fp64 kernels: 8 KiB); it counts against kCuLdsBytes with the dynamic LDS
+template <class Fam>
+__host__ __device__ constexpr size_t static_lds_bytes() {
+  return has_tables<Fam>::value ? sizeof(double) * 2 * CARL_SINCOS_TAB_N : 0;
+}
+
 template <bool LDS, int F>
 __device__ __forceinline__ ctx_t<LDS> make_ctx(const carl_batch_t& b, float* lds) {
   if constexpr (LDS) {
@@ -953,6 +959,22 @@ __device__ __forceinline__ void zero_flag_rows(char* out_buf, int l, int which) 
       *reinterpret_cast<vf4*>(out_buf + (size_t)u * SK::kStepBytes + SK::kFlagOff + 16 * l) = vf4{0.0f, 0.0f, 0.0f, 0.0f};
 }
 
+// A staged rollout's compute lane before the first step.  Padding lanes of a ragged last workgroup run as register-only
+// clones of the batch's last lane (valid numbers, so the step loop needs no per-lane predicate and takes no slow math
+// path); `active`: a lane of the batch.
+template <class Fam, class Ctx>
+__device__ __forceinline__ void load_staged_lane(const carl_batch_t& b, const Ctx& ctx, int lane, bool active,
+                                                 LaneRegs<Fam>& r) {
+  const int src = min(lane, b.n_lanes - 1);
+  load_lane<Fam>(b, ctx, src, r);
+  if (!r.episode_valid) {
+    r.episode = b.episode[src];
+    r.episode_valid = true;
+    settle(r.episode);
+  }
+  r.valid = active;
+}
+
 // Preconditions (checked by the host): row pitch % 16 == 0 and >= n_lanes (the last workgroup may be ragged; lanes
 // [n_lanes, pitch) are padding), global context table.
 // LDSCTX (short-episode families under a round-robin / random selector, small tables; chosen by the host):
@@ -1022,16 +1044,7 @@ __device__ __forceinline__ void rollout_staged_body(const carl_batch_t& b, const
     pipe.issue(act, n, n_cols, lane_base, hl, kStageChunk, n_steps);  // in flight across the barrier
     if constexpr (kDeep) pipe_b.issue(act, n, n_cols, lane_base, hl, 2 * kStageChunk, n_steps);
   } else if (compute) {
-    // padding lanes of a ragged last workgroup run as register-only clones of the batch's last lane
-    // (valid numbers, so the step loop needs no per-lane predicate and takes no slow math path)
-    const int src = min(lane, b.n_lanes - 1);
-    load_lane<Fam>(b, ctx, src, r);
-    if (!r.episode_valid) {
-      r.episode = b.episode[src];
-      r.episode_valid = true;
-      settle(r.episode);
-    }
-    r.valid = active;
+    load_staged_lane<Fam>(b, ctx, lane, active, r);
   }
   __syncthreads();
   // One chunk loop PER ROLE (the roles are wavefront-uniform: `wave` comes from readfirstlane), each with its own
@@ -1209,68 +1222,6 @@ rollout_staged_pair_kernel(const carl_batch_t ba, const carl_step_io_t ioa, cons
   else
     rollout_staged_body<FamB, false, true, false, false, false, ARB && dense_done_of<FamB>::value, kPairChunk>(
         bb, iob, n_steps, (int)blockIdx.x - grid_a, lds_dyn);
-}
-
-// -------------------------------- done-mask compaction ------------------------------
-// Ordered (ascending lane id) compaction of terminated|truncated in two launches:
-//   count: per-block popcount of wave ballots            -> block_counts[nb]
-//   write: block offset = sum of lower blocks' counts; within the block each wave's
-//          offset = sum of lower waves' popcounts, each lane's rank = mbcnt(ballot).
-constexpr int kCompactBlock = 1024;  // 16 waves
-
-__global__ void __launch_bounds__(kCompactBlock) done_count_kernel(const uint8_t* __restrict__ term,
-                                                                    const uint8_t* __restrict__ trunc, int n,
-                                                                    int32_t* __restrict__ block_counts) {
-  __shared__ int wave_counts[kCompactBlock / kWave];
-  const int i = blockIdx.x * kCompactBlock + threadIdx.x;
-  const bool done = (i < n) && ((term[i] | trunc[i]) != 0);
-  const unsigned long long m = ballot(done);
-  if (lane_id() == 0) wave_counts[threadIdx.x / kWave] = __popcll(m);
-  __syncthreads();
-  if (threadIdx.x == 0) {
-    int c = 0;
-#pragma unroll
-    for (int w = 0; w < kCompactBlock / kWave; ++w) c += wave_counts[w];
-    block_counts[blockIdx.x] = c;
-  }
-}
-
-__global__ void __launch_bounds__(kCompactBlock) done_write_kernel(const uint8_t* __restrict__ term,
-                                                                    const uint8_t* __restrict__ trunc, int n,
-                                                                    const int32_t* __restrict__ block_counts,
-                                                                    int32_t* __restrict__ idx_out,
-                                                                    int32_t* __restrict__ count_out) {
-  __shared__ int wave_counts[kCompactBlock / kWave];
-  __shared__ int partial[kCompactBlock / kWave];
-  __shared__ int block_base;
-  // offset of this block = sum of the counts of all lower blocks
-  int acc = 0;
-  for (int k = threadIdx.x; k < (int)blockIdx.x; k += kCompactBlock) acc += block_counts[k];
-#pragma unroll
-  for (int off = kWave / 2; off > 0; off >>= 1) acc += __shfl_down(acc, off);
-  if (lane_id() == 0) partial[threadIdx.x / kWave] = acc;
-  const int i = blockIdx.x * kCompactBlock + threadIdx.x;
-  const bool done = (i < n) && ((term[i] | trunc[i]) != 0);
-  const unsigned long long m = ballot(done);
-  if (lane_id() == 0) wave_counts[threadIdx.x / kWave] = __popcll(m);
-  __syncthreads();
-  if (threadIdx.x == 0) {
-    int base = 0;
-#pragma unroll
-    for (int w = 0; w < kCompactBlock / kWave; ++w) base += partial[w];
-    block_base = base;
-  }
-  __syncthreads();
-  int wave_off = 0;
-  const int wave = threadIdx.x / kWave;
-  for (int w = 0; w < wave; ++w) wave_off += wave_counts[w];
-  if (done) idx_out[block_base + wave_off + prefix_popc(m)] = i;
-  if (blockIdx.x == gridDim.x - 1 && threadIdx.x == 0) {
-    int total = block_base;
-#pragma unroll
-    for (int w = 0; w < kCompactBlock / kWave; ++w) total += wave_counts[w];
-    *count_out = total;
-  }
 }
 
 }  // namespace carl

@@ -25,14 +25,7 @@
 // result, only the instruction count (up to the sign of a zero sum: fma(0, 0, -0) = +0).
 #pragma once
 
-// engine_kernels.hip.h also DEFINES the two non-template done-compaction kernels, which carl_amd.hip owns: in this
-// translation unit they are compiled under names of their own (unused here), so that the library links without
-// touching the header the open-loop kernels are built from.
-#define done_count_kernel policy_unit_done_count_kernel
-#define done_write_kernel policy_unit_done_write_kernel
 #include "engine_kernels.hip.h"
-#undef done_count_kernel
-#undef done_write_kernel
 
 namespace carl {
 
@@ -55,23 +48,16 @@ struct PolicyLayout {
   static constexpr size_t kBytes = (size_t)kFloats * sizeof(float);
 };
 
-// transitions mode: steps per LDS record buffer -- 8 like carl_rollout where the records, the action column, the
-// largest weight set and the family's static tables fit 160 KiB; 4 otherwise (Acrobot: 24-byte observations)
-template <class Fam>
-__host__ __device__ constexpr size_t policy_records_bytes(int chunk) {
-  return (size_t)2 * chunk * (LdsSink<Fam>::kStepBytes + kPolicyLanes * sizeof(float));
-}
-template <class Fam>
-__host__ __device__ constexpr size_t policy_static_lds() {
-  return has_tables<Fam>::value ? sizeof(double) * 2 * CARL_SINCOS_TAB_N : 0;
-}
+// transitions mode: steps per LDS record buffer -- 8 like carl_rollout where the records and the action column (the
+// staged rollout's buffers), the largest weight set and the family's static tables fit a compute unit; 4 otherwise
+// (Acrobot: 24-byte observations)
 template <class Fam>
 __host__ __device__ constexpr int policy_chunk() {
-  return policy_records_bytes<Fam>(8) + PolicyLayout<Fam, 64>::kBytes + policy_static_lds<Fam>() <= 160 * 1024 ? 8 : 4;
+  return rollout_staged_lds_bytes<Fam, 8>() + PolicyLayout<Fam, 64>::kBytes + static_lds_bytes<Fam>() <= kCuLdsBytes ? 8 : 4;
 }
 template <class Fam, int H, bool SUMMARY>
 __host__ __device__ constexpr size_t policy_lds_bytes() {
-  return PolicyLayout<Fam, H>::kBytes + (SUMMARY ? 0 : policy_records_bytes<Fam>(policy_chunk<Fam>()));
+  return PolicyLayout<Fam, H>::kBytes + (SUMMARY ? 0 : rollout_staged_lds_bytes<Fam, policy_chunk<Fam>()>());
 }
 
 // Copy weight set `set` from its packed form (include/carl_amd.h) into the padded LDS layout; every thread of the
@@ -302,15 +288,7 @@ __global__ void __launch_bounds__(SUMMARY ? kPolicyThreadsSummary : kPolicyThrea
 
   if (compute) {
     LaneRegs<Fam> r{};
-    // padding lanes of a ragged last workgroup: register-only clones of the batch's last lane (rollout_staged_body)
-    const int src = min(lane, b.n_lanes - 1);
-    load_lane<Fam>(b, ctx, src, r);
-    if (!r.episode_valid) {
-      r.episode = b.episode[src];
-      r.episode_valid = true;
-      settle(r.episode);
-    }
-    r.valid = active;
+    load_staged_lane<Fam>(b, ctx, lane, active, r);
     float* const final_base = (!SUMMARY && io.final_obs != nullptr && active) ? io.final_obs + (size_t)lane * Fam::D : nullptr;
     const int n_ctx = pol.n_ctx, n_hidden = pol.n_hidden, act = pol.activation;
     const int w0 = pol.width[0], w1 = pol.width[1];  // (w1: read only when n_hidden == 2)

@@ -554,18 +554,9 @@ class VecEngine:
         repeating the last lane's action (the padding lanes run as clones of that lane: valid numbers)."""
         if out["reward"].shape[0] < T:
             raise ValueError("rollout output buffers are shorter than the action sequence")
-        n, D = self.n, self.D
+        n = self.n
         P = max(n, int(out["reward"].stride(0))) if out["reward"].dim() == 2 else n  # (a one-row buffer may carry any stride)
-        for k, tail in (("obs", (D,)), ("reward", ()), ("terminated", ()), ("truncated", ()), ("final_obs", (D,))):
-            t = out.get(k)
-            if t is None:
-                continue
-            inner = int(np.prod(tail, dtype=np.int64)) if tail else 1
-            want = (P * inner, inner, 1) if tail else (P, 1)
-            if tuple(t.shape[1:]) != (n,) + tail or P < n or any(
-                    sz > 1 and st != w for sz, st, w in zip(t.shape, t.stride(), want)):
-                raise ValueError(f"rollout output '{k}': shape {tuple(t.shape)} / strides {tuple(t.stride())} do not form "
-                                 f"[T, {n}{', ' + str(D) if tail else ''}] rows of one common pitch ({P} lanes)")
+        self._check_rows("rollout", out, ("obs", "reward", "terminated", "truncated", "final_obs"), P)
         io = _lib.StepIO()
         if P != n:
             a = self._pad_action_rows(a, T, P)
@@ -577,6 +568,23 @@ class VecEngine:
         io.branch_sig = _ptr(out.get("branch_sig"))
         self._rollout_actions = a  # (keeps a padded copy alive until the launch has been enqueued and beyond)
         return io
+
+    def _check_rows(self, who: str, out: dict, keys, P: int, min_rows: int | None = None, device=None) -> None:
+        """ValueError unless each of ``out[keys]`` that is present is ``[T, N]`` (``[T, N, D]``: obs, final_obs) rows of
+        pitch ``P`` lanes -- with ``T >= min_rows`` and on ``device`` when those are given."""
+        n, D = self.n, self.D
+        for k in keys:
+            t = out.get(k)
+            if t is None:
+                continue
+            tail = (D,) if k in ("obs", "final_obs") else ()
+            want = (P * D, D, 1) if tail else (P, 1)
+            if t.dim() == 0 or t.shape[0] < (min_rows or 0) or tuple(t.shape[1:]) != (n,) + tail or (
+                    device is not None and t.device != device) or any(
+                    sz > 1 and st != w for sz, st, w in zip(t.shape, t.stride(), want)):
+                rows = "T" if min_rows is None else f">= {min_rows}"
+                raise ValueError(f"{who} output '{k}': shape {tuple(t.shape)} / strides {tuple(t.stride())} do not form "
+                                 f"[{rows}, {n}{', ' + str(D) if tail else ''}] rows of one common pitch ({P} lanes)")
 
     def _pad_action_rows(self, a: torch.Tensor, T: int, P: int) -> torch.Tensor:
         key = (T, P, a.dtype)
@@ -651,22 +659,13 @@ class VecEngine:
         included, must be rows of one common pitch (``alloc_rollout``'s layout)."""
         if "action" not in out:
             raise ValueError("rollout_policy output needs an 'action' [T, N] buffer")
-        n, D = self.n, self.D
+        n = self.n
         P = max(n, int(out["reward"].stride(0))) if out["reward"].dim() == 2 else n
         adt = torch.int32 if self.info.action_is_discrete else torch.float32
         if out["action"].dtype != adt:
             raise ValueError(f"rollout_policy 'action' buffer must be {adt} for this family")
-        for k, tail in (("obs", (D,)), ("reward", ()), ("terminated", ()), ("truncated", ()), ("final_obs", (D,)),
-                        ("action", ())):
-            t = out.get(k)
-            if t is None:
-                continue
-            inner = int(np.prod(tail, dtype=np.int64)) if tail else 1
-            want = (P * inner, inner, 1) if tail else (P, 1)
-            if t.shape[0] < T or tuple(t.shape[1:]) != (n,) + tail or t.device != self.device or any(
-                    sz > 1 and st != w for sz, st, w in zip(t.shape, t.stride(), want)):
-                raise ValueError(f"rollout_policy output '{k}': shape {tuple(t.shape)} / strides {tuple(t.stride())} do "
-                                 f"not form [>= {T}, {n}{', ' + str(D) if tail else ''}] rows of one common pitch ({P} lanes)")
+        self._check_rows("rollout_policy", out, ("obs", "reward", "terminated", "truncated", "final_obs", "action"), P, T,
+                         self.device)
         io = _lib.StepIO()
         io.row_pitch = P if P != n else 0
         io.action = _ptr(out["action"])

@@ -368,9 +368,10 @@ typedef struct carl_policy_summary {
  *    engine state ends exactly as after a transitions-mode launch.  A summary (in either mode) needs
  *    CARL_FLAG_AUTORESET, else CARL_ERR_UNSUPPORTED: without auto-reset a finished lane reports done on every later
  *    step, and its one episode would be counted on each of them.
- * summary_out is optional in transitions mode (then both are written).  Bad arguments -- widths over their limits, a
- * head width that is not n_actions (discrete) or 1 (Box), a Brax family, a bad lanes_per_set, a context row >= F --
- * return CARL_ERR_INVALID_ARGUMENT before anything is enqueued. */
+ * summary_out is optional in transitions mode (then both are written).  The batch is validated exactly as carl_rollout
+ * validates it (same checks, same messages; e.g. a ctx_obs_feat[k] >= F is refused).  Bad arguments -- those batch
+ * checks, widths over their limits, a head width that is not n_actions (discrete) or 1 (Box), a Brax family, a bad
+ * lanes_per_set, a context row >= F -- return CARL_ERR_INVALID_ARGUMENT before anything is enqueued. */
 int carl_rollout_policy(const carl_batch_t* batch, const carl_policy_t* policy_host, const carl_step_io_t* io,
                         int32_t n_steps, const carl_policy_summary_t* summary_out, void* stream);
 int32_t carl_policy_lane_quantum(void); /* lanes_per_set must be a positive multiple of this (256) */

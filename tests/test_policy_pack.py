@@ -147,12 +147,19 @@ def test_python_refusals():
         MLPPolicy.for_env(eng, rand_layers(rng, [5, 2]), context_features=[5])
 
 
-def _batch(family=_lib.CARTPOLE, n=1000):
-    """A batch whose device pointers are never dereferenced: every call below is refused on the host first."""
+def _batch(family=_lib.CARTPOLE, n=1000, **kw):
+    """A batch whose device pointers are never dereferenced: every call below is refused on the host first.  kw: other
+    batch fields (ctx_obs_feat: a sequence)."""
     b = _lib.Batch()
     b.family, b.n_lanes, b.n_contexts, b.ctx_stride = family, n, 4, 4
     for f in ("state", "elapsed", "ctx_idx", "episode", "n_calls", "ep_return", "ctx_table"):
         setattr(b, f, 0x1000)
+    for k, v in kw.items():
+        if k == "ctx_obs_feat":
+            for i, f in enumerate(v):
+                b.ctx_obs_feat[i] = f
+        else:
+            setattr(b, k, v)
     return b
 
 
@@ -188,6 +195,9 @@ def _policy(**kw):
     ("head kind", {}, {"head": _lib.POLICY_HEAD_BOX}, b"head kind"),
     ("activation", {}, {"activation": 7}, b"unknown activation"),
     ("no params", {}, {"params": None}, b"params is NULL"),
+    # the batch checks are carl_rollout's: a context observation feature outside the context table
+    ("context observation feature >= F", {"n_ctx_obs": 1, "ctx_obs": 0x4000, "ctx_obs_feat": (8,)}, {},
+     b"ctx_obs_feat[0] = 8"),
 ])
 def test_c_entry_point_refuses(case, batch_kw, pol_kw, msg):
     lib = _lib.load()
