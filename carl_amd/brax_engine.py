@@ -200,10 +200,6 @@ class BraxVecEngine(VecEngine):
         n = self.lib.carl_brax_lane_widths(C.byref(self.sys), int(self.b.flags), out, 16)
         return [int(out[i]) for i in range(n)]
 
-    _PROBE_SAVED = ("state", "elapsed", "ctx_idx", "episode", "n_calls", "ep_return", "last_return", "last_length",
-                    "episodes_done", "obs", "ctx_obs", "reward", "terminated", "truncated", "done", "final_obs",
-                    "goal_pos", "success", "fin_count", "first_state", "branch_sig")
-
     def autotune(self, n_steps: int = 2, reps: int = 2, both_classes: bool = True) -> int:
         """Time ``carl_brax_rollout`` on THIS batch for every launchable lane-group width and keep
         the fastest (``sys.lanes_per_env``).  The width is a pure scheduling choice -- results are
@@ -226,8 +222,7 @@ class BraxVecEngine(VecEngine):
         return best
 
     def _probe_widths(self, n_steps: int, reps: int) -> int:
-        saved = {k: getattr(self, k).clone() for k in self._PROBE_SAVED
-                 if isinstance(getattr(self, k, None), torch.Tensor)}
+        saved = self.snapshot()
         width0, tuning0 = int(self.sys.lanes_per_env), getattr(self, "_tuning", False)
         lo, hi = float(min(self.sys.act_lo[: self.sys.n_act])), float(max(self.sys.act_hi[: self.sys.n_act]))
         gen = torch.Generator(device=self.device).manual_seed(0x5EED)
@@ -263,8 +258,7 @@ class BraxVecEngine(VecEngine):
             self._tuned[n_steps >= 4] = best  # per launch-length class (_shape_for)
         finally:
             self._tuning = tuning0
-            for k, v in saved.items():
-                getattr(self, k).copy_(v)
+            self.restore(saved)
         return best
 
     def reset_indexed(self, idx, count):

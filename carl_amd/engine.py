@@ -9,7 +9,7 @@ library behind include/carl_amd.h.  No CPU fallback exists.
 from __future__ import annotations
 
 import ctypes as C
-from typing import Sequence
+from typing import NamedTuple, Sequence
 
 import numpy as np
 import torch
@@ -31,6 +31,16 @@ def _ptr(t: torch.Tensor | None) -> int | None:
 _raw_stream = getattr(torch._C, "_cuda_getCurrentRawStream", None) or (
     lambda idx: torch.cuda.current_stream(idx).cuda_stream)
 _current_device = getattr(torch._C, "_cuda_getDevice", None) or torch.cuda.current_device
+
+
+class _PreparedRollout(NamedTuple):
+    """A ``rollout`` up to its launch (``VecEngine._prepare_rollout``): actions as converted, output buffers, the
+    ``carl_step_io_t`` over both, and the step count."""
+    a: torch.Tensor
+    dt: int
+    out: dict
+    io: "_lib.StepIO"
+    T: int
 
 
 class CapturedStep:
@@ -461,10 +471,12 @@ class VecEngine:
 
     # ------------------------------------------------------------------ replayable step (hipGraph)
     def snapshot(self) -> dict:
-        """Copies of every buffer a launch can change (state, counters, bookkeeping, step outputs)."""
+        """Copies of every buffer a launch can change (state, counters, bookkeeping, step outputs): the one list of them,
+        used by ``capture_step``'s warm-up and ``BraxVecEngine.autotune``'s probes."""
         names = ["state", "elapsed", "ctx_idx", "episode", "n_calls", "ep_return", "last_return", "last_length",
                  "episodes_done", "obs", "reward", "terminated", "truncated", "done", "final_obs", "ctx_obs"]
-        names += [k for k in ("goal_pos", "success", "fin_count", "first_state") if getattr(self, k, None) is not None]
+        names += [k for k in ("goal_pos", "success", "fin_count", "first_state", "branch_sig")
+                  if getattr(self, k, None) is not None]
         return {k: getattr(self, k).clone() for k in names}
 
     def restore(self, snap: dict) -> None:
@@ -520,54 +532,85 @@ class VecEngine:
         one byte per lane-step instead of four on the launch's only per-step read stream (CartPole x 65 536: +15 %
         env-steps/s); Box families: float32, or ``torch.float16`` / ``torch.bfloat16`` (widened exactly).  Same transitions
         bit for bit as the wide launch fed the same values."""
+        return self._launch_rollout(self._prepare_rollout(actions, out))
+
+    def _prepare_rollout(self, actions, out: dict | None) -> _PreparedRollout:
+        """Everything ``rollout`` does before its launch, done once: the actions converted (narrow formats kept), the output
+        buffers (``alloc_rollout``'s when none are given) and the ``carl_step_io_t`` over them."""
         T = int(actions.shape[0])
         a, dt = self._action_tensor(actions, (T,), allow_narrow=True)
         if out is None:
             out = self.alloc_rollout(T)
-        io = self._rollout_io(a, dt, out, T)
+        return _PreparedRollout(a, dt, out, self._rollout_io(a, dt, out, T), T)
+
+    def _launch_rollout(self, r: _PreparedRollout) -> dict:
+        """The launch of a prepared ``rollout`` on the current stream -> its output dict."""
         if self._has_direct_kernel and not self._warned_direct and \
-                self.lib.carl_rollout_variant_io(self._b_ref, C.byref(io)) == _lib.ROLLOUT_DIRECT_SHAPE:
+                self.lib.carl_rollout_variant_io(self._b_ref, C.byref(r.io)) == _lib.ROLLOUT_DIRECT_SHAPE:
             import warnings
 
             self._warned_direct = True
-            warnings.warn(f"carl_rollout: {self.n} lanes in rows {io.row_pitch or self.n} lanes long (not a multiple of 16, or "
-                          "a view into a wider array, or an array that does not start on a 16-byte boundary) -- this launch "
+            warnings.warn(f"carl_rollout: {self.n} lanes in rows {r.io.row_pitch or self.n} lanes long (not a multiple of 16, "
+                          "or a view into a wider array, or an array that does not start on a 16-byte boundary) -- this launch "
                           "takes the direct-store kernel (~50 % slower than the staged one; same results).  Use "
                           "alloc_rollout()'s buffers (rows padded to a multiple of 16) for the fast path.",
-                          RuntimeWarning, stacklevel=2)
+                          RuntimeWarning, stacklevel=3)
         with torch.cuda.device(self.device):
-            code = self._c_rollout(io, T)
-            if code == _lib.ERR_UNSUPPORTED and dt in (_lib.ACTION_U8, _lib.ACTION_F16, _lib.ACTION_BF16):
+            code = self._c_rollout(r.io, r.T)
+            if code == _lib.ERR_UNSUPPORTED and r.dt in (_lib.ACTION_U8, _lib.ACTION_F16, _lib.ACTION_BF16):
                 # the narrow formats are read by the lean staged rollout only (moving selectors, the finished-episode
                 # log, terminal observations and dense rows of an odd lane count take kernels that read int32 /
                 # float32): widen once, same results
-                a, dt = self._action_tensor(a.to(torch.int32 if dt == _lib.ACTION_U8 else torch.float32), (T,))
-                io = self._rollout_io(a, dt, out, T)
-                code = self._c_rollout(io, T)
+                a, dt = self._action_tensor(r.a.to(torch.int32 if r.dt == _lib.ACTION_U8 else torch.float32), (r.T,))
+                code = self._c_rollout(self._rollout_io(a, dt, r.out, r.T), r.T)
             _lib.check(code)
-        return out
+        return r.out
 
-    def _rollout_io(self, a: torch.Tensor, dt: int, out: dict, T: int) -> "_lib.StepIO":
-        """``carl_step_io_t`` of a fused rollout: validated actions + the caller's ``[T, ...]`` output buffers.  The row
-        pitch is read off the buffers (``alloc_rollout`` pads rows to a multiple of 16 lanes; dense caller-made buffers
-        keep working); actions of a padded layout are copied once into rows of the same pitch, the padding columns
-        repeating the last lane's action (the padding lanes run as clones of that lane: valid numbers)."""
-        if out["reward"].shape[0] < T:
+    def _rollout_io(self, a: torch.Tensor | None, dt: int | None, out: dict, T: int) -> "_lib.StepIO":
+        """``carl_step_io_t`` of a fused launch of ``T`` steps into the caller's ``[T, ...]`` output buffers, rows of one
+        common pitch (``_out_pitch``: ``alloc_rollout`` pads rows to a multiple of 16 lanes; dense caller-made buffers keep
+        working; an engine without the staged kernel takes dense rows only).  Where the actions come from is the one
+        difference: ``rollout`` passes its validated actions ``a`` of format ``dt``; for a padded layout they are copied once
+        into rows of the same pitch, the padding columns repeating the last lane's action (the padding lanes run as clones
+        of that lane: valid numbers).  ``rollout_policy`` passes ``a = None``: the launch writes each step's actions into
+        ``out["action"]``, which must be ``[>= T, N]`` rows of the same pitch, of the family's int32 / float32 dtype, on
+        this device."""
+        n, policy = self.n, a is None
+        keys = ("obs", "reward", "terminated", "truncated", "final_obs")
+        if policy:
+            if "action" not in out:
+                raise ValueError("rollout_policy output needs an 'action' [T, N] buffer")
+            adt = torch.int32 if self.info.action_is_discrete else torch.float32
+            if out["action"].dtype != adt:
+                raise ValueError(f"rollout_policy 'action' buffer must be {adt} for this family")
+            a, dt = out["action"], _lib.ACTION_I32 if self.info.action_is_discrete else _lib.ACTION_F32
+        elif out["reward"].shape[0] < T:
             raise ValueError("rollout output buffers are shorter than the action sequence")
-        n = self.n
-        P = max(n, int(out["reward"].stride(0))) if out["reward"].dim() == 2 else n  # (a one-row buffer may carry any stride)
-        self._check_rows("rollout", out, ("obs", "reward", "terminated", "truncated", "final_obs"), P)
+        P = self._out_pitch(out)
+        if P != n and not self._has_direct_kernel:
+            raise ValueError(f"{type(self).__name__}: dense rows only ({n} lanes per row); these output buffers have rows of "
+                             f"{P} lanes")
+        if policy:
+            self._check_rows("rollout_policy", out, keys + ("action",), P, T, self.device)
+        else:
+            self._check_rows("rollout", out, keys, P)
+            if P != n:
+                a = self._pad_action_rows(a, T, P)
+            self._rollout_actions = a  # (keeps a padded copy alive until the launch has been enqueued and beyond)
         io = _lib.StepIO()
-        if P != n:
-            a = self._pad_action_rows(a, T, P)
-            io.row_pitch = P
+        io.row_pitch = P if P != n else 0
         io.action, io.action_dtype = a.data_ptr(), dt
         io.obs, io.reward = _ptr(out["obs"]), _ptr(out["reward"])
         io.terminated, io.truncated = _ptr(out["terminated"]), _ptr(out["truncated"])
         io.final_obs = _ptr(out.get("final_obs"))
         io.branch_sig = _ptr(out.get("branch_sig"))
-        self._rollout_actions = a  # (keeps a padded copy alive until the launch has been enqueued and beyond)
         return io
+
+    def _out_pitch(self, out: dict) -> int:
+        """Lanes per row of a ``[T, N, ...]`` output dict, read off its ``reward`` array (a one-row buffer may carry any
+        stride)."""
+        r = out["reward"]
+        return max(self.n, int(r.stride(0))) if r.dim() == 2 else self.n
 
     def _check_rows(self, who: str, out: dict, keys, P: int, min_rows: int | None = None, device=None) -> None:
         """ValueError unless each of ``out[keys]`` that is present is ``[T, N]`` (``[T, N, D]``: obs, final_obs) rows of
@@ -645,35 +688,12 @@ class VecEngine:
             raise ValueError(f"mode {mode!r}: 'transitions' or 'summary'")
         if out is None:
             out = self.alloc_rollout(T, final_obs=final_obs)
-            P = int(out["reward"].stride(0)) if out["reward"].dim() == 2 else self.n
             adt = torch.int32 if self.info.action_is_discrete else torch.float32
-            full = torch.empty((T, max(P, self.n)), dtype=adt, device=self.device)
-            out["action"] = full if full.shape[1] == self.n else full[:, : self.n]
-        io = self._policy_io(out, T)
+            out["action"] = torch.empty((T, self._out_pitch(out)), dtype=adt, device=self.device)[:, : self.n]
+        io = self._rollout_io(None, None, out, T)
         with torch.cuda.device(self.device):
             _lib.check(self.lib.carl_rollout_policy(self._b_ref, C.byref(pol), C.byref(io), T, None, self._stream()))
         return out
-
-    def _policy_io(self, out: dict, T: int) -> "_lib.StepIO":
-        """``carl_step_io_t`` of a transitions-mode ``rollout_policy``: every ``[T, N(, D)]`` array, the action column
-        included, must be rows of one common pitch (``alloc_rollout``'s layout)."""
-        if "action" not in out:
-            raise ValueError("rollout_policy output needs an 'action' [T, N] buffer")
-        n = self.n
-        P = max(n, int(out["reward"].stride(0))) if out["reward"].dim() == 2 else n
-        adt = torch.int32 if self.info.action_is_discrete else torch.float32
-        if out["action"].dtype != adt:
-            raise ValueError(f"rollout_policy 'action' buffer must be {adt} for this family")
-        self._check_rows("rollout_policy", out, ("obs", "reward", "terminated", "truncated", "final_obs", "action"), P, T,
-                         self.device)
-        io = _lib.StepIO()
-        io.row_pitch = P if P != n else 0
-        io.action = _ptr(out["action"])
-        io.action_dtype = _lib.ACTION_I32 if self.info.action_is_discrete else _lib.ACTION_F32
-        io.obs, io.reward = _ptr(out["obs"]), _ptr(out["reward"])
-        io.terminated, io.truncated = _ptr(out["terminated"]), _ptr(out["truncated"])
-        io.final_obs = _ptr(out.get("final_obs"))
-        return io
 
     def rollout_variant(self) -> int:
         """Which kernel ``rollout`` launches for this batch into ``alloc_rollout``'s buffers: ``_lib.ROLLOUT_STAGED``

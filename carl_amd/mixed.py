@@ -29,10 +29,12 @@ to running the parts as separate engines (tests/test_gpu_parity.py).
 """
 from __future__ import annotations
 
+import ctypes as C
 from typing import Sequence
 
 import torch
 
+from carl_amd import _lib
 from carl_amd.engine import VecEngine
 
 _SHARED_1D = ("ep_return", "last_return", "last_length", "episodes_done", "reward", "terminated", "truncated", "done")
@@ -70,7 +72,7 @@ class MixedVecEngine:
         self._pending = []      # outputs allocated by free-running launches that were not joined yet (see rollout / join)
         self._in_flight = False  # a free-running launch was enqueued since the last join()
         self.pair_launches = 0   # fused rollouts that went out as ONE heterogeneous launch (carl_rollout_pair)
-        self._pair_ok = None     # False: this batch can never take the one-launch pair kernel (see _rollout_pair)
+        self._pair_ok = None     # False: this batch is not two classic-control parts (see _rollout_pair)
 
     # ------------------------------------------------------------------ fork / join
     def _each(self, fn):
@@ -192,59 +194,28 @@ class MixedVecEngine:
         return [p.rollout(actions[k], None if outs is None else outs[k]) for k, p in enumerate(self.parts)]
 
     def _rollout_pair(self, actions, outs):
-        """Two classic-control families, one of them the float64 Acrobot, in the lean staged configuration: ONE launch
-        for both (``carl_rollout_pair``: BASELINE config 3's Acrobot + MountainCar as a heterogeneous launch, the second
-        family's wavefronts issuing in the gaps of Acrobot's RK4).  Returns ``None`` when the library declines
-        (``CARL_ERR_UNSUPPORTED``: other families, int64 actions, terminal observations, moving selectors ...) -- the
-        caller then launches the parts one after the other; results are bit-identical either way."""
-        import ctypes as C
-
-        from carl_amd import _lib
-
+        """Two classic-control parts as ONE launch where the library has one (``carl_rollout_pair``: the float64 Acrobot + one
+        other family in the lean staged configuration -- BASELINE config 3's Acrobot + MountainCar as a heterogeneous
+        launch, the second family's wavefronts issuing in the gaps of Acrobot's RK4).  Each part is prepared once (actions
+        converted, outputs allocated) and the library decides; where it declines (``CARL_ERR_UNSUPPORTED``, nothing
+        enqueued) the prepared parts are launched one after the other on the caller's stream.  Results are bit-identical
+        either way.  Returns ``None`` where no pair launch is possible at all: not two classic parts, unequal lengths, or
+        no steps (a zero-step pair call succeeds without launching anything)."""
         if len(self.parts) != 2 or any(hasattr(p, "sys") for p in self.parts):
             self._pair_ok = False
             return None
-        pa, pb = self.parts
         T = int(actions[0].shape[0])
-        if int(actions[1].shape[0]) != T:
+        if T == 0 or int(actions[1].shape[0]) != T:
             return None
-        if any(torch.is_tensor(a) and a.dtype in (torch.uint8, torch.float16, torch.bfloat16) for a in actions[:2]):
-            return None  # the pair kernel reads int32 / float32 actions; narrow-format parts take their own launches
-        # What carl_rollout_pair declines is decided HERE, before any tensor is touched: an eligible family pair in a
-        # non-lean configuration (round-robin / random selector, int64 actions, terminal observations, a finished-episode
-        # log, rows that do not take the staged kernel) used to convert both action tensors and allocate full [T, N, ...]
-        # outputs on every call only to hear UNSUPPORTED and do it all again in the per-part path (ADVICE r04).  Which
-        # kernel the rows take is the library's answer for a probe of the launch's pitch and output arrays.
-        fams = {pa.family, pb.family}
-        if fams - set(range(_lib.CARL_N_FAMILIES)) or _lib.ACROBOT not in fams or pa.family == pb.family or \
-                any(p.family == _lib.ACROBOT and (p.b.flags & _lib.FLAG_ACROBOT_FP32) for p in self.parts):
-            self._pair_ok = False  # never eligible: stop asking
-            return None
-        for k, p in enumerate(self.parts):
-            a, out = actions[k], None if outs is None else outs[k]
-            probe = _lib.StepIO()
-            probe.row_pitch = p._row_pitch() if out is None else max(p.n, int(out["reward"].stride(0)))  # (engine.py: _rollout_io)
-            for name in () if out is None else ("obs", "reward", "terminated", "truncated"):
-                setattr(probe, name, out[name].data_ptr())
-            if (p.b.selector not in (_lib.SEL_STATIC, _lib.SEL_HOST) or p.fin_capacity != 0
-                    or (torch.is_tensor(a) and a.dtype == torch.int64)
-                    or (out is not None and out.get("final_obs") is not None)
-                    or p.lib.carl_rollout_variant_io(C.byref(p.b), C.byref(probe)) != _lib.ROLLOUT_STAGED):
-                return None
-        aa, dta = pa._action_tensor(actions[0], (T,))
-        ab, dtb = pb._action_tensor(actions[1], (T,))
-        if outs is None:
-            outs = [pa.alloc_rollout(T), pb.alloc_rollout(T)]
-        ioa, iob = pa._rollout_io(aa, dta, outs[0], T), pb._rollout_io(ab, dtb, outs[1], T)
+        pa, pb = self.parts
+        ra, rb = (p._prepare_rollout(actions[k], None if outs is None else outs[k]) for k, p in enumerate(self.parts))
         with torch.cuda.device(self.device):
-            code = pa.lib.carl_rollout_pair(C.byref(pa.b), C.byref(ioa), C.byref(pb.b), C.byref(iob), T, pa._stream())
+            code = pa.lib.carl_rollout_pair(pa._b_ref, C.byref(ra.io), pb._b_ref, C.byref(rb.io), T, pa._stream())
         if code == _lib.ERR_UNSUPPORTED:
-            if {pa.family, pb.family} - set(range(_lib.CARL_N_FAMILIES)) or _lib.ACROBOT not in (pa.family, pb.family):
-                self._pair_ok = False  # never eligible: stop asking
-            return None
+            return [pa._launch_rollout(ra), pb._launch_rollout(rb)]
         _lib.check(code)
         self.pair_launches += 1
-        return list(outs)
+        return [ra.out, rb.out]
 
     def join(self) -> None:
         """Order the caller's stream after everything the parts' streams hold (after ``rollout(free_running=True)``)."""

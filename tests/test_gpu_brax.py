@@ -673,12 +673,13 @@ def test_lane_width_is_a_pure_scheduling_choice_and_autotune_restores_state(devi
         else:
             assert all(torch.equal(a, b) for a, b in zip(ref, cur)), hint
     s2 = ant_sys(NAMES)
-    eng = engine(s2, context_rows(rng, 512), 512, device, selector=O.SEL_STATIC, seed=1, ctx_idx0=np.arange(512))
+    eng = engine(s2, context_rows(rng, 512), 512, device, selector=O.SEL_STATIC, seed=1, ctx_idx0=np.arange(512),
+                 branch_record=True)
     assert eng.lane_widths() == [9, 16]  # one lane per link or wider
     eng.reset()
     eng.step(torch.zeros((512, 8), device=device))
     before = {k: getattr(eng, k).clone() for k in ("state", "elapsed", "episode", "n_calls", "ep_return", "obs", "reward",
-                                                   "terminated", "truncated", "done")}
+                                                   "terminated", "truncated", "done", "branch_sig")}
     rng_state = torch.cuda.get_rng_state(torch.device(device))
     best = eng.autotune()
     assert best in eng.lane_widths() and eng.sys.lanes_per_env == best and set(eng.autotune_ms) == set(eng.lane_widths())
@@ -702,6 +703,37 @@ def test_lane_width_is_a_pure_scheduling_choice_and_autotune_restores_state(devi
     assert int(eng.sys.lanes_per_env) == width and not eng._tuning
     assert all(torch.equal(v, getattr(eng, k)) for k, v in before.items())
     eng.step(torch.zeros((512, 8), device=device))  # and keeps working
+
+
+def test_snapshot_restores_branch_sig_and_dense_rows_are_required(device):
+    """``snapshot`` / ``restore`` -- the one list of buffers a launch writes (``capture_step``'s warm-up, ``autotune``'s
+    probes) -- include the per-step branch signature; and a Brax rollout into rows padded beyond the lane count (the
+    classic families' staged layout) is refused with a ValueError before anything is padded or launched."""
+    s = ant_sys(NAMES)
+    rng = np.random.default_rng(31)
+    n, T = 333, 3
+    eng = engine(s, context_rows(rng, n), n, device, selector=O.SEL_STATIC, seed=2, ctx_idx0=np.arange(n),
+                 branch_record=True)
+    eng.reset()
+    eng.branch_sig.fill_(-1)  # (no hash of a step: the step below overwrites every lane's record)
+    snap = eng.snapshot()
+    assert "branch_sig" in snap
+    eng.step(torch.as_tensor(rng.uniform(-1, 1, (n, 8)).astype(np.float32), device=device))
+    assert not torch.equal(eng.branch_sig, snap["branch_sig"])
+    eng.restore(snap)
+    for k, v in snap.items():
+        assert torch.equal(getattr(eng, k), v), k
+    P = (n + 15) // 16 * 16
+    padded = {"obs": torch.zeros((T, P, eng.D), device=device)[:, :n], "reward": torch.zeros((T, P), device=device)[:, :n],
+              "terminated": torch.zeros((T, P), dtype=torch.uint8, device=device)[:, :n],
+              "truncated": torch.zeros((T, P), dtype=torch.uint8, device=device)[:, :n]}
+    acts = torch.as_tensor(rng.uniform(-1, 1, (T, n, 8)).astype(np.float32), device=device)
+    with pytest.raises(ValueError, match="dense rows only"):
+        eng.rollout(acts, padded)
+    torch.cuda.synchronize()
+    for k, v in snap.items():  # nothing launched
+        assert torch.equal(getattr(eng, k), v), k
+    assert not any(bool(t.any()) for t in padded.values())
 
 
 def test_reacher_env_api_and_goal_stays_put(device):

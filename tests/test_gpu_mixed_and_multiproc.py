@@ -111,32 +111,56 @@ def test_pair_launch_equals_two_launches_bit_for_bit(other, n_a, n_b, T, max_ste
 
 
 def test_pair_launch_is_refused_for_other_combinations(device):
-    """ABI: CARL_ERR_UNSUPPORTED, nothing enqueued, for two float32 families / two Acrobots / a moving selector"""
+    """ABI: CARL_ERR_UNSUPPORTED, nothing enqueued, for two float32 families / two Acrobots / a moving selector / the
+    float32 Acrobot, and for an eligible family pair outside the lean staged configuration: int64 or uint8 actions,
+    terminal observations, a finished-episode log, output rows that take the direct-store kernel.  MixedVecEngine asks
+    the library and nothing else, so every such condition must be refused HERE."""
     import ctypes as C
 
     from carl_amd import _lib
 
-    n, T = 1024, 8
+    n, T, P = 1024, 8, 1040
     rng = np.random.default_rng(0)
 
-    def call(ea, eb):
-        acts = [torch.as_tensor(random_actions(e.family, rng, (T, n)), device=device) for e in (ea, eb)]
-        ios = []
-        for e, a in zip((ea, eb), acts):
-            aa, dt = e._action_tensor(a, (T,))
-            ios.append(e._rollout_io(aa, dt, e.alloc_rollout(T), T))
-        return ea.lib.carl_rollout_pair(C.byref(ea.b), C.byref(ios[0]), C.byref(eb.b), C.byref(ios[1]), T, ea._stream())
+    def direct_rows(e):  # a column view one lane into a wider array: not on a 16-byte boundary
+        return {"obs": torch.zeros((T, P, e.D), device=device)[:, :n], "reward": torch.zeros((T, P), device=device)[:, 1:n + 1],
+                "terminated": torch.zeros((T, P), dtype=torch.uint8, device=device)[:, :n],
+                "truncated": torch.zeros((T, P), dtype=torch.uint8, device=device)[:, :n]}
+
+    def call(ea, eb, dtype=None, final_obs=False, rows=None):
+        ios, outs = [], []
+        for e in (ea, eb):
+            a = torch.as_tensor(random_actions(e.family, rng, (T, n)), device=device)
+            aa, dt = e._action_tensor(a if dtype is None else a.to(dtype), (T,), allow_narrow=True)
+            out = e.alloc_rollout(T, final_obs=final_obs) if rows is None else rows(e)
+            for v in out.values():
+                v.fill_(7)
+            ios.append(e._rollout_io(aa, dt, out, T))
+            outs.append(out)
+        code = ea.lib.carl_rollout_pair(C.byref(ea.b), C.byref(ios[0]), C.byref(eb.b), C.byref(ios[1]), T, ea._stream())
+        torch.cuda.synchronize()
+        return code, outs
+
+    def refused(ea, eb, **kw):
+        code, outs = call(ea, eb, **kw)
+        return code == _lib.ERR_UNSUPPORTED and all(bool((v == 7).all()) for out in outs for v in out.values())
 
     mk = lambda f, **kw: _engine(f, random_table(f, rng, n), n, device, **{"selector": O.SEL_STATIC, **kw})  # noqa: E731
-    assert call(mk(O.PENDULUM), mk(O.MOUNTAINCAR)) == _lib.ERR_UNSUPPORTED
-    assert call(mk(O.ACROBOT), mk(O.ACROBOT)) == _lib.ERR_UNSUPPORTED
-    assert call(mk(O.ACROBOT, selector=O.SEL_ROUND_ROBIN), mk(O.MOUNTAINCAR)) == _lib.ERR_UNSUPPORTED
-    assert call(mk(O.ACROBOT, acrobot_fp32=True), mk(O.MOUNTAINCAR)) == _lib.ERR_UNSUPPORTED
+    assert refused(mk(O.PENDULUM), mk(O.MOUNTAINCAR))
+    assert refused(mk(O.ACROBOT), mk(O.ACROBOT))
+    assert refused(mk(O.ACROBOT, selector=O.SEL_ROUND_ROBIN), mk(O.MOUNTAINCAR))
+    assert refused(mk(O.ACROBOT, acrobot_fp32=True), mk(O.MOUNTAINCAR))
     ea, eb = mk(O.ACROBOT), mk(O.MOUNTAINCAR)
     ea.reset()
     eb.reset()
-    assert call(ea, eb) == 0 and call(eb, ea) == 0  # either order
-    torch.cuda.synchronize()
+    assert refused(ea, eb, dtype=torch.int64)
+    assert refused(ea, eb, dtype=torch.uint8)
+    assert refused(ea, eb, final_obs=True)
+    assert refused(ea, eb, rows=direct_rows)
+    ef = mk(O.ACROBOT, fin_capacity=64)
+    ef.reset()
+    assert refused(ef, eb) and refused(eb, ef)
+    assert call(ea, eb)[0] == 0 and call(eb, ea)[0] == 0  # either order
 
 
 def test_mixed_batch_per_call_step(device):
@@ -611,3 +635,51 @@ def test_mixed_batch_with_uint8_actions_takes_separate_launches_same_results(dev
     for p8, p32 in zip(o8, o32):
         for k in ("obs", "reward", "terminated", "truncated"):
             assert torch.equal(p8[k], p32[k]), k
+
+
+def test_mixed_batch_the_pair_kernel_declines_prepares_each_part_once(device, monkeypatch):
+    """Acrobot + MountainCar with the round-robin selector (lanes change contexts on reset: not the lean staged
+    configuration the pair kernel runs): the library declines the pair launch and the two parts go out one after the
+    other -- the transitions of separate engines -- and each part's actions are converted and its outputs allocated
+    exactly ONCE per rollout (the library is asked with the prepared launch, not a copy of its rule)."""
+    from carl_amd.engine import VecEngine
+    from carl_amd.mixed import MixedVecEngine
+
+    rng = np.random.default_rng(12)
+    n, T = 1024, 23
+    fams = (O.ACROBOT, O.MOUNTAINCAR)
+    tables = [random_table(f, rng, 37) for f in fams]
+    mk = lambda: [_engine(f, t, n, device, selector=O.SEL_ROUND_ROBIN, seed=6, max_episode_steps=9,  # noqa: E731
+                          lane_offset=k * n) for k, (f, t) in enumerate(zip(fams, tables))]
+    sep, parts = mk(), mk()
+    mixed = MixedVecEngine(parts)
+    for e in sep:
+        e.reset()
+    mixed.reset()
+    calls = {}
+
+    def count(p, name):
+        real = getattr(VecEngine, name)
+
+        def wrapped(*a, **k):
+            calls[(id(p), name)] = calls.get((id(p), name), 0) + 1
+            return real(p, *a, **k)
+
+        monkeypatch.setattr(p, name, wrapped)
+
+    for p in parts:
+        count(p, "_action_tensor")
+        count(p, "alloc_rollout")
+    for rep in range(2):
+        acts = [torch.as_tensor(random_actions(f, rng, (T, n)), device=device) for f in fams]
+        calls.clear()
+        outs = mixed.rollout(acts)
+        assert calls == {(id(p), k): 1 for p in parts for k in ("_action_tensor", "alloc_rollout")}, (rep, calls)
+        ref = [e.rollout(a) for e, a in zip(sep, acts)]
+        for k in range(2):
+            for name in ("obs", "reward", "terminated", "truncated"):
+                assert torch.equal(outs[k][name], ref[k][name]), (rep, k, name)
+            for name in _BOOKKEEPING:
+                assert torch.equal(getattr(parts[k], name), getattr(sep[k], name)), (rep, k, name)
+    assert mixed.pair_launches == 0
+    assert int(mixed.episodes_done.min()) >= 2 * T // 9
