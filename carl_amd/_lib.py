@@ -256,9 +256,16 @@ class PolicySummary(C.Structure):
     _fields_ = [("episodes", _vp), ("return_sum", _vp), ("length_sum", _vp)]
 
 
+class PolicyEpisodes(C.Structure):
+    _fields_ = [("episodes", _vp), ("steps", _vp), ("ret", _vp), ("length", _vp), ("context_id", _vp),
+                ("terminated", _vp)]
+
+
 EXPORTS.update({
     "carl_rollout_policy": (C.c_int, [C.POINTER(Batch), C.POINTER(Policy), C.POINTER(StepIO), C.c_int32,
                                       C.POINTER(PolicySummary), _vp]),
     "carl_policy_lane_quantum": (C.c_int32, []),
     "carl_policy_set_floats": (C.c_int32, [C.POINTER(Policy)]),
+    "carl_evaluate_policy": (C.c_int, [C.POINTER(Batch), C.POINTER(Policy), C.c_int32, C.c_int32,
+                                       C.POINTER(PolicyEpisodes), _vp]),
 })

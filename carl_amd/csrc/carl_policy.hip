@@ -31,8 +31,8 @@ int set_floats_of(const carl_policy_t* p) {
   return (int)((total + 3) / 4 * 4);
 }
 
-int validate_policy(const carl_batch_t* b, const carl_policy_t* p, const carl_family_info_t& fi) {
-  const char* who = "carl_rollout_policy";
+int validate_policy(const carl_batch_t* b, const carl_policy_t* p, const carl_family_info_t& fi,
+                    const char* who = "carl_rollout_policy") {
   if (p->n_hidden < 0 || p->n_hidden > CARL_POLICY_MAX_HIDDEN)
     return fail(CARL_ERR_INVALID_ARGUMENT, "%s: n_hidden %d outside [0, %d]", who, p->n_hidden, CARL_POLICY_MAX_HIDDEN);
   for (int l = 0; l < p->n_hidden; ++l)
@@ -84,6 +84,13 @@ int validate_io(const carl_batch_t* b, const carl_step_io_t* io, const carl_fami
   return 0;
 }
 
+// the instantiated hidden width a policy is padded to: 0 (a linear policy), 32, 64
+int padded_hidden(const carl_policy_t* p) {
+  int wmax = 0;
+  for (int l = 0; l < p->n_hidden; ++l) wmax = wmax > p->width[l] ? wmax : p->width[l];
+  return p->n_hidden == 0 ? 0 : wmax <= 32 ? 32 : 64;
+}
+
 // a policy_rollout_kernel instance and the dynamic LDS it takes
 struct PolicyKernel {
   void (*fn)(carl_batch_t, carl_step_io_t, carl_policy_t, int, carl_policy_summary_t, int);
@@ -100,10 +107,7 @@ template <class Fam>
 int launch_policy(const carl_batch_t* b, const carl_policy_t* p, const carl_step_io_t* io, int n_steps,
                   const carl_policy_summary_t* sum, hipStream_t s) {
   const bool summary = io == nullptr;
-  int wmax = 0;
-  for (int l = 0; l < p->n_hidden; ++l) wmax = wmax > p->width[l] ? wmax : p->width[l];
-  // the hidden width is padded to an instantiated class: 0 (a linear policy), 32, 64
-  const int H = p->n_hidden == 0 ? 0 : wmax <= 32 ? 32 : 64;
+  const int H = padded_hidden(p);
   const PolicyKernel k = H == 0 ? policy_kernel<Fam, 0>(summary) : H == 32 ? policy_kernel<Fam, 32>(summary)
                                                                   : policy_kernel<Fam, 64>(summary);
   static_assert(carl::policy_lds_bytes<Fam, 64, false>() + carl::static_lds_bytes<Fam>() <= carl::kCuLdsBytes,
@@ -119,6 +123,30 @@ int launch_policy(const carl_batch_t* b, const carl_policy_t* p, const carl_step
   const int threads = summary ? carl::kPolicyThreadsSummary : carl::kPolicyThreadsTransitions;
   hipLaunchKernelGGL(k.fn, dim3(grid), dim3(threads), k.lds, s, *b, io_r, *p, set_floats_of(p), sum_r, n_steps);
   return check_launch("carl_rollout_policy");
+}
+
+// a policy_episodes_kernel instance and the dynamic LDS it takes (summary mode's: the weight set alone)
+struct EpisodesKernel {
+  void (*fn)(carl_batch_t, carl_policy_t, int, carl_policy_episodes_t, int, int);
+  size_t lds;
+};
+
+template <class Fam, int H>
+EpisodesKernel episodes_kernel() {
+  return {carl::policy_episodes_kernel<Fam, H>, carl::policy_lds_bytes<Fam, H, true>()};
+}
+
+template <class Fam>
+int launch_episodes(const carl_batch_t* b, const carl_policy_t* p, int n_episodes, int max_steps,
+                    const carl_policy_episodes_t* out, hipStream_t s) {
+  const int H = padded_hidden(p);
+  const EpisodesKernel k = H == 0 ? episodes_kernel<Fam, 0>() : H == 32 ? episodes_kernel<Fam, 32>()
+                                                               : episodes_kernel<Fam, 64>();
+  if (int e = carl_host::ensure_dynamic_lds(reinterpret_cast<const void*>(k.fn), k.lds, "carl_evaluate_policy")) return e;
+  const int grid = (b->n_lanes + carl::kPolicyLanes - 1) / carl::kPolicyLanes;
+  hipLaunchKernelGGL(k.fn, dim3(grid), dim3(carl::kPolicyThreadsSummary), k.lds, s, *b, *p, set_floats_of(p), *out,
+                     n_episodes, max_steps);
+  return check_launch("carl_evaluate_policy");
 }
 
 }  // namespace
@@ -169,6 +197,36 @@ int carl_rollout_policy(const carl_batch_t* batch, const carl_policy_t* policy_h
   }
   return carl_host::with_classic_family(batch, [&](auto fam) {
     return launch_policy<decltype(fam)>(batch, policy_host, io, n_steps, summary_out, (hipStream_t)stream);
+  });
+}
+
+int carl_evaluate_policy(const carl_batch_t* batch, const carl_policy_t* policy_host, int32_t n_episodes,
+                         int32_t max_steps, const carl_policy_episodes_t* out, void* stream) {
+  const char* who = "carl_evaluate_policy";
+  if (batch == nullptr || policy_host == nullptr)
+    return fail(CARL_ERR_INVALID_ARGUMENT, "%s: batch / policy is NULL", who);
+  if (batch->family >= CARL_N_FAMILIES)
+    return fail(CARL_ERR_INVALID_ARGUMENT, "%s: family %d is a Brax family -- the closed-loop rollout covers the "
+                "classic-control families only", who, batch->family);
+  if (int e = carl_host::validate_batch(batch, who)) return e;
+  carl_family_info_t fi;
+  if (int e = carl_family_info(batch->family, &fi)) return e;
+  if (int e = validate_policy(batch, policy_host, fi, who)) return e;
+  if (out == nullptr || !out->episodes || !out->steps || !out->ret || !out->length || !out->context_id ||
+      !out->terminated)
+    return fail(CARL_ERR_INVALID_ARGUMENT, "%s: out and all six of its arrays are required", who);
+  if (n_episodes < 1) return fail(CARL_ERR_INVALID_ARGUMENT, "%s: n_episodes %d < 1", who, n_episodes);
+  if (max_steps < 0) return fail(CARL_ERR_INVALID_ARGUMENT, "%s: max_steps %d < 0", who, max_steps);
+  if ((int64_t)n_episodes * batch->n_lanes >= ((int64_t)1 << 31))
+    return fail(CARL_ERR_INVALID_ARGUMENT, "%s: n_episodes %d x %d lanes records do not fit 2^31 - 1", who, n_episodes,
+                batch->n_lanes);
+  // as a summary: without auto-reset a finished lane reports done on every later step
+  if (!(batch->flags & CARL_FLAG_AUTORESET))
+    return fail(CARL_ERR_UNSUPPORTED, "%s: needs CARL_FLAG_AUTORESET (without auto-reset a finished lane reports done on "
+                "every later step, and its episode would be counted on each of them)", who);
+  if (batch->n_lanes == 0) return 0;
+  return carl_host::with_classic_family(batch, [&](auto fam) {
+    return launch_episodes<decltype(fam)>(batch, policy_host, n_episodes, max_steps, out, (hipStream_t)stream);
   });
 }
 

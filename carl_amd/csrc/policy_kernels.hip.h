@@ -14,6 +14,8 @@
 //   transitions  the records go through the LdsSink and storer-wave drain of the staged rollout (drain_records), and
 //                the action taken is one more [T][pitch] column, drained by the same waves;
 //   summary      no per-step stores at all: each lane writes its episode count / return sum / length sum once.
+// A kernel of its own (policy_episodes_kernel, carl_evaluate_policy) runs the summary layout until each lane has
+// finished K episodes and writes one record per finished episode.
 //
 // Weights in LDS (floats, every section on a 16-byte boundary), K = the family's F + D rounded up to 4, H = the
 // padded hidden width of the instantiation (0: a linear policy, else 32 or 64):
@@ -363,6 +365,106 @@ __global__ void __launch_bounds__(SUMMARY ? kPolicyThreadsSummary : kPolicyThrea
                          last_t0, n_steps - last_t0);
       drain_actions(act_buf + (size_t)(buf ^ 1) * CHUNK * kPolicyLanes * 4, const_cast<void*>(io.action), n, n_cols,
                     lane_base, hl, storer, last_t0, n_steps - last_t0);
+    }
+  }
+}
+
+// episodes mode's sink: no per-step store; put_flags keeps the terminated bit in the caller's register.  kLazyFlags:
+// step_lane calls put_flags on the done path only, and the constant also selects finish_episodes' Philox predraw path,
+// so the reset draws are those of every other kernel.
+template <class Fam>
+struct TermSink {
+  static constexpr bool kLazyFlags = true;
+  bool* te;
+  __device__ __forceinline__ void put_reward(float) const {}
+  __device__ __forceinline__ void put_flags(bool t, bool) const { *te = t; }
+  __device__ __forceinline__ void put_obs(const float (&)[Fam::D]) const {}
+  __device__ __forceinline__ float* final_obs_ptr() const { return nullptr; }
+};
+
+// Episodes mode (include/carl_amd.h: carl_evaluate_policy): the summary instantiation's layout -- 256 threads, four
+// compute waves, one weight set in LDS, no storer waves -- with a per-lane `live` predicate.  A lane is live while it
+// has finished fewer than K episodes and taken fewer than max_steps steps; the step runs through step_lane's
+// active_in path, so a frozen lane's registers stay as they are while it still takes part in the wave-level
+// operations inside (the done ballot, the finished-episode log's ballot + atomic).  Padding lanes are never live.
+// There is no barrier in the step loop: a wave leaves it as soon as none of its lanes is live, checked every step.
+// Each finished episode is written straight to row `done_eps` of the record arrays; the sentinels once, at the end.
+// Preconditions (host, carl_policy.hip): as policy_rollout_kernel's summary mode; K >= 1; K * n_lanes < 2^31.
+template <class Fam, int H>
+__global__ void __launch_bounds__(kPolicyThreadsSummary)
+    policy_episodes_kernel(const carl_batch_t b, const carl_policy_t pol, const int set_floats,
+                           const carl_policy_episodes_t ep, const int n_episodes, const int max_steps) {
+  using L = PolicyLayout<Fam, H>;
+  using Action = typename Fam::Action;
+  constexpr int CHUNK = policy_chunk<Fam>();
+  extern __shared__ float lds_dyn[];
+  stage_family_tables<Fam>();
+  float* const wts = lds_dyn;
+  const int lane_base = (int)blockIdx.x * kPolicyLanes;
+  stage_policy<Fam, H>(wts, pol, set_floats, lane_base / pol.lanes_per_set);
+  const GlobalCtx ctx{b.ctx_table, b.ctx_stride};
+  const int lane = lane_base + (int)threadIdx.x;
+  const bool active = lane < b.n_lanes;
+  const uint64_t glane = (uint64_t)(b.lane_offset + lane);
+  const size_t n = (size_t)b.n_lanes;
+  __syncthreads();
+
+  LaneRegs<Fam> r{};
+  load_staged_lane<Fam>(b, ctx, lane, active, r);
+  const int n_ctx = pol.n_ctx, n_hidden = pol.n_hidden, act = pol.activation;
+  const int w0 = pol.width[0], w1 = pol.width[1];  // (w1: read only when n_hidden == 2)
+  const float clip = wts[L::kClip];
+  float x[L::K];
+#pragma unroll
+  for (int s = 0; s < L::K; ++s) x[s] = 0.0f;
+  int x_cidx = -1;  // context whose values x[0, n_ctx) hold
+  int done_eps = 0, steps = 0;
+  bool live = active;
+  // (ballot(live) == 0: every lane of the wave is done -- a wave-uniform exit from both loops)
+  for (int t0 = 0; t0 < max_steps && ballot(live) != 0ull; t0 += CHUNK) {
+    if constexpr (predraw_of<Fam>::value) predraw<Fam>(b, glane, r);
+    const int n_u = min(CHUNK, max_steps - t0);
+#pragma unroll 1
+    for (int u = 0; u < n_u; ++u) {
+      if (ballot(live) == 0ull) break;
+      if (ballot(r.cidx != x_cidx) != 0ull) {
+#pragma unroll
+        for (int k = 0; k < Fam::F; ++k)
+          if (k < n_ctx) x[k] = normalize_input(ctx.get(pol.ctx_rows[k], r.cidx), wts[L::kShift + k], wts[L::kScale + k], clip);
+        x_cidx = r.cidx;
+      }
+      float o[Fam::D];
+      Fam::observe(r.s, r.aux, o);
+#pragma unroll
+      for (int d = 0; d < Fam::D; ++d)
+        x[Fam::F + d] = normalize_input(o[d], wts[L::kShift + Fam::F + d], wts[L::kScale + Fam::F + d], clip);
+      const Action a = policy_action<Fam, H>(wts, x, n_hidden, act, w0, w1);
+      const int before = r.n_new_episodes, cidx = r.cidx;
+      bool te = false;
+      step_lane<Fam, GlobalCtx, false, TermSink<Fam>>(b, ctx, TermSink<Fam>{&te}, b.max_episode_steps, live, lane,
+                                                       glane, a, r);
+      steps += live ? 1 : 0;
+      if (r.n_new_episodes != before) {  // (live lanes only: finish_episodes counts valid lanes that stepped)
+        const size_t at = (size_t)done_eps * n + lane;
+        ep.ret[at] = r.fin_return;
+        ep.length[at] = r.fin_length;
+        ep.context_id[at] = cidx;
+        ep.terminated[at] = (uint8_t)te;
+        done_eps += 1;
+      }
+      live = live && done_eps < n_episodes;
+    }
+  }
+  if (active) {
+    store_lane<Fam>(b, ctx, lane, r);
+    ep.episodes[lane] = done_eps;
+    ep.steps[lane] = steps;
+    for (int k = done_eps; k < n_episodes; ++k) {
+      const size_t at = (size_t)k * n + lane;
+      ep.ret[at] = __builtin_nanf("");
+      ep.length[at] = 0;
+      ep.context_id[at] = -1;
+      ep.terminated[at] = 0;
     }
   }
 }

@@ -695,6 +695,57 @@ class VecEngine:
             _lib.check(self.lib.carl_rollout_policy(self._b_ref, C.byref(pol), C.byref(io), T, None, self._stream()))
         return out
 
+    # (key, dtype, per-episode rows) of an evaluate_policy result
+    _EPISODE_KEYS = (("episodes", torch.int32, False), ("steps", torch.int32, False), ("return", torch.float32, True),
+                     ("length", torch.int32, True), ("context_id", torch.int32, True), ("terminated", torch.uint8, True))
+
+    def alloc_policy_episodes(self, n_episodes: int) -> dict:
+        """Output buffers of ``evaluate_policy``: ``episodes`` / ``steps`` int32 ``[N]``; ``return`` float32, ``length`` /
+        ``context_id`` int32, ``terminated`` uint8, ``[n_episodes, N]`` each.  The launch writes every element."""
+        K = int(n_episodes)
+        if K < 1:
+            raise ValueError(f"n_episodes {K} < 1")
+        return {k: torch.empty((K, self.n) if rows else (self.n,), dtype=dt, device=self.device)
+                for k, dt, rows in self._EPISODE_KEYS}
+
+    def evaluate_policy(self, policy, n_episodes: int, max_steps: int, out: dict | None = None) -> dict:
+        """Run ``policy`` (``carl_amd.policy.MLPPolicy``) on every lane until the lane has finished ``n_episodes``
+        episodes or taken ``max_steps`` steps, in ONE launch, from the current engine state (a running episode is counted
+        with its full length; ``CARLEnv.evaluate_policy`` resets first).  Returns ``alloc_policy_episodes``' dict:
+        ``episodes`` / ``steps`` per lane, and per lane and episode k < ``episodes`` its fp32 ``return``, ``length``, the
+        ``context_id`` it ran in and whether it ``terminated`` (NaN / 0 / -1 / 0 beyond).  A lane's records are those of
+        its first episodes in a transitions-mode ``rollout_policy``, bit for bit, and the engine state advances exactly as
+        for the steps each lane took.  Needs ``auto_reset``.  ``carl_amd.policy.episode_stats`` reduces the result per
+        context.  No host synchronisation."""
+        if not self._policy_rollout:
+            raise NotImplementedError(f"{type(self).__name__}: the closed-loop rollout covers the classic-control "
+                                      "families only")
+        if policy.family != self.family or policy.obs_dim != self.D:
+            raise ValueError(f"the policy was built for family {policy.family}, this engine runs family {self.family}")
+        if not self.auto_reset:
+            raise ValueError("evaluate_policy needs auto_reset=True: without it a finished lane reports done on every "
+                             "later step")
+        K, T = int(n_episodes), int(max_steps)
+        if K < 1:
+            raise ValueError(f"n_episodes {K} < 1")
+        if T < 0:
+            raise ValueError(f"max_steps {T} < 0")
+        if K * self.n >= 1 << 31:
+            raise ValueError(f"{K} episodes x {self.n} lanes: more than 2^31 - 1 records")
+        res = self.alloc_policy_episodes(K) if out is None else out
+        for k, dt, rows in self._EPISODE_KEYS:
+            t = res.get(k)
+            shape = (K, self.n) if rows else (self.n,)
+            if t is None or t.device != self.device or t.dtype != dt or tuple(t.shape) != shape or not t.is_contiguous():
+                raise ValueError(f"evaluate_policy output '{k}' must be a contiguous {dt} {list(shape)} tensor on "
+                                 f"{self.device}")
+        params = policy.device_params(self.device)
+        pol = policy.struct(self.n, params.data_ptr())
+        eps = _lib.PolicyEpisodes(*(_ptr(res[k]) for k, _, _ in self._EPISODE_KEYS))
+        with torch.cuda.device(self.device):
+            _lib.check(self.lib.carl_evaluate_policy(self._b_ref, C.byref(pol), K, T, C.byref(eps), self._stream()))
+        return res
+
     def rollout_variant(self) -> int:
         """Which kernel ``rollout`` launches for this batch into ``alloc_rollout``'s buffers: ``_lib.ROLLOUT_STAGED``
         (fast path: rows of a pitch that is a multiple of 16 -- any lane count since round 6), ``ROLLOUT_DIRECT_FLAG``

@@ -319,6 +319,13 @@ class CARLEnv(abc.ABC):
         engine's outputs (``step``'s views) are not touched; the host selector object is not consulted."""
         return self.env.rollout_policy(policy, n_steps, out=out, mode=mode, final_obs=final_obs)
 
+    def evaluate_policy(self, policy, n_episodes: int, max_steps: int, seed: int | None = None) -> dict:
+        """``n_episodes`` whole episodes of ``policy`` per lane (at most ``max_steps`` steps) in one launch:
+        ``reset(seed=seed)``, then ``VecEngine.evaluate_policy``.  ``carl_amd.policy.episode_stats`` reduces the result
+        per context (mean / std return, as SB3's ``evaluate_policy`` reports them)."""
+        self.reset(seed=seed)
+        return self.env.evaluate_policy(policy, n_episodes, max_steps)
+
     def _views(self) -> dict:
         eng = self.env
         key = (eng.obs.data_ptr(), eng.ctx_obs.data_ptr(), eng.ctx_idx.data_ptr(), eng.terminated.data_ptr(),

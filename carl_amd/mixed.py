@@ -133,6 +133,11 @@ class MixedVecEngine:
         raise NotImplementedError("MixedVecEngine: the closed-loop rollout has no pair launch; call rollout_policy on "
                                   "each part's engine")
 
+    def evaluate_policy(self, *args, **kwargs):
+        """Out of scope: run ``VecEngine.evaluate_policy`` on each part's engine instead (one launch per family)."""
+        raise NotImplementedError("MixedVecEngine: the closed-loop rollout has no pair launch; call evaluate_policy on "
+                                  "each part's engine")
+
     def rollout(self, actions: Sequence, outs: Sequence[dict] | None = None, *, free_running: bool = False,
                 overlap: bool | None = None) -> list[dict]:
         """T fused steps of every family; ``actions[k]`` is part k's ``[T, n_k(, A_k)]``.

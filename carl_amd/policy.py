@@ -4,7 +4,8 @@
 the kernel reads, plus the context rows its input starts with.  Its input is what ``FlattenObservation(env)`` gives a
 trained agent (the reference's examples/carl_with_sb3.py): gymnasium's ``Dict`` space orders its keys, so "context"
 comes before "obs", and inside the context part the feature names are sorted when ``obs_context_as_dict`` is set and
-in ``obs_context_features`` order otherwise.  ``VecEngine.rollout_policy`` / ``CARLEnv.rollout_policy`` run it.
+in ``obs_context_features`` order otherwise.  ``VecEngine.rollout_policy`` / ``CARLEnv.rollout_policy`` run it for T
+steps; ``evaluate_policy`` runs it for K whole episodes per lane, and ``episode_stats`` reduces those per context.
 
 Packed layout of one weight set (float32): for every layer in order -- the hidden layers, then the head -- ``W[out][in]``
 row-major followed by ``b[out]``; then ``shift[n_in]``, ``scale[n_in]`` and one ``clip``; zero padding to a multiple of
@@ -219,3 +220,36 @@ class MLPPolicy:
             t = torch.as_tensor(self.params).to(dev).contiguous()
             self._dev[dev] = t
         return t
+
+
+def episode_stats(result: dict, n_contexts: int | None = None) -> dict:
+    """Per-context statistics of an ``evaluate_policy`` result over its finished episodes (slot k of a lane counts when
+    k < ``episodes[lane]``), as float64 NumPy arrays after ONE device-to-host copy:
+    ``context_count``, ``context_mean_return``, ``context_std_return`` (ddof 0, as SB3 reports it),
+    ``context_mean_length`` and ``context_terminated_share``, ``[n_contexts]`` each (default: the largest context id
+    + 1), NaN where a context has no episode; ``mean_return`` / ``std_return`` over all episodes (the pair SB3's
+    ``evaluate_policy`` returns; NaN without any) and ``count``."""
+    keys = ("return", "length", "context_id", "terminated")
+    ret = torch.as_tensor(result["return"])
+    K, n = (int(s) for s in ret.shape)
+    parts = [torch.as_tensor(result[k]).to(torch.float64).reshape(K, n) for k in keys]
+    parts.append(torch.as_tensor(result["episodes"]).to(torch.float64).reshape(1, n).to(ret.device))
+    host = torch.cat(parts, dim=0).cpu().numpy()  # (every value exact in float64)
+    r, ln, cid, te = (host[j * K:(j + 1) * K] for j in range(4))
+    valid = np.arange(K)[:, None] < host[4 * K][None, :]
+    r, ln, te, cid = r[valid], ln[valid], te[valid], cid[valid].astype(np.int64)
+    C_ = (int(cid.max()) + 1 if cid.size else 0) if n_contexts is None else int(n_contexts)
+    if cid.size and (cid.min() < 0 or cid.max() >= C_):
+        raise ValueError(f"context ids {int(cid.min())} .. {int(cid.max())} outside [0, {C_})")
+    count = np.bincount(cid, minlength=C_).astype(np.float64)
+    with np.errstate(invalid="ignore", divide="ignore"):
+        mean = np.bincount(cid, weights=r, minlength=C_) / count
+        dev = r - mean[cid]
+        std = np.sqrt(np.bincount(cid, weights=dev * dev, minlength=C_) / count)
+        mean_len = np.bincount(cid, weights=ln, minlength=C_) / count
+        term = np.bincount(cid, weights=te, minlength=C_) / count
+    nan = np.float64(np.nan)
+    return {"context_count": count, "context_mean_return": mean, "context_std_return": std,
+            "context_mean_length": mean_len, "context_terminated_share": term,
+            "mean_return": np.float64(r.mean()) if r.size else nan, "std_return": np.float64(r.std()) if r.size else nan,
+            "count": np.float64(r.size)}

@@ -378,6 +378,36 @@ int32_t carl_policy_lane_quantum(void); /* lanes_per_set must be a positive mult
 /* floats per weight set of the packed parameters (see above) for this policy's shape; -1 for an invalid shape */
 int32_t carl_policy_set_floats(const carl_policy_t* policy_host);
 
+/* one record per finished episode of carl_evaluate_policy; the [n_episodes][n_lanes] arrays are dense rows (pitch
+ * n_lanes), row k holding each lane's k-th episode of the launch */
+typedef struct carl_policy_episodes {
+  int32_t* episodes;   /* [n_lanes] episodes finished in this launch, 0 .. n_episodes */
+  int32_t* steps;      /* [n_lanes] steps this lane took in this launch */
+  float* ret;          /* [n_episodes][n_lanes] fp32 return of each finished episode (ep_return, added in step order) */
+  int32_t* length;     /* [n_episodes][n_lanes] its length (elapsed at its end) */
+  int32_t* context_id; /* [n_episodes][n_lanes] the context-table index it ran in (ctx_idx before the step that ended it) */
+  uint8_t* terminated; /* [n_episodes][n_lanes] 1: ended by termination (also when truncated at the same step); 0:
+                          truncated only */
+} carl_policy_episodes_t;
+
+/* Episodes mode of the closed-loop rollout: every lane runs `policy_host` (as carl_rollout_policy) until it has
+ * finished n_episodes episodes or taken max_steps steps in this launch, whichever comes first, and then stops stepping.
+ * A lane stops right after the step that ends its n_episodes-th episode, with that step's auto-reset applied (its
+ * stored state is the start of the next episode, as per-call stepping leaves it); a lane that reaches max_steps first
+ * stops there, mid-episode.  Its state and bookkeeping (last_return / last_length / episodes_done, the finished-
+ * episode log, the episode counter of the reset streams) advance exactly as for the steps it took, so a lane's
+ * records are bit-identical to its first n_episodes episodes in a transitions-mode carl_rollout_policy from the same
+ * engine state.  Episodes are counted from the current state: an episode already running when the launch starts is
+ * reported with its full length and return.  A wavefront stops stepping once none of its lanes is live.
+ * Every slot of `out` is written: a slot at or beyond episodes[lane] holds ret = NaN, length = 0, context_id = -1,
+ * terminated = 0, so nothing needs clearing beforehand.  The batch and the policy are validated exactly as
+ * carl_rollout_policy validates them; then out and its six arrays non-NULL, n_episodes >= 1, max_steps >= 0 and
+ * n_episodes * n_lanes < 2^31.  Any failure returns CARL_ERR_INVALID_ARGUMENT before anything is enqueued; without
+ * CARL_FLAG_AUTORESET the call returns CARL_ERR_UNSUPPORTED (as a summary does).  n_lanes == 0 enqueues nothing;
+ * max_steps == 0 still fills every output.  No host synchronisation: stream-ordered and capturable. */
+int carl_evaluate_policy(const carl_batch_t* batch, const carl_policy_t* policy_host, int32_t n_episodes,
+                         int32_t max_steps, const carl_policy_episodes_t* out, void* stream);
+
 /* ======================= Brax-locomotion families (spring backend) =======================
  * Replaces CARLBraxEnv + BraxGymWrapper/VectorGymWrapper + brax.spring.pipeline.step x
  * n_frames + brax.envs.<env>.step/reset (carl/envs/brax/carl_brax_env.py:115-336,

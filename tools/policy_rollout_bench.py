@@ -5,11 +5,18 @@
   open_loop        VecEngine.rollout of pre-written int32 actions (the staged kernel), same T;
   graph_step_mlp   what a caller has without the feature: a captured hipGraph of `step` + a torch forward of the same
                    MLP + argmax per env step (100 steps per graph, replayed to 1 000).
+  evaluate         VecEngine.evaluate_policy (episodes mode), linear and 2x64 tanh: K = 10 episodes per lane, at most
+                   5 000 steps, every launch from the same snapshot.  Reports the launch time, the lane-steps taken
+                   (sum of `steps`), lane-steps/s, the same policy's summary-mode env-steps/s, the early-exit
+                   overhead (sum over wavefronts of 64 x that wave's largest `steps`, over the sum of `steps`), and
+                   the launch time per step of its longest lane against summary mode's time per step.
 
 Host timing with torch.cuda events around `--reps` launches after one warm-up launch; the median per launch is
 reported.  Kernel times belong to a separate `rocprofv3 --kernel-trace --stats` run of this script.
 
-  python tools/policy_rollout_bench.py [--lanes 65536] [--steps 1000] [--reps 5] [--out FILE]
+  python tools/policy_rollout_bench.py [--lanes 65536] [--steps 1000] [--reps 5] [--legs rollout,evaluate] [--out FILE]
+
+--out FILE: a JSON file whose keys of the legs run ("results": rollout, "evaluate") are replaced, others kept.
 """
 from __future__ import annotations
 
@@ -92,17 +99,63 @@ def graph_step_mlp(eng, mlp, T, per_graph=100):
     return run
 
 
+def evaluate_leg(eng, n_in, T_summary, reps, K=10, max_steps=5000):
+    """the episodes mode against the same policy's summary mode (module docstring)"""
+    rows = []
+    snap = eng.snapshot()
+    for name, widths in {"linear": [], "mlp_2x64_tanh": [64, 64]}.items():
+        pol = MLPPolicy.from_sequential(eng, make_mlp(widths, n_in))
+        res = eng.alloc_policy_episodes(K)
+        ts = []
+        for _ in range(reps + 1):  # (the first: warm-up)
+            eng.restore(snap)
+            torch.cuda.synchronize()
+            a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            a.record()
+            eng.evaluate_policy(pol, K, max_steps, out=res)
+            b.record()
+            b.synchronize()
+            ts.append(a.elapsed_time(b) * 1e-3)
+        sec = float(np.median(ts[1:]))
+        steps = res["steps"].to(torch.int64)
+        lane_steps = int(steps.sum())
+        wave_max = steps[: eng.n // 64 * 64].view(-1, 64).max(dim=1).values
+        eng.restore(snap)
+        s = eng.alloc_policy_summary()
+        ssec, sts = time_launches(lambda: eng.rollout_policy(pol, T_summary, out=s, mode="summary"), reps)
+        r = {"config": f"evaluate_{name}", "lanes": eng.n, "n_episodes": K, "max_steps": max_steps,
+             "sec_per_launch": sec, "lane_steps": lane_steps, "lane_steps_per_s": lane_steps / sec,
+             "episodes_finished": int(res["episodes"].sum()), "max_lane_steps": int(steps.max()),
+             "early_exit_overhead": float(64 * wave_max.sum()) / max(lane_steps, 1),
+             "summary_steps": T_summary, "summary_env_steps_per_s": eng.n * T_summary / ssec,
+             "lane_steps_per_s_over_summary": (lane_steps / sec) / (eng.n * T_summary / ssec),
+             # the launch lasts as long as its longest lane: time per step of that lane against summary mode's per step
+             "ns_per_step_longest_lane": sec / max(int(steps.max()), 1) * 1e9, "summary_ns_per_step": ssec / T_summary * 1e9,
+             "reps_sec": ts[1:]}
+        rows.append(r)
+        print(json.dumps(r), flush=True)
+    eng.restore(snap)
+    return rows
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--lanes", type=int, default=65536)
     ap.add_argument("--steps", type=int, default=1000)
     ap.add_argument("--reps", type=int, default=5)
+    ap.add_argument("--legs", default="rollout,evaluate")
     ap.add_argument("--out", default=None)
     args = ap.parse_args()
+    legs = set(args.legs.split(","))
     n, T = args.lanes, args.steps
     eng = make_engine(n)
     n_in = len(eng.ctx_obs_rows) + eng.D
     rows = []
+    doc = {}
+    if "evaluate" in legs:
+        doc["evaluate"] = evaluate_leg(eng, n_in, T, args.reps)
+    if "rollout" not in legs:
+        return write(args.out, doc)
 
     def record(name, sec, ts):
         r = {"config": name, "lanes": n, "steps": T, "sec_per_launch": sec, "env_steps_per_s": n * T / sec,
@@ -126,9 +179,20 @@ def main():
         with torch.no_grad():
             run = graph_step_mlp(eng, mlp.to(eng.device), T)
             record(f"graph_step_torch_{name}", *time_launches(run, max(1, args.reps // 2)))
-    if args.out:
-        with open(args.out, "w") as f:
-            json.dump({"device": torch.cuda.get_device_name(0), "results": rows}, f, indent=1)
+    doc["results"] = rows
+    write(args.out, doc)
+
+
+def write(path, doc):
+    if not path:
+        return
+    old = {}
+    if os.path.exists(path):
+        with open(path) as f:
+            old = json.load(f)
+    old.update(device=torch.cuda.get_device_name(0), **doc)
+    with open(path, "w") as f:
+        json.dump(old, f, indent=1)
 
 
 if __name__ == "__main__":
