@@ -261,9 +261,17 @@ class PolicyEpisodes(C.Structure):
                 ("terminated", _vp)]
 
 
+class PolicySampling(C.Structure):
+    _fields_ = [("seed", C.c_uint64), ("log_std", _vp), ("log_prob", _vp)]
+
+
 EXPORTS.update({
     "carl_rollout_policy": (C.c_int, [C.POINTER(Batch), C.POINTER(Policy), C.POINTER(StepIO), C.c_int32,
                                       C.POINTER(PolicySummary), _vp]),
+    "carl_rollout_policy_sampled": (C.c_int, [C.POINTER(Batch), C.POINTER(Policy), C.POINTER(PolicySampling),
+                                              C.POINTER(StepIO), C.c_int32, C.POINTER(PolicySummary), _vp]),
+    "carl_evaluate_policy_sampled": (C.c_int, [C.POINTER(Batch), C.POINTER(Policy), C.POINTER(PolicySampling), C.c_int32,
+                                               C.c_int32, C.POINTER(PolicyEpisodes), _vp]),
     "carl_policy_lane_quantum": (C.c_int32, []),
     "carl_policy_set_floats": (C.c_int32, [C.POINTER(Policy)]),
     "carl_evaluate_policy": (C.c_int, [C.POINTER(Batch), C.POINTER(Policy), C.c_int32, C.c_int32,

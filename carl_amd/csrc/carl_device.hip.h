@@ -36,6 +36,7 @@ __device__ __forceinline__ u32x4 philox4x32_10(u32x4 c, uint32_t k0, uint32_t k1
 constexpr uint32_t kSubInit = 0u;      // init-state draws
 constexpr uint32_t kSubSelector = 1u;  // random context selector
 constexpr uint32_t kSubStep0 = 2u;     // + elapsed: per-step noise
+constexpr uint32_t kSubSample = 0x80000000u;  // | elapsed: a sampled policy's action draw (its own key, sample_seed)
 
 __device__ __forceinline__ u32x4 lane_words(uint64_t seed, uint64_t glane, uint32_t episode,
                                             uint32_t sub) {

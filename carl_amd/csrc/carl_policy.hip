@@ -1,6 +1,7 @@
 // carl_policy.hip -- C-ABI entry points of the closed-loop rollout (include/carl_amd.h: carl_rollout_policy) and their
 // kernel dispatch.  A translation unit of its own: the kernels (policy_kernels.hip.h) instantiate the engine's device
-// templates anew, and the open-loop kernels of carl_amd.hip compile exactly as they did without them.
+// templates anew, and the open-loop kernels of carl_amd.hip compile exactly as they did without them.  The host rules
+// of policy_host.hpp live here too; the sampled twins (carl_policy_sample.hip) call them.
 #include <hip/hip_runtime.h>
 
 #include <cstdint>
@@ -8,15 +9,12 @@
 #include "../../include/carl_amd.h"
 #include "classic_control.hip.h"
 #include "host_common.hpp"
+#include "policy_host.hpp"
 #include "policy_kernels.hip.h"
 
-namespace {
+namespace carl_host {
 
-using carl_host::check_launch;
-using carl_host::fail;
-
-// floats of one packed weight set (include/carl_amd.h), or -1 for a shape outside the limits
-int set_floats_of(const carl_policy_t* p) {
+int policy_set_floats(const carl_policy_t* p) {
   if (p->n_in < 1 || p->n_in > CARL_POLICY_MAX_IN || p->n_out < 1 || p->n_out > 4 || p->n_hidden < 0 ||
       p->n_hidden > CARL_POLICY_MAX_HIDDEN)
     return -1;
@@ -31,8 +29,15 @@ int set_floats_of(const carl_policy_t* p) {
   return (int)((total + 3) / 4 * 4);
 }
 
-int validate_policy(const carl_batch_t* b, const carl_policy_t* p, const carl_family_info_t& fi,
-                    const char* who = "carl_rollout_policy") {
+int policy_padded_hidden(const carl_policy_t* p) {
+  int wmax = 0;
+  for (int l = 0; l < p->n_hidden; ++l) wmax = wmax > p->width[l] ? wmax : p->width[l];
+  return p->n_hidden == 0 ? 0 : wmax <= 32 ? 32 : 64;
+}
+
+namespace {
+
+int validate_policy(const carl_batch_t* b, const carl_policy_t* p, const carl_family_info_t& fi, const char* who) {
   if (p->n_hidden < 0 || p->n_hidden > CARL_POLICY_MAX_HIDDEN)
     return fail(CARL_ERR_INVALID_ARGUMENT, "%s: n_hidden %d outside [0, %d]", who, p->n_hidden, CARL_POLICY_MAX_HIDDEN);
   for (int l = 0; l < p->n_hidden; ++l)
@@ -67,8 +72,7 @@ int validate_policy(const carl_batch_t* b, const carl_policy_t* p, const carl_fa
 }
 
 // transitions mode: the staged layout of carl_rollout (see include/carl_amd.h: carl_step_io_t::row_pitch)
-int validate_io(const carl_batch_t* b, const carl_step_io_t* io, const carl_family_info_t& fi) {
-  const char* who = "carl_rollout_policy";
+int validate_io(const carl_batch_t* b, const carl_step_io_t* io, const carl_family_info_t& fi, const char* who) {
   if (!io->action || !io->obs || !io->reward || !io->terminated || !io->truncated)
     return fail(CARL_ERR_INVALID_ARGUMENT, "%s: a required io pointer is NULL", who);
   const int want = fi.action_is_discrete ? CARL_ACTION_I32 : CARL_ACTION_F32;
@@ -84,12 +88,79 @@ int validate_io(const carl_batch_t* b, const carl_step_io_t* io, const carl_fami
   return 0;
 }
 
-// the instantiated hidden width a policy is padded to: 0 (a linear policy), 32, 64
-int padded_hidden(const carl_policy_t* p) {
-  int wmax = 0;
-  for (int l = 0; l < p->n_hidden; ++l) wmax = wmax > p->width[l] ? wmax : p->width[l];
-  return p->n_hidden == 0 ? 0 : wmax <= 32 ? 32 : 64;
+}  // namespace
+
+int check_rollout_policy(const char* who, const carl_batch_t* batch, const carl_policy_t* policy_host,
+                         const carl_step_io_t* io, int32_t n_steps, const carl_policy_summary_t* summary_out,
+                         carl_family_info_t* fi) {
+  if (batch == nullptr || policy_host == nullptr) return fail(CARL_ERR_INVALID_ARGUMENT, "%s: batch / policy is NULL", who);
+  if (batch->family >= CARL_N_FAMILIES)
+    return fail(CARL_ERR_INVALID_ARGUMENT, "%s: family %d is a Brax family -- the closed-loop rollout covers the "
+                "classic-control families only", who, batch->family);
+  if (int e = validate_batch(batch, who)) return e;
+  if (int e = carl_family_info(batch->family, fi)) return e;
+  if (int e = validate_policy(batch, policy_host, *fi, who)) return e;
+  if (n_steps < 0) return fail(CARL_ERR_INVALID_ARGUMENT, "%s: n_steps %d < 0", who, n_steps);
+  if (io == nullptr) {
+    if (summary_out == nullptr || !summary_out->episodes || !summary_out->return_sum || !summary_out->length_sum)
+      return fail(CARL_ERR_INVALID_ARGUMENT, "%s: summary mode (io NULL) needs all three summary arrays", who);
+  } else {
+    if (int e = validate_io(batch, io, *fi, who)) return e;
+    if (summary_out != nullptr && (!summary_out->episodes || !summary_out->return_sum || !summary_out->length_sum))
+      return fail(CARL_ERR_INVALID_ARGUMENT, "%s: a summary needs all three arrays", who);
+  }
+  // Without auto-reset a finished lane stays done and reports done again on every later step (its return and length
+  // still growing): the per-lane totals would count one episode many times.  A summary needs CARL_FLAG_AUTORESET.
+  if (summary_out != nullptr && !(batch->flags & CARL_FLAG_AUTORESET))
+    return fail(CARL_ERR_UNSUPPORTED, "%s: a summary needs CARL_FLAG_AUTORESET (without auto-reset a finished lane "
+                "reports done on every later step, and its episode would be counted on each of them)", who);
+  return 0;
 }
+
+int policy_rollout_without_steps(const char* who, const carl_batch_t* batch, const carl_policy_summary_t* summary_out,
+                                 void* stream) {
+  if (summary_out == nullptr || batch->n_lanes == 0) return 0;
+  // no step: every total is zero
+  hipStream_t s = (hipStream_t)stream;
+  const size_t bytes = (size_t)batch->n_lanes * 4;
+  for (void* p : {(void*)summary_out->episodes, (void*)summary_out->return_sum, (void*)summary_out->length_sum})
+    if (const hipError_t e = hipMemsetAsync(p, 0, bytes, s); e != hipSuccess)
+      return fail((int)e, "%s: hipMemsetAsync: %s", who, hipGetErrorString(e));
+  return 0;
+}
+
+int check_evaluate_policy(const char* who, const carl_batch_t* batch, const carl_policy_t* policy_host,
+                          int32_t n_episodes, int32_t max_steps, const carl_policy_episodes_t* out,
+                          carl_family_info_t* fi) {
+  if (batch == nullptr || policy_host == nullptr)
+    return fail(CARL_ERR_INVALID_ARGUMENT, "%s: batch / policy is NULL", who);
+  if (batch->family >= CARL_N_FAMILIES)
+    return fail(CARL_ERR_INVALID_ARGUMENT, "%s: family %d is a Brax family -- the closed-loop rollout covers the "
+                "classic-control families only", who, batch->family);
+  if (int e = validate_batch(batch, who)) return e;
+  if (int e = carl_family_info(batch->family, fi)) return e;
+  if (int e = validate_policy(batch, policy_host, *fi, who)) return e;
+  if (out == nullptr || !out->episodes || !out->steps || !out->ret || !out->length || !out->context_id ||
+      !out->terminated)
+    return fail(CARL_ERR_INVALID_ARGUMENT, "%s: out and all six of its arrays are required", who);
+  if (n_episodes < 1) return fail(CARL_ERR_INVALID_ARGUMENT, "%s: n_episodes %d < 1", who, n_episodes);
+  if (max_steps < 0) return fail(CARL_ERR_INVALID_ARGUMENT, "%s: max_steps %d < 0", who, max_steps);
+  if ((int64_t)n_episodes * batch->n_lanes >= ((int64_t)1 << 31))
+    return fail(CARL_ERR_INVALID_ARGUMENT, "%s: n_episodes %d x %d lanes records do not fit 2^31 - 1", who, n_episodes,
+                batch->n_lanes);
+  // as a summary: without auto-reset a finished lane reports done on every later step
+  if (!(batch->flags & CARL_FLAG_AUTORESET))
+    return fail(CARL_ERR_UNSUPPORTED, "%s: needs CARL_FLAG_AUTORESET (without auto-reset a finished lane reports done on "
+                "every later step, and its episode would be counted on each of them)", who);
+  return 0;
+}
+
+}  // namespace carl_host
+
+namespace {
+
+using carl_host::check_launch;
+using carl_host::fail;
 
 // a policy_rollout_kernel instance and the dynamic LDS it takes
 struct PolicyKernel {
@@ -107,7 +178,7 @@ template <class Fam>
 int launch_policy(const carl_batch_t* b, const carl_policy_t* p, const carl_step_io_t* io, int n_steps,
                   const carl_policy_summary_t* sum, hipStream_t s) {
   const bool summary = io == nullptr;
-  const int H = padded_hidden(p);
+  const int H = carl_host::policy_padded_hidden(p);
   const PolicyKernel k = H == 0 ? policy_kernel<Fam, 0>(summary) : H == 32 ? policy_kernel<Fam, 32>(summary)
                                                                   : policy_kernel<Fam, 64>(summary);
   static_assert(carl::policy_lds_bytes<Fam, 64, false>() + carl::static_lds_bytes<Fam>() <= carl::kCuLdsBytes,
@@ -121,7 +192,7 @@ int launch_policy(const carl_batch_t* b, const carl_policy_t* p, const carl_step
   const carl_policy_summary_t sum_r = sum != nullptr ? *sum : carl_policy_summary_t{nullptr, nullptr, nullptr};
   const int grid = (b->n_lanes + carl::kPolicyLanes - 1) / carl::kPolicyLanes;
   const int threads = summary ? carl::kPolicyThreadsSummary : carl::kPolicyThreadsTransitions;
-  hipLaunchKernelGGL(k.fn, dim3(grid), dim3(threads), k.lds, s, *b, io_r, *p, set_floats_of(p), sum_r, n_steps);
+  hipLaunchKernelGGL(k.fn, dim3(grid), dim3(threads), k.lds, s, *b, io_r, *p, carl_host::policy_set_floats(p), sum_r, n_steps);
   return check_launch("carl_rollout_policy");
 }
 
@@ -139,12 +210,12 @@ EpisodesKernel episodes_kernel() {
 template <class Fam>
 int launch_episodes(const carl_batch_t* b, const carl_policy_t* p, int n_episodes, int max_steps,
                     const carl_policy_episodes_t* out, hipStream_t s) {
-  const int H = padded_hidden(p);
+  const int H = carl_host::policy_padded_hidden(p);
   const EpisodesKernel k = H == 0 ? episodes_kernel<Fam, 0>() : H == 32 ? episodes_kernel<Fam, 32>()
                                                                : episodes_kernel<Fam, 64>();
   if (int e = carl_host::ensure_dynamic_lds(reinterpret_cast<const void*>(k.fn), k.lds, "carl_evaluate_policy")) return e;
   const int grid = (b->n_lanes + carl::kPolicyLanes - 1) / carl::kPolicyLanes;
-  hipLaunchKernelGGL(k.fn, dim3(grid), dim3(carl::kPolicyThreadsSummary), k.lds, s, *b, *p, set_floats_of(p), *out,
+  hipLaunchKernelGGL(k.fn, dim3(grid), dim3(carl::kPolicyThreadsSummary), k.lds, s, *b, *p, carl_host::policy_set_floats(p), *out,
                      n_episodes, max_steps);
   return check_launch("carl_evaluate_policy");
 }
@@ -157,44 +228,15 @@ int32_t carl_policy_lane_quantum(void) { return carl::kPolicyLanes; }
 
 int32_t carl_policy_set_floats(const carl_policy_t* policy_host) {
   if (policy_host == nullptr) return -1;
-  return set_floats_of(policy_host);
+  return carl_host::policy_set_floats(policy_host);
 }
 
 int carl_rollout_policy(const carl_batch_t* batch, const carl_policy_t* policy_host, const carl_step_io_t* io,
                         int32_t n_steps, const carl_policy_summary_t* summary_out, void* stream) {
-  if (batch == nullptr || policy_host == nullptr)
-    return fail(CARL_ERR_INVALID_ARGUMENT, "carl_rollout_policy: batch / policy is NULL");
-  if (batch->family >= CARL_N_FAMILIES)
-    return fail(CARL_ERR_INVALID_ARGUMENT, "carl_rollout_policy: family %d is a Brax family -- the closed-loop rollout "
-                "covers the classic-control families only", batch->family);
-  if (int e = carl_host::validate_batch(batch, "carl_rollout_policy")) return e;
+  const char* who = "carl_rollout_policy";
   carl_family_info_t fi;
-  if (int e = carl_family_info(batch->family, &fi)) return e;
-  if (int e = validate_policy(batch, policy_host, fi)) return e;
-  if (n_steps < 0) return fail(CARL_ERR_INVALID_ARGUMENT, "carl_rollout_policy: n_steps %d < 0", n_steps);
-  if (io == nullptr) {
-    if (summary_out == nullptr || !summary_out->episodes || !summary_out->return_sum || !summary_out->length_sum)
-      return fail(CARL_ERR_INVALID_ARGUMENT, "carl_rollout_policy: summary mode (io NULL) needs all three summary arrays");
-  } else {
-    if (int e = validate_io(batch, io, fi)) return e;
-    if (summary_out != nullptr && (!summary_out->episodes || !summary_out->return_sum || !summary_out->length_sum))
-      return fail(CARL_ERR_INVALID_ARGUMENT, "carl_rollout_policy: a summary needs all three arrays");
-  }
-  // Without auto-reset a finished lane stays done and reports done again on every later step (its return and length
-  // still growing): the per-lane totals would count one episode many times.  A summary needs CARL_FLAG_AUTORESET.
-  if (summary_out != nullptr && !(batch->flags & CARL_FLAG_AUTORESET))
-    return fail(CARL_ERR_UNSUPPORTED, "carl_rollout_policy: a summary needs CARL_FLAG_AUTORESET (without auto-reset a "
-                "finished lane reports done on every later step, and its episode would be counted on each of them)");
-  if (batch->n_lanes == 0 || n_steps == 0) {
-    if (summary_out == nullptr || batch->n_lanes == 0) return 0;
-    // no step: every total is zero
-    hipStream_t s = (hipStream_t)stream;
-    const size_t bytes = (size_t)batch->n_lanes * 4;
-    for (void* p : {(void*)summary_out->episodes, (void*)summary_out->return_sum, (void*)summary_out->length_sum})
-      if (const hipError_t e = hipMemsetAsync(p, 0, bytes, s); e != hipSuccess)
-        return fail((int)e, "carl_rollout_policy: hipMemsetAsync: %s", hipGetErrorString(e));
-    return 0;
-  }
+  if (int e = carl_host::check_rollout_policy(who, batch, policy_host, io, n_steps, summary_out, &fi)) return e;
+  if (batch->n_lanes == 0 || n_steps == 0) return carl_host::policy_rollout_without_steps(who, batch, summary_out, stream);
   return carl_host::with_classic_family(batch, [&](auto fam) {
     return launch_policy<decltype(fam)>(batch, policy_host, io, n_steps, summary_out, (hipStream_t)stream);
   });
@@ -202,28 +244,9 @@ int carl_rollout_policy(const carl_batch_t* batch, const carl_policy_t* policy_h
 
 int carl_evaluate_policy(const carl_batch_t* batch, const carl_policy_t* policy_host, int32_t n_episodes,
                          int32_t max_steps, const carl_policy_episodes_t* out, void* stream) {
-  const char* who = "carl_evaluate_policy";
-  if (batch == nullptr || policy_host == nullptr)
-    return fail(CARL_ERR_INVALID_ARGUMENT, "%s: batch / policy is NULL", who);
-  if (batch->family >= CARL_N_FAMILIES)
-    return fail(CARL_ERR_INVALID_ARGUMENT, "%s: family %d is a Brax family -- the closed-loop rollout covers the "
-                "classic-control families only", who, batch->family);
-  if (int e = carl_host::validate_batch(batch, who)) return e;
   carl_family_info_t fi;
-  if (int e = carl_family_info(batch->family, &fi)) return e;
-  if (int e = validate_policy(batch, policy_host, fi, who)) return e;
-  if (out == nullptr || !out->episodes || !out->steps || !out->ret || !out->length || !out->context_id ||
-      !out->terminated)
-    return fail(CARL_ERR_INVALID_ARGUMENT, "%s: out and all six of its arrays are required", who);
-  if (n_episodes < 1) return fail(CARL_ERR_INVALID_ARGUMENT, "%s: n_episodes %d < 1", who, n_episodes);
-  if (max_steps < 0) return fail(CARL_ERR_INVALID_ARGUMENT, "%s: max_steps %d < 0", who, max_steps);
-  if ((int64_t)n_episodes * batch->n_lanes >= ((int64_t)1 << 31))
-    return fail(CARL_ERR_INVALID_ARGUMENT, "%s: n_episodes %d x %d lanes records do not fit 2^31 - 1", who, n_episodes,
-                batch->n_lanes);
-  // as a summary: without auto-reset a finished lane reports done on every later step
-  if (!(batch->flags & CARL_FLAG_AUTORESET))
-    return fail(CARL_ERR_UNSUPPORTED, "%s: needs CARL_FLAG_AUTORESET (without auto-reset a finished lane reports done on "
-                "every later step, and its episode would be counted on each of them)", who);
+  if (int e = carl_host::check_evaluate_policy("carl_evaluate_policy", batch, policy_host, n_episodes, max_steps, out, &fi))
+    return e;
   if (batch->n_lanes == 0) return 0;
   return carl_host::with_classic_family(batch, [&](auto fam) {
     return launch_episodes<decltype(fam)>(batch, policy_host, n_episodes, max_steps, out, (hipStream_t)stream);

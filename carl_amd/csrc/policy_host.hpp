@@ -1,0 +1,24 @@
+// policy_host.hpp -- host-side rules of the closed-loop rollout (defined in carl_policy.hip), shared by its deterministic
+// entry points and their sampled twins (carl_policy_sample.hip): one validation, one kernel-width rule.
+#pragma once
+
+#include <cstdint>
+
+#include "../../include/carl_amd.h"
+
+namespace carl_host {
+// floats of one packed weight set (include/carl_amd.h), or -1 for a shape outside the limits
+int policy_set_floats(const carl_policy_t* p);
+// the instantiated hidden width a policy is padded to: 0 (a linear policy), 32, 64
+int policy_padded_hidden(const carl_policy_t* p);
+
+// Every check of carl_rollout_policy / carl_evaluate_policy, in its order, with messages that begin with `who`; 0 when
+// the call may go on, `fi` then holds the batch family's info.
+int check_rollout_policy(const char* who, const carl_batch_t* batch, const carl_policy_t* policy, const carl_step_io_t* io,
+                         int32_t n_steps, const carl_policy_summary_t* summary_out, carl_family_info_t* fi);
+int check_evaluate_policy(const char* who, const carl_batch_t* batch, const carl_policy_t* policy, int32_t n_episodes,
+                          int32_t max_steps, const carl_policy_episodes_t* out, carl_family_info_t* fi);
+// a validated rollout without a step (n_lanes == 0 or n_steps == 0): zero the summary totals, if any
+int policy_rollout_without_steps(const char* who, const carl_batch_t* batch, const carl_policy_summary_t* summary_out,
+                                 void* stream);
+}  // namespace carl_host

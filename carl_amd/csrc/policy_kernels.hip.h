@@ -50,16 +50,24 @@ struct PolicyLayout {
   static constexpr size_t kBytes = (size_t)kFloats * sizeof(float);
 };
 
-// transitions mode: steps per LDS record buffer -- 8 like carl_rollout where the records and the action column (the
-// staged rollout's buffers), the largest weight set and the family's static tables fit a compute unit; 4 otherwise
-// (Acrobot: 24-byte observations)
-template <class Fam>
-__host__ __device__ constexpr int policy_chunk() {
-  return rollout_staged_lds_bytes<Fam, 8>() + PolicyLayout<Fam, 64>::kBytes + static_lds_bytes<Fam>() <= kCuLdsBytes ? 8 : 4;
+// LDS of a sampled launch's log_prob column (LOGP): [2][chunk][256] floats, after the action column
+template <bool LOGP>
+__host__ __device__ constexpr size_t policy_logp_lds_bytes(int chunk) {
+  return LOGP ? (size_t)2 * chunk * kPolicyLanes * 4 : 0;
 }
-template <class Fam, int H, bool SUMMARY>
+// transitions mode: steps per LDS record buffer -- 8 like carl_rollout where the records and the action column (the
+// staged rollout's buffers), the log_prob column of a sampled launch that stores one (LOGP), the largest weight set
+// and the family's static tables fit a compute unit; 4 otherwise (Acrobot: 24-byte observations)
+template <class Fam, bool LOGP = false>
+__host__ __device__ constexpr int policy_chunk() {
+  return rollout_staged_lds_bytes<Fam, 8>() + policy_logp_lds_bytes<LOGP>(8) + PolicyLayout<Fam, 64>::kBytes +
+                     static_lds_bytes<Fam>() <= kCuLdsBytes ? 8 : 4;
+}
+template <class Fam, int H, bool SUMMARY, bool LOGP = false>
 __host__ __device__ constexpr size_t policy_lds_bytes() {
-  return PolicyLayout<Fam, H>::kBytes + (SUMMARY ? 0 : rollout_staged_lds_bytes<Fam, policy_chunk<Fam>()>());
+  constexpr int CHUNK = policy_chunk<Fam, LOGP>();
+  return PolicyLayout<Fam, H>::kBytes +
+         (SUMMARY ? 0 : rollout_staged_lds_bytes<Fam, CHUNK>() + policy_logp_lds_bytes<LOGP>(CHUNK));
 }
 
 // Copy weight set `set` from its packed form (include/carl_amd.h) into the padded LDS layout; every thread of the
@@ -201,7 +209,31 @@ __device__ __forceinline__ float normalize_input(float v, float shift, float sca
   return fminf(fmaxf((v - shift) * scale, -clip), clip);
 }
 
-// The policy's action for input slots x (LDS layout above)
+// The policy's head outputs y[0, n_out) for input slots x (LDS layout above)
+template <class Fam, int H>
+__device__ __forceinline__ void policy_head(const float* w, const float (&x)[PolicyLayout<Fam, H>::K], int n_hidden,
+                                            int act, int w0, int w1, float (&y)[4]) {
+  using L = PolicyLayout<Fam, H>;
+  if constexpr (H == 0) {
+    head_layer<L::K>(w + L::kWh, w + L::kBh, x, y);
+  } else {
+    float h1[H];
+    dense_layer<H, L::K>(w + L::kW1, w + L::kB1, x, h1);
+    activate(h1, act, w0);
+    if (n_hidden > 1) {  // (wave-uniform)
+      float h2[H];
+      dense_layer<H, H>(w + L::kW2, w + L::kB2, h1, h2);
+      activate(h2, act, w1);
+      head_layer<H>(w + L::kWh, w + L::kBh, h2, y);
+    } else {
+      head_layer<H>(w + L::kWh, w + L::kBh, h1, y);
+    }
+  }
+}
+
+// The policy's deterministic action for input slots x: the first maximal head output (discrete), y[0] (Box).  It keeps
+// its own copy of policy_head's forward pass: calling policy_head from here moves the register allocation of the
+// deterministic kernels (same results; profiles/policy_sample_isa_identity.txt holds their code unchanged).
 template <class Fam, int H>
 __device__ __forceinline__ typename Fam::Action policy_action(const float* w, const float (&x)[PolicyLayout<Fam, H>::K],
                                                               int n_hidden, int act, int w0, int w1) {
@@ -237,6 +269,76 @@ __device__ __forceinline__ typename Fam::Action policy_action(const float* w, co
   }
 }
 
+// How a step's action comes from the network: ModePick, the deterministic policy (carl_rollout_policy /
+// carl_evaluate_policy: policy_action), or SampledPick, whose choose() returns a sampled action and, when kLogProb, its
+// log-probability in `lp`.
+template <class Fam>
+struct ModePick {
+  static constexpr bool kSampled = false, kLogProb = false;
+};
+
+// Sampled actions (include/carl_amd.h: carl_policy_sampling_t).  The Philox block is drawn and reduced to the one
+// float the rule needs (u, or the Gaussian z) BEFORE the network runs, so its four words are dead again by the time
+// the hidden layers need their registers.  The counter reads the lane's episode counter, which load_staged_lane has
+// fetched up front for every lane.
+template <class Fam, bool LOGP>
+struct SampledPick {
+  static constexpr bool kSampled = true, kLogProb = LOGP;
+  uint64_t seed;
+  float sigma;  // Box: exp(log_std) of the workgroup's weight set
+  float lp0;    // Box: -log_std - ln(2 pi) / 2
+
+  // the workgroup's values (one weight set per workgroup: wave-uniform, scalar loads)
+  static __device__ __forceinline__ SampledPick of(const carl_policy_sampling_t& smp, const carl_policy_t& pol) {
+    SampledPick p{smp.seed, 1.0f, 0.0f};
+    if constexpr (std::is_same_v<typename Fam::Action, float>) {
+      const float ls = smp.log_std[(int)blockIdx.x * kPolicyLanes / pol.lanes_per_set];
+      p.sigma = expf(ls);
+      p.lp0 = -ls - 0.918938533204672742f;
+    }
+    return p;
+  }
+
+  template <int H>
+  __device__ __forceinline__ typename Fam::Action choose(const float* w, const float (&x)[PolicyLayout<Fam, H>::K],
+                                                         int n_hidden, int act, int w0, int w1, uint64_t glane,
+                                                         const LaneRegs<Fam>& r, float& lp) const {
+#pragma clang fp contract(off)
+    const u32x4 wd = lane_words(seed, glane, r.episode - 1u, kSubSample | (uint32_t)r.elapsed);
+    float y[4];
+    if constexpr (std::is_same_v<typename Fam::Action, float>) {
+      const float u1 = (float)((wd.x >> 8) + 1u) * (1.0f / 16777216.0f);  // (0, 1]
+      const float u2 = u01(wd.y);
+      const float z = sqrtf(-2.0f * logf(u1)) * cospif(2.0f * u2);
+      policy_head<Fam, H>(w, x, n_hidden, act, w0, w1, y);
+      if constexpr (LOGP) lp = __fmaf_rn(-0.5f * z, z, lp0);
+      return __fmaf_rn(sigma, z, y[0]);
+    } else {
+      constexpr int NA = policy_outputs<Fam>::value;
+      const float u = u01(wd.x);
+      policy_head<Fam, H>(w, x, n_hidden, act, w0, w1, y);
+      float m = y[0];
+#pragma unroll
+      for (int k = 1; k < NA; ++k) m = fmaxf(m, y[k]);
+      float c[NA];  // prefix sums of exp(y_k - m); c[NA - 1] = S
+      float s = 0.0f;
+#pragma unroll
+      for (int k = 0; k < NA; ++k) c[k] = s = s + expf(y[k] - m);
+      const float t = u * s;
+      int a = NA - 1;
+      float ya = y[NA - 1];
+#pragma unroll
+      for (int k = NA - 2; k >= 0; --k) {  // the first k with t < c_k
+        const bool in = t < c[k];
+        a = in ? k : a;
+        ya = in ? y[k] : ya;
+      }
+      if constexpr (LOGP) lp = (ya - m) - logf(s);
+      return a;
+    }
+  }
+};
+
 // summary mode's sink: step_lane writes nothing anywhere (flags are lazy: only the done path would write them)
 template <class Fam>
 struct NullSink {
@@ -264,109 +366,23 @@ template <class Fam, int H, bool SUMMARY>
 __global__ void __launch_bounds__(SUMMARY ? kPolicyThreadsSummary : kPolicyThreadsTransitions)
     policy_rollout_kernel(const carl_batch_t b, const carl_step_io_t io, const carl_policy_t pol, const int set_floats,
                           const carl_policy_summary_t sum, const int n_steps) {
-  using L = PolicyLayout<Fam, H>;
-  using SK = LdsSink<Fam>;
-  using Action = typename Fam::Action;
-  constexpr int CHUNK = policy_chunk<Fam>();
-  extern __shared__ float lds_dyn[];
-  stage_family_tables<Fam>();
-  float* const wts = lds_dyn;
-  char* const out_buf = reinterpret_cast<char*>(lds_dyn) + L::kBytes;         // [2][CHUNK] records (transitions)
-  char* const act_buf = out_buf + (size_t)2 * CHUNK * SK::kStepBytes;         // [2][CHUNK][256] actions
-  const int lane_base = (int)blockIdx.x * kPolicyLanes;
-  stage_policy<Fam, H>(wts, pol, set_floats, lane_base / pol.lanes_per_set);
-  const GlobalCtx ctx{b.ctx_table, b.ctx_stride};
-  const int wave = __builtin_amdgcn_readfirstlane((int)(threadIdx.x / kWave));
-  const bool compute = wave < kPolicyLanes / kWave;
-  const int hl = threadIdx.x % kWave;
-  const int storer = wave - kPolicyLanes / kWave;
-  const int lane = lane_base + (compute ? (int)threadIdx.x : 0);
-  const bool active = compute && lane < b.n_lanes;
-  const uint64_t glane = (uint64_t)(b.lane_offset + lane);
-  const size_t n = (size_t)io.row_pitch;
-  const int n_cols = (b.n_lanes + 15) & ~15;
-  if (!SUMMARY && !compute) zero_flag_rows<Fam, CHUNK>(out_buf, hl, storer);
-  __syncthreads();
+  using Pick = ModePick<Fam>;
+  const Pick pick{};
+  float* const log_prob = nullptr;
+#include "policy_rollout_body.inc"
+}
 
-  if (compute) {
-    LaneRegs<Fam> r{};
-    load_staged_lane<Fam>(b, ctx, lane, active, r);
-    float* const final_base = (!SUMMARY && io.final_obs != nullptr && active) ? io.final_obs + (size_t)lane * Fam::D : nullptr;
-    const int n_ctx = pol.n_ctx, n_hidden = pol.n_hidden, act = pol.activation;
-    const int w0 = pol.width[0], w1 = pol.width[1];  // (w1: read only when n_hidden == 2)
-    const float clip = wts[L::kClip];
-    float x[L::K];
-#pragma unroll
-    for (int s = 0; s < L::K; ++s) x[s] = 0.0f;
-    int x_cidx = -1;  // context whose values x[0, n_ctx) hold
-    int ep_count = 0, len_sum = 0;
-    float ret_sum = 0.0f;
-    int buf = 0;
-    for (int t0 = 0; t0 < n_steps; t0 += CHUNK, buf ^= 1) {
-      const int steps = min(CHUNK, n_steps - t0);
-      if constexpr (predraw_of<Fam>::value) predraw<Fam>(b, glane, r);
-      char* const rec = out_buf + (size_t)buf * CHUNK * SK::kStepBytes;
-      Action* const my_act = reinterpret_cast<Action*>(act_buf + (size_t)buf * CHUNK * kPolicyLanes * 4) + threadIdx.x;
-#pragma unroll 1
-      for (int u = 0; u < steps; ++u) {
-        // context inputs: re-read when some lane of the wave moved to another context (a reset under a round-robin /
-        // random selector, or the launch's first step)
-        if (ballot(r.cidx != x_cidx) != 0ull) {
-#pragma unroll
-          for (int k = 0; k < Fam::F; ++k)
-            if (k < n_ctx) x[k] = normalize_input(ctx.get(pol.ctx_rows[k], r.cidx), wts[L::kShift + k], wts[L::kScale + k], clip);
-          x_cidx = r.cidx;
-        }
-        float o[Fam::D];
-        Fam::observe(r.s, r.aux, o);
-#pragma unroll
-        for (int d = 0; d < Fam::D; ++d)
-          x[Fam::F + d] = normalize_input(o[d], wts[L::kShift + Fam::F + d], wts[L::kScale + Fam::F + d], clip);
-        const Action a = policy_action<Fam, H>(wts, x, n_hidden, act, w0, w1);
-        const int before = r.n_new_episodes;
-        if constexpr (SUMMARY) {
-          step_lane<Fam, GlobalCtx, true, NullSink<Fam>>(b, ctx, NullSink<Fam>{}, b.max_episode_steps, true, lane, glane,
-                                                          a, r);
-        } else {
-          my_act[u * kPolicyLanes] = a;
-          const SK sink{rec + (size_t)u * SK::kStepBytes, final_base, n * Fam::D, t0 + u, (int)threadIdx.x};
-          step_lane<Fam, GlobalCtx, true, SK>(b, ctx, sink, b.max_episode_steps, true, lane, glane, a, r);
-        }
-        const bool fin = r.n_new_episodes != before;  // (valid lanes only: finish_episodes counts those)
-        ep_count += fin ? 1 : 0;
-        len_sum += fin ? r.fin_length : 0;
-        ret_sum = fin ? ret_sum + r.fin_return : ret_sum;
-      }
-      if constexpr (!SUMMARY) __syncthreads();
-    }
-    if (active) {
-      store_lane<Fam>(b, ctx, lane, r);
-      if (sum.episodes != nullptr) {
-        sum.episodes[lane] = ep_count;
-        sum.return_sum[lane] = ret_sum;
-        sum.length_sum[lane] = len_sum;
-      }
-    }
-  } else if constexpr (!SUMMARY) {
-    // storer waves: the previous chunk's records and actions while the compute waves run the current one
-    int buf = 0;
-    for (int t0 = 0; t0 < n_steps; t0 += CHUNK, buf ^= 1) {
-      if (t0 > 0) {
-        drain_records<Fam>(out_buf + (size_t)(buf ^ 1) * CHUNK * SK::kStepBytes, io, n, n_cols, lane_base, hl, storer,
-                           t0 - CHUNK, CHUNK);
-        drain_actions(act_buf + (size_t)(buf ^ 1) * CHUNK * kPolicyLanes * 4, const_cast<void*>(io.action), n, n_cols,
-                      lane_base, hl, storer, t0 - CHUNK, CHUNK);
-      }
-      __syncthreads();
-    }
-    if (n_steps > 0) {
-      const int last_t0 = ((n_steps - 1) / CHUNK) * CHUNK;
-      drain_records<Fam>(out_buf + (size_t)(buf ^ 1) * CHUNK * SK::kStepBytes, io, n, n_cols, lane_base, hl, storer,
-                         last_t0, n_steps - last_t0);
-      drain_actions(act_buf + (size_t)(buf ^ 1) * CHUNK * kPolicyLanes * 4, const_cast<void*>(io.action), n, n_cols,
-                    lane_base, hl, storer, last_t0, n_steps - last_t0);
-    }
-  }
+// carl_rollout_policy_sampled (carl_policy_sample.hip); LOGP: transitions mode with the log_prob column
+template <class Fam, int H, bool SUMMARY, bool LOGP>
+__global__ void __launch_bounds__(SUMMARY ? kPolicyThreadsSummary : kPolicyThreadsTransitions)
+    policy_rollout_sampled_kernel(const carl_batch_t b, const carl_step_io_t io, const carl_policy_t pol,
+                                  const int set_floats, const carl_policy_summary_t sum, const int n_steps,
+                                  const carl_policy_sampling_t smp) {
+  static_assert(!(SUMMARY && LOGP), "a summary stores no per-step column");
+  using Pick = SampledPick<Fam, LOGP>;
+  const Pick pick = Pick::of(smp, pol);
+  float* const log_prob = smp.log_prob;
+#include "policy_rollout_body.inc"
 }
 
 // episodes mode's sink: no per-step store; put_flags keeps the terminated bit in the caller's register.  kLazyFlags:
@@ -394,79 +410,20 @@ template <class Fam, int H>
 __global__ void __launch_bounds__(kPolicyThreadsSummary)
     policy_episodes_kernel(const carl_batch_t b, const carl_policy_t pol, const int set_floats,
                            const carl_policy_episodes_t ep, const int n_episodes, const int max_steps) {
-  using L = PolicyLayout<Fam, H>;
-  using Action = typename Fam::Action;
-  constexpr int CHUNK = policy_chunk<Fam>();
-  extern __shared__ float lds_dyn[];
-  stage_family_tables<Fam>();
-  float* const wts = lds_dyn;
-  const int lane_base = (int)blockIdx.x * kPolicyLanes;
-  stage_policy<Fam, H>(wts, pol, set_floats, lane_base / pol.lanes_per_set);
-  const GlobalCtx ctx{b.ctx_table, b.ctx_stride};
-  const int lane = lane_base + (int)threadIdx.x;
-  const bool active = lane < b.n_lanes;
-  const uint64_t glane = (uint64_t)(b.lane_offset + lane);
-  const size_t n = (size_t)b.n_lanes;
-  __syncthreads();
+  using Pick = ModePick<Fam>;
+  const Pick pick{};
+#include "policy_episodes_body.inc"
+}
 
-  LaneRegs<Fam> r{};
-  load_staged_lane<Fam>(b, ctx, lane, active, r);
-  const int n_ctx = pol.n_ctx, n_hidden = pol.n_hidden, act = pol.activation;
-  const int w0 = pol.width[0], w1 = pol.width[1];  // (w1: read only when n_hidden == 2)
-  const float clip = wts[L::kClip];
-  float x[L::K];
-#pragma unroll
-  for (int s = 0; s < L::K; ++s) x[s] = 0.0f;
-  int x_cidx = -1;  // context whose values x[0, n_ctx) hold
-  int done_eps = 0, steps = 0;
-  bool live = active;
-  // (ballot(live) == 0: every lane of the wave is done -- a wave-uniform exit from both loops)
-  for (int t0 = 0; t0 < max_steps && ballot(live) != 0ull; t0 += CHUNK) {
-    if constexpr (predraw_of<Fam>::value) predraw<Fam>(b, glane, r);
-    const int n_u = min(CHUNK, max_steps - t0);
-#pragma unroll 1
-    for (int u = 0; u < n_u; ++u) {
-      if (ballot(live) == 0ull) break;
-      if (ballot(r.cidx != x_cidx) != 0ull) {
-#pragma unroll
-        for (int k = 0; k < Fam::F; ++k)
-          if (k < n_ctx) x[k] = normalize_input(ctx.get(pol.ctx_rows[k], r.cidx), wts[L::kShift + k], wts[L::kScale + k], clip);
-        x_cidx = r.cidx;
-      }
-      float o[Fam::D];
-      Fam::observe(r.s, r.aux, o);
-#pragma unroll
-      for (int d = 0; d < Fam::D; ++d)
-        x[Fam::F + d] = normalize_input(o[d], wts[L::kShift + Fam::F + d], wts[L::kScale + Fam::F + d], clip);
-      const Action a = policy_action<Fam, H>(wts, x, n_hidden, act, w0, w1);
-      const int before = r.n_new_episodes, cidx = r.cidx;
-      bool te = false;
-      step_lane<Fam, GlobalCtx, false, TermSink<Fam>>(b, ctx, TermSink<Fam>{&te}, b.max_episode_steps, live, lane,
-                                                       glane, a, r);
-      steps += live ? 1 : 0;
-      if (r.n_new_episodes != before) {  // (live lanes only: finish_episodes counts valid lanes that stepped)
-        const size_t at = (size_t)done_eps * n + lane;
-        ep.ret[at] = r.fin_return;
-        ep.length[at] = r.fin_length;
-        ep.context_id[at] = cidx;
-        ep.terminated[at] = (uint8_t)te;
-        done_eps += 1;
-      }
-      live = live && done_eps < n_episodes;
-    }
-  }
-  if (active) {
-    store_lane<Fam>(b, ctx, lane, r);
-    ep.episodes[lane] = done_eps;
-    ep.steps[lane] = steps;
-    for (int k = done_eps; k < n_episodes; ++k) {
-      const size_t at = (size_t)k * n + lane;
-      ep.ret[at] = __builtin_nanf("");
-      ep.length[at] = 0;
-      ep.context_id[at] = -1;
-      ep.terminated[at] = 0;
-    }
-  }
+// carl_evaluate_policy_sampled (carl_policy_sample.hip)
+template <class Fam, int H>
+__global__ void __launch_bounds__(kPolicyThreadsSummary)
+    policy_episodes_sampled_kernel(const carl_batch_t b, const carl_policy_t pol, const int set_floats,
+                                   const carl_policy_episodes_t ep, const int n_episodes, const int max_steps,
+                                   const carl_policy_sampling_t smp) {
+  using Pick = SampledPick<Fam, false>;
+  const Pick pick = Pick::of(smp, pol);
+#include "policy_episodes_body.inc"
 }
 
 }  // namespace carl

@@ -649,8 +649,21 @@ class VecEngine:
         z = lambda dt: torch.zeros(self.n, dtype=dt, device=self.device)  # noqa: E731
         return {"episodes": z(torch.int32), "return_sum": z(torch.float32), "length_sum": z(torch.int32)}
 
+    def _sampling(self, policy, deterministic: bool, sample_seed: int, log_prob: torch.Tensor | None = None):
+        """the ``carl_policy_sampling_t`` of a sampled launch (include/carl_amd.h), None for a deterministic one"""
+        if deterministic:
+            if log_prob is not None:
+                raise ValueError("log_prob: sampled launches only (deterministic=False)")
+            return None
+        s = _lib.PolicySampling()
+        s.seed = int(sample_seed) & (2**64 - 1)
+        s.log_std = None if policy.discrete else policy.device_log_std(self.device).data_ptr()
+        s.log_prob = _ptr(log_prob)
+        return s
+
     def rollout_policy(self, policy, n_steps: int, out: dict | None = None, mode: str = "transitions",
-                       final_obs: bool = False) -> dict:
+                       final_obs: bool = False, deterministic: bool = True, sample_seed: int = 0,
+                       log_prob: bool = False) -> dict:
         """``n_steps`` steps in ONE launch, each lane's action chosen on the device by ``policy`` (``carl_amd.policy.
         MLPPolicy``) from the lane's current context and observation -- closed loop, where ``rollout`` replays actions
         written beforehand.
@@ -660,7 +673,11 @@ class VecEngine:
         ``{"episodes", "return_sum", "length_sum"}`` per lane (episodes finished in the launch, the float32 sum of their
         returns in step order, the sum of their lengths).  Either way the engine state advances exactly as in
         ``rollout``; a summary needs ``auto_reset`` (ValueError otherwise).  No host synchronisation (the policy's parameters
-        are uploaded on its first use on a device)."""
+        are uploaded on its first use on a device).
+        ``deterministic=False``: each action is sampled from the policy's distribution (a categorical over the logits /
+        a Gaussian of ``policy.log_std``; include/carl_amd.h: carl_rollout_policy_sampled), the draws keyed by
+        ``sample_seed`` and by (lane, episode, step in episode).  ``log_prob=True`` (transitions mode) adds
+        ``"log_prob"`` ``[T, N]`` float32: each action's log-probability under the policy."""
         if not self._policy_rollout:
             raise NotImplementedError(f"{type(self).__name__}: the closed-loop rollout covers the classic-control "
                                       "families only")
@@ -672,17 +689,27 @@ class VecEngine:
         T = int(n_steps)
         params = policy.device_params(self.device)
         pol = policy.struct(self.n, params.data_ptr())
+        if log_prob and deterministic:
+            raise ValueError("log_prob=True: sampled launches only (deterministic=False)")
         if mode == "summary":
             if final_obs:
                 raise ValueError("final_obs: transitions mode only (a summary launch stores nothing per step)")
+            if log_prob:
+                raise ValueError("log_prob=True: transitions mode only (a summary launch stores nothing per step)")
             res = self.alloc_policy_summary() if out is None else out
             for k in ("episodes", "return_sum", "length_sum"):
                 t = res[k]
                 if t.device != self.device or not t.is_contiguous() or t.numel() != self.n or t.element_size() != 4:
                     raise ValueError(f"summary output '{k}' must be a contiguous 4-byte [{self.n}] tensor on {self.device}")
             summ = _lib.PolicySummary(_ptr(res["episodes"]), _ptr(res["return_sum"]), _ptr(res["length_sum"]))
+            smp = self._sampling(policy, deterministic, sample_seed)
             with torch.cuda.device(self.device):
-                _lib.check(self.lib.carl_rollout_policy(self._b_ref, C.byref(pol), None, T, C.byref(summ), self._stream()))
+                if smp is None:
+                    _lib.check(self.lib.carl_rollout_policy(self._b_ref, C.byref(pol), None, T, C.byref(summ),
+                                                            self._stream()))
+                else:
+                    _lib.check(self.lib.carl_rollout_policy_sampled(self._b_ref, C.byref(pol), C.byref(smp), None, T,
+                                                                    C.byref(summ), self._stream()))
             return res
         if mode != "transitions":
             raise ValueError(f"mode {mode!r}: 'transitions' or 'summary'")
@@ -690,9 +717,21 @@ class VecEngine:
             out = self.alloc_rollout(T, final_obs=final_obs)
             adt = torch.int32 if self.info.action_is_discrete else torch.float32
             out["action"] = torch.empty((T, self._out_pitch(out)), dtype=adt, device=self.device)[:, : self.n]
+        if log_prob and "log_prob" not in out:
+            out["log_prob"] = torch.empty((T, self._out_pitch(out)), dtype=torch.float32, device=self.device)[:, : self.n]
         io = self._rollout_io(None, None, out, T)
+        lp = out.get("log_prob") if log_prob else None
+        if lp is not None:
+            if lp.dtype != torch.float32:
+                raise ValueError("rollout_policy 'log_prob' buffer must be torch.float32")
+            self._check_rows("rollout_policy", {"log_prob": lp}, ("log_prob",), self._out_pitch(out), T, self.device)
+        smp = self._sampling(policy, deterministic, sample_seed, lp)
         with torch.cuda.device(self.device):
-            _lib.check(self.lib.carl_rollout_policy(self._b_ref, C.byref(pol), C.byref(io), T, None, self._stream()))
+            if smp is None:
+                _lib.check(self.lib.carl_rollout_policy(self._b_ref, C.byref(pol), C.byref(io), T, None, self._stream()))
+            else:
+                _lib.check(self.lib.carl_rollout_policy_sampled(self._b_ref, C.byref(pol), C.byref(smp), C.byref(io), T,
+                                                                None, self._stream()))
         return out
 
     # (key, dtype, per-episode rows) of an evaluate_policy result
@@ -708,7 +747,8 @@ class VecEngine:
         return {k: torch.empty((K, self.n) if rows else (self.n,), dtype=dt, device=self.device)
                 for k, dt, rows in self._EPISODE_KEYS}
 
-    def evaluate_policy(self, policy, n_episodes: int, max_steps: int, out: dict | None = None) -> dict:
+    def evaluate_policy(self, policy, n_episodes: int, max_steps: int, out: dict | None = None,
+                        deterministic: bool = True, sample_seed: int = 0) -> dict:
         """Run ``policy`` (``carl_amd.policy.MLPPolicy``) on every lane until the lane has finished ``n_episodes``
         episodes or taken ``max_steps`` steps, in ONE launch, from the current engine state (a running episode is counted
         with its full length; ``CARLEnv.evaluate_policy`` resets first).  Returns ``alloc_policy_episodes``' dict:
@@ -716,7 +756,9 @@ class VecEngine:
         ``context_id`` it ran in and whether it ``terminated`` (NaN / 0 / -1 / 0 beyond).  A lane's records are those of
         its first episodes in a transitions-mode ``rollout_policy``, bit for bit, and the engine state advances exactly as
         for the steps each lane took.  Needs ``auto_reset``.  ``carl_amd.policy.episode_stats`` reduces the result per
-        context.  No host synchronisation."""
+        context.  No host synchronisation.  ``deterministic=False``: sampled actions, as ``rollout_policy``'s (SB3's
+        ``evaluate_policy(..., deterministic=False)``); the records are then those of a sampled transitions launch with
+        the same ``sample_seed``."""
         if not self._policy_rollout:
             raise NotImplementedError(f"{type(self).__name__}: the closed-loop rollout covers the classic-control "
                                       "families only")
@@ -742,8 +784,13 @@ class VecEngine:
         params = policy.device_params(self.device)
         pol = policy.struct(self.n, params.data_ptr())
         eps = _lib.PolicyEpisodes(*(_ptr(res[k]) for k, _, _ in self._EPISODE_KEYS))
+        smp = self._sampling(policy, deterministic, sample_seed)
         with torch.cuda.device(self.device):
-            _lib.check(self.lib.carl_evaluate_policy(self._b_ref, C.byref(pol), K, T, C.byref(eps), self._stream()))
+            if smp is None:
+                _lib.check(self.lib.carl_evaluate_policy(self._b_ref, C.byref(pol), K, T, C.byref(eps), self._stream()))
+            else:
+                _lib.check(self.lib.carl_evaluate_policy_sampled(self._b_ref, C.byref(pol), C.byref(smp), K, T,
+                                                                 C.byref(eps), self._stream()))
         return res
 
     def rollout_variant(self) -> int:

@@ -313,18 +313,24 @@ class CARLEnv(abc.ABC):
         return obs, reward, c["term"], c["trunc"], info
 
     def rollout_policy(self, policy, n_steps: int, out: dict | None = None, mode: str = "transitions",
-                       final_obs: bool = False) -> dict:
+                       final_obs: bool = False, deterministic: bool = True, sample_seed: int = 0,
+                       log_prob: bool = False) -> dict:
         """``n_steps`` closed-loop steps of every lane in one launch, actions chosen on the device by ``policy``
-        (``carl_amd.policy.MLPPolicy.for_env(self, ...)``): ``VecEngine.rollout_policy`` of this env's engine.  The
-        engine's outputs (``step``'s views) are not touched; the host selector object is not consulted."""
-        return self.env.rollout_policy(policy, n_steps, out=out, mode=mode, final_obs=final_obs)
+        (``carl_amd.policy.MLPPolicy.for_env(self, ...)``): ``VecEngine.rollout_policy`` of this env's engine (sampled
+        actions with ``deterministic=False``).  The engine's outputs (``step``'s views) are not touched; the host selector
+        object is not consulted."""
+        return self.env.rollout_policy(policy, n_steps, out=out, mode=mode, final_obs=final_obs,
+                                       deterministic=deterministic, sample_seed=sample_seed, log_prob=log_prob)
 
-    def evaluate_policy(self, policy, n_episodes: int, max_steps: int, seed: int | None = None) -> dict:
+    def evaluate_policy(self, policy, n_episodes: int, max_steps: int, seed: int | None = None,
+                        deterministic: bool = True, sample_seed: int = 0) -> dict:
         """``n_episodes`` whole episodes of ``policy`` per lane (at most ``max_steps`` steps) in one launch:
-        ``reset(seed=seed)``, then ``VecEngine.evaluate_policy``.  ``carl_amd.policy.episode_stats`` reduces the result
-        per context (mean / std return, as SB3's ``evaluate_policy`` reports them)."""
+        ``reset(seed=seed)``, then ``VecEngine.evaluate_policy`` (sampled actions with ``deterministic=False``).
+        ``carl_amd.policy.episode_stats`` reduces the result per context (mean / std return, as SB3's
+        ``evaluate_policy`` reports them)."""
         self.reset(seed=seed)
-        return self.env.evaluate_policy(policy, n_episodes, max_steps)
+        return self.env.evaluate_policy(policy, n_episodes, max_steps, deterministic=deterministic,
+                                        sample_seed=sample_seed)
 
     def _views(self) -> dict:
         eng = self.env

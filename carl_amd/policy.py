@@ -13,6 +13,14 @@ four floats.  The kernel computes ``x = clip((x - shift) * scale, -clip, clip)``
 ``scale = 1 / sqrt(var + eps)``), ``h = act(W h + b)`` per hidden layer and a linear head; discrete families take the
 first index of the largest head output, Box families the head output itself (the env clips it as usual).
 
+Stochastic policies: ``rollout_policy(..., deterministic=False, sample_seed=s)`` and ``evaluate_policy(...,
+deterministic=False, sample_seed=s)`` sample each action on the device instead (include/carl_amd.h:
+carl_policy_sampling_t) -- a categorical over the head's logits for discrete families, a diagonal Gaussian with mean
+the head output and a state-independent ``log_std`` (``log_std=`` of the constructors, one value per weight set; SB3's
+PPO default) for Box families.  The draws are keyed by ``sample_seed`` and by (lane, episode, step in episode), apart
+from the reset and context streams; a transitions launch can also return each action's log-probability
+(``log_prob=True``), what an on-policy learner (PPO, A2C) stores next to the action.
+
 Out of scope: the Brax families, ``MixedVecEngine`` pairs, the gymnasium drop-in (``carl_amd.dropin``) and the
 multi-process helpers (``carl_amd.distributed``).
 """
@@ -74,7 +82,8 @@ class MLPPolicy:
     """One or more weight sets of one MLP shape, for one env family (see the module docstring)."""
 
     def __init__(self, family: int, obs_dim: int, ctx_rows: Sequence[int], layers: Sequence, activation: str = "tanh",
-                 input_shift=None, input_scale=None, input_clip: float | None = None, context_names: Sequence | None = None):
+                 input_shift=None, input_scale=None, input_clip: float | None = None, context_names: Sequence | None = None,
+                 log_std=None):
         info = _lib.family_info(int(family))
         self.family, self.obs_dim = int(family), int(obs_dim)
         self.ctx_rows = [int(r) for r in ctx_rows]
@@ -114,24 +123,33 @@ class MLPPolicy:
             raise ValueError(f"input_shift / input_scale need {self.n_in} values")
         self.clip = np.float32(np.inf if input_clip is None else input_clip)
         self.params = self._pack()[None]  # [n_sets, set_floats]
+        if log_std is not None and self.discrete:
+            raise ValueError("log_std: Box families only (a discrete policy samples from its logits)")
+        ls = np.asarray(log_std.detach().cpu() if isinstance(log_std, torch.Tensor) else (0.0 if log_std is None else log_std),
+                        np.float32).reshape(-1)
+        if ls.size != 1:
+            raise ValueError(f"log_std: one value (state-independent), got {ls.size}")
+        self.log_std = ls  # [n_sets] float32: the Gaussian's log standard deviation per weight set (Box families)
         self.lanes_per_set = None  # one set: every lane
         self._dev = {}
 
     # ------------------------------------------------------------------ construction
     @classmethod
     def for_env(cls, env, layers: Sequence, activation: str = "tanh", input_shift=None, input_scale=None,
-                input_clip: float | None = None, context_features: Sequence | None = None) -> "MLPPolicy":
+                input_clip: float | None = None, context_features: Sequence | None = None, log_std=None) -> "MLPPolicy":
         """A policy for ``env`` (a classic-control ``CARLEnv`` or ``VecEngine``) from explicit ``(W [out, in], b [out])``
         arrays, hidden layers first, the head last.  The input is ``FlattenObservation(env)``'s vector (module docstring);
-        ``context_features`` narrows its context part (``[]``: observation only)."""
+        ``context_features`` narrows its context part (``[]``: observation only).  ``log_std`` (Box families only; a float
+        or a one-element tensor, default 0): the log standard deviation of the sampled Gaussian."""
         eng, _ = _engine_of(env)
         rows, names = flattened_context_rows(env, context_features)
-        return cls(eng.family, eng.D, rows, layers, activation, input_shift, input_scale, input_clip, names)
+        return cls(eng.family, eng.D, rows, layers, activation, input_shift, input_scale, input_clip, names, log_std)
 
     @classmethod
     def from_sequential(cls, env, seq: torch.nn.Sequential, **kw) -> "MLPPolicy":
         """The same from a ``torch.nn.Sequential`` of ``Linear`` layers with ``Tanh`` / ``ReLU`` / ``Identity`` between
-        them (one activation kind for every hidden layer; nothing after the head but ``Identity``)."""
+        them (one activation kind for every hidden layer; nothing after the head but ``Identity``); ``log_std=`` as
+        ``for_env``."""
         linears, acts = [], []
         for m in seq:
             if isinstance(m, torch.nn.Linear):
@@ -173,6 +191,7 @@ class MLPPolicy:
         out = object.__new__(MLPPolicy)
         out.__dict__.update(p0.__dict__)
         out.params = np.concatenate([p.params for p in policies], axis=0)
+        out.log_std = np.concatenate([p.log_std for p in policies])
         out.lanes_per_set = int(lanes_per_set)
         out._dev = {}
         return out
@@ -214,11 +233,18 @@ class MLPPolicy:
 
     def device_params(self, device) -> torch.Tensor:
         """The packed parameters on ``device`` (uploaded once per device)."""
+        return self._upload("params", self.params, device)
+
+    def device_log_std(self, device) -> torch.Tensor:
+        """``log_std`` ``[n_sets]`` float32 on ``device`` (uploaded once per device)."""
+        return self._upload("log_std", self.log_std, device)
+
+    def _upload(self, key: str, a: np.ndarray, device) -> torch.Tensor:
         dev = torch.device(device)
-        t = self._dev.get(dev)
+        t = self._dev.get((key, dev))
         if t is None:
-            t = torch.as_tensor(self.params).to(dev).contiguous()
-            self._dev[dev] = t
+            t = torch.as_tensor(a).to(dev).contiguous()
+            self._dev[(key, dev)] = t
         return t
 
 

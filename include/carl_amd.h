@@ -408,6 +408,51 @@ typedef struct carl_policy_episodes {
 int carl_evaluate_policy(const carl_batch_t* batch, const carl_policy_t* policy_host, int32_t n_episodes,
                          int32_t max_steps, const carl_policy_episodes_t* out, void* stream);
 
+/* ---- stochastic policies: sampled actions and their log-probabilities (additive; ABI version unchanged) ----
+ * The same network as above; the action is drawn from the distribution the family implies instead of taken as its
+ * mode:
+ *  - discrete families: a categorical over the head's n_out logits y;
+ *  - Box families: a diagonal Gaussian, mean y[0], state-independent log_std: one float per weight set (SB3's PPO
+ *    default), a DEVICE array [n_sets] of its own.
+ * Random words: each lane-step draws one Philox4x32-10 block w, key sample_seed (separate from the batch seed: new
+ * actions leave the reset and context streams alone), counter (glane lo, glane hi, e, 0x80000000 | elapsed), with e the
+ * index of the episode the step belongs to (episode counter - 1, the index the per-step noise of Acrobot uses) and
+ * elapsed the lane's step count in that episode before the step.  A draw is therefore a pure function of (sample_seed,
+ * lane, episode, step in episode): it does not depend on how a horizon is split into launches or on which mode runs the
+ * step.  The high bit keeps the stream apart from the engine's own sub-streams (0, 1, 2 + elapsed), even when a caller
+ * passes the batch seed as sample_seed.
+ * Categorical:  u = (w.x >> 8) * 2^-24;  m = max_k y_k, e_k = exp(y_k - m), S = sum_k e_k, all in index order;
+ *               t = u * S in fp32; the action is the first k with t < c_k, c_k the fp32 prefix sums of e in index
+ *               order (the last index if there is none);  log_prob = (y_a - m) - log(S).
+ * Gaussian:     u1 = ((w.x >> 8) + 1) * 2^-24 in (0, 1], u2 = (w.y >> 8) * 2^-24;
+ *               z = sqrt(-2 ln u1) * cos(2 pi u2);  a = mu + exp(log_std) * z (one fma);
+ *               log_prob = -z^2 / 2 - log_std - ln(2 pi) / 2.
+ *               The recorded action is the raw a; the step clips it as it clips a deterministic Box policy's action
+ *               (SB3 also stores the unclipped sample).
+ * exp / log / sqrt / cos are the device's accurate fp32 functions (not the hardware approximations). */
+typedef struct carl_policy_sampling {
+  uint64_t seed;          /* sample_seed: the Philox key of the action draws */
+  const float* log_std;   /* DEVICE [n_sets]: required for Box families, ignored for discrete ones */
+  float* log_prob;        /* optional DEVICE [T][pitch] fp32, the layout of io->action: each action's log-probability;
+                             transitions mode only */
+} carl_policy_sampling_t;
+
+/* carl_rollout_policy with sampled actions.  Everything carl_rollout_policy validates, in the same order and with the
+ * same codes; then `sampling` non-NULL, a log_std for Box families, and no log_prob in summary mode (io == NULL): each
+ * refused with CARL_ERR_INVALID_ARGUMENT before anything is enqueued.  Records, state and replay guarantees as
+ * carl_rollout_policy's: replaying the recorded actions with carl_rollout gives the same bits; a summary launch leaves
+ * the state a transitions launch leaves.  A categorical policy whose mode has probability 1 in fp32 (every other
+ * exp(y_k - m) underflows to 0) takes exactly carl_rollout_policy's actions, with log_prob 0. */
+int carl_rollout_policy_sampled(const carl_batch_t* batch, const carl_policy_t* policy_host,
+                                const carl_policy_sampling_t* sampling, const carl_step_io_t* io, int32_t n_steps,
+                                const carl_policy_summary_t* summary_out, void* stream);
+/* carl_evaluate_policy with sampled actions: its validation, then `sampling` non-NULL, a log_std for Box families and
+ * no log_prob (episodes mode stores no per-step output), each refused with CARL_ERR_INVALID_ARGUMENT.  A lane's records
+ * are its first n_episodes episodes in a transitions-mode carl_rollout_policy_sampled with the same sample_seed. */
+int carl_evaluate_policy_sampled(const carl_batch_t* batch, const carl_policy_t* policy_host,
+                                 const carl_policy_sampling_t* sampling, int32_t n_episodes, int32_t max_steps,
+                                 const carl_policy_episodes_t* out, void* stream);
+
 /* ======================= Brax-locomotion families (spring backend) =======================
  * Replaces CARLBraxEnv + BraxGymWrapper/VectorGymWrapper + brax.spring.pipeline.step x
  * n_frames + brax.envs.<env>.step/reset (carl/envs/brax/carl_brax_env.py:115-336,

@@ -1,0 +1,175 @@
+"""Sampled closed-loop rollout, host side: the carl_policy_sampling_t layout, every new refusal of
+carl_rollout_policy_sampled / carl_evaluate_policy_sampled and of the Python layer, log_std through the constructors and
+stack(), and the host reference of the sampling rule (sampling_ref.py) against oracle.philox4x32_10 and
+torch.distributions.  CPU-only: nothing here launches a kernel (the C entry points refuse before they would enqueue)."""
+import ctypes as C
+import os
+import subprocess
+
+import numpy as np
+import pytest
+import torch
+
+import sampling_ref as SR
+from carl_amd import _lib
+from carl_amd.policy import MLPPolicy
+from oracle import oracle as O
+from test_policy_pack import HEADER, _batch, _policy, fake_engine, rand_layers
+
+
+def test_sampling_struct_layout_matches_c(tmp_path):
+    prog = tmp_path / "layout.c"
+    fs = [f[0] for f in _lib.PolicySampling._fields_]
+    lines = ["#include <stdio.h>", "#include <stddef.h>", f'#include "{HEADER}"', "int main(void){",
+             'printf("%zu\\n", sizeof(carl_policy_sampling_t));']
+    lines += [f'printf("%zu\\n", offsetof(carl_policy_sampling_t, {f}));' for f in fs]
+    lines += ["return 0;}"]
+    prog.write_text("\n".join(lines))
+    exe = tmp_path / "layout"
+    subprocess.run(["gcc", "-std=c11", "-o", str(exe), str(prog)], check=True)
+    out = list(map(int, subprocess.run([str(exe)], check=True, capture_output=True, text=True).stdout.split()))
+    assert out == [C.sizeof(_lib.PolicySampling)] + [getattr(_lib.PolicySampling, f).offset for f in fs]
+
+
+def _io():
+    io = _lib.StepIO()
+    io.action, io.obs, io.reward, io.terminated, io.truncated = 0x1000, 0x1000, 0x1000, 0x1000, 0x1000
+    io.action_dtype = _lib.ACTION_I32
+    return io
+
+
+def _episodes():
+    return _lib.PolicyEpisodes(0x3000, 0x3000, 0x3000, 0x3000, 0x3000, 0x3000)
+
+
+def _flags(b):
+    b.flags = _lib.FLAG_AUTORESET
+    return b
+
+
+def test_sampled_entry_points_refuse_what_their_twins_refuse():
+    """the deterministic twin's checks come first, same codes, messages naming the sampled entry point"""
+    lib = _lib.load()
+    smp = _lib.PolicySampling(1, None, None)
+    summ = _lib.PolicySummary(0x3000, 0x3000, 0x3000)
+    b, p = _flags(_batch()), _policy(width=(65, 64))
+    assert lib.carl_rollout_policy_sampled(C.byref(b), C.byref(p), C.byref(smp), None, 10, C.byref(summ), None) == -1
+    assert b"carl_rollout_policy_sampled: hidden width[0] = 65" in lib.carl_last_error()
+    assert lib.carl_evaluate_policy_sampled(C.byref(b), C.byref(p), C.byref(smp), 2, 10, C.byref(_episodes()), None) == -1
+    assert b"carl_evaluate_policy_sampled: hidden width[0] = 65" in lib.carl_last_error()
+    # the batch checks (Brax family), io layout, summary without auto-reset
+    bb = _batch(family=_lib.CARL_N_FAMILIES)
+    assert lib.carl_rollout_policy_sampled(C.byref(bb), C.byref(_policy()), C.byref(smp), None, 10, C.byref(summ),
+                                           None) == -1
+    assert b"Brax family" in lib.carl_last_error()
+    io = _io()
+    io.row_pitch = 1004
+    assert lib.carl_rollout_policy_sampled(C.byref(b), C.byref(_policy()), C.byref(smp), C.byref(io), 10, None,
+                                           None) == _lib.ERR_UNSUPPORTED
+    assert lib.carl_rollout_policy_sampled(C.byref(_batch()), C.byref(_policy()), C.byref(smp), None, 10, C.byref(summ),
+                                           None) == _lib.ERR_UNSUPPORTED
+    assert lib.carl_evaluate_policy_sampled(C.byref(b), C.byref(_policy()), C.byref(smp), 0, 10, C.byref(_episodes()),
+                                            None) == -1
+    assert b"n_episodes 0 < 1" in lib.carl_last_error()
+
+
+def test_sampled_entry_points_refuse_bad_sampling():
+    lib = _lib.load()
+    b, p = _flags(_batch()), _policy()
+    summ = _lib.PolicySummary(0x3000, 0x3000, 0x3000)
+    for fn, args in ((lib.carl_rollout_policy_sampled, lambda s: (C.byref(b), C.byref(p), s, None, 10, C.byref(summ), None)),
+                     (lib.carl_evaluate_policy_sampled, lambda s: (C.byref(b), C.byref(p), s, 2, 10, C.byref(_episodes()),
+                                                                   None))):
+        assert fn(*args(None)) == _lib.ERR_INVALID_ARGUMENT
+        assert b"sampling is NULL" in lib.carl_last_error()
+        assert fn(*args(C.byref(_lib.PolicySampling(1, None, 0x4000)))) == _lib.ERR_INVALID_ARGUMENT  # summary / episodes
+        assert b"log_prob" in lib.carl_last_error()
+    # a Box family without log_std
+    bp = _flags(_batch(family=_lib.PENDULUM))
+    pp = _policy(n_in=5, n_out=1, head=_lib.POLICY_HEAD_BOX)
+    assert lib.carl_rollout_policy_sampled(C.byref(bp), C.byref(pp), C.byref(_lib.PolicySampling(1, None, None)), None, 10,
+                                           C.byref(summ), None) == _lib.ERR_INVALID_ARGUMENT
+    assert b"log_std" in lib.carl_last_error()
+    assert lib.carl_evaluate_policy_sampled(C.byref(bp), C.byref(pp), C.byref(_lib.PolicySampling(1, None, None)), 2, 10,
+                                            C.byref(_episodes()), None) == _lib.ERR_INVALID_ARGUMENT
+    assert b"log_std" in lib.carl_last_error()
+    # transitions mode takes a log_prob, on a 16-byte boundary
+    io = _io()
+    assert lib.carl_rollout_policy_sampled(C.byref(b), C.byref(p), C.byref(_lib.PolicySampling(1, None, 0x4004)),
+                                           C.byref(io), 10, None, None) == _lib.ERR_UNSUPPORTED
+    assert b"16-byte" in lib.carl_last_error()
+
+
+def test_python_refusals():
+    from carl_amd.engine import VecEngine
+    from carl_amd.mixed import MixedVecEngine
+
+    eng = fake_engine(_lib.PENDULUM)
+    rng = np.random.default_rng(0)
+    with pytest.raises(ValueError, match="Box families only"):
+        cp = fake_engine()
+        MLPPolicy.for_env(cp, rand_layers(rng, [cp.F + cp.D, 2]), log_std=0.5)
+    with pytest.raises(ValueError, match="one value"):
+        MLPPolicy.for_env(eng, rand_layers(rng, [eng.F + 3, 1]), log_std=[0.1, 0.2])
+    pol = MLPPolicy.for_env(eng, rand_layers(rng, [eng.F + 3, 1]), log_std=torch.tensor([-0.5]))
+    assert pol.log_std.dtype == np.float32 and pol.log_std.tolist() == [-0.5]
+    # a launch's refusals before anything reaches the C ABI
+    class Eng:  # what rollout_policy reads before its launch
+        _policy_rollout, family, D, n, device, auto_reset = True, eng.family, eng.D, 1000, torch.device("cpu"), True
+
+    with pytest.raises(ValueError, match="log_prob=True: sampled launches only"):
+        VecEngine.rollout_policy(Eng(), pol, 8, log_prob=True)
+    with pytest.raises(ValueError, match="transitions mode only"):
+        VecEngine.rollout_policy(Eng(), pol, 8, mode="summary", deterministic=False, log_prob=True)
+    with pytest.raises(NotImplementedError, match="pair launch"):
+        MixedVecEngine.rollout_policy(object.__new__(MixedVecEngine), pol, 8, deterministic=False)
+    with pytest.raises(NotImplementedError, match="pair launch"):
+        MixedVecEngine.evaluate_policy(object.__new__(MixedVecEngine), pol, 2, 8, deterministic=False)
+
+
+def test_stack_carries_log_std():
+    eng = fake_engine(_lib.MOUNTAINCAR_CONT)
+    rng = np.random.default_rng(1)
+    pols = [MLPPolicy.for_env(eng, rand_layers(rng, [eng.F + eng.D, 8, 1]), log_std=v) for v in (-1.0, 0.25, 0.0)]
+    s = MLPPolicy.stack(pols, 512)
+    np.testing.assert_array_equal(s.log_std, np.float32([-1.0, 0.25, 0.0]))
+    assert s.n_sets == 3
+    assert MLPPolicy.for_env(eng, rand_layers(rng, [eng.F + eng.D, 1])).log_std.tolist() == [0.0]
+
+
+def test_host_philox_matches_the_oracle():
+    rng = np.random.default_rng(2)
+    for _ in range(20):
+        ctr = rng.integers(0, 2**32, 4, dtype=np.uint64)
+        key = rng.integers(0, 2**32, 2, dtype=np.uint64)
+        got = SR.philox(*ctr, int(key[0]), int(key[1]))
+        np.testing.assert_array_equal(np.array([int(g) for g in got], np.uint32), O.philox4x32_10(ctr, key))
+    seed, glane, e, el = 0x123456789ABCDEF0, 70000, 5, 17
+    w = SR.sample_words(seed, np.array([glane]), np.array([e]), np.array([el]))
+    want = O.philox4x32_10([glane & 0xFFFFFFFF, glane >> 32, e, 0x80000000 | el], [seed & 0xFFFFFFFF, seed >> 32])
+    np.testing.assert_array_equal(np.array([int(v[0]) for v in w], np.uint32), want)
+
+
+def test_host_rule_agrees_with_torch_distributions():
+    """inverse-CDF categorical and Box-Muller z: the frequencies / moments of torch's distributions, and log-probs equal"""
+    rng = np.random.default_rng(3)
+    n = 400_000
+    w = [rng.integers(0, 2**32, n, dtype=np.uint64).astype(np.uint32) for _ in range(2)]
+    y = np.array([[0.3, -1.2, 1.1]])
+    a, _ = SR.categorical64(np.repeat(y, n, 0), SR.u_categorical(w[0]).astype(np.float64))
+    p = torch.distributions.Categorical(logits=torch.tensor(y[0])).probs.numpy()
+    freq = np.bincount(a, minlength=3) / n
+    assert np.all(np.abs(freq - p) < 5 * np.sqrt(p * (1 - p) / n)), (freq, p)
+    lp = torch.distributions.Categorical(logits=torch.tensor(y[0])).log_prob(torch.tensor(a[:5])).numpy()
+    np.testing.assert_allclose(lp, (y[0] - y.max())[a[:5]] - np.log(np.exp(y[0] - y.max()).sum()), rtol=1e-12)
+    z = SR.z_gaussian64(w[0], w[1])
+    assert abs(z.mean()) < 5 / np.sqrt(n) and abs(z.var() - 1) < 5 * np.sqrt(2 / n)
+    mu, ls = 0.7, -0.4
+    a = mu + np.exp(ls) * z[:5]
+    lp = torch.distributions.Normal(torch.tensor(mu, dtype=torch.float64), torch.tensor(np.exp(ls))).log_prob(torch.tensor(a)).numpy()
+    np.testing.assert_allclose(lp, -z[:5] ** 2 / 2 - ls - 0.5 * np.log(2 * np.pi), rtol=1e-12, atol=1e-12)
+    # equal logits: the fp32 mirror is the float64 rule wherever t is not on a boundary
+    u = SR.u_categorical(w[0][:1000])
+    a32 = SR.categorical_equal_logits(u, 3)
+    a64, margin = SR.categorical64(np.zeros((1000, 3)), u.astype(np.float64))
+    assert np.array_equal(a32[margin > 1e-6], a64[margin > 1e-6])

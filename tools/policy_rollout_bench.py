@@ -11,6 +11,9 @@
                    overhead (sum over wavefronts of 64 x that wave's largest `steps`, over the sum of `steps`), and
                    the launch time per step of its longest lane against summary mode's time per step.
 
+  --sampled        also the sampled launches (rollout_policy(..., deterministic=False)) of the same policies:
+                   transitions with and without log_prob, and summary.
+
 Host timing with torch.cuda events around `--reps` launches after one warm-up launch; the median per launch is
 reported.  Kernel times belong to a separate `rocprofv3 --kernel-trace --stats` run of this script.
 
@@ -145,6 +148,7 @@ def main():
     ap.add_argument("--reps", type=int, default=5)
     ap.add_argument("--legs", default="rollout,evaluate")
     ap.add_argument("--out", default=None)
+    ap.add_argument("--sampled", action="store_true")
     args = ap.parse_args()
     legs = set(args.legs.split(","))
     n, T = args.lanes, args.steps
@@ -176,6 +180,15 @@ def main():
         s = eng.alloc_policy_summary()
         record(f"policy_summary_{name}", *time_launches(lambda: eng.rollout_policy(pol, T, out=s, mode="summary"),
                                                        args.reps))
+        if args.sampled:
+            kw = dict(deterministic=False, sample_seed=1)
+            sout = eng.rollout_policy(pol, T, log_prob=True, **kw)
+            record(f"sampled_transitions_{name}", *time_launches(lambda: eng.rollout_policy(
+                pol, T, out={k: v for k, v in sout.items() if k != "log_prob"}, **kw), args.reps))
+            record(f"sampled_transitions_log_prob_{name}", *time_launches(lambda: eng.rollout_policy(
+                pol, T, out=sout, log_prob=True, **kw), args.reps))
+            record(f"sampled_summary_{name}", *time_launches(lambda: eng.rollout_policy(pol, T, out=s, mode="summary",
+                                                                                        **kw), args.reps))
         with torch.no_grad():
             run = graph_step_mlp(eng, mlp.to(eng.device), T)
             record(f"graph_step_torch_{name}", *time_launches(run, max(1, args.reps // 2)))
