@@ -429,7 +429,10 @@ int carl_evaluate_policy(const carl_batch_t* batch, const carl_policy_t* policy_
  *               log_prob = -z^2 / 2 - log_std - ln(2 pi) / 2.
  *               The recorded action is the raw a; the step clips it as it clips a deterministic Box policy's action
  *               (SB3 also stores the unclipped sample).
- * exp / log / sqrt / cos are the device's accurate fp32 functions (not the hardware approximations). */
+ * exp / log / sqrt / cos are the device's accurate fp32 functions (not the hardware approximations).
+ * Padding lanes (the columns [n_lanes, pitch) a transitions launch writes) run as clones of lane n_lanes - 1 -- its
+ * state, context, weight set, episode index and elapsed count -- but draw with their own glane = lane_offset + lane, so
+ * their actions and log-probabilities are valid samples, not copies of lane n_lanes - 1's. */
 typedef struct carl_policy_sampling {
   uint64_t seed;          /* sample_seed: the Philox key of the action draws */
   const float* log_std;   /* DEVICE [n_sets]: required for Box families, ignored for discrete ones */

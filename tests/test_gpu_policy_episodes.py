@@ -74,19 +74,24 @@ def check_state(a, b, lanes=None):
         assert torch.equal(x, y), k
 
 
-def exact_case(eng, pol, K, T, warm=0):
-    """evaluate_policy against the transitions-mode reference (module docstring); returns the result"""
-    if warm:  # lanes mid-episode at the launch: the running episode counts with its full length and return
-        eng.rollout_policy(pol, warm, mode="summary")
-    snap = eng.snapshot()
-    out = eng.rollout_policy(pol, T)
+def exact_case(eng, pol, K, T, warm=0, transitions=None, **kw):
+    """evaluate_policy against the transitions-mode reference (module docstring); returns the result.  transitions:
+    (snapshot, rollout_policy output) of a launch already made from that snapshot, instead of a new one; kw: the
+    sampling arguments of both launches (deterministic=False, sample_seed=...)"""
+    if transitions is not None:
+        snap, out = transitions
+    else:
+        if warm:  # lanes mid-episode at the launch: the running episode counts with its full length and return
+            eng.rollout_policy(pol, warm, mode="summary")
+        snap = eng.snapshot()
+        out = eng.rollout_policy(pol, T, **kw)
     count, stop, ret, length, term, at_step = host_records(snap, out, K, T)
     ctx_before, want_state = replay(eng, snap, out["action"][:T], stop)
     cid = np.full((K, eng.n), -1, np.int32)
     has = at_step >= 0
     cid[has] = ctx_before[at_step[has], np.nonzero(has)[1]]
     eng.restore(snap)
-    res = eng.evaluate_policy(pol, K, T)
+    res = eng.evaluate_policy(pol, K, T, **kw)
     np.testing.assert_array_equal(res["episodes"].cpu().numpy(), count)
     np.testing.assert_array_equal(res["steps"].cpu().numpy(), stop)
     np.testing.assert_array_equal(res["return"].cpu().numpy().view(np.int32), ret.view(np.int32))  # NaN sentinels too

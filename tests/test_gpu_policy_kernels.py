@@ -75,10 +75,10 @@ def ctx_rows(eng, mode, rng):
             "repeated": [vis[0], vis[-1], vis[0]]}[mode]
 
 
-def make_policy(eng, widths, act, rng, ctx="all", clip=None, saturate=False):
+def make_policy(eng, widths, act, rng, ctx="all", clip=None, saturate=False, log_std=None):
     """A random policy over the given context rows, inputs centred / scaled to about +-1 (clip: a bound that binds);
     saturate: first-layer pre-activations up to 100 on the engine's current inputs (tanh then returns exactly +-1 for
-    many units; first_layer_pre measures what a launch reached)."""
+    many units; first_layer_pre measures what a launch reached); log_std: a Box policy's, for sampled launches."""
     rows = ctx_rows(eng, ctx, rng)
     d = defaults(eng.family)[rows] if rows else np.zeros(0)
     o_shift, o_scale = OBS_NORM[eng.family]
@@ -90,7 +90,7 @@ def make_policy(eng, widths, act, rng, ctx="all", clip=None, saturate=False):
     if saturate:
         layers[0] = saturate_units(eng, rows, shift, scale, clip, *layers[0])
     return MLPPolicy.for_env(eng, layers, act, input_shift=shift, input_scale=scale, input_clip=clip,
-                             context_features=rows)
+                             context_features=rows, log_std=log_std)
 
 
 def saturate_units(eng, rows, shift, scale, clip, W, b):
@@ -265,23 +265,39 @@ def test_tied_head_rows_take_the_first_index(step_type):
 
 
 # ---------------------------------------------------------------- b. launch shapes
-def canary_out(eng, T, extra_rows=3):
-    """rollout_policy buffers of T + extra_rows rows, NaN / 0xAB / -7 filled; pitch wider than n where n % 16 == 0"""
+# the log_prob column's canary: a float32 bit pattern no log-probability of these tests takes (1.03e7), compared as int32
+LOG_PROB_FILL = 0x4B1D4B1D
+
+
+def canary_out(eng, T, extra_rows=3, log_prob=False):
+    """rollout_policy buffers of T + extra_rows rows, NaN / 0xAB / -7 filled (log_prob: a "log_prob" column as well,
+    LOG_PROB_FILL); pitch wider than n where n % 16 == 0"""
     n, P0 = eng.n, eng._row_pitch()
     P = P0 + 32 if n % 16 == 0 else P0
     adt = torch.int32 if eng.info.action_is_discrete else torch.float32
     spec = {"obs": ((eng.D,), torch.float32, float("nan")), "reward": ((), torch.float32, float("nan")),
             "terminated": ((), torch.uint8, 0xAB), "truncated": ((), torch.uint8, 0xAB),
             "action": ((), adt, -7 if adt == torch.int32 else float("nan"))}
-    full = {k: torch.full((T + extra_rows, P) + tail, fill, dtype=dt, device=eng.device) for k, (tail, dt, fill) in spec.items()}
+    if log_prob:
+        spec["log_prob"] = ((), torch.float32, LOG_PROB_FILL)
+    full = {}
+    for k, (tail, dt, fill) in spec.items():
+        if dt == torch.float32 and isinstance(fill, int):  # a bit pattern
+            full[k] = torch.full((T + extra_rows, P) + tail, fill, dtype=torch.int32, device=eng.device).view(dt)
+        else:
+            full[k] = torch.full((T + extra_rows, P) + tail, fill, dtype=dt, device=eng.device)
     return full, {k: v[:, :n] for k, v in full.items()}, spec, P0
 
 
 def is_canary(t, fill):
+    if t.dtype == torch.float32 and isinstance(fill, int):
+        return t.view(torch.int32) == fill
     return torch.isnan(t) if t.dtype == torch.float32 and fill != fill else t == fill
 
 
-def check_canaries(eng, T, full, spec, P0):
+def check_canaries(eng, T, full, spec, P0, sampled=False):
+    """sampled: the padding lanes draw their own actions, so their first step is not lane n - 1's (the sampled module
+    checks it against the reference rule instead)"""
     n = eng.n
     for k, t in full.items():
         fill = spec[k][2]
@@ -289,6 +305,8 @@ def check_canaries(eng, T, full, spec, P0):
         assert bool(is_canary(t[:, P0:], fill).all()), f"{k}: a column >= carl_rollout_pitch(n) was written"
         assert not bool(is_canary(t[:T, :n], fill).any()), f"{k}: a lane's record is missing"
         assert not bool(is_canary(t[:T, n:P0], fill).any()), f"{k}: a padding lane's record is missing"
+    if sampled:
+        return
     # the padding lanes are clones of the last lane: the same first step
     for k in ("action", "reward"):
         assert bool((full[k][0, n:P0] == full[k][0, n - 1]).all()), k

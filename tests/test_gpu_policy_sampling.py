@@ -39,9 +39,12 @@ def teacher(eng, pol, snap, actions):
     return np.stack(xs), np.stack(es), np.stack(els)
 
 
-def words(eng, e, el, seed=SEED):
+def words(eng, e, el, seed=SEED, lanes=None):
+    """the Philox words of lanes `lanes` (default: every lane, in order) at counter fields e, el [T, len(lanes)]: global
+    lane ids from the engine's lane_offset"""
     T, n = e.shape
-    return SR.sample_words(seed, np.broadcast_to(np.arange(n), (T, n)), e, el)
+    lanes = np.arange(n) if lanes is None else np.asarray(lanes)
+    return SR.sample_words(seed, np.broadcast_to(lanes, (T, n)), e, el, lane_offset=int(eng.b.lane_offset))
 
 
 def zero_head_policy(eng, head_bias=None, widths=(), log_std=None):

@@ -173,3 +173,84 @@ def test_host_rule_agrees_with_torch_distributions():
     a32 = SR.categorical_equal_logits(u, 3)
     a64, margin = SR.categorical64(np.zeros((1000, 3)), u.astype(np.float64))
     assert np.array_equal(a32[margin > 1e-6], a64[margin > 1e-6])
+
+
+def test_sample_words_take_the_lane_offset():
+    """glane = lane_offset + lane, split into the counter's lo and hi words (hi non-zero past 2^32)"""
+    seed, L = 0x0123456789ABCDEF, 5_000_000_000
+    lanes, e, el = np.array([0, 1, 4111]), np.array([0, 3, 7]), np.array([0, 11, 499])
+    got = SR.sample_words(seed, lanes, e, el, lane_offset=L)
+    for j in range(lanes.size):
+        g = L + int(lanes[j])
+        want = O.philox4x32_10([g & 0xFFFFFFFF, g >> 32, int(e[j]), 0x80000000 | int(el[j])],
+                               [seed & 0xFFFFFFFF, seed >> 32])
+        np.testing.assert_array_equal(np.array([int(v[j]) for v in got], np.uint32), want)
+    same = SR.sample_words(seed, np.uint64(L) + lanes.astype(np.uint64), e, el)
+    assert all(np.array_equal(a, b) for a, b in zip(got, same))
+    lo = SR.sample_words(seed, lanes, e, el, lane_offset=L & 0xFFFFFFFF)  # the hi word matters
+    assert not any(np.array_equal(a, b) for a, b in zip(got, lo))
+
+
+def test_log_prob_references_agree_with_torch():
+    rng = np.random.default_rng(4)
+    y = rng.normal(0, 1, (2000, 3)) * rng.choice([0.1, 1.0, 30.0, 90.0], (2000, 1))  # gaps up to ~300: exp underflows
+    a = rng.integers(0, 3, 2000)
+    want = torch.distributions.Categorical(logits=torch.tensor(y)).log_prob(torch.tensor(a)).numpy()
+    np.testing.assert_allclose(SR.categorical_log_prob64(y, a), want, rtol=1e-12, atol=1e-12)
+    z = rng.normal(0, 1.5, 2000)
+    for ls in (-20.0, -0.5, 0.0, 2.0):
+        ls32 = np.float32(ls)
+        sigma = np.exp(np.float64(ls32))
+        want = torch.distributions.Normal(torch.tensor(0.3, dtype=torch.float64), torch.tensor(sigma)).log_prob(
+            torch.tensor(0.3 + sigma * z)).numpy()
+        np.testing.assert_allclose(SR.gaussian_log_prob64(z, ls32), want, rtol=1e-9, atol=1e-9 if ls > -1 else 1e-6)
+
+
+def _categorical_fp32(y32, u):
+    """the device's categorical rule and log_prob in fp32 (include/carl_amd.h), one lane-step per row"""
+    f = np.float32
+    m = y32.max(axis=1)
+    s = np.zeros(len(y32), f)
+    c = np.empty_like(y32)
+    for k in range(y32.shape[1]):
+        s = (s + np.exp((y32[:, k] - m).astype(f)).astype(f)).astype(f)
+        c[:, k] = s
+    t = (u.astype(f) * s).astype(f)
+    a = np.full(len(y32), y32.shape[1] - 1)
+    for k in range(y32.shape[1] - 2, -1, -1):
+        a = np.where(t < c[:, k], k, a)
+    ya = y32[np.arange(len(y32)), a]
+    return a, ((ya - m).astype(f) - np.log(s).astype(f)).astype(f)
+
+
+def test_fp32_mirrors_stay_within_the_bounds():
+    """an fp32 evaluation from outputs within the forward bound of y64 meets categorical_tolerance /
+    categorical_log_prob_bound, and one of the Gaussian rule meets gaussian_log_prob_bound: the bounds are not tighter
+    than fp32 arithmetic allows"""
+    rng = np.random.default_rng(5)
+    N = 200_000
+    for na in (2, 3):
+        y64 = rng.normal(0, 1, (N, na)) * rng.choice([0.3, 3.0, 30.0, 90.0], (N, 1))
+        bound = np.abs(y64) * 2.0 ** -20 + 1e-7  # a forward pass's bound
+        y32 = (y64 + rng.uniform(-0.9, 0.9, y64.shape) * bound).astype(np.float32)
+        w = rng.integers(0, 2**32, N, dtype=np.uint64).astype(np.uint32)
+        u = SR.u_categorical(w)
+        a32, lp32 = _categorical_fp32(y32, u)
+        a64, margin = SR.categorical64(y64, u.astype(np.float64))
+        clear = margin > SR.categorical_tolerance(y64, bound)
+        assert (~clear).mean() < 1e-3
+        np.testing.assert_array_equal(a32[clear], a64[clear])
+        err = np.abs(lp32 - SR.categorical_log_prob64(y64, a32))
+        assert np.all(err <= SR.categorical_log_prob_bound(y64, bound, a32)), err.max()
+    wx, wy = (rng.integers(0, 2**32, N, dtype=np.uint64).astype(np.uint32) for _ in range(2))
+    z64 = SR.z_gaussian64(wx, wy)
+    f = np.float32
+    u1 = (((wx >> 8) + 1).astype(f) * f(2.0 ** -24)).astype(f)
+    u2 = ((wy >> 8).astype(f) * f(2.0 ** -24)).astype(f)
+    z32 = (np.sqrt(f(-2) * np.log(u1)).astype(f) * np.cos(np.float64(2 * u2) * np.pi).astype(f)).astype(f)
+    assert np.all(np.abs(z32 - z64) <= SR.gaussian_z_bound(z64))
+    for ls in (-20.0, -0.5, 0.0, 2.0):
+        lp0 = f(-f(ls) - f(0.918938533204672742))
+        lp32 = (np.float64(f(-0.5) * z32) * np.float64(z32) + np.float64(lp0)).astype(f)  # one fma: round once
+        err = np.abs(lp32 - SR.gaussian_log_prob64(z64, f(ls)))
+        assert np.all(err <= SR.gaussian_log_prob_bound(z64, f(ls))), err.max()
