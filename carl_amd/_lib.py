@@ -71,6 +71,13 @@ class StepIO(C.Structure):
     ]
 
 
+class RolloutPlan(C.Structure):
+    """carl_rollout_plan_t: which kernel instance a launch takes (carl_rollout_plan_io; host logic, no GPU needed)"""
+    _fields_ = [(k, C.c_int32) for k in ("variant", "lean", "unsupported", "ak", "plain", "ldsctx", "moves", "fin", "ar",
+                                          "deep", "has_staged_kernel", "use_lds_ctx", "step_block", "acrobot_fp32")] + [
+        ("lds_bytes", C.c_int64)]
+
+
 EXPORTS = {
     "carl_abi_version": (C.c_int, []),
     "carl_last_error": (C.c_char_p, []),
@@ -82,6 +89,7 @@ EXPORTS = {
     "carl_rollout_pair": (C.c_int, [C.POINTER(Batch), C.POINTER(StepIO), C.POINTER(Batch), C.POINTER(StepIO), C.c_int32, _vp]),
     "carl_rollout_variant": (C.c_int, [C.POINTER(Batch)]),
     "carl_rollout_variant_io": (C.c_int, [C.POINTER(Batch), C.POINTER(StepIO)]),
+    "carl_rollout_plan_io": (C.c_int, [C.POINTER(Batch), C.POINTER(StepIO), C.POINTER(RolloutPlan)]),
     "carl_rollout_pitch": (C.c_int32, [C.c_int32]),
     "carl_done_compact": (C.c_int, [_vp, _vp, C.c_int32, _vp, _vp, _vp, _vp]),
     "carl_done_compact_scratch_elems": (C.c_int32, [C.c_int32]),

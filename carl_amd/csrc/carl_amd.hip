@@ -316,6 +316,10 @@ staged_kern_t staged_kernel(const RolloutPlan& p) {
 // lanes = 1024 waves = one per SIMD); large batches use 256.
 int pick_block(int n, bool lds) { return (lds || n > 256 * 1024) ? 256 : 64; }
 
+// threads per workgroup of a per-call step launch (launch_step; reported by carl_rollout_plan_io)
+template <class Fam>
+int step_block(const carl_batch_t* b) { return pick_block(b->n_lanes, use_lds_ctx<Fam>(b)); }
+
 template <class Fam>
 int launch_reset(const carl_batch_t* b, const uint8_t* mask, const int32_t* idx, const int32_t* count, float* obs,
                  hipStream_t s) {
@@ -359,7 +363,7 @@ int launch_step(const carl_batch_t* b, const carl_step_io_t* io, int n_steps, hi
   // rollout_kernel: 256 compute lanes + one loader wave per workgroup, actions double-buffered in LDS; per-call step:
   // plain lane-per-thread workgroups
   const bool lds = use_lds_ctx<Fam>(b), a64 = io->action_dtype == CARL_ACTION_I64;
-  const int block = rollout ? carl::kRolloutThreads : pick_block(b->n_lanes, lds);
+  const int block = rollout ? carl::kRolloutThreads : step_block<Fam>(b);
   const int lanes_per_block = rollout ? carl::kRolloutLanes : block;
   const dim3 g((b->n_lanes + lanes_per_block - 1) / lanes_per_block), t(block);
   const size_t sh = (lds ? (size_t)Fam::F * b->n_contexts * sizeof(float) : 0) +
@@ -530,6 +534,35 @@ int carl_rollout_variant_io(const carl_batch_t* batch, const carl_step_io_t* io)
   }
   const carl_step_io_t dense{};  // no io: dense rows, arrays on 16-byte boundaries
   return with_classic_family(batch, [&](auto fam) { return plan_rollout<decltype(fam)>(batch, io != nullptr ? io : &dense).variant; });
+}
+
+int carl_rollout_plan_io(const carl_batch_t* batch, const carl_step_io_t* io, carl_rollout_plan_t* out) {
+  if (batch == nullptr || out == nullptr) return fail(CARL_ERR_INVALID_ARGUMENT, "carl_rollout_plan_io: batch / out is NULL");
+  if (batch->family < 0 || batch->family >= CARL_N_FAMILIES)
+    return fail(CARL_ERR_INVALID_ARGUMENT, "carl_rollout_plan_io: family %d is not a classic-control family", batch->family);
+  if (batch->n_lanes < 0 || batch->n_contexts <= 0)
+    return fail(CARL_ERR_INVALID_ARGUMENT, "carl_rollout_plan_io: n_lanes %d / n_contexts %d invalid", batch->n_lanes,
+                batch->n_contexts);
+  if (io != nullptr && io->row_pitch != 0 && io->row_pitch < batch->n_lanes)
+    return fail(CARL_ERR_INVALID_ARGUMENT, "carl_rollout_plan_io: io.row_pitch %d < n_lanes %d", io->row_pitch, batch->n_lanes);
+  const carl_step_io_t dense{};  // no io: dense rows, arrays on 16-byte boundaries, int32 actions
+  return with_classic_family(batch, [&](auto fam) {
+    using Fam = decltype(fam);
+    // the plan launch_step acts on, and the kernel-choosing values of launch_reset / launch_step beside it
+    const RolloutPlan p = plan_rollout<Fam>(batch, io != nullptr ? io : &dense);
+    *out = carl_rollout_plan_t{};
+    out->variant = p.variant;
+    out->lean = p.lean;
+    out->unsupported = p.unsupported;
+    out->ak = p.ak;
+    out->plain = p.plain, out->ldsctx = p.ldsctx, out->moves = p.moves, out->fin = p.fin, out->ar = p.ar, out->deep = p.deep;
+    out->has_staged_kernel = p.variant == CARL_ROLLOUT_STAGED && staged_kernel<Fam>(p) != nullptr;
+    out->use_lds_ctx = use_lds_ctx<Fam>(batch);
+    out->step_block = step_block<Fam>(batch);
+    out->acrobot_fp32 = std::is_same_v<Fam, carl::AcrobotFast>;
+    out->lds_bytes = (int64_t)p.lds_bytes;
+    return 0;
+  });
 }
 
 int32_t carl_rollout_pitch(int32_t n_lanes) { return n_lanes <= 0 ? 0 : (n_lanes + 15) / 16 * 16; }

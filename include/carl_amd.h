@@ -287,6 +287,28 @@ int carl_rollout_variant(const carl_batch_t* batch); /* CARL_ERR_INVALID_ARGUMEN
  * carl_amd/distributed.py::lane_shard).  No reference counterpart: the reference has no batched layout at all
  * (carl/envs/carl_env.py:321-342 returns one env's tuple). */
 int carl_rollout_variant_io(const carl_batch_t* batch, const carl_step_io_t* io);
+/* ... and which INSTANCE (additive; ABI version unchanged: a new symbol and a new struct, no existing layout moves): what
+ * the library's one launch rule decided for this batch with these buffers, field by field -- rollout_staged_kernel's
+ * template arguments and dynamic LDS where variant == CARL_ROLLOUT_STAGED, and the LDS argument / block size of the
+ * reset, per-call step and direct-store rollout kernels.  Host logic only (no HIP call, no allocation, nothing
+ * dereferenced: the pointers' alignment is all that is read), so a test can hold a table of configurations against it
+ * without a GPU.  io NULL = dense rows, aligned arrays, int32 actions (as carl_rollout_variant).  No reference
+ * counterpart.  Returns 0, or CARL_ERR_INVALID_ARGUMENT (NULL batch / out, a non-classic family, n_lanes < 0,
+ * n_contexts <= 0, io.row_pitch < n_lanes).  The action dtype is reported as given: whether the family accepts it is
+ * carl_step's / carl_rollout's own check. */
+typedef struct carl_rollout_plan {
+  int32_t variant;      /* CARL_ROLLOUT_* */
+  int32_t lean;         /* the lean staged configuration (static / host selector, no finished-episode log, no final_obs) */
+  int32_t unsupported;  /* a narrow action format outside the lean staged configuration: carl_rollout declines */
+  int32_t ak;           /* action kind: 0 int32 / float32, 1 int64, 2 uint8, 3 float16, 4 bfloat16 */
+  int32_t plain, ldsctx, moves, fin, ar, deep; /* rollout_staged_kernel<Fam, AK, PLAIN, LDSCTX, MOVES, FIN, AR, DEEP> */
+  int32_t has_staged_kernel; /* an instance with these arguments exists (variant == CARL_ROLLOUT_STAGED only) */
+  int32_t use_lds_ctx;  /* reset / step / direct rollout kernels: context table staged in LDS (their LDS argument) */
+  int32_t step_block;   /* threads per workgroup of a carl_step launch */
+  int32_t acrobot_fp32; /* the batch runs the float32 Acrobot (CARL_FLAG_ACROBOT_FP32 on CARL_ACROBOT) */
+  int64_t lds_bytes;    /* dynamic LDS of the staged launch */
+} carl_rollout_plan_t;
+int carl_rollout_plan_io(const carl_batch_t* batch, const carl_step_io_t* io, carl_rollout_plan_t* out);
 int32_t carl_rollout_pitch(int32_t n_lanes); /* n_lanes rounded up to the next multiple of 16 (0 for n_lanes <= 0) */
 
 /* done-mask compaction: ascending lane ids with terminated|truncated set.
