@@ -1,4 +1,4 @@
-"""Lane engine for the Brax-locomotion families: ``VecEngine`` with a model table
+"""Lane engine for the Brax-locomotion families: a ``LaneEngine`` over a model table
 (``carl_brax_sys_t``) instead of a built-in family.  Replaces, for N lanes at once, what
 ``CARLBraxEnv`` builds with ``brax.envs.create(env_name, backend="spring", batch_size)`` +
 ``VectorGymWrapper`` (reference: carl/envs/brax/carl_brax_env.py:163-190,
@@ -11,7 +11,7 @@ from dataclasses import dataclass
 import torch
 
 from carl_amd import _lib
-from carl_amd.engine import VecEngine, _ptr
+from carl_amd.engine import LaneEngine, _ptr
 
 
 @dataclass
@@ -27,59 +27,62 @@ class _BraxInfo:
     action_high: float
 
 
-class BraxVecEngine(VecEngine):
-    _narrow_actions = False  # carl_brax_step / carl_brax_rollout read float32 actions: narrower dtypes are widened here
-    _policy_rollout = False  # the closed-loop rollout (VecEngine.rollout_policy) is classic-control only
+_BRAX_FAMILY = -1  # ``carl_batch_t.family`` of a Brax batch: none of the built-in families (include/carl_amd.h)
+
+
+class BraxVecEngine(LaneEngine):
+    # optional buffers (None: not built): BraxWalkerGoalWrapper state, the first_state auto-reset's copy, the branch record
+    goal_pos = success = first_state = branch_sig = None
+    _SNAPSHOT = LaneEngine._SNAPSHOT + ("goal_pos", "success", "first_state", "branch_sig")
 
     def __init__(self, sys_table: _lib.BraxSys, n_features: int, ctx_table, n_lanes: int, device="cuda", *,
-                 autoreset_mode: str = "redraw", **kw):
+                 autoreset_mode: str = "redraw", branch_record: bool = False, generic_substep: bool = False,
+                 pose_float32: bool = False, **kw):
         """``autoreset_mode``: what the in-kernel auto-reset does with a done env --
         "redraw" (default; SURVEY.md 8a): selector advance, new init-state draw, like an explicit reset;
         "first_state": put the env back to the state its last explicit ``reset()`` produced, same context,
-        nothing drawn -- brax's ``AutoResetWrapper`` as the reference reaches it (wrappers.py:54-78,121-145)."""
+        nothing drawn -- brax's ``AutoResetWrapper`` as the reference reaches it (wrappers.py:54-78,121-145).
+        ``branch_record``: per-step hash of the physics' discrete decisions (carl_step_io_t::branch_sig).
+        ``generic_substep``: planar models step with the general 3-D substep (A/B, tests).
+        ``pose_float32``: OPT-IN, never a default: the substeps' pose algebra in float32 -- brax's own precision under JAX's
+        default; faster, and off the float64 restatement by more than north_star's 1e-5 (include/carl_amd.h:
+        CARL_FLAG_BRAX_FP32).  ``kw``: ``LaneEngine``'s keywords."""
         if autoreset_mode not in ("redraw", "first_state"):
             raise ValueError("autoreset_mode must be 'redraw' or 'first_state'")
-        self.sys = sys_table
-        self._n_features = int(n_features)
-        kw.pop("cartpole_recompute", None)
-        self.goal_pos = self.success = self.first_state = self.branch_sig = None
-        self.autoreset_mode = autoreset_mode
-        branch_record = bool(kw.pop("branch_record", False))
-        generic = bool(kw.pop("generic_substep", False))  # planar models: step with the general 3-D substep (A/B, tests)
-        # OPT-IN, never a default: the substeps' pose algebra in float32 -- brax's own precision under JAX's default; faster,
-        # and off the float64 restatement by more than north_star's 1e-5 (include/carl_amd.h: CARL_FLAG_BRAX_FP32, DESIGN 5.5)
-        pose_float32 = bool(kw.pop("pose_float32", False))
-        if pose_float32 and (sys_table.target_link > 0 or sys_table.push_link > 0):
+        s = sys_table
+        if pose_float32 and (s.target_link > 0 or s.push_link > 0):
             raise ValueError("pose_float32 is not built for the reach / push task models")
-        super().__init__(-1, ctx_table, n_lanes, device, **kw)
-        if generic:
-            self.b.flags |= _lib.FLAG_BRAX_GENERIC
-        if pose_float32:
-            self.b.flags |= _lib.FLAG_BRAX_FP32
-        if autoreset_mode == "first_state":
-            self.b.flags |= _lib.FLAG_AUTORESET_FIRST_STATE
-            self.first_state = torch.zeros((self.n, self.S), dtype=torch.float32, device=self.device)
+        info = _BraxInfo(_lib.BRAX_LINK_RECORD * s.n_links, s.obs_dim, int(n_features), s.n_act, 0, 0,
+                         s.max_episode_steps, float(min(s.act_lo[: s.n_act])), float(max(s.act_hi[: s.n_act])))
+        super().__init__(info, _BRAX_FAMILY, ctx_table, n_lanes, device, **kw, flags=(
+            _lib.FLAG_BRAX_GENERIC if generic_substep else 0) | (_lib.FLAG_BRAX_FP32 if pose_float32 else 0) | (
+            _lib.FLAG_AUTORESET_FIRST_STATE if autoreset_mode == "first_state" else 0))
+        self.sys, self.autoreset_mode = s, autoreset_mode
+        dev = self.device
         # Brax state is env-major in HBM ([N][L][20]: per link pose head 7 | pose tail 7 | velocities 6,
         # include/carl_amd.h ABI 8); ``self.state`` is the [20 L, N] VIEW of that storage (the classic-control
         # engine's indexing); ``state64()`` returns it as float64 [N, L, 13].
-        self._state_storage = torch.zeros((self.n, self.S), dtype=torch.float32, device=self.device)
+        self._state_storage = self.state.view(self.n, self.S)  # (the same zeroed memory, env-major)
         self.state = self._state_storage.t()
-        if branch_record:  # per-step hash of the physics' discrete decisions (carl_step_io_t::branch_sig)
-            self.branch_sig = torch.zeros((self.n, 2), dtype=torch.int32, device=self.device)
+        if autoreset_mode == "first_state":
+            self.first_state = torch.zeros((self.n, self.S), dtype=torch.float32, device=dev)
+        if branch_record:
+            self.branch_sig = torch.zeros((self.n, 2), dtype=torch.int32, device=dev)
+        if s.goal_mode:  # BraxWalkerGoalWrapper state: integrated (x, y) + per-step success flag
+            self.goal_pos = torch.zeros((2, self.n), dtype=torch.float32, device=dev)
+            self.success = torch.zeros(self.n, dtype=torch.uint8, device=dev)
         self._sync_pointers()
-        if self.sys.goal_mode:  # BraxWalkerGoalWrapper state: integrated (x, y) + per-step success flag
-            self.goal_pos = torch.zeros((2, self.n), dtype=torch.float32, device=self.device)
-            self.success = torch.zeros(self.n, dtype=torch.uint8, device=self.device)
-            self._sync_pointers()
         # device copy of the model table (the kernels stage it into LDS once per workgroup)
-        raw = bytes(self.sys)
-        self.sys_dev = torch.frombuffer(bytearray(raw), dtype=torch.uint8).to(self.device)
-        self._sys_ref = C.byref(self.sys)
+        self.sys_dev = torch.frombuffer(bytearray(bytes(s)), dtype=torch.uint8).to(dev)
+        self._sys_ref = C.byref(s)
+        # launch-shape autotuning: fastest width per launch-length class (_shape_for), a probe is running, the last timings
+        self._tuned, self._tuning, self.autotune_ms = {}, False, None
 
-    def _family_info(self):
-        s = self.sys
-        return _BraxInfo(_lib.BRAX_LINK_RECORD * s.n_links, s.obs_dim, self._n_features, s.n_act, 0, 0,
-                         s.max_episode_steps, float(min(s.act_lo[: s.n_act])), float(max(s.act_hi[: s.n_act])))
+    def _sync_pointers(self) -> None:
+        super()._sync_pointers()
+        b = self.b
+        b.goal_pos, b.success, b.first_state = _ptr(self.goal_pos), _ptr(self.success), _ptr(self.first_state)
+        self._io.branch_sig = _ptr(self.branch_sig)
 
     def _c_reset(self, mask_ptr) -> int:
         return self.lib.carl_brax_reset(C.byref(self.b), _ptr(self.sys_dev), C.byref(self.sys), mask_ptr,
@@ -150,10 +153,15 @@ class BraxVecEngine(VecEngine):
         """Brax families have ONE rollout kernel (no staged / direct-store pair): nothing to warn about."""
         return _lib.ROLLOUT_STAGED
 
-    _has_direct_kernel = False
-
     def _row_pitch(self) -> int:
         return self.n  # dense rows: the Brax kernel writes per-env pieces, not 16-byte pieces of lane rows
+
+    def _out_pitch(self, out: dict) -> int:
+        r = out["reward"]
+        if r.dim() == 2 and r.stride(0) > self.n:
+            raise ValueError(f"{type(self).__name__}: dense rows only ({self.n} lanes per row); these output buffers have "
+                             f"rows of {int(r.stride(0))} lanes")
+        return self.n
 
     def alloc_rollout(self, n_steps: int, final_obs: bool = False, branch_record: bool = False) -> dict:
         out = super().alloc_rollout(n_steps, final_obs)
@@ -169,8 +177,8 @@ class BraxVecEngine(VecEngine):
         (carl_brax.hip: launch_brax), and the best width differs (Halfcheetah x 32 768: a 2-step probe picks 8 lanes per
         env, 50-step rollouts are 30 % faster at 7).  The class not probed yet is probed on first use (state saved and
         restored; results never depend on the width)."""
-        tuned = getattr(self, "_tuned", None)
-        if tuned is None or getattr(self, "_tuning", False) or torch.cuda.is_current_stream_capturing():
+        tuned = self._tuned
+        if not tuned or self._tuning or torch.cuda.is_current_stream_capturing():
             return  # (never probe inside a hipGraph capture: the width in force is recorded as it is)
         long_launch = n_steps >= 4
         if long_launch not in tuned:  # only after autotune(both_classes=False)
@@ -223,7 +231,7 @@ class BraxVecEngine(VecEngine):
 
     def _probe_widths(self, n_steps: int, reps: int) -> int:
         saved = self.snapshot()
-        width0, tuning0 = int(self.sys.lanes_per_env), getattr(self, "_tuning", False)
+        width0, tuning0 = int(self.sys.lanes_per_env), self._tuning
         lo, hi = float(min(self.sys.act_lo[: self.sys.n_act])), float(max(self.sys.act_hi[: self.sys.n_act]))
         gen = torch.Generator(device=self.device).manual_seed(0x5EED)
         acts = torch.rand((n_steps, self.n, self.sys.n_act), device=self.device, generator=gen) * (hi - lo) + lo
@@ -253,8 +261,6 @@ class BraxVecEngine(VecEngine):
         else:
             self.sys.lanes_per_env = best
             self.autotune_ms = timings
-            if getattr(self, "_tuned", None) is None:
-                self._tuned = {}
             self._tuned[n_steps >= 4] = best  # per launch-length class (_shape_for)
         finally:
             self._tuning = tuning0
@@ -263,6 +269,12 @@ class BraxVecEngine(VecEngine):
 
     def reset_indexed(self, idx, count):
         raise NotImplementedError("Brax families reset through a lane mask (reset(mask)) or in-kernel auto-reset")
+
+    def rollout_policy(self, *args, **kwargs):
+        raise NotImplementedError(f"{type(self).__name__}: the closed-loop rollout covers the classic-control "
+                                  "families only")
+
+    evaluate_policy = rollout_policy
 
     def reset_done(self):
         return self.reset((self.terminated | self.truncated))

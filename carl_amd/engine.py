@@ -1,5 +1,7 @@
 """Device-resident batch of env lanes: buffers (PyTorch-ROCm tensors) + C-ABI calls.
 
+``LaneEngine`` is what every lane engine does (buffers, contexts, the per-call step, the dense-row fused rollout);
+``VecEngine`` is the classic-control engine on top of it, ``carl_amd.brax_engine.BraxVecEngine`` the Brax one.
 ``VecEngine`` is the object the CARL-shaped envs wrap -- the replacement for the
 gymnasium env (+ TimeLimit) that ``CARLGymnasiumEnv`` builds with ``gymnasium.make``
 (reference: carl/envs/gymnasium/carl_gymnasium_env.py:63-64) -- for N lanes at once.
@@ -34,7 +36,7 @@ _current_device = getattr(torch._C, "_cuda_getDevice", None) or torch.cuda.curre
 
 
 class _PreparedRollout(NamedTuple):
-    """A ``rollout`` up to its launch (``VecEngine._prepare_rollout``): actions as converted, output buffers, the
+    """A ``rollout`` up to its launch (``LaneEngine._prepare_rollout``): actions as converted, output buffers, the
     ``carl_step_io_t`` over both, and the step count."""
     a: torch.Tensor
     dt: int
@@ -44,9 +46,9 @@ class _PreparedRollout(NamedTuple):
 
 
 class CapturedStep:
-    """``VecEngine.capture_step``: a hipGraph of ``n_steps`` ``carl_step`` launches on a fixed action buffer."""
+    """``LaneEngine.capture_step``: a hipGraph of ``n_steps`` ``carl_step`` launches on a fixed action buffer."""
 
-    def __init__(self, eng: "VecEngine", action_buffer: torch.Tensor, n_steps: int = 1):
+    def __init__(self, eng: "LaneEngine", action_buffer: torch.Tensor, n_steps: int = 1):
         a, dt = eng._action_tensor(action_buffer, ())
         if a.data_ptr() != action_buffer.data_ptr():
             raise ValueError("capture_step needs the action buffer in its final form (device, dtype, contiguous): "
@@ -81,42 +83,30 @@ class CapturedStep:
         return e.obs, e.reward, e.terminated, e.truncated
 
 
-class VecEngine:
-    """N lanes of one env family on one device.
+class LaneEngine:
+    """N lanes on one device: what the classic-control engine (``VecEngine``) and the Brax engine
+    (``carl_amd.brax_engine.BraxVecEngine``) share.  A subclass computes its family info record (``info``: state / obs /
+    action dimensions, feature count, default episode length) and its ``carl_batch_t.family`` value before it calls
+    up, and supplies the library calls (``_c_reset``, ``_c_step``, ``_c_step_fast``, ``_c_rollout``), the row pitch of a
+    fused rollout's arrays (``_row_pitch``, ``_out_pitch``) and, where it has any, its narrow action formats
+    (``_narrow_action``); one whose rows can be longer than the lane count also ``_pad_action_rows``.  ``flags``: the
+    subclass's ``CARL_FLAG_*`` bits; every other parameter is described at ``VecEngine``."""
 
-    Parameters
-    ----------
-    family : int | str
-        ``carl_family_t`` (or its lower-case name).
-    ctx_table : array [C, F]
-        Context set in the family's feature order (defaults already filled).
-    n_lanes : int
-    device : torch.device | str
-    selector : int
-        ``carl_selector_t`` rule applied on every lane reset.
-    ctx_idx0 : array [n_lanes] | None
-        Context id each lane holds BEFORE its first reset.  Default: round robin
-        ``(g - stride) mod C`` (so the first reset lands on ``g mod C``; with one lane
-        this is the reference's 0, 1, 2, ...), otherwise ``g mod C`` (g = global lane id).
-    lane_offset : int
-        Global id of lane 0: lanes sharded over GPUs keep their global ids, so RNG
-        streams and initial context assignment do not depend on the GPU count.
-    """
+    # every buffer a launch can change (snapshot / restore); a subclass appends its own, None = not built
+    _SNAPSHOT = ("state", "elapsed", "ctx_idx", "episode", "n_calls", "ep_return", "last_return", "last_length",
+                 "episodes_done", "obs", "reward", "terminated", "truncated", "done", "final_obs", "ctx_obs", "fin_count")
 
-    def __init__(self, family, ctx_table, n_lanes: int, device="cuda", *, selector: int = _lib.SEL_ROUND_ROBIN,
-                 selector_stride: int = 1, auto_reset: bool = True, max_episode_steps: int | None = None,
-                 seed: int = 0, lane_offset: int = 0, cartpole_recompute: bool = False,
+    def __init__(self, info, family: int, ctx_table, n_lanes: int, device="cuda", *,
+                 selector: int = _lib.SEL_ROUND_ROBIN, selector_stride: int = 1, auto_reset: bool = True,
+                 max_episode_steps: int | None = None, seed: int = 0, lane_offset: int = 0,
                  ctx_obs_rows: Sequence[int] | None = None, ctx_idx0=None, fin_capacity: int = 0,
-                 acrobot_fp32: bool = False, context_offset: int | None = None):
+                 context_offset: int | None = None, flags: int = 0):
         self.lib = _lib.load()
-        if isinstance(family, str):
-            family = _FAMILY_BY_NAME[family]
-        self.family = int(family)
-        self.info = self._family_info()
+        self.family, self.info = int(family), info
         self.device = torch.device(device)
         if self.device.type != "cuda":
             raise _lib.CarlHipError(
-                f"VecEngine needs a ROCm device (got {self.device}); there is no CPU path")
+                f"{type(self).__name__} needs a ROCm device (got {self.device}); there is no CPU path")
         if self.device.index is None:
             self.device = torch.device("cuda", torch.cuda.current_device())
         self.n = int(n_lanes)
@@ -153,10 +143,6 @@ class VecEngine:
         self.done = self._out_slab[o_done: o_done + self.n]  # terminated | truncated of the last step()
         self._out_host = None  # pinned mirror of the slab, made on first use (read_transition)
         self.final_obs = torch.zeros((self.n, D), dtype=f32, device=dev)
-        # done-mask compaction buffers
-        self.done_idx = torch.zeros(max(self.n, 1), dtype=i32, device=dev)
-        self.done_count = torch.zeros(1, dtype=i32, device=dev)
-        self._scratch = torch.zeros(int(self.lib.carl_done_compact_scratch_elems(self.n)), dtype=i32, device=dev)
         # finished-episode log
         self.fin_capacity = int(fin_capacity)
         if self.fin_capacity > 0:
@@ -173,9 +159,7 @@ class VecEngine:
         self.b.max_episode_steps = self.info.max_episode_steps if max_episode_steps is None else int(max_episode_steps)
         self.b.selector = int(selector)
         self.b.selector_stride = int(selector_stride)
-        self.b.flags = (_lib.FLAG_AUTORESET if auto_reset else 0) | (
-            _lib.FLAG_CARTPOLE_RECOMPUTE if cartpole_recompute else 0) | (
-            _lib.FLAG_ACROBOT_FP32 if acrobot_fp32 else 0)
+        self.b.flags = (_lib.FLAG_AUTORESET if auto_reset else 0) | int(flags)
         self.b.lane_offset = int(lane_offset)
         self.b.seed = int(seed) & 0xFFFFFFFFFFFFFFFF
         # global id of context-table row 0 (see default_ctx_idx); None: decided per table
@@ -187,16 +171,15 @@ class VecEngine:
         self.ctx_obs = torch.zeros((len(self.ctx_obs_rows), self.n), dtype=f32, device=dev)
         self.ctx_table = None
         self.ctx_idx = None
-        self.set_contexts(ctx_table, ctx_idx0)
         self._io = _lib.StepIO()
-        self._sync_pointers()
+        self.set_contexts(ctx_table, ctx_idx0)  # (fills in every pointer: _sync_pointers)
         # per-call fast path (see step()): everything the ctypes call needs, prepared once
         self._dev_index = int(self.device.index)
         self._b_ref, self._io_ref = C.byref(self.b), C.byref(self._io)
-        self._step_fn = self.lib.carl_step
         self._last_action = None
         self._last_action_meta = None
-        self._warned_direct = False
+        self._a_host = None  # pinned staging buffer of stage_scalar_action, made on first use
+        self._a_pending = False
 
     # ------------------------------------------------------------------ contexts
     def default_ctx_idx(self, n_contexts: int) -> torch.Tensor:
@@ -223,22 +206,8 @@ class VecEngine:
         t = torch.as_tensor(np.asarray(ctx_table, dtype=np.float64) if not torch.is_tensor(ctx_table) else ctx_table)
         if t.ndim != 2 or t.shape[1] != self.F:
             raise ValueError(f"ctx_table must be [C, {self.F}], got {tuple(t.shape)}")
-        C_ = int(t.shape[0])
-        if C_ < 1:
-            raise ValueError("empty context set")
         # feature-major [F, C] fp32 on device
-        self.ctx_table = t.to(torch.float32).t().contiguous().to(self.device)
-        self.b.n_contexts = C_
-        self.b.ctx_stride = C_
-        if ctx_idx0 is None:
-            idx = self.default_ctx_idx(C_)
-        else:
-            idx = torch.as_tensor(ctx_idx0).to(torch.int32).reshape(self.n)
-            if idx.numel() and (int(idx.min()) < 0 or int(idx.max()) >= C_):
-                raise ValueError("ctx_idx0 out of range")
-        self.ctx_idx = idx.to(self.device).contiguous()
-        if hasattr(self, "_io"):
-            self._sync_pointers()
+        self._adopt_contexts(t.to(torch.float32).t().contiguous().to(self.device), ctx_idx0, check_range=True)
 
     def set_contexts_device(self, table_fc, ctx_idx0=None) -> None:
         """Adopt a context table that already lives on this device as feature-major ``[F][C]``
@@ -248,19 +217,24 @@ class VecEngine:
             raise ValueError(f"device context table must be a [{self.F}, C] tensor")
         if t.dtype != torch.float32 or t.device != self.device or not t.is_contiguous():
             t = t.to(device=self.device, dtype=torch.float32).contiguous()
-        C_ = int(t.shape[1])
+        self._adopt_contexts(t, ctx_idx0, check_range=False)  # (a range check would synchronise)
+
+    def _adopt_contexts(self, table_fc: torch.Tensor, ctx_idx0, check_range: bool) -> None:
+        """``table_fc`` (feature-major ``[F, C]`` float32 on this device) becomes the context table; lanes start on
+        ``ctx_idx0`` (default: ``default_ctx_idx``)."""
+        C_ = int(table_fc.shape[1])
         if C_ < 1:
             raise ValueError("empty context set")
-        self.ctx_table = t
-        self.b.n_contexts = C_
-        self.b.ctx_stride = C_
+        self.ctx_table = table_fc
+        self.b.n_contexts = self.b.ctx_stride = C_
         if ctx_idx0 is None:
             idx = self.default_ctx_idx(C_)
         else:
             idx = torch.as_tensor(ctx_idx0).to(torch.int32).reshape(self.n)
+            if check_range and idx.numel() and (int(idx.min()) < 0 or int(idx.max()) >= C_):
+                raise ValueError("ctx_idx0 out of range")
         self.ctx_idx = idx.to(self.device).contiguous()
-        if hasattr(self, "_io"):
-            self._sync_pointers()
+        self._sync_pointers()
 
     def set_ctx_idx(self, idx) -> None:
         """Host-driven context switch (``context_id`` setter, carl_env.py:139-157)."""
@@ -274,21 +248,18 @@ class VecEngine:
             rows = torch.as_tensor(self.ctx_obs_rows, device=self.device)
             self.ctx_obs.copy_(self.ctx_table[rows][:, self.ctx_idx.long()])
 
-    # ------------------------------------------------------------------ family hooks
-    def _family_info(self):
-        return _lib.family_info(self.family)
-
+    # ------------------------------------------------------------------ library calls (the subclass's)
     def _c_reset(self, mask_ptr) -> int:
-        return self.lib.carl_reset(C.byref(self.b), mask_ptr, _ptr(self.obs), self._stream())
+        raise NotImplementedError
 
     def _c_step(self, io) -> int:
-        return self.lib.carl_step(C.byref(self.b), C.byref(io), self._stream())
+        raise NotImplementedError
 
     def _c_step_fast(self, stream: int) -> int:  # self._io, prepared references
-        return self._step_fn(self._b_ref, self._io_ref, stream)
+        raise NotImplementedError
 
     def _c_rollout(self, io, n_steps: int) -> int:
-        return self.lib.carl_rollout(C.byref(self.b), C.byref(io), n_steps, self._stream())
+        raise NotImplementedError
 
     # ------------------------------------------------------------------ plumbing
     def _sync_pointers(self) -> None:
@@ -305,16 +276,11 @@ class VecEngine:
         b.fin_capacity = self.fin_capacity
         b.fin_count, b.fin_lane = _ptr(self.fin_count), _ptr(self.fin_lane)
         b.fin_return, b.fin_length = _ptr(self.fin_return), _ptr(self.fin_length)
-        b.goal_pos = _ptr(getattr(self, "goal_pos", None))
-        b.success = _ptr(getattr(self, "success", None))
-        b.first_state = _ptr(getattr(self, "first_state", None))
-        io = getattr(self, "_io", None)
-        if io is not None:  # the per-call outputs never move: step() only fills in the action
-            io.obs, io.reward = _ptr(self.obs), _ptr(self.reward)
-            io.terminated, io.truncated = _ptr(self.terminated), _ptr(self.truncated)
-            io.final_obs = _ptr(self.final_obs)
-            io.done = _ptr(self.done)
-            io.branch_sig = _ptr(getattr(self, "branch_sig", None))
+        io = self._io  # the per-call outputs never move: step() only fills in the action
+        io.obs, io.reward = _ptr(self.obs), _ptr(self.reward)
+        io.terminated, io.truncated = _ptr(self.terminated), _ptr(self.truncated)
+        io.final_obs = _ptr(self.final_obs)
+        io.done = _ptr(self.done)
 
     def _stream(self) -> int:
         return torch.cuda.current_stream(self.device).cuda_stream
@@ -331,27 +297,21 @@ class VecEngine:
     def n_contexts(self) -> int:
         return int(self.b.n_contexts)
 
-    # the narrow rollout-only action formats (uint8 / float16 / bfloat16: include/carl_amd.h) exist in the classic-control
-    # kernels' loader wave; the Brax entry points take float32 only -- BraxVecEngine turns this off, so that half-precision
-    # actions (a policy under autocast) are widened once instead of being rejected by carl_brax_rollout
-    _narrow_actions = True
+    def _narrow_action(self, a: torch.Tensor) -> tuple[torch.Tensor, int] | None:
+        """``(a, CARL_ACTION_*)`` where ``a`` is in a narrow format that this engine's fused rollout reads as it is, else
+        None.  Here: there is none -- every action is widened to int32 / int64 / float32 (a policy under autocast hands
+        half-precision actions to an engine whose library calls read float32 only: ADVICE r04)."""
+        return None
 
     def _action_tensor(self, action, lead: tuple[int, ...], allow_narrow: bool = False) -> tuple[torch.Tensor, int]:
-        allow_narrow = allow_narrow and self._narrow_actions
         a = action if torch.is_tensor(action) else torch.as_tensor(np.asarray(action))
-        if self.info.action_is_discrete:
-            if allow_narrow and a.dtype == torch.uint8:  # rollout-only input format (include/carl_amd.h: CARL_ACTION_U8)
-                dt = _lib.ACTION_U8
-                if a.is_contiguous() and a.data_ptr() % 4:  # (a view into a larger buffer: the kernel reads dwords)
-                    a = a.clone()
-            else:
-                if a.dtype not in (torch.int32, torch.int64):
-                    a = a.to(torch.int64)
-                dt = _lib.ACTION_I32 if a.dtype == torch.int32 else _lib.ACTION_I64
-        elif allow_narrow and a.dtype in (torch.float16, torch.bfloat16):  # (likewise: CARL_ACTION_F16 / BF16)
-            dt = _lib.ACTION_F16 if a.dtype == torch.float16 else _lib.ACTION_BF16
-            if a.is_contiguous() and a.data_ptr() % 8:
-                a = a.clone()
+        narrow = self._narrow_action(a) if allow_narrow else None  # (a fused rollout's actions only)
+        if narrow is not None:
+            a, dt = narrow
+        elif self.info.action_is_discrete:
+            if a.dtype not in (torch.int32, torch.int64):
+                a = a.to(torch.int64)
+            dt = _lib.ACTION_I32 if a.dtype == torch.int32 else _lib.ACTION_I64
         else:
             if a.dtype != torch.float32:
                 a = a.to(torch.float32)
@@ -381,25 +341,6 @@ class VecEngine:
         with torch.cuda.device(self.device):
             _lib.check(self._c_reset(_ptr(m)))
         return self.obs
-
-    def done_compact(self) -> tuple[torch.Tensor, torch.Tensor]:
-        """Ascending ids of lanes whose last step ended their episode -> (idx[n], count[1])."""
-        with torch.cuda.device(self.device):
-            _lib.check(self.lib.carl_done_compact(
-                _ptr(self.terminated), _ptr(self.truncated), self.n, _ptr(self.done_idx),
-                _ptr(self.done_count), _ptr(self._scratch), self._stream()))
-        return self.done_idx, self.done_count
-
-    def reset_indexed(self, idx: torch.Tensor, count: torch.Tensor) -> torch.Tensor:
-        with torch.cuda.device(self.device):
-            _lib.check(self.lib.carl_reset_indexed(C.byref(self.b), _ptr(idx), _ptr(count), _ptr(self.obs),
-                                                   self._stream()))
-        return self.obs
-
-    def reset_done(self) -> torch.Tensor:
-        """Explicit-reset path: compact the done mask, reset exactly those lanes."""
-        idx, count = self.done_compact()
-        return self.reset_indexed(idx, count)
 
     def step(self, action):
         """One step of every lane -> (obs[N,D], reward[N], terminated[N] u8, truncated[N] u8).
@@ -433,13 +374,12 @@ class VecEngine:
         """A host scalar / small array as THE device action tensor of this engine (pinned staging buffer, asynchronous
         copy on the launch stream): what a scalar caller passes to ``step`` -- the same tensor object every call, so
         ``step`` takes its validated-once fast path, and no blocking host-to-device copy per call."""
-        if getattr(self, "_a_host", None) is None:
+        if self._a_host is None:
             dt = torch.int32 if self.info.action_is_discrete else torch.float32
             self._a_host = torch.empty(self.n * self._action_dim, dtype=dt).pin_memory()
             self._a_dev = torch.empty((self.n, self._action_dim) if self._action_dim > 1 or not self.info.action_is_discrete
                                       else (self.n,), dtype=dt, device=self.device)
             self._a_host_np = self._a_host.numpy()
-            self._a_pending = False
         a = np.asarray(action).reshape(-1)
         if a.size != self._a_host_np.size:  # (NumPy would broadcast one value over every actuator silently)
             raise ValueError(f"action has {a.size} elements, this engine takes {self.n} x {self._action_dim}")
@@ -471,13 +411,9 @@ class VecEngine:
 
     # ------------------------------------------------------------------ replayable step (hipGraph)
     def snapshot(self) -> dict:
-        """Copies of every buffer a launch can change (state, counters, bookkeeping, step outputs): the one list of them,
-        used by ``capture_step``'s warm-up and ``BraxVecEngine.autotune``'s probes."""
-        names = ["state", "elapsed", "ctx_idx", "episode", "n_calls", "ep_return", "last_return", "last_length",
-                 "episodes_done", "obs", "reward", "terminated", "truncated", "done", "final_obs", "ctx_obs"]
-        names += [k for k in ("goal_pos", "success", "fin_count", "first_state", "branch_sig")
-                  if getattr(self, k, None) is not None]
-        return {k: getattr(self, k).clone() for k in names}
+        """Copies of every buffer a launch can change (state, counters, bookkeeping, step outputs: ``_SNAPSHOT``), used
+        by ``capture_step``'s warm-up and ``BraxVecEngine.autotune``'s probes."""
+        return {k: getattr(self, k).clone() for k in self._SNAPSHOT if getattr(self, k) is not None}
 
     def restore(self, snap: dict) -> None:
         for k, v in snap.items():
@@ -493,17 +429,6 @@ class VecEngine:
         3.7 us per env step, the same as a ``torch.cuda.graph`` around 100 ``step`` calls) and is meant for a policy that
         is captured into the same graph region or for open-loop replays.  Engine state is untouched by the capture."""
         return CapturedStep(self, action_buffer, n_steps)
-
-    _has_direct_kernel = True  # (the classic-control families: staged / direct-store pair of rollout kernels)
-
-    def _row_pitch(self) -> int:
-        """Lanes per ROW of a rollout's action / output arrays (``carl_step_io_t.row_pitch``): the lane count rounded up
-        to a multiple of 16, so that every row's 16-byte pieces stay aligned and ANY lane count -- 10, 65 537, the uneven
-        shards of ``distributed.lane_shard`` -- takes the staged kernel (round 6; such batches used to fall back to the
-        ~50 % slower direct-store kernel).  Dense rows under ``FLAG_ROLLOUT_DIRECT`` (the A/B switch)."""
-        if self.b.flags & _lib.FLAG_ROLLOUT_DIRECT:
-            return self.n
-        return int(self.lib.carl_rollout_pitch(self.n))
 
     def alloc_rollout(self, n_steps: int, final_obs: bool = False) -> dict:
         """Output buffers of a ``rollout`` of ``n_steps``: ``obs [T, N, D]``, ``reward`` / ``terminated`` / ``truncated``
@@ -545,7 +470,177 @@ class VecEngine:
 
     def _launch_rollout(self, r: _PreparedRollout) -> dict:
         """The launch of a prepared ``rollout`` on the current stream -> its output dict."""
-        if self._has_direct_kernel and not self._warned_direct and \
+        with torch.cuda.device(self.device):
+            _lib.check(self._c_rollout(r.io, r.T))
+        return r.out
+
+    def _rollout_io(self, a: torch.Tensor | None, dt: int | None, out: dict, T: int) -> "_lib.StepIO":
+        """``carl_step_io_t`` of a fused launch of ``T`` steps into the caller's ``[T, ...]`` output buffers, rows of one
+        common pitch (``_out_pitch``: ``alloc_rollout`` pads rows to a multiple of 16 lanes; dense caller-made buffers keep
+        working; an engine without padded rows refuses any other pitch there).  Where the actions come from is the one
+        difference: ``rollout`` passes its validated actions ``a`` of format ``dt``; for a padded layout they are copied once
+        into rows of the same pitch, the padding columns repeating the last lane's action (the padding lanes run as clones
+        of that lane: valid numbers).  ``rollout_policy`` passes ``a = None``: the launch writes each step's actions into
+        ``out["action"]``, which must be ``[>= T, N]`` rows of the same pitch, of the family's int32 / float32 dtype, on
+        this device."""
+        n, policy = self.n, a is None
+        keys = ("obs", "reward", "terminated", "truncated", "final_obs")
+        if policy:
+            if "action" not in out:
+                raise ValueError("rollout_policy output needs an 'action' [T, N] buffer")
+            adt = torch.int32 if self.info.action_is_discrete else torch.float32
+            if out["action"].dtype != adt:
+                raise ValueError(f"rollout_policy 'action' buffer must be {adt} for this family")
+            a, dt = out["action"], _lib.ACTION_I32 if self.info.action_is_discrete else _lib.ACTION_F32
+        elif out["reward"].shape[0] < T:
+            raise ValueError("rollout output buffers are shorter than the action sequence")
+        P = self._out_pitch(out)
+        if policy:
+            self._check_rows("rollout_policy", out, keys + ("action",), P, T, self.device)
+        else:
+            self._check_rows("rollout", out, keys, P)
+            if P != n:
+                a = self._pad_action_rows(a, T, P)
+            self._rollout_actions = a  # (keeps a padded copy alive until the launch has been enqueued and beyond)
+        io = _lib.StepIO()
+        io.row_pitch = P if P != n else 0
+        io.action, io.action_dtype = a.data_ptr(), dt
+        io.obs, io.reward = _ptr(out["obs"]), _ptr(out["reward"])
+        io.terminated, io.truncated = _ptr(out["terminated"]), _ptr(out["truncated"])
+        io.final_obs = _ptr(out.get("final_obs"))
+        io.branch_sig = _ptr(out.get("branch_sig"))
+        return io
+
+    def _check_rows(self, who: str, out: dict, keys, P: int, min_rows: int | None = None, device=None) -> None:
+        """ValueError unless each of ``out[keys]`` that is present is ``[T, N]`` (``[T, N, D]``: obs, final_obs) rows of
+        pitch ``P`` lanes -- with ``T >= min_rows`` and on ``device`` when those are given."""
+        n, D = self.n, self.D
+        for k in keys:
+            t = out.get(k)
+            if t is None:
+                continue
+            tail = (D,) if k in ("obs", "final_obs") else ()
+            want = (P * D, D, 1) if tail else (P, 1)
+            if t.dim() == 0 or t.shape[0] < (min_rows or 0) or tuple(t.shape[1:]) != (n,) + tail or (
+                    device is not None and t.device != device) or any(
+                    sz > 1 and st != w for sz, st, w in zip(t.shape, t.stride(), want)):
+                rows = "T" if min_rows is None else f">= {min_rows}"
+                raise ValueError(f"{who} output '{k}': shape {tuple(t.shape)} / strides {tuple(t.stride())} do not form "
+                                 f"[{rows}, {n}{', ' + str(D) if tail else ''}] rows of one common pitch ({P} lanes)")
+
+    def drain_finished(self):
+        """Finished-episode log since the last drain -> (global lane ids, returns, lengths,
+        n_dropped); resets the counter.  Synchronises."""
+        if self.fin_count is None:
+            raise RuntimeError("engine was built with fin_capacity=0")
+        n = int(self.fin_count.item())
+        k = min(n, self.fin_capacity)
+        out = (self.fin_lane[:k].clone(), self.fin_return[:k].clone(), self.fin_length[:k].clone(), n - k)
+        self.fin_count.zero_()
+        return out
+
+
+class VecEngine(LaneEngine):
+    """N lanes of one env family on one device.
+
+    Parameters
+    ----------
+    family : int | str
+        ``carl_family_t`` (or its lower-case name).
+    ctx_table : array [C, F]
+        Context set in the family's feature order (defaults already filled).
+    n_lanes : int
+    device : torch.device | str
+    selector : int
+        ``carl_selector_t`` rule applied on every lane reset.
+    ctx_idx0 : array [n_lanes] | None
+        Context id each lane holds BEFORE its first reset.  Default: round robin
+        ``(g - stride) mod C`` (so the first reset lands on ``g mod C``; with one lane
+        this is the reference's 0, 1, 2, ...), otherwise ``g mod C`` (g = global lane id).
+    lane_offset : int
+        Global id of lane 0: lanes sharded over GPUs keep their global ids, so RNG
+        streams and initial context assignment do not depend on the GPU count.
+    """
+
+    def __init__(self, family, ctx_table, n_lanes: int, device="cuda", *, selector: int = _lib.SEL_ROUND_ROBIN,
+                 selector_stride: int = 1, auto_reset: bool = True, max_episode_steps: int | None = None,
+                 seed: int = 0, lane_offset: int = 0, cartpole_recompute: bool = False,
+                 ctx_obs_rows: Sequence[int] | None = None, ctx_idx0=None, fin_capacity: int = 0,
+                 acrobot_fp32: bool = False, context_offset: int | None = None):
+        if isinstance(family, str):
+            family = _FAMILY_BY_NAME[family]
+        super().__init__(_lib.family_info(int(family)), family, ctx_table, n_lanes, device, selector=selector,
+                         selector_stride=selector_stride, auto_reset=auto_reset, max_episode_steps=max_episode_steps,
+                         seed=seed, lane_offset=lane_offset, ctx_obs_rows=ctx_obs_rows, ctx_idx0=ctx_idx0,
+                         fin_capacity=fin_capacity, context_offset=context_offset,
+                         flags=(_lib.FLAG_CARTPOLE_RECOMPUTE if cartpole_recompute else 0) | (
+                             _lib.FLAG_ACROBOT_FP32 if acrobot_fp32 else 0))
+        # done-mask compaction buffers
+        self.done_idx = torch.zeros(max(self.n, 1), dtype=torch.int32, device=self.device)
+        self.done_count = torch.zeros(1, dtype=torch.int32, device=self.device)
+        self._scratch = torch.zeros(int(self.lib.carl_done_compact_scratch_elems(self.n)), dtype=torch.int32,
+                                    device=self.device)
+        self._step_fn = self.lib.carl_step  # (_c_step_fast)
+        self._warned_direct = False
+        self._act_pad = None  # the one padded copy of a rollout's actions that is kept (_pad_action_rows)
+
+    # ------------------------------------------------------------------ library calls
+    def _c_reset(self, mask_ptr) -> int:
+        return self.lib.carl_reset(C.byref(self.b), mask_ptr, _ptr(self.obs), self._stream())
+
+    def _c_step(self, io) -> int:
+        return self.lib.carl_step(C.byref(self.b), C.byref(io), self._stream())
+
+    def _c_step_fast(self, stream: int) -> int:  # self._io, prepared references
+        return self._step_fn(self._b_ref, self._io_ref, stream)
+
+    def _c_rollout(self, io, n_steps: int) -> int:
+        return self.lib.carl_rollout(C.byref(self.b), C.byref(io), n_steps, self._stream())
+
+    def _narrow_action(self, a: torch.Tensor) -> tuple[torch.Tensor, int] | None:
+        """The narrow rollout-only input formats (uint8 / float16 / bfloat16: include/carl_amd.h) that the classic-control
+        kernels' loader wave reads."""
+        if a.dtype == torch.uint8 and self.info.action_is_discrete:
+            align, dt = 4, _lib.ACTION_U8
+        elif a.dtype in (torch.float16, torch.bfloat16) and not self.info.action_is_discrete:
+            align, dt = 8, _lib.ACTION_F16 if a.dtype == torch.float16 else _lib.ACTION_BF16
+        else:
+            return None
+        # (a view into a larger buffer: the kernel reads dwords / 8-byte pieces)
+        return (a.clone() if a.is_contiguous() and a.data_ptr() % align else a), dt
+
+    def done_compact(self) -> tuple[torch.Tensor, torch.Tensor]:
+        """Ascending ids of lanes whose last step ended their episode -> (idx[n], count[1])."""
+        with torch.cuda.device(self.device):
+            _lib.check(self.lib.carl_done_compact(
+                _ptr(self.terminated), _ptr(self.truncated), self.n, _ptr(self.done_idx),
+                _ptr(self.done_count), _ptr(self._scratch), self._stream()))
+        return self.done_idx, self.done_count
+
+    def reset_indexed(self, idx: torch.Tensor, count: torch.Tensor) -> torch.Tensor:
+        with torch.cuda.device(self.device):
+            _lib.check(self.lib.carl_reset_indexed(C.byref(self.b), _ptr(idx), _ptr(count), _ptr(self.obs),
+                                                   self._stream()))
+        return self.obs
+
+    def reset_done(self) -> torch.Tensor:
+        """Explicit-reset path: compact the done mask, reset exactly those lanes."""
+        idx, count = self.done_compact()
+        return self.reset_indexed(idx, count)
+
+    def _row_pitch(self) -> int:
+        """Lanes per ROW of a rollout's action / output arrays (``carl_step_io_t.row_pitch``): the lane count rounded up
+        to a multiple of 16, so that every row's 16-byte pieces stay aligned and ANY lane count -- 10, 65 537, the uneven
+        shards of ``distributed.lane_shard`` -- takes the staged kernel (round 6; such batches used to fall back to the
+        ~50 % slower direct-store kernel).  Dense rows under ``FLAG_ROLLOUT_DIRECT`` (the A/B switch)."""
+        if self.b.flags & _lib.FLAG_ROLLOUT_DIRECT:
+            return self.n
+        return int(self.lib.carl_rollout_pitch(self.n))
+
+    def _launch_rollout(self, r: _PreparedRollout) -> dict:
+        """``LaneEngine._launch_rollout`` with what the staged / direct-store pair of kernels adds: one warning when a
+        launch takes the direct-store kernel, and narrow actions widened once where only wide ones are read."""
+        if not self._warned_direct and \
                 self.lib.carl_rollout_variant_io(self._b_ref, C.byref(r.io)) == _lib.ROLLOUT_DIRECT_SHAPE:
             import warnings
 
@@ -566,72 +661,15 @@ class VecEngine:
             _lib.check(code)
         return r.out
 
-    def _rollout_io(self, a: torch.Tensor | None, dt: int | None, out: dict, T: int) -> "_lib.StepIO":
-        """``carl_step_io_t`` of a fused launch of ``T`` steps into the caller's ``[T, ...]`` output buffers, rows of one
-        common pitch (``_out_pitch``: ``alloc_rollout`` pads rows to a multiple of 16 lanes; dense caller-made buffers keep
-        working; an engine without the staged kernel takes dense rows only).  Where the actions come from is the one
-        difference: ``rollout`` passes its validated actions ``a`` of format ``dt``; for a padded layout they are copied once
-        into rows of the same pitch, the padding columns repeating the last lane's action (the padding lanes run as clones
-        of that lane: valid numbers).  ``rollout_policy`` passes ``a = None``: the launch writes each step's actions into
-        ``out["action"]``, which must be ``[>= T, N]`` rows of the same pitch, of the family's int32 / float32 dtype, on
-        this device."""
-        n, policy = self.n, a is None
-        keys = ("obs", "reward", "terminated", "truncated", "final_obs")
-        if policy:
-            if "action" not in out:
-                raise ValueError("rollout_policy output needs an 'action' [T, N] buffer")
-            adt = torch.int32 if self.info.action_is_discrete else torch.float32
-            if out["action"].dtype != adt:
-                raise ValueError(f"rollout_policy 'action' buffer must be {adt} for this family")
-            a, dt = out["action"], _lib.ACTION_I32 if self.info.action_is_discrete else _lib.ACTION_F32
-        elif out["reward"].shape[0] < T:
-            raise ValueError("rollout output buffers are shorter than the action sequence")
-        P = self._out_pitch(out)
-        if P != n and not self._has_direct_kernel:
-            raise ValueError(f"{type(self).__name__}: dense rows only ({n} lanes per row); these output buffers have rows of "
-                             f"{P} lanes")
-        if policy:
-            self._check_rows("rollout_policy", out, keys + ("action",), P, T, self.device)
-        else:
-            self._check_rows("rollout", out, keys, P)
-            if P != n:
-                a = self._pad_action_rows(a, T, P)
-            self._rollout_actions = a  # (keeps a padded copy alive until the launch has been enqueued and beyond)
-        io = _lib.StepIO()
-        io.row_pitch = P if P != n else 0
-        io.action, io.action_dtype = a.data_ptr(), dt
-        io.obs, io.reward = _ptr(out["obs"]), _ptr(out["reward"])
-        io.terminated, io.truncated = _ptr(out["terminated"]), _ptr(out["truncated"])
-        io.final_obs = _ptr(out.get("final_obs"))
-        io.branch_sig = _ptr(out.get("branch_sig"))
-        return io
-
     def _out_pitch(self, out: dict) -> int:
         """Lanes per row of a ``[T, N, ...]`` output dict, read off its ``reward`` array (a one-row buffer may carry any
         stride)."""
         r = out["reward"]
         return max(self.n, int(r.stride(0))) if r.dim() == 2 else self.n
 
-    def _check_rows(self, who: str, out: dict, keys, P: int, min_rows: int | None = None, device=None) -> None:
-        """ValueError unless each of ``out[keys]`` that is present is ``[T, N]`` (``[T, N, D]``: obs, final_obs) rows of
-        pitch ``P`` lanes -- with ``T >= min_rows`` and on ``device`` when those are given."""
-        n, D = self.n, self.D
-        for k in keys:
-            t = out.get(k)
-            if t is None:
-                continue
-            tail = (D,) if k in ("obs", "final_obs") else ()
-            want = (P * D, D, 1) if tail else (P, 1)
-            if t.dim() == 0 or t.shape[0] < (min_rows or 0) or tuple(t.shape[1:]) != (n,) + tail or (
-                    device is not None and t.device != device) or any(
-                    sz > 1 and st != w for sz, st, w in zip(t.shape, t.stride(), want)):
-                rows = "T" if min_rows is None else f">= {min_rows}"
-                raise ValueError(f"{who} output '{k}': shape {tuple(t.shape)} / strides {tuple(t.stride())} do not form "
-                                 f"[{rows}, {n}{', ' + str(D) if tail else ''}] rows of one common pitch ({P} lanes)")
-
     def _pad_action_rows(self, a: torch.Tensor, T: int, P: int) -> torch.Tensor:
         key = (T, P, a.dtype)
-        buf = self._act_pad.get(key) if getattr(self, "_act_pad", None) else None
+        buf = self._act_pad.get(key) if self._act_pad else None
         if buf is None:
             self._act_pad = {key: torch.empty((T, P), dtype=a.dtype, device=self.device)}  # (one size kept)
             buf = self._act_pad[key]
@@ -641,8 +679,6 @@ class VecEngine:
         return buf
 
     # ------------------------------------------------------------------ closed loop (carl_amd/policy.py)
-    _policy_rollout = True  # (the classic-control families; BraxVecEngine turns it off)
-
     def alloc_policy_summary(self) -> dict:
         """Per-lane totals of a summary-mode ``rollout_policy``: ``episodes`` / ``length_sum`` int32, ``return_sum``
         float32, ``[N]`` each."""
@@ -678,9 +714,6 @@ class VecEngine:
         a Gaussian of ``policy.log_std``; include/carl_amd.h: carl_rollout_policy_sampled), the draws keyed by
         ``sample_seed`` and by (lane, episode, step in episode).  ``log_prob=True`` (transitions mode) adds
         ``"log_prob"`` ``[T, N]`` float32: each action's log-probability under the policy."""
-        if not self._policy_rollout:
-            raise NotImplementedError(f"{type(self).__name__}: the closed-loop rollout covers the classic-control "
-                                      "families only")
         if policy.family != self.family or policy.obs_dim != self.D:
             raise ValueError(f"the policy was built for family {policy.family}, this engine runs family {self.family}")
         if mode == "summary" and not self.auto_reset:
@@ -759,9 +792,6 @@ class VecEngine:
         context.  No host synchronisation.  ``deterministic=False``: sampled actions, as ``rollout_policy``'s (SB3's
         ``evaluate_policy(..., deterministic=False)``); the records are then those of a sampled transitions launch with
         the same ``sample_seed``."""
-        if not self._policy_rollout:
-            raise NotImplementedError(f"{type(self).__name__}: the closed-loop rollout covers the classic-control "
-                                      "families only")
         if policy.family != self.family or policy.obs_dim != self.D:
             raise ValueError(f"the policy was built for family {policy.family}, this engine runs family {self.family}")
         if not self.auto_reset:
@@ -801,14 +831,3 @@ class VecEngine:
         io = _lib.StepIO()
         io.row_pitch = self._row_pitch()
         return int(self.lib.carl_rollout_variant_io(C.byref(self.b), C.byref(io)))
-
-    def drain_finished(self):
-        """Finished-episode log since the last drain -> (global lane ids, returns, lengths,
-        n_dropped); resets the counter.  Synchronises."""
-        if self.fin_count is None:
-            raise RuntimeError("engine was built with fin_capacity=0")
-        n = int(self.fin_count.item())
-        k = min(n, self.fin_capacity)
-        out = (self.fin_lane[:k].clone(), self.fin_return[:k].clone(), self.fin_length[:k].clone(), n - k)
-        self.fin_count.zero_()
-        return out

@@ -33,7 +33,7 @@ from carl_amd.context.selection import (
     RoundRobinSelector,
 )
 from carl_amd.context.table import ContextTable
-from carl_amd.engine import VecEngine
+from carl_amd.engine import LaneEngine
 from carl_amd.utils.types import Context, Contexts
 
 
@@ -80,7 +80,7 @@ class CARLEnv(abc.ABC):
 
     def __init__(
         self,
-        env: VecEngine | None = None,
+        env: LaneEngine | None = None,
         contexts: Contexts | None = None,
         obs_context_features: list[str] | None = None,
         obs_context_as_dict: bool = True,

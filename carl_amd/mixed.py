@@ -35,13 +35,14 @@ from typing import Sequence
 import torch
 
 from carl_amd import _lib
-from carl_amd.engine import VecEngine
+from carl_amd.brax_engine import BraxVecEngine
+from carl_amd.engine import LaneEngine
 
 _SHARED_1D = ("ep_return", "last_return", "last_length", "episodes_done", "reward", "terminated", "truncated", "done")
 
 
 class MixedVecEngine:
-    def __init__(self, parts: Sequence[VecEngine], names: Sequence[str] | None = None):
+    def __init__(self, parts: Sequence[LaneEngine], names: Sequence[str] | None = None):
         if not parts:
             raise ValueError("a mixed batch needs at least one part")
         dev = parts[0].device
@@ -126,7 +127,7 @@ class MixedVecEngine:
     SMALL_BRAX_PART = 8192
 
     def _small_brax_parts(self) -> bool:
-        return len(self.parts) > 1 and all(hasattr(p, "sys") and p.n <= self.SMALL_BRAX_PART for p in self.parts)
+        return len(self.parts) > 1 and all(isinstance(p, BraxVecEngine) and p.n <= self.SMALL_BRAX_PART for p in self.parts)
 
     def rollout_policy(self, *args, **kwargs):
         """Out of scope: run ``VecEngine.rollout_policy`` on each part's engine instead (one launch per family)."""
@@ -206,7 +207,7 @@ class MixedVecEngine:
         enqueued) the prepared parts are launched one after the other on the caller's stream.  Results are bit-identical
         either way.  Returns ``None`` where no pair launch is possible at all: not two classic parts, unequal lengths, or
         no steps (a zero-step pair call succeeds without launching anything)."""
-        if len(self.parts) != 2 or any(hasattr(p, "sys") for p in self.parts):
+        if len(self.parts) != 2 or any(isinstance(p, BraxVecEngine) for p in self.parts):
             self._pair_ok = False
             return None
         T = int(actions[0].shape[0])
@@ -237,7 +238,7 @@ class MixedVecEngine:
 
     def autotune(self, n_steps: int = 2) -> None:
         for p in self.parts:
-            if hasattr(p, "autotune"):
+            if isinstance(p, BraxVecEngine):
                 p.autotune(n_steps=n_steps)
 
     @property

@@ -39,16 +39,16 @@ _ACTIVATIONS = {"identity": _lib.POLICY_IDENTITY, "tanh": _lib.POLICY_TANH, "rel
 
 def _engine_of(env):
     """(VecEngine, CARLEnv or None) of what the caller passes; refuses the out-of-scope engines."""
-    from carl_amd.engine import VecEngine
+    from carl_amd.engine import LaneEngine, VecEngine
 
     carl_env = None
     eng = env
-    if not isinstance(env, VecEngine) and isinstance(getattr(env, "env", None), VecEngine):
+    if not isinstance(env, LaneEngine) and isinstance(getattr(env, "env", None), LaneEngine):
         carl_env, eng = env, env.env
-    if not isinstance(eng, VecEngine):
+    if not isinstance(eng, LaneEngine):
         raise TypeError(f"MLPPolicy: {type(env).__name__} is not a classic-control CARLEnv or VecEngine (MixedVecEngine "
                         "pairs, the gymnasium drop-in and the distributed helpers are out of scope of the closed-loop rollout)")
-    if not getattr(eng, "_policy_rollout", False):
+    if not isinstance(eng, VecEngine):
         raise TypeError(f"MLPPolicy: the closed-loop rollout covers the classic-control families only, not "
                         f"{type(eng).__name__}")
     return eng, carl_env
