@@ -1,8 +1,8 @@
 """Host reference of the sampled closed-loop rollout's rule (include/carl_amd.h: carl_policy_sampling_t), shared by
-test_policy_sampling.py and test_gpu_policy_sampling.py: a vectorised Philox4x32-10 (checked against
-oracle.philox4x32_10), the counter of a lane-step, the categorical rule as an fp32 mirror and in float64, the
+test_policy_sampling.py, test_gpu_policy_sampling.py and the policy toolkit: a vectorised Philox4x32-10 (checked
+against oracle.philox4x32_10), the counter of a lane-step, the categorical rule as an fp32 mirror and in float64, the
 Gaussian z in float64, and both log-probabilities in float64 with the bounds a device's fp32 evaluation must meet
-(test_gpu_policy_sampled_kernels.py derives them)."""
+(policy_checks.check_rule derives them)."""
 import numpy as np
 
 _M = 0xFFFFFFFF

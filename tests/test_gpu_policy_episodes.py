@@ -1,105 +1,19 @@
-"""The episodes mode of the closed-loop rollout (VecEngine.evaluate_policy / carl_evaluate_policy) on the GPU.
-
-Reference: a transitions-mode rollout_policy of T = max_steps steps from the same engine state.  Each lane's first K
-episodes are derived from its transition rows on the host (fp32 return accumulated in step order, length, the
-terminated bit), and the stop step of each lane with them: right after its K-th episode ends, else T.  The recorded
-actions are then replayed per call from the snapshot (the teacher_inputs pattern), reading ctx_idx before every step
-(the context an episode ran in) and keeping each lane's engine state at its own stop step.  evaluate_policy from the
-snapshot must reproduce all of it bit for bit: counts, steps, every record, every sentinel, the engine state.  (The
-observation is a function of the state: equal state bits are equal observations.)"""
+"""The episodes mode of the closed-loop rollout (VecEngine.evaluate_policy / carl_evaluate_policy) on the GPU, bit for bit
+against the first K episodes of a transitions-mode launch from the same engine state (policy_checks.exact_case) over
+step types, selectors and policy shapes; the finished-episode log, weight sets, the full size, refusals, max_steps = 0
+and the env entry point.  (The observation is a function of the state: equal state bits are equal observations.)"""
 import numpy as np
 import pytest
 import torch
 
 from carl_amd import _lib
 from carl_amd.policy import MLPPolicy, episode_stats, flattened_context_rows
-from test_gpu_policy_kernels import STEP_TYPES, make_engine, make_policy
-from test_gpu_policy_rollout import SELECTORS, STATE_KEYS, engine_state, random_policy
+from policy_cases import SELECTORS, STEP_TYPES, host_records, make_engine, make_policy, random_policy
+from policy_checks import assert_same_state, engine_state, exact_case
 
 pytestmark = pytest.mark.gpu
 
 H_SHAPES = {0: ((), "identity"), 32: ((32,), "tanh"), 64: ((64, 33), "relu")}
-
-
-def host_records(snap, out, K, T):
-    """(episodes, stop step, return, length, terminated, (step, lane) of each record) of each lane's first K episodes,
-    from transition rows [>= T, n]"""
-    rew = out["reward"][:T].cpu().numpy()
-    te = out["terminated"][:T].cpu().numpy().astype(bool)
-    done = te | out["truncated"][:T].cpu().numpy().astype(bool)
-    ep_ret = snap["ep_return"].cpu().numpy().astype(np.float32).copy()
-    elapsed = snap["elapsed"].cpu().numpy().astype(np.int64).copy()
-    n = ep_ret.size
-    count, stop = np.zeros(n, np.int64), np.full(n, T, np.int64)
-    ret, length = np.full((K, n), np.nan, np.float32), np.zeros((K, n), np.int32)
-    term, at_step = np.zeros((K, n), np.uint8), np.full((K, n), -1, np.int64)
-    for t in range(T):
-        ep_ret = (ep_ret + rew[t]).astype(np.float32)
-        elapsed += 1
-        idx = np.nonzero(done[t] & (count < K))[0]
-        k = count[idx]
-        ret[k, idx], length[k, idx], term[k, idx], at_step[k, idx] = ep_ret[idx], elapsed[idx], te[t, idx], t
-        count[idx] += 1
-        stop[idx[count[idx] == K]] = t + 1
-        ep_ret = np.where(done[t], np.float32(0), ep_ret)
-        elapsed = np.where(done[t], 0, elapsed)
-    return count, stop, ret, length, term, at_step
-
-
-def replay(eng, snap, actions, stop):
-    """per-call replay of the recorded actions from snap: ctx_idx before every step [T, n], and every lane's engine state
-    at its own stop step"""
-    eng.restore(snap)
-    T = int(actions.shape[0])
-    stop_d = torch.as_tensor(stop, device=eng.device)
-    final = engine_state(eng)
-    ctx = []
-    for t in range(T):
-        ctx.append(eng.ctx_idx.cpu().numpy().copy())
-        eng.step(actions[t].contiguous())
-        m = stop_d == t + 1
-        for k in STATE_KEYS:
-            final[k] = torch.where(m, getattr(eng, k), final[k])
-    torch.cuda.synchronize()
-    return np.stack(ctx) if ctx else np.zeros((0, eng.n), np.int32), final
-
-
-def check_state(a, b, lanes=None):
-    for k in STATE_KEYS:
-        x, y = a[k], b[k]
-        if lanes is not None:
-            x, y = x[..., lanes], y[..., lanes]
-        if x.dtype == torch.float32:
-            x, y = x.view(torch.int32), y.view(torch.int32)
-        assert torch.equal(x, y), k
-
-
-def exact_case(eng, pol, K, T, warm=0, transitions=None, **kw):
-    """evaluate_policy against the transitions-mode reference (module docstring); returns the result.  transitions:
-    (snapshot, rollout_policy output) of a launch already made from that snapshot, instead of a new one; kw: the
-    sampling arguments of both launches (deterministic=False, sample_seed=...)"""
-    if transitions is not None:
-        snap, out = transitions
-    else:
-        if warm:  # lanes mid-episode at the launch: the running episode counts with its full length and return
-            eng.rollout_policy(pol, warm, mode="summary")
-        snap = eng.snapshot()
-        out = eng.rollout_policy(pol, T, **kw)
-    count, stop, ret, length, term, at_step = host_records(snap, out, K, T)
-    ctx_before, want_state = replay(eng, snap, out["action"][:T], stop)
-    cid = np.full((K, eng.n), -1, np.int32)
-    has = at_step >= 0
-    cid[has] = ctx_before[at_step[has], np.nonzero(has)[1]]
-    eng.restore(snap)
-    res = eng.evaluate_policy(pol, K, T, **kw)
-    np.testing.assert_array_equal(res["episodes"].cpu().numpy(), count)
-    np.testing.assert_array_equal(res["steps"].cpu().numpy(), stop)
-    np.testing.assert_array_equal(res["return"].cpu().numpy().view(np.int32), ret.view(np.int32))  # NaN sentinels too
-    np.testing.assert_array_equal(res["length"].cpu().numpy(), length)
-    np.testing.assert_array_equal(res["context_id"].cpu().numpy(), cid)
-    np.testing.assert_array_equal(res["terminated"].cpu().numpy(), term)
-    check_state(want_state, engine_state(eng))
-    return res, count
 
 
 # ---------------------------------------------------------------- 1 + 2. exact records and engine state
@@ -161,7 +75,7 @@ def test_each_lane_runs_its_own_weight_set():
         for k in res:
             assert torch.equal(res[k][..., lanes], one[k][..., lanes]) or (
                 k == "return" and torch.equal(res[k][..., lanes].view(torch.int32), one[k][..., lanes].view(torch.int32))), (s, k)
-        check_state(after, engine_state(eng), lanes)
+        assert_same_state(after, engine_state(eng), lanes=lanes)
 
 
 # ---------------------------------------------------------------- 5. full size
@@ -216,7 +130,7 @@ def test_python_refusals_and_zero_steps():
     assert int(res["episodes"].abs().sum()) == 0 and int(res["steps"].abs().sum()) == 0
     assert bool(torch.isnan(res["return"]).all()) and int(res["length"].abs().sum()) == 0
     assert bool((res["context_id"] == -1).all()) and int(res["terminated"].sum()) == 0
-    check_state(before, engine_state(eng))
+    assert_same_state(before, engine_state(eng))
     eng.auto_reset = False
     with pytest.raises(ValueError, match="auto_reset"):
         eng.evaluate_policy(pol, 1, 10)

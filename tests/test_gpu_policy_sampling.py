@@ -1,5 +1,6 @@
-"""Sampled closed-loop rollout on the device (carl_rollout_policy_sampled / carl_evaluate_policy_sampled) against the
-host reference of its rule (sampling_ref.py, include/carl_amd.h: carl_policy_sampling_t).
+"""Sampled closed-loop rollout on the device (carl_rollout_policy_sampled / carl_evaluate_policy_sampled) by its
+properties, against the host reference of its rule (sampling_ref.py, include/carl_amd.h: carl_policy_sampling_t) and
+torch.distributions -- what test_gpu_policy_sampled_kernels.py's per-instance bounds do not show:
 
 1. the random-word convention bit for bit (zero heads: equal logits make every operation of the categorical rule exact;
    mu = 0, log_std = 0 gives a = z);  2. teacher-forced actions against a float64 sample of oracle.policy_forward's
@@ -14,57 +15,21 @@ import sampling_ref as SR
 from carl_amd import _lib
 from carl_amd.policy import MLPPolicy
 from oracle import oracle as O
-from test_gpu_policy_kernels import assert_same_state, make_engine
-from test_gpu_policy_rollout import engine_state, host_summary
+from policy_cases import SELECTORS, make_engine, n_outputs, words, zero_head_policy
+from policy_checks import assert_replays, assert_same_state, assert_summary_reduces, engine_state, teacher
 
 pytestmark = pytest.mark.gpu
 
-SELECTORS = {"static": _lib.SEL_STATIC, "round_robin": _lib.SEL_ROUND_ROBIN, "random": _lib.SEL_RANDOM}
 SEED = 0x5EED5EED12345
-
-
-def teacher(eng, pol, snap, actions):
-    """per-call replay of the recorded actions from `snap`: the inputs the policy saw [T, n, n_in] and each lane-step's
-    counter fields (episode index e = episode counter - 1, elapsed before the step) [T, n]"""
-    eng.restore(snap)
-    tab = eng.ctx_table.cpu().numpy()
-    xs, es, els = [], [], []
-    for t in range(actions.shape[0]):
-        cidx = eng.ctx_idx.cpu().numpy().astype(np.int64)
-        xs.append(np.concatenate([tab[pol.ctx_rows][:, cidx].T, eng.obs.cpu().numpy()], axis=1).astype(np.float32))
-        es.append(eng.episode.cpu().numpy().astype(np.int64) - 1)
-        els.append(eng.elapsed.cpu().numpy().astype(np.int64))
-        eng.step(actions[t].contiguous())
-    torch.cuda.synchronize()
-    return np.stack(xs), np.stack(es), np.stack(els)
-
-
-def words(eng, e, el, seed=SEED, lanes=None):
-    """the Philox words of lanes `lanes` (default: every lane, in order) at counter fields e, el [T, len(lanes)]: global
-    lane ids from the engine's lane_offset"""
-    T, n = e.shape
-    lanes = np.arange(n) if lanes is None else np.asarray(lanes)
-    return SR.sample_words(seed, np.broadcast_to(lanes, (T, n)), e, el, lane_offset=int(eng.b.lane_offset))
-
-
-def zero_head_policy(eng, head_bias=None, widths=(), log_std=None):
-    """every weight random except the head's, which is zero: the head outputs are its biases whatever the input"""
-    rng = np.random.default_rng(5)
-    n_out = int(eng.info.n_actions) if eng.info.action_is_discrete else 1
-    dims = [len(eng.ctx_obs_rows) + eng.D, *widths, n_out]
-    layers = [(rng.normal(0, 0.3, (o, i)), rng.normal(0, 0.1, o)) for i, o in zip(dims[:-1], dims[1:])]
-    layers[-1] = (np.zeros((n_out, dims[-2])), np.zeros(n_out) if head_bias is None else np.asarray(head_bias))
-    return MLPPolicy.for_env(eng, layers, "tanh", log_std=log_std)
 
 
 def torch_policy(eng, widths, seed, gain=0.5):
     torch.manual_seed(seed)
-    n_out = int(eng.info.n_actions) if eng.info.action_is_discrete else 1
     mods, prev = [], len(eng.ctx_obs_rows) + eng.D
     for w in widths:
         mods += [torch.nn.Linear(prev, w), torch.nn.Tanh()]
         prev = w
-    mods.append(torch.nn.Linear(prev, n_out))
+    mods.append(torch.nn.Linear(prev, n_outputs(eng)))
     seq = torch.nn.Sequential(*mods).double()
     with torch.no_grad():
         for m in seq:
@@ -86,7 +51,7 @@ def test_equal_logits_take_the_documented_words(family, sel):
     done = (out["terminated"] | out["truncated"]).cpu().numpy()
     assert done.any(), "the launch must cross auto-resets"
     _, e, el = teacher(eng, pol, snap, acts)
-    w = words(eng, e, el)
+    w = words(eng, e, el, SEED)
     na = int(eng.info.n_actions)
     want = SR.categorical_equal_logits(SR.u_categorical(w[0]), na)
     np.testing.assert_array_equal(acts.cpu().numpy(), want)
@@ -101,7 +66,7 @@ def test_gaussian_z_follows_the_documented_words():
     out = eng.rollout_policy(pol, T, deterministic=False, sample_seed=SEED, log_prob=True)
     acts = out["action"][:T]
     _, e, el = teacher(eng, pol, snap, acts)
-    w = words(eng, e, el)
+    w = words(eng, e, el, SEED)
     z = SR.z_gaussian64(w[0], w[1])
     a = acts.cpu().numpy().astype(np.float64)
     bound = 2e-6 * np.maximum(1.0, np.abs(z))  # logf / cospif / sqrtf: a few ulp each
@@ -166,19 +131,12 @@ def test_modes_and_launch_splits_agree(family):
     after = engine_state(eng)
     # replay through rollout()
     eng.restore(snap)
-    ref = eng.rollout(out["action"][:T], out=eng.alloc_rollout(T))
-    for k in ("obs", "reward", "terminated", "truncated"):
-        assert torch.equal(out[k][:T], ref[k]), k
-    assert_same_state(after, engine_state(eng))
+    assert_replays(eng, out, T, after)
     # summary = the exact reduction, same state
     eng.restore(snap)
     s = eng.rollout_policy(pol, T, mode="summary", **kw)
-    assert_same_state(after, engine_state(eng))
-    count, ret_sum, len_sum = host_summary(snap, {k: v[:T] for k, v in out.items()}, T)
+    count = assert_summary_reduces(eng, s, snap, out, T, after)
     assert count.sum() > 0
-    np.testing.assert_array_equal(s["episodes"].cpu().numpy(), count)
-    np.testing.assert_array_equal(s["return_sum"].cpu().numpy(), ret_sum)
-    np.testing.assert_array_equal(s["length_sum"].cpu().numpy(), len_sum)
     # four launches of 16 = one of 64 (actions, log-probs, records, state)
     eng.restore(snap)
     parts = [eng.rollout_policy(pol, T // 4, log_prob=True, **kw) for _ in range(4)]

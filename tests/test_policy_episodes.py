@@ -10,7 +10,7 @@ import torch
 
 from carl_amd import _lib
 from carl_amd.policy import episode_stats
-from test_policy_pack import HEADER, _batch, _policy
+from policy_cases import HEADER, c_batch, c_policy
 
 
 def test_episodes_struct_layout_matches_c(tmp_path):
@@ -59,7 +59,7 @@ def _call(b, p, K=3, T=100, out="default"):
 ])
 def test_c_entry_point_validates_batch_and_policy(case, batch_kw, pol_kw, msg):
     """the checks and messages of carl_rollout_policy, under this entry point's name"""
-    b, p = _batch(flags=_lib.FLAG_AUTORESET, **batch_kw), _policy(**pol_kw)
+    b, p = c_batch(flags=_lib.FLAG_AUTORESET, **batch_kw), c_policy(**pol_kw)
     assert _call(b, p) == _lib.ERR_INVALID_ARGUMENT, case
     err = _lib.load().carl_last_error()
     assert msg in err and err.startswith(b"carl_evaluate_policy"), (case, err)
@@ -67,27 +67,27 @@ def test_c_entry_point_validates_batch_and_policy(case, batch_kw, pol_kw, msg):
 
 @pytest.mark.parametrize("field", ["episodes", "steps", "ret", "length", "context_id", "terminated"])
 def test_c_entry_point_needs_every_output_array(field):
-    b, p = _batch(flags=_lib.FLAG_AUTORESET), _policy()
+    b, p = c_batch(flags=_lib.FLAG_AUTORESET), c_policy()
     assert _call(b, p, out=_eps(**{field: None})) == _lib.ERR_INVALID_ARGUMENT
     assert b"six" in _lib.load().carl_last_error()
 
 
 def test_c_entry_point_refuses_bad_counts_and_no_auto_reset():
     lib = _lib.load()
-    b, p = _batch(flags=_lib.FLAG_AUTORESET), _policy()
+    b, p = c_batch(flags=_lib.FLAG_AUTORESET), c_policy()
     assert lib.carl_evaluate_policy(None, C.byref(p), 1, 1, C.byref(_eps()), None) == _lib.ERR_INVALID_ARGUMENT
     assert lib.carl_evaluate_policy(C.byref(b), None, 1, 1, C.byref(_eps()), None) == _lib.ERR_INVALID_ARGUMENT
     assert _call(b, p, out=None) == _lib.ERR_INVALID_ARGUMENT
     assert _call(b, p, K=0) == _lib.ERR_INVALID_ARGUMENT and b"n_episodes 0" in lib.carl_last_error()
     assert _call(b, p, K=-2) == _lib.ERR_INVALID_ARGUMENT
     assert _call(b, p, T=-1) == _lib.ERR_INVALID_ARGUMENT and b"max_steps -1" in lib.carl_last_error()
-    big = _batch(n=1 << 20, flags=_lib.FLAG_AUTORESET)
-    assert _call(big, _policy(lanes_per_set=1 << 20), K=2048) == _lib.ERR_INVALID_ARGUMENT  # 2^31 records
+    big = c_batch(n=1 << 20, flags=_lib.FLAG_AUTORESET)
+    assert _call(big, c_policy(lanes_per_set=1 << 20), K=2048) == _lib.ERR_INVALID_ARGUMENT  # 2^31 records
     assert b"2^31" in lib.carl_last_error()
-    assert _call(_batch(), p) == _lib.ERR_UNSUPPORTED  # no CARL_FLAG_AUTORESET
+    assert _call(c_batch(), p) == _lib.ERR_UNSUPPORTED  # no CARL_FLAG_AUTORESET
     assert b"CARL_FLAG_AUTORESET" in lib.carl_last_error()
     # n_lanes == 0: valid, nothing to do, nothing enqueued
-    assert _call(_batch(n=0, flags=_lib.FLAG_AUTORESET), p) == 0
+    assert _call(c_batch(n=0, flags=_lib.FLAG_AUTORESET), p) == 0
 
 
 def test_out_of_scope_engines_refuse():

@@ -2,7 +2,6 @@
 carl_rollout_policy's validation and of the Python constructors, and the ctypes layout of carl_policy_t.
 CPU-only: nothing here launches a kernel (the C entry point refuses before it would enqueue anything)."""
 import ctypes as C
-import os
 import subprocess
 
 import numpy as np
@@ -10,23 +9,11 @@ import pytest
 import torch
 
 from carl_amd import _lib
-from carl_amd.engine import VecEngine
 from carl_amd.envs import CARLCartPole
 from carl_amd.policy import MLPPolicy
+from policy_cases import HEADER, c_batch, fake_engine, c_policy, rand_layers
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-HEADER = os.path.join(ROOT, "include", "carl_amd.h")
 CP_NAMES = list(CARLCartPole.get_context_features())  # table order of the CartPole family
-
-
-def fake_engine(family=_lib.CARTPOLE, visible=None):
-    """An engine object with the attributes the policy constructors read, never launched (no GPU here)."""
-    info = _lib.family_info(family)
-    eng = object.__new__(VecEngine)
-    eng.family, eng.D, eng.F, eng.n = family, int(info.obs_dim), int(info.n_features), 1000
-    eng.info = info
-    eng.ctx_obs_rows = list(range(eng.F)) if visible is None else list(visible)
-    return eng
 
 
 class FakeCARLEnv:
@@ -40,11 +27,6 @@ class FakeCARLEnv:
         self.obs_context_as_dict = as_dict
         self.obs_context_features = list(visible_names)
         self.env = fake_engine(_lib.CARTPOLE, [CP_NAMES.index(n) for n in visible_names])
-
-
-def rand_layers(rng, dims):
-    return [(rng.normal(size=(o, i)).astype(np.float32), rng.normal(size=o).astype(np.float32))
-            for i, o in zip(dims[:-1], dims[1:])]
 
 
 def expected_pack(layers, shift, scale, clip):
@@ -147,38 +129,6 @@ def test_python_refusals():
         MLPPolicy.for_env(eng, rand_layers(rng, [5, 2]), context_features=[5])
 
 
-def _batch(family=_lib.CARTPOLE, n=1000, **kw):
-    """A batch whose device pointers are never dereferenced: every call below is refused on the host first.  kw: other
-    batch fields (ctx_obs_feat: a sequence)."""
-    b = _lib.Batch()
-    b.family, b.n_lanes, b.n_contexts, b.ctx_stride = family, n, 4, 4
-    for f in ("state", "elapsed", "ctx_idx", "episode", "n_calls", "ep_return", "ctx_table"):
-        setattr(b, f, 0x1000)
-    for k, v in kw.items():
-        if k == "ctx_obs_feat":
-            for i, f in enumerate(v):
-                b.ctx_obs_feat[i] = f
-        else:
-            setattr(b, k, v)
-    return b
-
-
-def _policy(**kw):
-    p = _lib.Policy()
-    p.n_in, p.n_ctx, p.n_hidden, p.n_out = 6, 2, 2, 2
-    p.ctx_rows[0], p.ctx_rows[1] = 0, 3
-    p.width[0], p.width[1] = 64, 64
-    p.activation, p.head, p.n_sets, p.lanes_per_set, p.params = _lib.POLICY_TANH, _lib.POLICY_HEAD_ARGMAX, 1, 1024, 0x2000
-    for k, v in kw.items():
-        if k == "width":
-            p.width[0], p.width[1] = v
-        elif k == "ctx_rows":
-            p.ctx_rows[0], p.ctx_rows[1] = v
-        else:
-            setattr(p, k, v)
-    return p
-
-
 @pytest.mark.parametrize("case, batch_kw, pol_kw, msg", [
     ("width over the limit", {}, {"width": (65, 64)}, b"hidden width[0] = 65"),
     ("width zero", {}, {"width": (64, 0)}, b"hidden width[1] = 0"),
@@ -201,7 +151,7 @@ def _policy(**kw):
 ])
 def test_c_entry_point_refuses(case, batch_kw, pol_kw, msg):
     lib = _lib.load()
-    b, p = _batch(**batch_kw), _policy(**pol_kw)
+    b, p = c_batch(**batch_kw), c_policy(**pol_kw)
     summ = _lib.PolicySummary(0x3000, 0x3000, 0x3000)
     assert lib.carl_rollout_policy(C.byref(b), C.byref(p), None, 10, C.byref(summ), None) == _lib.ERR_INVALID_ARGUMENT, case
     assert msg in lib.carl_last_error(), (case, lib.carl_last_error())
@@ -209,7 +159,7 @@ def test_c_entry_point_refuses(case, batch_kw, pol_kw, msg):
 
 def test_c_entry_point_refuses_bad_io_and_summary():
     lib = _lib.load()
-    b, p = _batch(), _policy()
+    b, p = c_batch(), c_policy()
     assert lib.carl_rollout_policy(C.byref(b), C.byref(p), None, 10, None, None) == _lib.ERR_INVALID_ARGUMENT
     assert b"summary" in lib.carl_last_error()
     io = _lib.StepIO()
@@ -221,9 +171,9 @@ def test_c_entry_point_refuses_bad_io_and_summary():
     assert lib.carl_rollout_policy(C.byref(b), C.byref(p), C.byref(io), 10, None, None) == _lib.ERR_UNSUPPORTED
     assert lib.carl_rollout_policy(C.byref(b), C.byref(p), None, -1, C.byref(_lib.PolicySummary(1, 1, 1)), None) == -1
     assert lib.carl_policy_lane_quantum() == 256
-    assert lib.carl_policy_set_floats(C.byref(_policy(width=(65, 1)))) == -1
+    assert lib.carl_policy_set_floats(C.byref(c_policy(width=(65, 1)))) == -1
     # 6 -> 64 -> 64 -> 2: 6*64 + 64 + 64*64 + 64 + 64*2 + 2 + 6 + 6 + 1 = 4751 -> 4752
-    assert lib.carl_policy_set_floats(C.byref(_policy())) == 4752
+    assert lib.carl_policy_set_floats(C.byref(c_policy())) == 4752
 
 
 def test_policy_struct_layout_matches_c(tmp_path):

@@ -12,10 +12,7 @@ from carl_amd import _lib
 from carl_amd.engine import VecEngine
 from carl_amd.policy import MLPPolicy
 from oracle import oracle as O
-
-# (n_hidden, widths) of the GPU matrix (tests/test_gpu_policy_kernels.py)
-SHAPES = [()] + [(w,) for w in (1, 4, 31, 32, 33, 64)] + [(64, 64), (33, 7), (5, 64), (32, 32)]
-ACTS = ["identity", "tanh", "relu"]
+from policy_cases import ACTS, HIDDEN_SHAPES, c_batch, forward64
 
 
 def _libm_fmaf():
@@ -91,18 +88,8 @@ def _policy(rng, family, widths, act, n_ctx, weight_scale=1.0, clip=None):
                      input_scale=rng.uniform(0.2, 3.0, dims[0]), input_clip=clip)
 
 
-def _numpy64(pol, x, params=None):
-    """float64 forward pass from the policy's own layer arrays (not from the packed block)"""
-    h = np.clip((x.astype(np.float64) - pol.shift) * pol.scale.astype(np.float64), -float(pol.clip), float(pol.clip))
-    for k, (W, b) in enumerate(pol.layers):
-        h = h @ W.astype(np.float64).T + b
-        if k < len(pol.layers) - 1:
-            h = np.tanh(h) if pol.activation == "tanh" else np.maximum(h, 0) if pol.activation == "relu" else h
-    return h
-
-
 # a linear policy has no activation: it is listed once
-CASES = [((), "identity")] + [(w, a) for w in SHAPES[1:] for a in ACTS]
+CASES = [((), "identity")] + [(w, a) for w in HIDDEN_SHAPES for a in ACTS]
 
 
 @pytest.mark.parametrize("widths, act", CASES, ids=["x".join(map(str, w)) + "-" + a if w else "linear" for w, a in CASES])
@@ -115,7 +102,7 @@ def test_fp32_forward_is_within_its_bound_of_float64(widths, act):
         x = rng.normal(size=(2000, pol.n_in)) * rng.choice([0.01, 1.0, 30.0], size=(2000, 1))
         r = O.policy_forward(pol.params, pol.n_in, pol.widths, pol.n_out, act, x)
         x32 = x.astype(np.float32)
-        np.testing.assert_allclose(r.y64, _numpy64(pol, x32), rtol=1e-10, atol=1e-12)
+        np.testing.assert_allclose(r.y64, forward64(pol, x32), rtol=1e-10, atol=1e-12)
         err = np.abs(r.y32.astype(np.float64) - r.y64)
         assert np.all(err <= r.bound + 1e-12 * np.abs(r.y64)), (family, err.max(), r.bound.max())
         assert np.all(np.isfinite(r.bound))
@@ -144,7 +131,7 @@ def test_reads_every_set_of_a_stack_and_the_input_tail():
         r = O.policy_forward(st.params, st.n_in, st.widths, st.n_out, act, x, which)
         for k, p in enumerate(sets):
             m = which == k
-            np.testing.assert_allclose(r.y64[m], _numpy64(p, x[m].astype(np.float32)), rtol=1e-10, atol=1e-12)
+            np.testing.assert_allclose(r.y64[m], forward64(p, x[m].astype(np.float32)), rtol=1e-10, atol=1e-12)
             alone = O.policy_forward(p.params, p.n_in, p.widths, p.n_out, act, x[m])
             np.testing.assert_array_equal(r.y32[m], alone.y32)
         # the sets differ in every part of the block: the same inputs give different outputs under different sets
@@ -173,11 +160,7 @@ def test_clip_shift_scale_and_nan_inputs():
 def test_summary_without_auto_reset_is_refused():
     # C: refused before anything is enqueued (the batch's device pointers are never dereferenced)
     lib = _lib.load()
-    b = _lib.Batch()
-    b.family, b.n_lanes, b.n_contexts, b.ctx_stride = _lib.CARTPOLE, 1000, 4, 4
-    for f in ("state", "elapsed", "ctx_idx", "episode", "n_calls", "ep_return", "ctx_table"):
-        setattr(b, f, 0x1000)
-    b.flags = 0
+    b = c_batch(flags=0)
     pol = _policy(np.random.default_rng(0), _lib.CARTPOLE, (8,), "tanh", 2)
     p = pol.struct(1000, 0x2000)
     summ = _lib.PolicySummary(0x3000, 0x3000, 0x3000)

@@ -3,7 +3,6 @@ carl_rollout_policy_sampled / carl_evaluate_policy_sampled and of the Python lay
 stack(), and the host reference of the sampling rule (sampling_ref.py) against oracle.philox4x32_10 and
 torch.distributions.  CPU-only: nothing here launches a kernel (the C entry points refuse before they would enqueue)."""
 import ctypes as C
-import os
 import subprocess
 
 import numpy as np
@@ -14,7 +13,7 @@ import sampling_ref as SR
 from carl_amd import _lib
 from carl_amd.policy import MLPPolicy
 from oracle import oracle as O
-from test_policy_pack import HEADER, _batch, _policy, fake_engine, rand_layers
+from policy_cases import HEADER, c_batch, fake_engine, c_policy, rand_layers
 
 
 def test_sampling_struct_layout_matches_c(tmp_path):
@@ -52,30 +51,30 @@ def test_sampled_entry_points_refuse_what_their_twins_refuse():
     lib = _lib.load()
     smp = _lib.PolicySampling(1, None, None)
     summ = _lib.PolicySummary(0x3000, 0x3000, 0x3000)
-    b, p = _flags(_batch()), _policy(width=(65, 64))
+    b, p = _flags(c_batch()), c_policy(width=(65, 64))
     assert lib.carl_rollout_policy_sampled(C.byref(b), C.byref(p), C.byref(smp), None, 10, C.byref(summ), None) == -1
     assert b"carl_rollout_policy_sampled: hidden width[0] = 65" in lib.carl_last_error()
     assert lib.carl_evaluate_policy_sampled(C.byref(b), C.byref(p), C.byref(smp), 2, 10, C.byref(_episodes()), None) == -1
     assert b"carl_evaluate_policy_sampled: hidden width[0] = 65" in lib.carl_last_error()
     # the batch checks (Brax family), io layout, summary without auto-reset
-    bb = _batch(family=_lib.CARL_N_FAMILIES)
-    assert lib.carl_rollout_policy_sampled(C.byref(bb), C.byref(_policy()), C.byref(smp), None, 10, C.byref(summ),
+    bb = c_batch(family=_lib.CARL_N_FAMILIES)
+    assert lib.carl_rollout_policy_sampled(C.byref(bb), C.byref(c_policy()), C.byref(smp), None, 10, C.byref(summ),
                                            None) == -1
     assert b"Brax family" in lib.carl_last_error()
     io = _io()
     io.row_pitch = 1004
-    assert lib.carl_rollout_policy_sampled(C.byref(b), C.byref(_policy()), C.byref(smp), C.byref(io), 10, None,
+    assert lib.carl_rollout_policy_sampled(C.byref(b), C.byref(c_policy()), C.byref(smp), C.byref(io), 10, None,
                                            None) == _lib.ERR_UNSUPPORTED
-    assert lib.carl_rollout_policy_sampled(C.byref(_batch()), C.byref(_policy()), C.byref(smp), None, 10, C.byref(summ),
+    assert lib.carl_rollout_policy_sampled(C.byref(c_batch()), C.byref(c_policy()), C.byref(smp), None, 10, C.byref(summ),
                                            None) == _lib.ERR_UNSUPPORTED
-    assert lib.carl_evaluate_policy_sampled(C.byref(b), C.byref(_policy()), C.byref(smp), 0, 10, C.byref(_episodes()),
+    assert lib.carl_evaluate_policy_sampled(C.byref(b), C.byref(c_policy()), C.byref(smp), 0, 10, C.byref(_episodes()),
                                             None) == -1
     assert b"n_episodes 0 < 1" in lib.carl_last_error()
 
 
 def test_sampled_entry_points_refuse_bad_sampling():
     lib = _lib.load()
-    b, p = _flags(_batch()), _policy()
+    b, p = _flags(c_batch()), c_policy()
     summ = _lib.PolicySummary(0x3000, 0x3000, 0x3000)
     for fn, args in ((lib.carl_rollout_policy_sampled, lambda s: (C.byref(b), C.byref(p), s, None, 10, C.byref(summ), None)),
                      (lib.carl_evaluate_policy_sampled, lambda s: (C.byref(b), C.byref(p), s, 2, 10, C.byref(_episodes()),
@@ -85,8 +84,8 @@ def test_sampled_entry_points_refuse_bad_sampling():
         assert fn(*args(C.byref(_lib.PolicySampling(1, None, 0x4000)))) == _lib.ERR_INVALID_ARGUMENT  # summary / episodes
         assert b"log_prob" in lib.carl_last_error()
     # a Box family without log_std
-    bp = _flags(_batch(family=_lib.PENDULUM))
-    pp = _policy(n_in=5, n_out=1, head=_lib.POLICY_HEAD_BOX)
+    bp = _flags(c_batch(family=_lib.PENDULUM))
+    pp = c_policy(n_in=5, n_out=1, head=_lib.POLICY_HEAD_BOX)
     assert lib.carl_rollout_policy_sampled(C.byref(bp), C.byref(pp), C.byref(_lib.PolicySampling(1, None, None)), None, 10,
                                            C.byref(summ), None) == _lib.ERR_INVALID_ARGUMENT
     assert b"log_std" in lib.carl_last_error()
