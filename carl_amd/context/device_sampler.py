@@ -41,9 +41,11 @@ def _bound(v: float) -> float:
     return max(-_F32_MAX, min(_F32_MAX, v))
 
 
-def feature_spec(feature: ContextFeature, sampled: bool) -> _lib.FeatureSpec:
+def feature_spec(feature: ContextFeature, sampled: bool, membership: bool = False) -> _lib.FeatureSpec:
     """One ``carl_feature_spec_t``: the feature's distribution if ``sampled``, else its default as a
-    constant; bounds are always carried (verification)."""
+    constant; bounds are always carried (verification).  ``membership``: a categorical feature's spec for
+    ``carl_verify_contexts`` -- kind CATEGORICAL so that values are held against the choices, drawn from never, so what
+    only the sampler cannot do (weights) is no refusal."""
     sp = _lib.FeatureSpec()
     if isinstance(feature, CategoricalContextFeature):
         try:
@@ -60,7 +62,7 @@ def feature_spec(feature: ContextFeature, sampled: bool) -> _lib.FeatureSpec:
         sp.lower, sp.upper = min(choices), max(choices)
         sp.value = float(feature.default_value)
         # a constant categorical keeps kind CATEGORICAL only for verification: mark via n_choices
-        sp.kind = _lib.FEAT_CATEGORICAL if sampled else _lib.FEAT_CONSTANT
+        sp.kind = _lib.FEAT_CATEGORICAL if sampled or membership else _lib.FEAT_CONSTANT
         return sp
     sp.lower, sp.upper = _bound(feature.lower), _bound(feature.upper)
     sp.value = float(feature.default_value)
@@ -91,6 +93,15 @@ def build_specs(context_space: ContextSpace, distributions: Sequence[ContextFeat
     specs = (_lib.FeatureSpec * len(names))()
     for j, n in enumerate(names):
         specs[j] = feature_spec(dist[n], True) if n in dist else feature_spec(context_space.context_space[n], False)
+    return names, specs
+
+
+def verify_specs(context_space: ContextSpace):
+    """Specs ``carl_verify_contexts`` holds a table against: every feature's bounds, a categorical's choices."""
+    names = list(context_space.context_feature_names)
+    specs = (_lib.FeatureSpec * len(names))()
+    for j, n in enumerate(names):
+        specs[j] = feature_spec(context_space.context_space[n], False, membership=True)
     return names, specs
 
 
@@ -147,13 +158,9 @@ def verify_table_device(context_space: ContextSpace, table: DeviceContextTable) 
     import torch
 
     lib = _lib.load()
-    names = list(context_space.context_feature_names)
+    names, specs = verify_specs(context_space)
     if list(table.names) != names:
         raise ValueError("table feature order differs from the context space")
-    specs = (_lib.FeatureSpec * len(names))()
-    for j, n in enumerate(names):
-        f = context_space.context_space[n]
-        specs[j] = feature_spec(f, isinstance(f, CategoricalContextFeature))  # categorical: check membership
     t = table.tensor
     specs_dev = _upload_specs(specs, t.device)
     n_bad = torch.zeros(1, dtype=torch.int32, device=t.device)

@@ -5,6 +5,7 @@
 // (device, kernel), guarded by a mutex: it only saves a ~2 us driver call per launch).
 #include <hip/hip_runtime.h>
 
+#include <cmath>
 #include <cstdarg>
 #include <cstdio>
 #include <cstdlib>
@@ -432,6 +433,12 @@ int validate_specs(const carl_feature_spec_t* sd, const carl_feature_spec_t* sh,
     if ((s.kind == CARL_FEAT_UNIFORM_FLOAT || s.kind == CARL_FEAT_UNIFORM_INT) &&
         !(s.lower > -3.0e38f && s.upper < 3.0e38f))
       return fail(CARL_ERR_INVALID_ARGUMENT, "%s: feature %d: a uniform distribution needs finite bounds", who, f);
+    if (s.kind == CARL_FEAT_UNIFORM_FLOAT || s.kind == CARL_FEAT_UNIFORM_INT) {
+      const float span = s.upper - s.lower;  // the kernel's float32 span: finite bounds can still overflow it
+      if (!std::isfinite(span))
+        return fail(CARL_ERR_INVALID_ARGUMENT, "%s: feature %d: upper - lower = %g - %g overflows float32", who, f,
+                    s.upper, s.lower);
+    }
     if (s.kind == CARL_FEAT_UNIFORM_FLOAT && s.log_scale && !(s.lower > 0.0f))
       return fail(CARL_ERR_INVALID_ARGUMENT, "%s: feature %d: log-uniform needs lower > 0", who, f);
     if (s.kind == CARL_FEAT_NORMAL_FLOAT && !(s.sigma >= 0.0f))

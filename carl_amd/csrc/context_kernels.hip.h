@@ -22,7 +22,9 @@ __device__ __forceinline__ float sample_feature(const carl_feature_spec_t& sp, u
   if (sp.kind == CARL_FEAT_UNIFORM_FLOAT) {
     if (sp.log_scale) {
       const float lo = logf(sp.lower), hi = logf(sp.upper);
-      return expf(__fmaf_rn(hi - lo, u, lo));
+      // expf(logf(x)) need not round back to x: clamp, like the host sampler clips, so a table verifies against
+      // its own bounds; an in-range draw keeps its bits
+      return fminf(fmaxf(expf(__fmaf_rn(hi - lo, u, lo)), sp.lower), sp.upper);
     }
     return __fmaf_rn(sp.upper - sp.lower, u, sp.lower);
   }

@@ -226,23 +226,67 @@ class Engine:
 
 
 # ---- device context sampler restatement (oracle/context_sampler.c) -------------------------
-def sample_contexts(specs, n_contexts: int, seed: int, context_offset: int = 0) -> np.ndarray:
-    """[F][C] float32 table from an array of carl_amd._lib.FeatureSpec (ctypes array)."""
+def sample_contexts(specs, n_contexts: int, seed: int, context_offset: int = 0, ctx_stride: int | None = None,
+                    out: np.ndarray | None = None) -> np.ndarray:
+    """[F][C] float32 table from an array of carl_amd._lib.FeatureSpec (ctypes array).  With ``ctx_stride`` the rows
+    are ``ctx_stride`` floats apart ([F][ctx_stride] is returned; ``out`` supplies the padding's contents)."""
     n_features = len(specs)
-    out = np.empty((n_features, n_contexts), dtype=np.float32)
+    stride = n_contexts if ctx_stride is None else int(ctx_stride)
+    assert stride >= n_contexts
+    if out is None:
+        out = np.empty((n_features, stride), dtype=np.float32)
+    assert out.shape == (n_features, stride) and out.dtype == np.float32 and out.flags.c_contiguous
     fn = lib().oracle_sample_contexts
     fn.restype = None
     fn.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int64, C.c_uint64, C.c_void_p]
-    fn(C.addressof(specs), n_features, n_contexts, n_contexts, context_offset, seed & (2**64 - 1), _p(out))
+    fn(C.addressof(specs), n_features, n_contexts, stride, context_offset, seed & (2**64 - 1), _p(out))
     return out
 
 
-def verify_contexts(specs, table: np.ndarray) -> int:
+def verify_contexts(specs, table: np.ndarray, n_contexts: int | None = None) -> int:
+    """Entries outside their feature's bounds / choices among the first ``n_contexts`` (default: all) columns of the
+    [F][ctx_stride] table."""
     table = np.ascontiguousarray(table, dtype=np.float32)
+    n = table.shape[1] if n_contexts is None else int(n_contexts)
+    assert 0 <= n <= table.shape[1]
     fn = lib().oracle_verify_contexts
     fn.restype = C.c_int
     fn.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p]
-    return int(fn(C.addressof(specs), table.shape[0], table.shape[1], table.shape[1], _p(table)))
+    return int(fn(C.addressof(specs), table.shape[0], n, table.shape[1], _p(table)))
+
+
+def scan_u(seed: int, feature: int, start: int, count: int, cap: int = 4):
+    """Context ids in [start, start + count) whose first draw for ``feature`` is u = 0 / u = 1 - 2^-24, and the id
+    with the largest draw: (ids_zero, ids_top, (best_id, best_24_bit_draw))."""
+    zero, top = np.zeros(cap, np.uint64), np.zeros(cap, np.uint64)
+    found, best = np.zeros(2, np.int32), np.zeros(2, np.uint64)
+    fn = lib().oracle_scan_u
+    fn.restype = None
+    fn.argtypes = [C.c_uint64, C.c_uint32, C.c_uint64, C.c_uint64, C.c_int] + [C.c_void_p] * 4
+    fn(seed & (2**64 - 1), feature, start, count, cap, _p(zero), _p(top), _p(found), _p(best))
+    return ([int(v) for v in zero[: found[0]]], [int(v) for v in top[: found[1]]], (int(best[0]), int(best[1])))
+
+
+@dataclass
+class NormalTrace:
+    u1: np.ndarray        # [C, 32] float32
+    u2: np.ndarray        # [C, 32] float32
+    z: np.ndarray         # [C, 32] float64 standard-normal draw of each attempt
+    candidate: np.ndarray  # [C, 32] float64 mu + sigma z, before the rounding to float32
+    accepted: np.ndarray  # [C] int32 attempt taken; 32 = every attempt failed (last candidate, clipped)
+
+
+def normal_trace(spec, seed: int, context_offset: int, n_contexts: int, feature: int) -> NormalTrace:
+    """The 32 attempts of one NORMAL_FLOAT ``spec`` (a carl_amd._lib.FeatureSpec) at table row ``feature``."""
+    shape = (n_contexts, 32)
+    t = NormalTrace(np.empty(shape, np.float32), np.empty(shape, np.float32), np.empty(shape, np.float64),
+                    np.empty(shape, np.float64), np.empty(n_contexts, np.int32))
+    fn = lib().oracle_normal_trace
+    fn.restype = None
+    fn.argtypes = [C.c_void_p, C.c_uint64, C.c_int64, C.c_int, C.c_uint32] + [C.c_void_p] * 5
+    fn(C.addressof(spec), seed & (2**64 - 1), context_offset, n_contexts, feature, _p(t.u1), _p(t.u2), _p(t.z),
+       _p(t.candidate), _p(t.accepted))
+    return t
 
 
 # ---- closed-loop policy restatement (oracle/carl_oracle.c: oracle_policy_forward) ----------------------------------

@@ -199,6 +199,13 @@ def test_brax_and_sampler_entry_points_validate_arguments():
     spec[0].kind, spec[0].lower, spec[0].upper = _lib.FEAT_UNIFORM_FLOAT, 2.0, 1.0
     assert lib.carl_sample_contexts(C.addressof(spec), spec, 1, 4, 4, 0, 0, 1, None) == -1
     assert b"lower" in lib.carl_last_error()
+    # each bound finite and inside the +-3e38 limit, their float32 difference is not: every draw would be inf or NaN
+    spec[0].lower, spec[0].upper = -2e38, 2e38
+    assert lib.carl_sample_contexts(C.addressof(spec), spec, 1, 4, 4, 0, 0, 1, None) == _lib.ERR_INVALID_ARGUMENT
+    assert b"overflows float32" in lib.carl_last_error()
+    spec[0].kind = _lib.FEAT_UNIFORM_INT
+    assert lib.carl_verify_contexts(C.addressof(spec), spec, 1, 4, 4, 1, 1, None) == _lib.ERR_INVALID_ARGUMENT
+    assert b"overflows float32" in lib.carl_last_error()
 
 
 def test_first_state_flag_needs_its_buffer():

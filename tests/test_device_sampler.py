@@ -11,32 +11,10 @@ import numpy as np
 import pytest
 
 from carl_amd import _lib
-from carl_amd.context.context_space import (
-    CategoricalContextFeature,
-    ContextSpace,
-    NormalFloatContextFeature,
-    UniformFloatContextFeature,
-    UniformIntegerContextFeature,
-)
-from carl_amd.context.device_sampler import build_specs
+from carl_amd.context.context_space import CategoricalContextFeature, ContextSpace, UniformFloatContextFeature
+from carl_amd.context.device_sampler import build_specs, verify_specs
+from context_kernel_cases import DISTS, SPACE
 from oracle import oracle as O
-
-SPACE = ContextSpace({
-    "gravity": UniformFloatContextFeature("gravity", lower=0.1, upper=np.inf, default_value=9.8),
-    "length": UniformFloatContextFeature("length", lower=0.05, upper=5.0, default_value=0.5),
-    "mass": UniformFloatContextFeature("mass", lower=1e-3, upper=10.0, default_value=1.0),
-    "n_legs": UniformIntegerContextFeature("n_legs", lower=1, upper=8, default_value=4),
-    "direction": CategoricalContextFeature("direction", choices=[1, 3, 2, 4, 12, 32], default_value=1),
-    "noise": UniformFloatContextFeature("noise", lower=-np.inf, upper=np.inf, default_value=0.0),
-})
-DISTS = [
-    UniformFloatContextFeature("gravity", 5, 15),
-    NormalFloatContextFeature("length", mu=0.5, sigma=0.4, lower=0.05, upper=5.0),
-    UniformFloatContextFeature("mass", 0.01, 10.0, log=True),
-    UniformIntegerContextFeature("n_legs", 2, 6),
-    CategoricalContextFeature("direction", choices=[1, 3, 2, 4, 12, 32]),
-]
-
 
 def test_feature_spec_layout_matches_c(tmp_path):
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -110,3 +88,18 @@ def test_verify_counts_out_of_bounds_entries():
     t[4, 7] = 5.0        # not a direction code
     t[3, 0] = np.nan
     assert O.verify_contexts(specs, t) == 4
+
+
+def test_verify_specs_check_a_weighted_categorical_by_membership():
+    """Sampling a weighted categorical on the device is refused (host only); verifying a table against a context
+    space that holds one only asks whether each value is a choice."""
+    weighted = CategoricalContextFeature("direction", choices=[1, 3, 2], weights=[0.7, 0.2, 0.1], default_value=1)
+    space = ContextSpace({"gravity": UniformFloatContextFeature("gravity", lower=0.1, upper=np.inf, default_value=9.8),
+                          "direction": weighted})
+    with pytest.raises(ValueError, match="host only"):
+        build_specs(space, [weighted])
+    names, specs = verify_specs(space)
+    assert names == ["gravity", "direction"]
+    assert specs[0].kind == _lib.FEAT_CONSTANT and specs[1].kind == _lib.FEAT_CATEGORICAL and specs[1].n_choices == 3
+    table = np.array([[9.8, 0.05, 3.0], [3.0, 2.0, 2.5]], np.float32)  # gravity 0.05 below its bound, 2.5 no choice
+    assert O.verify_contexts(specs, table) == 2

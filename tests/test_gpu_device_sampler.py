@@ -10,8 +10,8 @@ from carl_amd.context.device_sampler import build_specs, sample_context_table_de
 from carl_amd.context.sampler import ContextSampler
 from carl_amd.context.selection import StaticSelector
 from carl_amd.context.table import ContextTable
+from context_kernel_cases import DISTS, SPACE
 from oracle import oracle as O
-from test_device_sampler import DISTS, SPACE
 
 pytestmark = pytest.mark.gpu
 
