@@ -78,6 +78,14 @@ def _refuse_ablation(extra_flags: list[str] | None) -> None:
 
 def build(force: bool = False, verbose: bool = False, extra_flags: list[str] | None = None) -> str:
     _refuse_ablation(extra_flags)
+    path = _build_product(force, verbose, extra_flags)
+    if not extra_flags:  # (an experiment's flags are the product's alone)
+        # the test library follows the headers and its own source: rebuilt by content hash whether or not the product was
+        build_probe(force=force, verbose=verbose)
+    return path
+
+
+def _build_product(force: bool, verbose: bool, extra_flags: list[str] | None) -> str:
     if not force and not needs_build(extra_flags):
         return LIB_PATH
     import fcntl
@@ -116,6 +124,58 @@ def _build_locked(verbose: bool, extra_flags: list[str] | None) -> str:
     with open(HASH_PATH, "w") as f:
         f.write(_source_hash(extra_flags) + "\n")
     return LIB_PATH
+
+
+# ---- the math probe: a TEST library (tests/probe/math_probe.hip: one trivial kernel per device math primitive of
+# fast_math.hip.h / classic_control.hip.h / brax_kernels.hip.h, for tests/test_gpu_math_primitives.py).  A shared object
+# of its own beside the product's, same common flags, same content-hash staleness rule; NOT in SOURCES, never linked
+# into libcarl_amd.so.  One translation unit, compiled and linked in one hipcc call (no object file is kept).
+PROBE_SRC = os.path.join(os.path.dirname(_HERE), "tests", "probe", "math_probe.hip")
+PROBE_LIB_PATH = os.path.join(LIB_DIR, "libcarl_math_probe.so")
+PROBE_HASH_PATH = os.path.join(LIB_DIR, "math_probe.sha256")
+PROBE_FLAGS = ["-fno-slp-vectorize"]
+
+
+def _probe_hash() -> str:
+    import hashlib
+
+    h = hashlib.sha256(_source_hash().encode())
+    with open(PROBE_SRC, "rb") as f:
+        h.update(f.read())
+    h.update(repr(PROBE_FLAGS).encode())
+    return h.hexdigest()
+
+
+def probe_needs_build() -> bool:
+    if not os.path.exists(PROBE_LIB_PATH) or not os.path.exists(PROBE_HASH_PATH):
+        return True
+    with open(PROBE_HASH_PATH) as f:
+        return f.read().strip() != _probe_hash()
+
+
+def build_probe(force: bool = False, verbose: bool = False) -> str | None:
+    """libcarl_math_probe.so; None where the tree has no tests/ (an installed package)."""
+    if not os.path.exists(PROBE_SRC):
+        return None
+    if not force and not probe_needs_build():
+        return PROBE_LIB_PATH
+    import fcntl
+
+    os.makedirs(LIB_DIR, exist_ok=True)
+    with open(os.path.join(LIB_DIR, ".probe.lock"), "w") as lock:
+        fcntl.flock(lock, fcntl.LOCK_EX)
+        if not force and not probe_needs_build():
+            return PROBE_LIB_PATH
+        tmp = PROBE_LIB_PATH + f".tmp{os.getpid()}"
+        cmd = [_hipcc(), f"--offload-arch={ARCH}", "-O3", "-std=c++17", "-fPIC", "-fno-gpu-rdc", "-Wall",
+               "-Wno-unused-function", *PROBE_FLAGS, "-shared", f"-I{CSRC}", PROBE_SRC, "-o", tmp]
+        if verbose:
+            print(" ".join(cmd), flush=True)
+        subprocess.run(cmd, check=True)
+        os.replace(tmp, PROBE_LIB_PATH)
+        with open(PROBE_HASH_PATH, "w") as f:
+            f.write(_probe_hash() + "\n")
+    return PROBE_LIB_PATH
 
 
 if __name__ == "__main__":

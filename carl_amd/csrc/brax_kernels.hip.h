@@ -240,8 +240,8 @@ __device__ __forceinline__ BodyT<float> narrow_body(const Body& b) { return Body
 __device__ __forceinline__ Body widen_body(const BodyT<float>& b) { return Body{tod(b.p), tod(b.r), b.v, b.w}; }
 __device__ __forceinline__ Body widen_body(const Body& b) { return b; }
 
-// atan2 in float64 to ~3e-13 (one octant reduction, one division, degree-7 polynomial in t^2 on
-// [0, tan^2(pi/8)], Chebyshev-node fit): a joint angle is multiplied by the limit / joint / locking stiffness
+// atan2 in float64 to 2.7e-13, restated on the host and on the device alike (tests/math_primitive_cases.py): one octant
+// reduction, one division, degree-7 polynomial in t^2 on [0, tan^2(pi/8)], Chebyshev-node fit.  A joint angle is multiplied by the limit / joint / locking stiffness
 // (k dt / I up to 30 per substep), so the 2.8e-7 of atan2_fast would reach the velocities at 1e-5 within one env
 // step.  ~36 instructions.  XPOS: the caller guarantees x >= 0 (a hinge's half angle: the relative rotation's scalar
 // part after the sign flip) -- the quadrant fix-up for x < 0 is compiled out.
@@ -264,11 +264,12 @@ __device__ __forceinline__ double atan2_f64(double y, double x) {
   p = fma(z, p, 9.99999999999244826e-01);
   double r = fma(t, p, mid ? 0.78539816339744831 : 0.0);
   r = (ay > ax) ? 1.5707963267948966 - r : r;
-  if (!XPOS) r = (x < 0.0) ? 3.1415926535897932 - r : r;
+  if (!XPOS) r = (__double2hiint(x) < 0) ? 3.1415926535897932 - r : r;  // (x's sign bit: atan2(+-0, -0) = +-pi, see atan2_fast)
   return copysign(r, y);
 }
-// sqrt(x), 0 <= x <= 1, to ~2e-16 relative: v_rsq_f32 seed (1 ulp of float32) and two coupled Newton steps -- the library
-// sqrt is v_rsq_f64 (a sixteen-cycle instruction) plus scaling and a correctly rounded finish the angle does not need.
+// sqrt(x), 1e-30 < x <= 1, to 1.1e-16 relative, restated on the host and on the device alike; exactly 0 at and below
+// 1e-30.  v_rsq_f32 seed (1 ulp of float32) and two coupled Newton steps -- the library sqrt is v_rsq_f64 (a
+// sixteen-cycle instruction) plus scaling and a correctly rounded finish the angle does not need.
 __device__ __forceinline__ double sqrt01_f64(double x) {
   const double y = (double)__builtin_amdgcn_rsqf((float)x);
   double g = x * y, h = 0.5 * y;

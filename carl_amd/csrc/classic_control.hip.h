@@ -184,14 +184,21 @@ struct Pendulum {
     const float max_speed = 8.0f, max_torque = 2.0f;
     const float th = s[0], thdot = s[1];
     const float u = fminf(fmaxf(action, -max_torque), max_torque);
-    // angle_normalize(x) = ((x + pi) % (2 pi)) - pi with Python's floor-mod
-    const float two_pi = 2.0f * kPi, inv_two_pi = 1.0f / (2.0f * kPi);
-    const float y = th + kPi;
-    // r may land a rounding error outside [0, 2 pi); the reference's own float64 mod has the
-    // same ambiguity at the seam, and an^2 is continuous there ((-pi - e)^2 vs (pi - e)^2
-    // differ by 4 pi e), so no fix-up is needed for the cost
-    const float r = __fmaf_rn(-floorf(y * inv_two_pi), two_pi, y);
-    const float an = r - kPi;
+    // angle_normalize(x) = ((x + pi) % (2 pi)) - pi; only its square is used, so |an| is enough.  Evaluated as
+    // x - 2 pi rint(x / (2 pi)) with 2 pi split in two floats (4 x the pi / 2 split of fast_math.hip.h): the first fma is
+    // exact (th and turns x hi are multiples of ulp(th) or 2^-21, the difference is below 4), the second rounds once.  The
+    // float product th / (2 pi) carries |th| x 6e-8 turns of error, so near the seam rint() can pick the neighbouring turn
+    // and leave |an| up to that much beyond pi: folded back as 2 pi - |an| (at the seam itself an^2 is continuous, and the
+    // reference's own float64 mod has the same ambiguity there).  |an| is good to 3e-7 for |th| <= 1e6, the range tested
+    // (one fold recovers the angle while the quotient's error stays below half a turn, |th| < 2.6e7; the dynamics stall
+    // near 8e6, where th + omega dt no longer changes a float32 th) -- Pendulum never normalises its state; the earlier `y = th + pi; y - floor(y / 2 pi) 2 pi - pi` rounded y at ulp(th) / 2 and
+    // carried floor() x the error of the float 2 pi: a reward 3.6e-5 off the float64 reference at |th| = 1e3, 5e-2 beyond
+    // 1e5 (tests/test_gpu_parity.py::test_pendulum_reward_at_every_angle_magnitude).  8 instructions for 5.
+    const float inv_two_pi = 1.0f / (2.0f * kPi);
+    const float two_pi_hi = 0x1.921fb6p+2f, two_pi_lo = -0x1.777a5cp-23f;
+    const float turns = rintf(th * inv_two_pi);
+    const float a0 = fabsf(__fmaf_rn(-turns, two_pi_lo, __fmaf_rn(-turns, two_pi_hi, th)));
+    const float an = (a0 > kPi) ? (two_pi_hi - a0) + two_pi_lo : a0;
     // costs = an^2 + 0.1 thdot^2 + 0.001 u^2
     const float costs = __fmaf_rn(an, an, __fmaf_rn(0.1f, thdot * thdot, 0.001f * (u * u)));
     // newthdot = thdot + (3 g / (2 l) sin th + 3 / (m l^2) u) dt
@@ -227,8 +234,9 @@ struct Pendulum {
 // 512-entry table of correctly rounded doubles (8 KiB of LDS, staged once per workgroup from a constant array;
 // generated by tools/gen_sincos_table.py), sin r and cos r need two terms each, and
 //   sin x = S cos r + C sin r,   cos x = C cos r - S sin r
-// -- 13 vector instructions + the table read, no quadrant logic; max error < 1e-13 (tests/test_sincos_table.py: table
-// entries against mpmath, the formula against long-double libm over +-40 rad).  Round 4 shortened the evaluation (magic-number
+// -- 13 vector instructions + the table read, no quadrant logic; max error 7.4e-14 restated / 7.4e-14 on the device over
+// +-40 rad incl. every grid point and half-step tie, 4.2e-13 / 4.2e-13 up to +-1e4 rad (the dropped k lo)
+// (tests/test_sincos_table.py: table entries against mpmath; tests/math_primitive_cases.py, test_gpu_math_primitives.py).  Round 4 shortened the evaluation (magic-number
 // rounding, one-term reduction, sin r without its r^5 term, cos r without its r^4 term: 6e-11) because Acrobot is
 // vector-ALU-bound.  Round 6 took the cosine's r^4 / 24 term BACK (one fma per angle): inside the reference's
 // declared context bounds (link masses / lengths / MOI x 3, MAX_VEL x 3, velocities up to those bounds) a transition

@@ -5,10 +5,12 @@
 // large-argument path inlined twice) dominated that stream.  These versions are
 //   k = rint(x * 2/pi);  r = x - k*(pi/2) with a 3-term Cody-Waite split (fma);
 //   sin r, cos r by degree-9 / degree-8 polynomials on [-pi/4, pi/4];  quadrant fix-up.
-// Measured against libm in extended precision (oracle-side C harness, 4e6 samples per
-// range): max abs error 9.3e-8 (fp32, |x| <= 1e5) and 1.8e-16 (fp64, |x| <= 1e6), i.e.
-// ~1 ulp -- far inside the 1e-5 parity budget.  Beyond those ranges the library
-// functions are used (rare, wave-divergent branch; keeps huge angles correct).
+// Measured against longdouble libm over the cases of tests/math_primitive_cases.py (every float nearest j pi / 4 up to
+// the guard with its neighbours, the guards, sweeps; host restatement / on the device, tests/test_gpu_math_primitives.py):
+// max abs error 9.2e-8 / 9.2e-8 (fp32, |x| <= 1e5: the sine's worst 9.18e-8 at x = 87084.16, the cosine's 9.22e-8 at
+// x = -192.42 -- polynomial and final rounding where the result is near 1, not the reduction) and 1.73e-16 / 1.73e-16
+// (fp64, |x| <= 1e6: the cosine at x = -829857.2), i.e. ~1.5 ulp -- far inside the 1e-5 parity budget.
+// Beyond those ranges the library functions are used (rare, wave-divergent branch; keeps huge angles correct).
 #pragma once
 
 #include <hip/hip_runtime.h>
@@ -132,8 +134,10 @@ __device__ __forceinline__ double sconst(double c) {
   return c;
 }
 
-// 1 / d from v_rcp_f64 and two Newton steps (relative error ~1e-16, not correctly rounded): 5 instructions
-// against the ~12 of the IEEE division sequence (div_scale x2, rcp, 5 fma, div_fmas, div_fixup)
+// 1 / d from v_rcp_f64 and two Newton steps (relative error 1.11e-16 restated / 1.11e-16 on the device over 1e-290 ..
+// 1e290, both signs; not correctly rounded): 5 instructions against the ~12 of the IEEE division sequence (div_scale
+// x2, rcp, 5 fma, div_fmas, div_fixup).  d = +-0 and d = +-inf give NaN, not +-inf / +-0: the seed is +-inf / +-0 and the
+// Newton step's fma(-d, r, 1) is 0 x inf (the same for rcp_fast1; the callers' divisors are finite and non-zero).
 __device__ __forceinline__ double rcp_fast(double d) {
   double r = __builtin_amdgcn_rcp(d);
   double e = fma(-d, r, 1.0);
@@ -218,7 +222,8 @@ __device__ __forceinline__ void sincos2_fast(double xa, double xb, double& sna, 
   csb = ((qb + 1) & 2) ? -c2b : c2b;
 }
 
-// ... and with ONE Newton step: v_rcp_f64 is good to 2^29 ulp (2^-24 relative), one step squares that (~4e-15) -- what
+// ... and with ONE Newton step: v_rcp_f64 is good to 2^29 ulp (2^-24 relative), one step squares that (3.7e-15 restated
+// with the seed at that bound; 2.2e-15 on the device, whose seed is better than its bound) -- what
 // Acrobot's `_dsdt` uses for 1 / det: its result feeds float32 state at a 1e-5 parity bar (131 072 random transitions
 // against the float64 oracle: tests/test_gpu_parity.py::test_random_transitions_100k), two dependent float64 fmas
 // fewer per RK4 stage
@@ -239,8 +244,8 @@ __device__ __attribute__((noinline)) float cos_fast_outlined(float x) { return c
 // the default contexts, so |h| <= 1.8): c = cos h by an even degree-10 polynomial fitted on |h| <= 1.86 (least
 // squares on Chebyshev nodes, coefficients rounded to fp32), then the double-angle identity 2 c^2 - 1 -- no
 // reduction, no sine polynomial, no quadrant logic: 9 vector instructions against the 34 of sincos_fast.  Max abs
-// error against libm's double cos over |2h| <= 3.7 (2e6 samples, the fp32 roundings emulated:
-// tests/test_sincos_table.py): 1.7e-7.  A lane outside the fitted range (contexts that move min_position /
+// error against longdouble libm over |2h| <= 3.7 on a 4e5-point grid and the wide lanes (tests/math_primitive_cases.py):
+// 1.59e-7 restated, 1.59e-7 on the device.  A lane outside the fitted range (contexts that move min_position /
 // max_position) takes cos_fast(2h) itself -- selected PER LANE inside the rare wave-uniform branch, so a lane's
 // result never depends on its wave mates -- and as a CALL: inlined, the range-reduced version and its library path
 // sat in the middle of the step loop (of BOTH loops of the Acrobot + MountainCar pair kernel, whose Acrobot half then
@@ -261,9 +266,9 @@ __device__ __forceinline__ float cos_twice_fast(float h) {
 }
 
 // atan2 with one reduction step and a degree-7 odd polynomial (Cephes atanf coefficients):
-// max abs error 2.8e-7 over [-1, 1]^2 incl. tiny arguments (host harness against libm's double
-// atan2, 2e7 samples) -- the rounding of the result itself near +-pi is 2.4e-7.  ~25
-// instructions against ~70 for the library call.
+// max abs error 3.4e-7 restated (v_rcp_f32 at its documented 1 ulp) / 2.8e-7 on the device over all four quadrants,
+// both axes, |y| = |x|, t either side of tan(pi / 8) and magnitudes 1e-30 .. 1e30 (tests/math_primitive_cases.py) -- the
+// rounding of the result itself near +-pi is 2.4e-7.  ~25 instructions against ~70 for the library call.
 __device__ __forceinline__ float atan2_fast(float y, float x) {
   const float ax = fabsf(x), ay = fabsf(y);
   const float mx = fmaxf(ax, ay), mn = fminf(ax, ay);
@@ -277,11 +282,14 @@ __device__ __forceinline__ float atan2_fast(float y, float x) {
   p = __fmaf_rn(z, p, -3.33329491539e-1f);
   float r = __fmaf_rn(p * z, tr, tr) + (mid ? 0.78539816339f : 0.0f);
   r = (ay > ax) ? 1.57079632679f - r : r;
-  r = (x < 0.0f) ? 3.14159265359f - r : r;
+  // the left half plane by x's SIGN BIT, not `x < 0`: atan2(+-0, -0) = +-pi as in libm (and the float64 oracle), one
+  // integer compare for one float compare
+  r = (__float_as_int(x) < 0) ? 3.14159265359f - r : r;
   return copysignf(r, y);
 }
 
-// a / b with one v_rcp_f32 (1 ulp) instead of the ~10-instruction IEEE sequence
+// a / b with one v_rcp_f32 (1 ulp) instead of the ~10-instruction IEEE sequence: relative error 2.3e-7 restated (the
+// reciprocal's ulp, its rounding and the product's), 1.3e-7 on the device; a, b and a / b normal
 __device__ __forceinline__ float div_fast(float a, float b) { return a * __builtin_amdgcn_rcpf(b); }
 
 }  // namespace carl

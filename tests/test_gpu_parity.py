@@ -183,6 +183,102 @@ def test_mountaincar_wide_track_contexts(fam, device):
     assert np.array_equal(p_s2, s2[perm])
 
 
+def test_cartpole_pole_angle_through_every_sincos_path(device):
+    """Without auto-reset a lane keeps stepping after termination and the pole swings through every angle, so CartPole's
+    inlined `sincos_fast_smallarg` meets all of its paths: the bare polynomials (|theta| <= 0.78 in the whole wave), the
+    fall-through into `sincos_fast` (0.78f and its neighbours, up to +-40 rad) and that function's library path beyond
+    1e5 -- mixed lane by lane, so most waves hold all of them."""
+    rng = np.random.default_rng(4242)
+    n = 65536
+    ctx = random_table(O.CARTPOLE, rng, n)
+    U = rng.uniform
+    g = np.float32(0.78)
+    edge = np.array([g, np.nextafter(g, np.float32(0)), np.nextafter(g, np.float32(1))], dtype=np.float32)
+    kind = rng.integers(0, 5, n)
+    theta = np.select([kind == 0, kind == 1, kind == 2, kind == 3],
+                      [U(-0.21, 0.21, n), U(0.21, 0.78, n) * rng.choice([-1, 1], n),
+                       rng.choice(np.concatenate([edge, -edge]), n).astype(np.float64), U(-40, 40, n)],
+                      np.round(U(1.0e5, 4.0e5, n)) * rng.choice([-1, 1], n))  # whole numbers: exact in float32
+    s = np.stack([U(-2.5, 2.5, n), U(-3, 3, n), theta, U(-3, 3, n)], 1).astype(np.float32)
+    assert all(((np.abs(s[:, 2]) > lo) & (np.abs(s[:, 2]) <= hi)).sum() > 10000 for lo, hi in ((-1, 0.21), (0.21, 0.78), (0.78, 40), (1e5, 4e5)))
+    a = random_actions(O.CARTPOLE, rng, n)
+    s2, obs, rew, term, _ = run_transitions(O.CARTPOLE, ctx, s, a, device)
+    w_s2, w_obs, w_rew, w_term = O.transitions(O.CARTPOLE, ctx, s.astype(np.float64), a, precision="f64")
+    print(f"cartpole, every sincos path: worst rel_err state {rel_err(s2, w_s2).max():.2e}, obs {rel_err(obs, w_obs).max():.2e}, "
+          f"reward {rel_err(rew, w_rew).max():.2e}", flush=True)
+    assert rel_err(s2, w_s2).max() <= TOL
+    assert rel_err(obs, w_obs).max() <= TOL
+    assert rel_err(rew, w_rew).max() <= TOL
+    # a lane's result does not depend on its wave mates: the same rows in another order give the same bits
+    perm = rng.permutation(n)
+    p_s2, p_obs, *_ = run_transitions(O.CARTPOLE, ctx[perm], s[perm], a[perm], device)
+    assert np.array_equal(p_s2.view(np.uint32), s2[perm].view(np.uint32))
+    assert np.array_equal(p_obs.view(np.uint32), obs[perm].view(np.uint32))
+
+
+def _pendulum_wide_angles(rng, n):
+    U = rng.uniform
+    g = np.float32(1.0e5)
+    edge = np.array([g, np.nextafter(g, np.float32(0)), np.nextafter(g, np.float32(np.inf))], dtype=np.float32)
+    kind = rng.integers(0, 4, n)
+    theta = np.select([kind == 0, kind == 1, kind == 2],
+                      [U(-10, 10, n), U(-1.0e4, 1.0e4, n),
+                       np.where(rng.random(n) < 0.3, rng.choice(np.concatenate([edge, -edge]), n).astype(np.float64),
+                                U(0.99e5, 1.01e5, n) * rng.choice([-1, 1], n))],
+                      U(1.0e5, 1.0e6, n) * rng.choice([-1, 1], n))
+    s = np.stack([theta, U(-8, 8, n)], 1).astype(np.float32)
+    return s
+
+
+def _pendulum_wide_run(device):
+    rng = np.random.default_rng(777)
+    n = 65536
+    ctx = random_table(O.PENDULUM, rng, n)
+    s = _pendulum_wide_angles(rng, n)
+    a = random_actions(O.PENDULUM, rng, n)
+    got = run_transitions(O.PENDULUM, ctx, s, a, device)
+    want = O.transitions(O.PENDULUM, ctx, s.astype(np.float64), a, precision="f64")
+    return rng, ctx, s, a, got, want
+
+
+def test_pendulum_angle_through_every_sincos_path(device):
+    """Pendulum never normalises its stored angle, so `sincos_fast_pk` meets what a long rollout or a context with a huge
+    initial angle feeds it: |theta| <= 10, up to +-1e4 (the three-term reduction), either side of the 1e5 guard and the
+    outlined library call beyond it, mixed lane by lane.  At these magnitudes the float32 state's own rounding exceeds the
+    bar (ulp(1e5) = 7.8e-3), so each output is held to what the kernel computes from exact inputs: the new velocity
+    against the oracle at TOL; the new angle against theta + omega' dt within one float32 ulp of the result; the
+    observation against float64 cos / sin of the RETURNED float32 angle (the kernel takes its trig at the stored angle)."""
+    rng, ctx, s, a, (s2, obs, rew, term, _), (w_s2, w_obs, w_rew, w_term) = _pendulum_wide_run(device)
+    n = s.shape[0]
+    assert all(((np.abs(s[:, 0]) > lo) & (np.abs(s[:, 0]) <= hi)).sum() > 5000 for lo, hi in ((-1, 10), (10, 1e4), (0.99e5, 1e5), (1e5, 1e6)))
+    th2 = s[:, 0].astype(np.float64) + s2[:, 1].astype(np.float64) * ctx[:, 1]  # theta + omega' dt from the RETURNED omega'
+    e_v = rel_err(s2[:, 1], w_s2[:, 1]).max()
+    e_th = (np.abs(s2[:, 0].astype(np.float64) - th2) / np.spacing(np.abs(th2).astype(np.float32)).astype(np.float64)).max()
+    trig = np.stack([np.cos(s2[:, 0].astype(np.longdouble)), np.sin(s2[:, 0].astype(np.longdouble))], 1).astype(np.float64)
+    e_o = max(rel_err(obs[:, :2], trig).max(), rel_err(obs[:, 2], w_obs[:, 2]).max())
+    print(f"pendulum, every sincos path: velocity {e_v:.2e}, angle {e_th:.2f} ulp, observation {e_o:.2e}", flush=True)
+    assert e_v <= TOL
+    assert e_th <= 1.0
+    assert e_o <= TOL
+    assert np.array_equal(obs[:, 2].view(np.uint32), s2[:, 1].view(np.uint32)) and not term.any()
+    perm = rng.permutation(n)
+    p_s2, p_obs, p_rew, *_ = run_transitions(O.PENDULUM, ctx[perm], s[perm], a[perm], device)
+    assert np.array_equal(p_s2.view(np.uint32), s2[perm].view(np.uint32))
+    assert np.array_equal(p_obs.view(np.uint32), obs[perm].view(np.uint32))
+    assert np.array_equal(p_rew.view(np.uint32), rew[perm].view(np.uint32))
+
+
+def test_pendulum_reward_at_every_angle_magnitude(device):
+    """the reward of the same transitions (computed from the exact float32 inputs: angle_normalize(theta)^2 + ...) against
+    the oracle at TOL"""
+    rng, ctx, s, a, (s2, obs, rew, term, _), (w_s2, w_obs, w_rew, w_term) = _pendulum_wide_run(device)
+    e = rel_err(rew, w_rew)
+    for lo, hi in ((0, 10), (10, 1e2), (1e2, 1e3), (1e3, 1e4), (1e4, 1e5), (1e5, 1e6)):
+        m = (np.abs(s[:, 0]) > lo) & (np.abs(s[:, 0]) <= hi)
+        print(f"pendulum reward, {lo:g} < |theta| <= {hi:g}: worst rel_err {e[m].max(initial=0):.2e} over {int(m.sum())} rows", flush=True)
+    assert e.max() <= TOL
+
+
 @pytest.mark.parametrize("fam", range(5), ids=O.FAMILY_NAMES)
 def test_random_transitions_100k(fam, device):
     """>= 1e5 random (context, state, action) triples per family vs the float64 oracle"""
