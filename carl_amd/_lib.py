@@ -285,3 +285,22 @@ EXPORTS.update({
     "carl_evaluate_policy": (C.c_int, [C.POINTER(Batch), C.POINTER(Policy), C.c_int32, C.c_int32,
                                        C.POINTER(PolicyEpisodes), _vp]),
 })
+
+
+# ---- a critic in the closed-loop launch, and GAE (include/carl_amd.h: carl_policy_value_t, carl_gae_t) ----------
+class PolicyValue(C.Structure):
+    _fields_ = [("value", _vp), ("last_value", _vp), ("boot_value", _vp)]
+
+
+class Gae(C.Structure):
+    _fields_ = [("n_lanes", _i), ("n_steps", _i), ("row_pitch", _i), ("gamma", C.c_float), ("lam", C.c_float),
+                ("reserved", _i), ("reward", _vp), ("value", _vp), ("boot_value", _vp), ("last_value", _vp),
+                ("terminated", _vp), ("truncated", _vp), ("advantage", _vp), ("ret", _vp)]
+
+
+EXPORTS.update({
+    "carl_rollout_policy_valued": (C.c_int, [C.POINTER(Batch), C.POINTER(Policy), C.POINTER(Policy),
+                                             C.POINTER(PolicySampling), C.POINTER(StepIO), C.c_int32,
+                                             C.POINTER(PolicySummary), C.POINTER(PolicyValue), _vp]),
+    "carl_gae": (C.c_int, [C.POINTER(Gae), _vp]),
+})

@@ -21,9 +21,10 @@ ARCH = "gfx950"
 # is 3.5 % slower at 65 536 lanes per family and 2.5 % at 8 192, CartPole at 8 192 lanes 2 % slower, and the one
 # packing that paid (Pendulum's sine / cosine polynomials) is written out by hand in fast_math.hip.h: sincos_fast_pk.
 # carl_policy.hip (the closed-loop rollout) and carl_policy_sample.hip (its sampled twins) instantiate the same device
-# templates as carl_amd.hip: same flags.
+# templates as carl_amd.hip, and so does carl_policy_value.hip (the rollout with a critic, and GAE): same flags.
 SOURCES = {"carl_amd.hip": ["-fno-slp-vectorize"], "carl_brax.hip": ["-fno-slp-vectorize"],
-           "carl_policy.hip": ["-fno-slp-vectorize"], "carl_policy_sample.hip": ["-fno-slp-vectorize"]}
+           "carl_policy.hip": ["-fno-slp-vectorize"], "carl_policy_sample.hip": ["-fno-slp-vectorize"],
+           "carl_policy_value.hip": ["-fno-slp-vectorize"]}
 
 
 def _hipcc() -> str:

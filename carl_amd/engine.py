@@ -699,7 +699,8 @@ class VecEngine(LaneEngine):
 
     def rollout_policy(self, policy, n_steps: int, out: dict | None = None, mode: str = "transitions",
                        final_obs: bool = False, deterministic: bool = True, sample_seed: int = 0,
-                       log_prob: bool = False) -> dict:
+                       log_prob: bool = False, *, value_net=None, bootstrap_truncated: bool = True,
+                       gae: tuple | None = None) -> dict:
         """``n_steps`` steps in ONE launch, each lane's action chosen on the device by ``policy`` (``carl_amd.policy.
         MLPPolicy``) from the lane's current context and observation -- closed loop, where ``rollout`` replays actions
         written beforehand.
@@ -713,9 +714,28 @@ class VecEngine(LaneEngine):
         ``deterministic=False``: each action is sampled from the policy's distribution (a categorical over the logits /
         a Gaussian of ``policy.log_std``; include/carl_amd.h: carl_rollout_policy_sampled), the draws keyed by
         ``sample_seed`` and by (lane, episode, step in episode).  ``log_prob=True`` (transitions mode) adds
-        ``"log_prob"`` ``[T, N]`` float32: each action's log-probability under the policy."""
+        ``"log_prob"`` ``[T, N]`` float32: each action's log-probability under the policy.
+        ``value_net=critic`` (an ``MLPPolicy`` with ``head="value"``; transitions mode): the critic runs inside the same
+        launch on the inputs the actor sees (include/carl_amd.h: carl_rollout_policy_valued) and ``out`` gains ``"value"``
+        ``[T, N]`` (V of the input each action was chosen from), ``"last_value"`` ``[N]`` (V of each lane's input after the
+        last step) and, with ``bootstrap_truncated`` (needs ``auto_reset``), ``"boot_value"`` ``[T, N]``: V of the
+        terminal observation where a step ended an episode by truncation alone, +0 elsewhere (SB3's timeout bootstrap).
+        A sampled launch with a critic always returns ``"log_prob"``.  Everything else the launch writes keeps its bits.
+        ``gae=(gamma, lam)`` adds ``"advantage"`` and ``"return"`` ``[T, N]`` from one ``carl_gae`` launch on the same
+        stream (``VecEngine.gae`` of the launch's own columns)."""
         if policy.family != self.family or policy.obs_dim != self.D:
             raise ValueError(f"the policy was built for family {policy.family}, this engine runs family {self.family}")
+        if gae is not None and value_net is None:
+            raise ValueError("gae=(gamma, lam) needs value_net: advantages are computed from the critic's values")
+        if value_net is not None:
+            if mode == "summary":
+                raise ValueError("value_net: transitions mode only (mode='summary' stores nothing per step)")
+            self._check_value_net(policy, value_net)
+            if bootstrap_truncated and not self.auto_reset:
+                raise ValueError("bootstrap_truncated=True needs auto_reset=True: without it no terminal observation is "
+                                 "kept apart from the next one (pass bootstrap_truncated=False)")
+            if gae is not None:
+                gamma, lam = (float(v) for v in gae)
         if mode == "summary" and not self.auto_reset:
             raise ValueError("mode='summary' needs auto_reset=True: without it a finished lane reports done on every later "
                              "step, and the totals would count its episode on each of them")
@@ -750,6 +770,8 @@ class VecEngine(LaneEngine):
             out = self.alloc_rollout(T, final_obs=final_obs)
             adt = torch.int32 if self.info.action_is_discrete else torch.float32
             out["action"] = torch.empty((T, self._out_pitch(out)), dtype=adt, device=self.device)[:, : self.n]
+        if value_net is not None and not deterministic:
+            log_prob = True  # (a sampled launch with a critic always stores the log-probabilities)
         if log_prob and "log_prob" not in out:
             out["log_prob"] = torch.empty((T, self._out_pitch(out)), dtype=torch.float32, device=self.device)[:, : self.n]
         io = self._rollout_io(None, None, out, T)
@@ -759,6 +781,33 @@ class VecEngine(LaneEngine):
                 raise ValueError("rollout_policy 'log_prob' buffer must be torch.float32")
             self._check_rows("rollout_policy", {"log_prob": lp}, ("log_prob",), self._out_pitch(out), T, self.device)
         smp = self._sampling(policy, deterministic, sample_seed, lp)
+        if value_net is not None:
+            P = self._out_pitch(out)
+            cols = ("value", "boot_value") if bootstrap_truncated else ("value",)
+            for k in cols:
+                if k not in out:
+                    out[k] = torch.empty((T, P), dtype=torch.float32, device=self.device)[:, : self.n]
+                elif out[k].dtype != torch.float32:
+                    raise ValueError(f"rollout_policy '{k}' buffer must be torch.float32")
+            self._check_rows("rollout_policy", {k: out[k] for k in cols}, cols, P, T, self.device)
+            if "last_value" not in out:
+                out["last_value"] = torch.empty(self.n, dtype=torch.float32, device=self.device)
+            lv = out["last_value"]
+            if lv.dtype != torch.float32 or lv.device != self.device or tuple(lv.shape) != (self.n,) or not lv.is_contiguous():
+                raise ValueError(f"rollout_policy 'last_value' must be a contiguous float32 [{self.n}] tensor on {self.device}")
+            cparams = value_net.device_params(self.device)
+            crit = value_net.struct(self.n, cparams.data_ptr())
+            vout = _lib.PolicyValue(_ptr(out["value"]), _ptr(lv), _ptr(out["boot_value"]) if bootstrap_truncated else None)
+            with torch.cuda.device(self.device):
+                _lib.check(self.lib.carl_rollout_policy_valued(self._b_ref, C.byref(pol), C.byref(crit),
+                                                               None if smp is None else C.byref(smp), C.byref(io), T, None,
+                                                               C.byref(vout), self._stream()))
+            if gae is not None:
+                res = self.gae(out["reward"][:T], out["value"][:T], out["terminated"][:T], out["truncated"][:T], lv, gamma,
+                               lam, boot_value=out["boot_value"][:T] if bootstrap_truncated else None,
+                               out={k: out[k] for k in ("advantage", "return") if k in out} or None)
+                out["advantage"], out["return"] = res["advantage"], res["return"]
+            return out
         with torch.cuda.device(self.device):
             if smp is None:
                 _lib.check(self.lib.carl_rollout_policy(self._b_ref, C.byref(pol), C.byref(io), T, None, self._stream()))
@@ -766,6 +815,69 @@ class VecEngine(LaneEngine):
                 _lib.check(self.lib.carl_rollout_policy_sampled(self._b_ref, C.byref(pol), C.byref(smp), C.byref(io), T,
                                                                 None, self._stream()))
         return out
+
+    def _check_value_net(self, policy, value_net) -> None:
+        """ValueError unless ``value_net`` is a critic the valued launch can run next to ``policy``: a value head, the same
+        family, inputs and set layout, and a shift | scale | clip section equal to the actor's bit for bit (the critic
+        reads the actor's transformed inputs; with equal sections the critic's packed block alone defines V)."""
+        if getattr(value_net, "head", None) != "value":
+            raise ValueError("value_net must be an MLPPolicy built with head='value'")
+        if policy.head != "policy":
+            raise ValueError("the acting policy must have head='policy'")
+        if value_net.family != policy.family or value_net.obs_dim != policy.obs_dim:
+            raise ValueError(f"value_net was built for family {value_net.family}, the policy for family {policy.family}")
+        if list(value_net.ctx_rows) != list(policy.ctx_rows):
+            raise ValueError(f"value_net reads context rows {value_net.ctx_rows}, the policy {policy.ctx_rows}: the critic "
+                             "sees the actor's inputs")
+        if value_net.n_sets != policy.n_sets or value_net.lanes_per_set != policy.lanes_per_set:
+            raise ValueError(f"value_net has {value_net.n_sets} weight sets of {value_net.lanes_per_set} lanes, the policy "
+                             f"{policy.n_sets} of {policy.lanes_per_set}: one set layout for both")
+        a, c = policy.transform_section(), value_net.transform_section()
+        if not np.array_equal(np.ascontiguousarray(a).view(np.int32), np.ascontiguousarray(c).view(np.int32)):
+            raise ValueError("value_net's input_shift / input_scale / input_clip must equal the policy's bit for bit: the "
+                             "critic reads the actor's transformed inputs")
+
+    def gae(self, reward, value, terminated, truncated, last_value, gamma: float, lam: float, boot_value=None,
+            out: dict | None = None) -> dict:
+        """Generalised advantage estimation in one launch (include/carl_amd.h: carl_gae) over ``[T, N]`` float32
+        ``reward`` / ``value`` (/ ``boot_value``), uint8 or bool ``terminated`` / ``truncated`` and ``last_value`` ``[N]``:
+        rows of one common pitch (``alloc_rollout``-style views or dense), on this engine's device.  Returns
+        ``{"advantage", "return"}`` ``[T, N]`` float32 (``out``: buffers of the same layout to write into).  The rule is
+        SB3's ``RolloutBuffer.compute_returns_and_advantage`` with ``boot_value`` as the timeout bootstrap; a finished
+        step (either flag) cuts the recurrence.  No host synchronisation."""
+        T, N = (int(v) for v in reward.shape)
+        P = int(reward.stride(0)) if T > 1 else N
+
+        def rows(name, t, dtypes):
+            if t.dtype not in dtypes or t.device != self.device or tuple(t.shape) != (T, N) or (
+                    N > 1 and t.stride(1) != 1) or (T > 1 and t.stride(0) != P):
+                raise ValueError(f"gae '{name}': needs {dtypes[0]} [{T}, {N}] rows of pitch {P} on {self.device}, got "
+                                 f"{t.dtype} {tuple(t.shape)} strides {tuple(t.stride())}")
+            return t
+
+        if P < N:
+            raise ValueError(f"gae 'reward': rows of pitch {P} < {N} lanes")
+        f32, u8 = (torch.float32,), (torch.uint8, torch.bool)
+        rows("reward", reward, f32), rows("value", value, f32), rows("terminated", terminated, u8)
+        rows("truncated", truncated, u8)
+        if boot_value is not None:
+            rows("boot_value", boot_value, f32)
+        if last_value.dtype != torch.float32 or last_value.device != self.device or tuple(last_value.shape) != (N,) or (
+                N > 1 and last_value.stride(0) != 1):
+            raise ValueError(f"gae 'last_value': needs a contiguous float32 [{N}] tensor on {self.device}")
+        res = {} if out is None else out
+        for k in ("advantage", "return"):
+            if k not in res:
+                res[k] = torch.empty((T, P), dtype=torch.float32, device=self.device)[:, :N]
+            rows(k, res[k], f32)
+        g = _lib.Gae()
+        g.n_lanes, g.n_steps, g.row_pitch, g.gamma, g.lam = N, T, (P if P != N else 0), float(gamma), float(lam)
+        g.reward, g.value, g.boot_value, g.last_value = _ptr(reward), _ptr(value), _ptr(boot_value), _ptr(last_value)
+        g.terminated, g.truncated = _ptr(terminated), _ptr(truncated)
+        g.advantage, g.ret = _ptr(res["advantage"]), _ptr(res["return"])
+        with torch.cuda.device(self.device):
+            _lib.check(self.lib.carl_gae(C.byref(g), self._stream()))
+        return res
 
     # (key, dtype, per-episode rows) of an evaluate_policy result
     _EPISODE_KEYS = (("episodes", torch.int32, False), ("steps", torch.int32, False), ("return", torch.float32, True),

@@ -314,13 +314,16 @@ class CARLEnv(abc.ABC):
 
     def rollout_policy(self, policy, n_steps: int, out: dict | None = None, mode: str = "transitions",
                        final_obs: bool = False, deterministic: bool = True, sample_seed: int = 0,
-                       log_prob: bool = False) -> dict:
+                       log_prob: bool = False, *, value_net=None, bootstrap_truncated: bool = True,
+                       gae: tuple | None = None) -> dict:
         """``n_steps`` closed-loop steps of every lane in one launch, actions chosen on the device by ``policy``
         (``carl_amd.policy.MLPPolicy.for_env(self, ...)``): ``VecEngine.rollout_policy`` of this env's engine (sampled
-        actions with ``deterministic=False``).  The engine's outputs (``step``'s views) are not touched; the host selector
+        actions with ``deterministic=False``; ``value_net`` / ``bootstrap_truncated`` / ``gae``: critic values and GAE
+        advantages from the same call).  The engine's outputs (``step``'s views) are not touched; the host selector
         object is not consulted."""
         return self.env.rollout_policy(policy, n_steps, out=out, mode=mode, final_obs=final_obs,
-                                       deterministic=deterministic, sample_seed=sample_seed, log_prob=log_prob)
+                                       deterministic=deterministic, sample_seed=sample_seed, log_prob=log_prob,
+                                       value_net=value_net, bootstrap_truncated=bootstrap_truncated, gae=gae)
 
     def evaluate_policy(self, policy, n_episodes: int, max_steps: int, seed: int | None = None,
                         deterministic: bool = True, sample_seed: int = 0) -> dict:

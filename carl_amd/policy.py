@@ -21,6 +21,12 @@ PPO default) for Box families.  The draws are keyed by ``sample_seed`` and by (l
 from the reset and context streams; a transitions launch can also return each action's log-probability
 (``log_prob=True``), what an on-policy learner (PPO, A2C) stores next to the action.
 
+Value networks: ``head="value"`` (``for_env`` / ``from_sequential`` / ``stack``) builds a critic for the env -- one
+scalar output whatever the family's action space.  ``rollout_policy(..., value_net=critic)`` evaluates it inside the
+same launch on the inputs the actor sees (include/carl_amd.h: carl_rollout_policy_valued) and ``gae=(gamma, lam)`` adds
+advantages and returns from one more launch (carl_gae).  The critic reads the actor's transformed inputs, so its
+``input_shift`` / ``input_scale`` / ``input_clip`` must equal the actor's bit for bit.
+
 Out of scope: the Brax families, ``MixedVecEngine`` pairs, the gymnasium drop-in (``carl_amd.dropin``) and the
 multi-process helpers (``carl_amd.distributed``).
 """
@@ -83,7 +89,7 @@ class MLPPolicy:
 
     def __init__(self, family: int, obs_dim: int, ctx_rows: Sequence[int], layers: Sequence, activation: str = "tanh",
                  input_shift=None, input_scale=None, input_clip: float | None = None, context_names: Sequence | None = None,
-                 log_std=None):
+                 log_std=None, head: str = "policy"):
         info = _lib.family_info(int(family))
         self.family, self.obs_dim = int(family), int(obs_dim)
         self.ctx_rows = [int(r) for r in ctx_rows]
@@ -91,6 +97,9 @@ class MLPPolicy:
         if activation not in _ACTIVATIONS:
             raise ValueError(f"activation {activation!r}: one of {sorted(_ACTIVATIONS)}")
         self.activation = activation
+        if head not in ("policy", "value"):
+            raise ValueError(f"head {head!r}: 'policy' or 'value'")
+        self.head = head  # "value": a critic -- one scalar output, evaluated next to an actor (rollout_policy(value_net=))
         self.discrete = bool(info.action_is_discrete)
         self.n_in = len(self.ctx_rows) + self.obs_dim
         if len(self.ctx_rows) > _lib.POLICY_MAX_IN or self.n_in > _lib.POLICY_MAX_IN:
@@ -114,15 +123,18 @@ class MLPPolicy:
             raise ValueError(f"hidden widths {self.widths}: at most {_lib.POLICY_MAX_HIDDEN} layers of width <= "
                              f"{_lib.POLICY_MAX_WIDTH}")
         self.n_out = self.layers[-1][0].shape[0]
-        want = int(info.n_actions) if self.discrete else 1
+        want = 1 if head == "value" else int(info.n_actions) if self.discrete else 1
         if self.n_out != want:
-            raise ValueError(f"head width {self.n_out}: this family needs {want} ({'n_actions' if self.discrete else 'Box'})")
+            kind = "a value network has one output" if head == "value" else "n_actions" if self.discrete else "Box"
+            raise ValueError(f"head width {self.n_out}: this family needs {want} ({kind})")
         self.shift = np.zeros(self.n_in, np.float32) if input_shift is None else np.asarray(input_shift, np.float32).reshape(-1)
         self.scale = np.ones(self.n_in, np.float32) if input_scale is None else np.asarray(input_scale, np.float32).reshape(-1)
         if self.shift.shape != (self.n_in,) or self.scale.shape != (self.n_in,):
             raise ValueError(f"input_shift / input_scale need {self.n_in} values")
         self.clip = np.float32(np.inf if input_clip is None else input_clip)
         self.params = self._pack()[None]  # [n_sets, set_floats]
+        if log_std is not None and head == "value":
+            raise ValueError("log_std: a value network samples nothing")
         if log_std is not None and self.discrete:
             raise ValueError("log_std: Box families only (a discrete policy samples from its logits)")
         ls = np.asarray(log_std.detach().cpu() if isinstance(log_std, torch.Tensor) else (0.0 if log_std is None else log_std),
@@ -136,20 +148,22 @@ class MLPPolicy:
     # ------------------------------------------------------------------ construction
     @classmethod
     def for_env(cls, env, layers: Sequence, activation: str = "tanh", input_shift=None, input_scale=None,
-                input_clip: float | None = None, context_features: Sequence | None = None, log_std=None) -> "MLPPolicy":
+                input_clip: float | None = None, context_features: Sequence | None = None, log_std=None,
+                head: str = "policy") -> "MLPPolicy":
         """A policy for ``env`` (a classic-control ``CARLEnv`` or ``VecEngine``) from explicit ``(W [out, in], b [out])``
         arrays, hidden layers first, the head last.  The input is ``FlattenObservation(env)``'s vector (module docstring);
         ``context_features`` narrows its context part (``[]``: observation only).  ``log_std`` (Box families only; a float
-        or a one-element tensor, default 0): the log standard deviation of the sampled Gaussian."""
+        or a one-element tensor, default 0): the log standard deviation of the sampled Gaussian.  ``head="value"``: a
+        value network instead -- the last layer has one output whatever the family's action space."""
         eng, _ = _engine_of(env)
         rows, names = flattened_context_rows(env, context_features)
-        return cls(eng.family, eng.D, rows, layers, activation, input_shift, input_scale, input_clip, names, log_std)
+        return cls(eng.family, eng.D, rows, layers, activation, input_shift, input_scale, input_clip, names, log_std, head)
 
     @classmethod
     def from_sequential(cls, env, seq: torch.nn.Sequential, **kw) -> "MLPPolicy":
         """The same from a ``torch.nn.Sequential`` of ``Linear`` layers with ``Tanh`` / ``ReLU`` / ``Identity`` between
-        them (one activation kind for every hidden layer; nothing after the head but ``Identity``); ``log_std=`` as
-        ``for_env``."""
+        them (one activation kind for every hidden layer; nothing after the head but ``Identity``); ``log_std=`` and
+        ``head=`` as ``for_env``."""
         linears, acts = [], []
         for m in seq:
             if isinstance(m, torch.nn.Linear):
@@ -175,13 +189,16 @@ class MLPPolicy:
         return cls.for_env(env, layers, activation=kinds.pop() if kinds else "tanh", **kw)
 
     @staticmethod
-    def stack(policies: Sequence["MLPPolicy"], lanes_per_set: int) -> "MLPPolicy":
+    def stack(policies: Sequence["MLPPolicy"], lanes_per_set: int, head: str | None = None) -> "MLPPolicy":
         """Several weight sets of one shape: lane ``l`` uses set ``l // lanes_per_set`` (a multiple of
-        ``carl_policy_lane_quantum()``, 256 -- the lanes of one workgroup)."""
+        ``carl_policy_lane_quantum()``, 256 -- the lanes of one workgroup).  ``head``: what every set must be
+        (``"policy"`` / ``"value"``; default: whatever the first one is)."""
         if not policies:
             raise ValueError("stack() needs at least one policy")
         p0 = policies[0]
-        key = lambda p: (p.family, p.ctx_rows, p.obs_dim, [W.shape for W, _ in p.layers], p.activation)  # noqa: E731
+        if head is not None and any(p.head != head for p in policies):
+            raise ValueError(f"stack(head={head!r}): every weight set must have that head")
+        key = lambda p: (p.family, p.ctx_rows, p.obs_dim, [W.shape for W, _ in p.layers], p.activation, p.head)  # noqa: E731
         for p in policies[1:]:
             if key(p) != key(p0):
                 raise ValueError("stack(): every weight set must have the same family, inputs, shape and activation")
@@ -221,7 +238,7 @@ class MLPPolicy:
             p.width[k] = w
         p.n_out = self.n_out
         p.activation = _ACTIVATIONS[self.activation]
-        p.head = _lib.POLICY_HEAD_ARGMAX if self.discrete else _lib.POLICY_HEAD_BOX
+        p.head = _lib.POLICY_HEAD_ARGMAX if self.discrete and self.head != "value" else _lib.POLICY_HEAD_BOX
         p.n_sets = self.n_sets
         if self.lanes_per_set is None:
             q = int(_lib.load().carl_policy_lane_quantum())
@@ -230,6 +247,11 @@ class MLPPolicy:
             p.lanes_per_set = self.lanes_per_set
         p.params = params_ptr
         return p
+
+    def transform_section(self) -> np.ndarray:
+        """The shift | scale | clip section of every packed weight set ``[n_sets, 2 * n_in + 1]`` (a view)."""
+        off = sum(W.size + b.size for W, b in self.layers)
+        return self.params[:, off: off + 2 * self.n_in + 1]
 
     def device_params(self, device) -> torch.Tensor:
         """The packed parameters on ``device`` (uploaded once per device)."""

@@ -478,6 +478,69 @@ int carl_evaluate_policy_sampled(const carl_batch_t* batch, const carl_policy_t*
                                  const carl_policy_sampling_t* sampling, int32_t n_episodes, int32_t max_steps,
                                  const carl_policy_episodes_t* out, void* stream);
 
+/* ---- a critic in the closed-loop launch, and GAE on the device (additive; ABI version unchanged) ----
+ * carl_rollout_policy_valued is the transitions-mode carl_rollout_policy (sampling == NULL) or
+ * carl_rollout_policy_sampled (sampling != NULL) with a second network, the critic, evaluated on the inputs the actor
+ * sees: everything those calls write, bit for bit, plus the columns of carl_policy_value_t.
+ * The critic is a carl_policy_t with n_out == 1, hidden widths and an activation of its own, and the actor's n_in, n_ctx,
+ * ctx_rows, n_sets and lanes_per_set; `head` is not read.  It reads the actor's transformed inputs x (after the actor's
+ * shift / scale / clip): the shift / scale / clip section of its own packed block is NOT READ, so a block whose section
+ * equals the actor's makes the documented forward pass of that block the exact reference.  V = y[0], the same explicit
+ * fma order, bias first, the same tanh.
+ *   value      [n_steps][pitch] fp32, the layout of io->action: V(x_t), x_t the input step t's action was chosen from
+ *   last_value [n_lanes] fp32: V of each lane's input after the launch's last step (its current context, re-read if
+ *              the last step moved the lane, and its current observation)
+ *   boot_value [n_steps][pitch] fp32, NULL: not wanted.  Needs CARL_FLAG_AUTORESET (CARL_ERR_UNSUPPORTED without).  On a
+ *              step that ends a lane's episode by truncation only (truncated && !terminated):
+ *              V([context values of the context the episode ran in, terminal observation]); +0.0f everywhere else
+ *              (SB3's timeout bootstrap: reward + gamma * boot_value).
+ * Validation: carl_rollout_policy's, in its order; then io != NULL (transitions mode only: CARL_ERR_INVALID_ARGUMENT),
+ * the sampling checks of carl_rollout_policy_sampled when sampling != NULL, plus sampling->log_prob != NULL (a sampled
+ * valued launch always stores the log-probabilities); then the critic and `out`.  value / boot_value on 16-byte
+ * boundaries.  n_lanes == 0 or n_steps == 0 enqueues nothing and writes nothing.  summary_out as carl_rollout_policy's
+ * transitions mode.  Padding columns [n_lanes, pitch) of value / boot_value receive the padding lanes' values. */
+typedef struct carl_policy_value {
+  float* value;      /* DEVICE [n_steps][pitch] */
+  float* last_value; /* DEVICE [n_lanes] */
+  float* boot_value; /* DEVICE [n_steps][pitch], nullable */
+} carl_policy_value_t;
+
+int carl_rollout_policy_valued(const carl_batch_t* batch, const carl_policy_t* policy_host,
+                               const carl_policy_t* critic_host, const carl_policy_sampling_t* sampling,
+                               const carl_step_io_t* io, int32_t n_steps, const carl_policy_summary_t* summary_out,
+                               const carl_policy_value_t* out, void* stream);
+
+/* Generalised advantage estimation over [n_steps][pitch] rows (row_pitch lanes per row, 0 = n_lanes; no alignment
+ * rule), one launch, stream-ordered.  With gl = fp32(gamma) * fp32(lambda) (one fp32 rounding), A = 0 and, for
+ * t = n_steps - 1 .. 0:
+ *   done  = terminated[t] | truncated[t]
+ *   vn    = done ? ((truncated[t] && !terminated[t] && boot_value) ? boot_value[t] : 0)
+ *                : (t == n_steps - 1 ? last_value : value[t + 1])
+ *   delta = fma(gamma, vn, reward[t]) - value[t]
+ *   A     = fma(gl, done ? 0 : A, delta);   advantage[t] = A;   ret[t] = A + value[t]
+ * every operation in fp32, selects not mask products (a masked-out NaN or infinity changes nothing).  This is SB3's
+ * RolloutBuffer.compute_returns_and_advantage with the timeout bootstrap folded in.  Only columns [0, n_lanes) of rows
+ * [0, n_steps) of advantage / ret are written.  All pointers but boot_value are required; n_lanes, n_steps >= 0;
+ * row_pitch 0 or >= n_lanes: else CARL_ERR_INVALID_ARGUMENT before anything is enqueued. */
+typedef struct carl_gae {
+  int32_t n_lanes;
+  int32_t n_steps;
+  int32_t row_pitch;
+  float gamma;
+  float lambda;
+  int32_t reserved;
+  const float* reward;       /* DEVICE [n_steps][pitch] */
+  const float* value;        /* DEVICE [n_steps][pitch] */
+  const float* boot_value;   /* DEVICE [n_steps][pitch], nullable */
+  const float* last_value;   /* DEVICE [n_lanes] */
+  const uint8_t* terminated; /* DEVICE [n_steps][pitch] */
+  const uint8_t* truncated;  /* DEVICE [n_steps][pitch] */
+  float* advantage;          /* DEVICE [n_steps][pitch] */
+  float* ret;                /* DEVICE [n_steps][pitch] */
+} carl_gae_t;
+
+int carl_gae(const carl_gae_t* gae_host, void* stream);
+
 /* ======================= Brax-locomotion families (spring backend) =======================
  * Replaces CARLBraxEnv + BraxGymWrapper/VectorGymWrapper + brax.spring.pipeline.step x
  * n_frames + brax.envs.<env>.step/reset (carl/envs/brax/carl_brax_env.py:115-336,

@@ -14,6 +14,13 @@
   --sampled        also the sampled launches (rollout_policy(..., deterministic=False)) of the same policies:
                    transitions with and without log_prob, and summary.
 
+  --legs value     the critic inside the launch and GAE on the device, T = 256 and --steps, linear / 2x32 / 2x64 tanh for
+                   both networks, each against the way to the same arrays without them:
+                   (a) rollout_policy(..., value_net=) against the sampled + log_prob launch followed by the torch critic
+                       on the inputs rebuilt from its `obs` rows (static selector: the context part is constant);
+                   (b) VecEngine.gae against the torch reverse loop over the same columns.
+                   Written to key "value" of --out.
+
 Host timing with torch.cuda events around `--reps` launches after one warm-up launch; the median per launch is
 reported.  Kernel times belong to a separate `rocprofv3 --kernel-trace --stats` run of this script.
 
@@ -141,6 +148,68 @@ def evaluate_leg(eng, n_in, T_summary, reps, K=10, max_steps=5000):
     return rows
 
 
+def torch_gae(reward, value, te, tr, last_value, boot, gamma, lam):
+    """the reverse loop a caller writes without carl_gae (SB3's rule, timeout bootstrap folded into the reward)"""
+    T = reward.shape[0]
+    adv = torch.empty_like(reward)
+    a = torch.zeros_like(last_value)
+    nxt = last_value
+    for t in range(T - 1, -1, -1):
+        live = 1.0 - (te[t] | tr[t]).float()
+        rew = reward[t] + gamma * boot[t]
+        delta = rew + gamma * nxt * live - value[t]
+        a = delta + gamma * lam * live * a
+        adv[t] = a
+        nxt = value[t]
+    return adv, adv + value
+
+
+def value_leg(eng, n_in, steps, reps, block=64):
+    rows = []
+    ctx = eng.ctx_obs.t().contiguous()
+    for T in sorted({256, steps}):
+        for name, widths in {"linear": [], "mlp_2x32_tanh": [32, 32], "mlp_2x64_tanh": [64, 64]}.items():
+            actor = make_mlp(widths, n_in)
+            critic = make_mlp(widths, n_in, seed=1)
+            critic[-1] = torch.nn.Linear(critic[-1].in_features, 1)
+            pol = MLPPolicy.from_sequential(eng, actor)
+            vf = MLPPolicy.from_sequential(eng, critic, head="value")
+            critic = critic.to(eng.device)
+            kw = dict(deterministic=False, sample_seed=1)
+            vout = eng.rollout_policy(pol, T, value_net=vf, **kw)
+            sout = eng.rollout_policy(pol, T, log_prob=True, **kw)
+            val = torch.empty((T, eng.n), device=eng.device)
+
+            def parent_way():
+                obs0 = eng.obs.clone()
+                eng.rollout_policy(pol, T, out=sout, log_prob=True, **kw)
+                with torch.no_grad():
+                    for t0 in range(0, T, block):
+                        t1 = min(T, t0 + block)
+                        o = torch.cat([obs0[None] if t0 == 0 else sout["obs"][t0 - 1: t0], sout["obs"][t0: t1 - 1]])
+                        x = torch.cat([ctx[None].expand(t1 - t0, -1, -1), o], dim=2)
+                        val[t0:t1] = critic(x)[..., 0]
+                    critic(torch.cat([ctx, sout["obs"][T - 1]], dim=1))  # last_value
+
+            sec_v, ts_v = time_launches(lambda: eng.rollout_policy(pol, T, out=vout, value_net=vf, **kw), reps)
+            sec_s, _ = time_launches(lambda: eng.rollout_policy(pol, T, out=sout, log_prob=True, **kw), reps)
+            sec_p, ts_p = time_launches(parent_way, reps)
+            g = {k: vout[k] for k in ("advantage", "return")} if "advantage" in vout else None
+            args = (vout["reward"], vout["value"], vout["terminated"], vout["truncated"], vout["last_value"])
+            res = eng.gae(*args, 0.99, 0.95, boot_value=vout["boot_value"], out=g)
+            sec_g, ts_g = time_launches(lambda: eng.gae(*args, 0.99, 0.95, boot_value=vout["boot_value"], out=res), reps)
+            sec_t, ts_t = time_launches(lambda: torch_gae(*args, vout["boot_value"], 0.99, 0.95), max(1, reps // 2))
+            r = {"config": f"value_{name}", "lanes": eng.n, "steps": T, "valued_launch_sec": sec_v,
+                 "sampled_log_prob_launch_sec": sec_s, "valued_over_sampled": sec_v / sec_s,
+                 "sampled_launch_plus_torch_critic_sec": sec_p, "valued_speedup_over_parent_way": sec_p / sec_v,
+                 "gae_sec": sec_g, "gae_bytes_per_s": 26.0 * eng.n * T / sec_g, "torch_reverse_loop_sec": sec_t,
+                 "gae_speedup_over_torch_loop": sec_t / sec_g, "reps_sec": {"valued": ts_v, "parent": ts_p, "gae": ts_g,
+                                                                             "torch_gae": ts_t}}
+            rows.append(r)
+            print(json.dumps(r), flush=True)
+    return rows
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--lanes", type=int, default=65536)
@@ -158,6 +227,8 @@ def main():
     doc = {}
     if "evaluate" in legs:
         doc["evaluate"] = evaluate_leg(eng, n_in, T, args.reps)
+    if "value" in legs:
+        doc["value"] = value_leg(eng, n_in, T, args.reps)
     if "rollout" not in legs:
         return write(args.out, doc)
 
