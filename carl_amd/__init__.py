@@ -27,6 +27,7 @@ _LAZY = {
     "CARLBraxHalfcheetahStiffness": "carl_amd.envs.brax",  # opt-in extension classes (joint_stiffness feature)
     "CARLBraxHumanoidStiffness": "carl_amd.envs.brax",
     "VecEngine": "carl_amd.engine",
+    "EvolutionStrategy": "carl_amd.es",
 }
 
 

@@ -304,3 +304,16 @@ EXPORTS.update({
                                              C.POINTER(PolicySummary), C.POINTER(PolicyValue), _vp]),
     "carl_gae": (C.c_int, [C.POINTER(Gae), _vp]),
 })
+
+
+# ---- evolution strategies on the device (include/carl_amd.h: carl_es_t) ---------------------------------------
+class Es(C.Structure):
+    _fields_ = [("seed", C.c_uint64), ("generation", C.c_uint32), ("n_pairs", _i), ("set_floats", _i), ("n_noisy", _i),
+                ("sigma", C.c_float), ("reserved", _i)]
+
+
+EXPORTS.update({
+    "carl_es_perturb": (C.c_int, [C.POINTER(Es), _vp, _vp, _vp, _vp]),
+    "carl_es_gradient": (C.c_int, [C.POINTER(Es), _vp, _vp, _vp]),
+    "carl_es_slice_pairs": (C.c_int32, []),
+})

@@ -22,9 +22,10 @@ ARCH = "gfx950"
 # packing that paid (Pendulum's sine / cosine polynomials) is written out by hand in fast_math.hip.h: sincos_fast_pk.
 # carl_policy.hip (the closed-loop rollout) and carl_policy_sample.hip (its sampled twins) instantiate the same device
 # templates as carl_amd.hip, and so does carl_policy_value.hip (the rollout with a critic, and GAE): same flags.
+# carl_es.hip (evolution strategies: perturb / gradient) shares Philox with them and takes the same flags.
 SOURCES = {"carl_amd.hip": ["-fno-slp-vectorize"], "carl_brax.hip": ["-fno-slp-vectorize"],
            "carl_policy.hip": ["-fno-slp-vectorize"], "carl_policy_sample.hip": ["-fno-slp-vectorize"],
-           "carl_policy_value.hip": ["-fno-slp-vectorize"]}
+           "carl_policy_value.hip": ["-fno-slp-vectorize"], "carl_es.hip": ["-fno-slp-vectorize"]}
 
 
 def _hipcc() -> str:

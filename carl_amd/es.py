@@ -1,0 +1,183 @@
+"""Evolution strategies on the device: perturb, evaluate, update (include/carl_amd.h: carl_es_t).
+
+``EvolutionStrategy`` runs one generation of antithetic ES (Salimans et al. 2017; ``fitness_shaping="difference"`` gives
+ARS's raw form, Mania et al. 2018) as a fixed sequence of launches on the engine's stream, with no host synchronisation
+and no Python loop over the population:
+
+1. ``carl_es_perturb`` writes the ``P = n_lanes // lanes_per_set`` weight sets ``centre +- sigma * z_i`` straight into the
+   packed block an ``MLPPolicy.on_device`` policy points at;
+2. the env resets and ``evaluate_policy`` runs every set on its ``lanes_per_set`` lanes in one launch;
+3. each set's fitness is the mean over its lanes of the lane's mean finished-episode return (torch, on the device);
+4. the fitnesses are shaped into one weight per pair;
+5. ``carl_es_gradient`` rebuilds ``sum_i weight[i] * z_i`` by regenerating the noise from its counter -- it is never stored;
+6. the centre moves.
+
+The noise is a pure function of (seed, generation, pair, parameter), like every other random stream here, so a
+generation does not depend on the GPU count or on how many launches it takes.
+
+Choosing contexts: with a static selector and a context count that divides ``lanes_per_set``, every member of the
+population is evaluated on every context once per episode slot -- the CARL question ES is asked here.
+
+Out of scope, and refused as ``carl_amd.policy`` refuses them: the Brax families, ``MixedVecEngine`` pairs, the
+gymnasium drop-in.
+"""
+from __future__ import annotations
+
+import ctypes as C
+from typing import Callable
+
+import torch
+
+from carl_amd import _lib
+from carl_amd.policy import MLPPolicy, _engine_of
+
+
+def centered_rank_weights(fitness: torch.Tensor) -> torch.Tensor:
+    """``[P]`` fitness -> ``[P / 2]`` pair weights: rank by a stable ascending argsort (NaN last, as torch sorts),
+    ``u_k = rank_k / (P - 1) - 0.5`` in float32, ``weight[i] = u_{2i} - u_{2i+1}``."""
+    P = fitness.numel()
+    rank = torch.argsort(torch.argsort(fitness, stable=True), stable=True).to(torch.float32)
+    u = rank / torch.full_like(rank, float(P - 1)) - 0.5
+    return (u[0::2] - u[1::2]).contiguous()
+
+
+def difference_weights(fitness: torch.Tensor) -> torch.Tensor:
+    """``weight[i] = F_{2i} - F_{2i+1}`` (ARS's raw form)."""
+    return (fitness[0::2] - fitness[1::2]).contiguous()
+
+
+def set_fitness(result: dict, n_sets: int) -> torch.Tensor:
+    """Fitness ``[n_sets]`` float32 of an ``evaluate_policy`` result whose lanes are ``n_sets`` equal runs: the mean over
+    a set's lanes of each lane's mean finished-episode return.  A lane without a finished episode is left out; a set
+    without any gets ``-inf``.  Plain torch on the tensors' device (no host synchronisation)."""
+    ret, ep = result["return"], result["episodes"]
+    K = ret.shape[0]
+    valid = torch.arange(K, device=ret.device, dtype=ep.dtype)[:, None] < ep[None, :]
+    lane_mean = torch.where(valid, ret, torch.zeros_like(ret)).sum(dim=0) / ep.to(torch.float32)
+    has = (ep > 0).view(n_sets, -1)
+    lane_mean = lane_mean.view(n_sets, -1)
+    total = torch.where(has, lane_mean, torch.zeros_like(lane_mean)).sum(dim=1)
+    count = has.sum(dim=1).to(torch.float32)
+    return torch.where(count > 0, total / count, torch.full_like(total, float("-inf")))
+
+
+_SHAPING = {"centered_rank": centered_rank_weights, "difference": difference_weights}
+
+
+class EvolutionStrategy:
+    """One ES generation per ``step`` on a classic-control ``CARLEnv`` or ``VecEngine`` with ``auto_reset``.
+
+    ``policy``: a one-set ``MLPPolicy`` for ``env`` -- the shape, the inputs and the starting centre (its shift | scale |
+    clip section is carried into every member unchanged).  The population is ``P = n_lanes // lanes_per_set`` weight sets,
+    even and at least 2; ``n_lanes`` must be exactly ``P * lanes_per_set``.  ``sigma``: the noise scale; ``lr``: the step
+    of the default update ``center[:n_noisy] += lr / (P * sigma) * grad``; ``seed``: the Philox key of the noise.
+    ``fitness_shaping``: ``"centered_rank"``, ``"difference"`` or a callable ``fitness [P] -> weight [P / 2]`` (float32,
+    on the device).  ``optimizer``: a factory ``lambda param: torch.optim.X([param], ...)``: it receives the noisy slice of
+    the centre as a leaf tensor, and each step sets its ``.grad = -grad / (P * sigma)`` and calls ``step()`` instead of
+    the default update.
+
+    ``center``: the ``[set_floats]`` float32 device tensor of the packed centre (readable at any time; assign a tensor to
+    replace its values).  ``generation``: starts at 0, one more per ``step``.  ``population``: the ``on_device`` policy
+    the members are written into."""
+
+    def __init__(self, env, policy: MLPPolicy, lanes_per_set: int = 256, sigma: float = 0.1, lr: float = 0.05, seed: int = 0,
+                 fitness_shaping: str | Callable = "centered_rank", optimizer: Callable | None = None):
+        eng, cenv = _engine_of(env)
+        if not eng.auto_reset:
+            raise ValueError("EvolutionStrategy needs auto_reset=True (evaluate_policy counts whole episodes)")
+        if not isinstance(policy, MLPPolicy) or policy._on_device or policy.n_sets != 1 or policy.lanes_per_set is not None:
+            raise ValueError("EvolutionStrategy: the template must be a one-set host-built MLPPolicy")
+        if policy.head != "policy":
+            raise ValueError("EvolutionStrategy: the template must have head='policy'")
+        if policy.family != eng.family or policy.obs_dim != eng.D:
+            raise ValueError(f"the policy was built for family {policy.family}, this engine runs family {eng.family}")
+        L = int(lanes_per_set)
+        q = int(_lib.load().carl_policy_lane_quantum())
+        if L <= 0 or L % q:
+            raise ValueError(f"lanes_per_set {L} is not a positive multiple of {q}")
+        P = eng.n // L
+        if eng.n != P * L:
+            raise ValueError(f"{eng.n} lanes are not a whole number of sets of {L}: {eng.n - P * L} lanes beyond "
+                             f"{P} x {L} would run without a population member")
+        if P < 2 or P % 2:
+            raise ValueError(f"a population of {P} weight sets ({eng.n} lanes / {L}): it must be even and at least 2 "
+                             "(antithetic pairs)")
+        if not (sigma > 0 and sigma < float("inf")):
+            raise ValueError(f"sigma {sigma}: finite and positive")
+        if not callable(fitness_shaping) and fitness_shaping not in _SHAPING:
+            raise ValueError(f"fitness_shaping {fitness_shaping!r}: one of {sorted(_SHAPING)} or a callable")
+        self.env, self.engine, self._carl_env = env, eng, cenv
+        self.template = policy
+        self.lanes_per_set, self.n_sets, self.n_pairs = L, P, P // 2
+        self.sigma, self.lr, self.seed = float(sigma), float(lr), int(seed) & (2**64 - 1)
+        self.set_floats, self.n_noisy = policy.set_floats, policy.weight_floats
+        self.generation = 0
+        self._shape = fitness_shaping if callable(fitness_shaping) else _SHAPING[fitness_shaping]
+        dev = eng.device
+        self._center = torch.as_tensor(policy.params[0]).to(dev).contiguous().clone()
+        self._params = torch.empty((P, self.set_floats), dtype=torch.float32, device=dev)
+        self.population = MLPPolicy.on_device(policy, self._params, L)
+        self._noisy = self._center[: self.n_noisy]  # (a view: the optimizer's parameter)
+        self._opt = optimizer(self._noisy) if optimizer is not None else None
+        self.lib = _lib.load()
+
+    # ------------------------------------------------------------------ state
+    @property
+    def center(self) -> torch.Tensor:
+        return self._center
+
+    @center.setter
+    def center(self, value) -> None:
+        v = torch.as_tensor(value)
+        if v.dtype != torch.float32 or tuple(v.shape) != (self.set_floats,):
+            raise ValueError(f"center: a float32 [{self.set_floats}] tensor, got {v.dtype} {tuple(v.shape)}")
+        self._center.copy_(v)  # (in place: the optimizer's parameter is a view of this storage)
+
+    def policy(self) -> MLPPolicy:
+        """The centre as a one-set host ``MLPPolicy`` (one device-to-host copy)."""
+        return MLPPolicy.unpack(self.template, self._center.cpu().numpy())
+
+    def struct(self, generation: int | None = None) -> "_lib.Es":
+        """The ``carl_es_t`` of a generation (default: the next ``step``'s)."""
+        es = _lib.Es()
+        es.seed = self.seed
+        es.generation = (self.generation if generation is None else int(generation)) & 0xFFFFFFFF
+        es.n_pairs, es.set_floats, es.n_noisy, es.sigma = self.n_pairs, self.set_floats, self.n_noisy, self.sigma
+        return es
+
+    # ------------------------------------------------------------------ one generation
+    def step(self, n_episodes: int = 1, max_steps: int = 500, deterministic: bool = True,
+             sample_seed: int | None = None) -> dict:
+        """One generation: perturb, reset, ``evaluate_policy`` (``n_episodes`` per lane, at most ``max_steps`` steps;
+        sampled actions with ``deterministic=False``, keyed by ``sample_seed``, default the generation), fitness, shaping,
+        gradient, update.  Returns ``{"fitness" [P], "weight" [P / 2], "grad" [n_noisy], "result": evaluate_policy's
+        dict}``, every value a device tensor.  No host synchronisation."""
+        eng = self.engine
+        es = self.struct()
+        stream = eng._stream()
+        with torch.cuda.device(eng.device):
+            _lib.check(self.lib.carl_es_perturb(C.byref(es), self._center.data_ptr(), self._params.data_ptr(), None, stream))
+        seed = self.generation if sample_seed is None else int(sample_seed)
+        if self._carl_env is not None:
+            res = self._carl_env.evaluate_policy(self.population, n_episodes, max_steps, deterministic=deterministic,
+                                                 sample_seed=seed)
+        else:
+            eng.reset()
+            res = eng.evaluate_policy(self.population, n_episodes, max_steps, deterministic=deterministic, sample_seed=seed)
+        fitness = set_fitness(res, self.n_sets)
+        weight = self._shape(fitness)
+        if (not isinstance(weight, torch.Tensor) or weight.dtype != torch.float32 or weight.device != eng.device
+                or tuple(weight.shape) != (self.n_pairs,)):
+            raise ValueError(f"fitness_shaping must return a float32 [{self.n_pairs}] tensor on {eng.device}")
+        weight = weight.contiguous()
+        grad = torch.empty(self.n_noisy, dtype=torch.float32, device=eng.device)
+        with torch.cuda.device(eng.device):
+            _lib.check(self.lib.carl_es_gradient(C.byref(es), weight.data_ptr(), grad.data_ptr(), stream))
+        scale = self.n_sets * self.sigma
+        if self._opt is None:
+            self._noisy += grad * (self.lr / scale)
+        else:
+            self._noisy.grad = grad * (-1.0 / scale)
+            self._opt.step()
+        self.generation += 1
+        return {"fitness": fitness, "weight": weight, "grad": grad, "result": res}

@@ -27,6 +27,10 @@ same launch on the inputs the actor sees (include/carl_amd.h: carl_rollout_polic
 advantages and returns from one more launch (carl_gae).  The critic reads the actor's transformed inputs, so its
 ``input_shift`` / ``input_scale`` / ``input_clip`` must equal the actor's bit for bit.
 
+Weight sets made on the device: ``MLPPolicy.on_device(template, params, lanes_per_set)`` wraps a caller-owned device
+tensor ``[n_sets, set_floats]`` in the packed layout as a multi-set policy, with no host copy -- what an on-device
+producer of weight sets (``carl_amd.es.EvolutionStrategy``) hands to ``rollout_policy`` / ``evaluate_policy``.
+
 Out of scope: the Brax families, ``MixedVecEngine`` pairs, the gymnasium drop-in (``carl_amd.dropin``) and the
 multi-process helpers (``carl_amd.distributed``).
 """
@@ -143,6 +147,7 @@ class MLPPolicy:
             raise ValueError(f"log_std: one value (state-independent), got {ls.size}")
         self.log_std = ls  # [n_sets] float32: the Gaussian's log standard deviation per weight set (Box families)
         self.lanes_per_set = None  # one set: every lane
+        self._on_device = False  # on_device(): params is the caller's device tensor, never copied
         self._dev = {}
 
     # ------------------------------------------------------------------ construction
@@ -196,6 +201,8 @@ class MLPPolicy:
         if not policies:
             raise ValueError("stack() needs at least one policy")
         p0 = policies[0]
+        if any(p._on_device for p in policies):
+            raise ValueError("stack(): a policy whose parameters live on the device (on_device) is not stacked on the host")
         if head is not None and any(p.head != head for p in policies):
             raise ValueError(f"stack(head={head!r}): every weight set must have that head")
         key = lambda p: (p.family, p.ctx_rows, p.obs_dim, [W.shape for W, _ in p.layers], p.activation, p.head)  # noqa: E731
@@ -213,9 +220,85 @@ class MLPPolicy:
         out._dev = {}
         return out
 
+    @classmethod
+    def on_device(cls, template: "MLPPolicy", params: torch.Tensor, lanes_per_set: int, log_std=None) -> "MLPPolicy":
+        """A multi-set policy whose packed block is the caller's device tensor: ``params`` ``[n_sets, set_floats]``,
+        contiguous float32 on a GPU, 16-byte aligned, each row one weight set in the packed layout (module docstring) --
+        written by whoever owns it, at any time, in stream order; never copied, never read back except for
+        ``transform_section``.  ``template``: a one-set host-built policy that gives the family, the context rows, the
+        shape, the activation and the head (its own weights are not used).  Lane ``l`` uses set ``l // lanes_per_set``
+        (as ``stack``).  ``log_std`` (Box families): a ``[n_sets]`` float32 tensor on the same device, or None: the
+        template's value for every set."""
+        if not isinstance(template, MLPPolicy) or template._on_device or template.n_sets != 1 or template.lanes_per_set is not None:
+            raise ValueError("on_device(): the template must be a one-set host-built MLPPolicy")
+        if not isinstance(params, torch.Tensor):
+            raise ValueError("on_device(): params must be a torch tensor")
+        if params.dtype != torch.float32:
+            raise ValueError(f"on_device(): params must be torch.float32, got {params.dtype}")
+        if params.dim() != 2 or params.shape[0] < 1 or params.shape[1] != template.set_floats:
+            raise ValueError(f"on_device(): params {tuple(params.shape)} is not [n_sets, {template.set_floats}] (the "
+                             "template's set_floats)")
+        if not params.is_contiguous():
+            raise ValueError("on_device(): params must be contiguous")
+        if not params.is_cuda:
+            raise ValueError(f"on_device(): params must live on a GPU, not on {params.device}")
+        if params.data_ptr() % 16:
+            raise ValueError("on_device(): params must start on a 16-byte boundary")
+        q = _lib.load().carl_policy_lane_quantum()
+        if lanes_per_set <= 0 or lanes_per_set % q:
+            raise ValueError(f"lanes_per_set {lanes_per_set} is not a positive multiple of {q}")
+        n_sets = int(params.shape[0])
+        if log_std is None:
+            ls = torch.full((n_sets,), float(template.log_std[0]), dtype=torch.float32, device=params.device)
+        else:
+            if template.discrete or template.head == "value":
+                raise ValueError("log_std: Box policies only")
+            ls = log_std
+            if (not isinstance(ls, torch.Tensor) or ls.device != params.device or ls.dtype != torch.float32
+                    or tuple(ls.shape) != (n_sets,) or not ls.is_contiguous()):
+                raise ValueError(f"on_device(): log_std must be a contiguous float32 [{n_sets}] tensor on {params.device}")
+        out = object.__new__(MLPPolicy)
+        out.__dict__.update(template.__dict__)
+        out.params, out.log_std = params, ls
+        out.lanes_per_set = int(lanes_per_set)
+        out._on_device = True
+        out._dev = {}
+        return out
+
+    @staticmethod
+    def unpack(template: "MLPPolicy", packed, log_std=None) -> "MLPPolicy":
+        """A one-set host policy of ``template``'s family, inputs, shape, activation and head from one packed weight set
+        ``[set_floats]`` (host floats; the inverse of the packing, bit for bit, its shift | scale | clip section
+        included).  ``log_std``: default the template's."""
+        if template._on_device or template.n_sets != 1:
+            raise ValueError("unpack(): the template must be a one-set host-built MLPPolicy")
+        flat = np.ascontiguousarray(np.asarray(packed, dtype=np.float32).reshape(-1))
+        if flat.size != template.set_floats:
+            raise ValueError(f"unpack(): {flat.size} floats, the template's weight set has {template.set_floats}")
+        layers, off = [], 0
+        for W, b in template.layers:
+            layers.append((flat[off: off + W.size].reshape(W.shape), flat[off + W.size: off + W.size + b.size]))
+            off += W.size + b.size
+        n = template.n_in
+        if log_std is None and not template.discrete and template.head != "value":
+            log_std = float(template.log_std[0])
+        return MLPPolicy(template.family, template.obs_dim, template.ctx_rows, layers, template.activation, flat[off: off + n],
+                         flat[off + n: off + 2 * n], flat[off + 2 * n], template.context_names, log_std, template.head)
+
     @property
     def n_sets(self) -> int:
         return int(self.params.shape[0])
+
+    @property
+    def weight_floats(self) -> int:
+        """Leading floats of a packed weight set that are network parameters: the sum of ``W.size + b.size`` over the
+        layers (the shift | scale | clip section and the padding follow)."""
+        return int(sum(W.size + b.size for W, b in self.layers))
+
+    @property
+    def set_floats(self) -> int:
+        """Floats of one packed weight set (``carl_policy_set_floats`` of the shape): a multiple of 4."""
+        return int(self.params.shape[1])
 
     def _pack(self) -> np.ndarray:
         parts = []
@@ -249,17 +332,30 @@ class MLPPolicy:
         return p
 
     def transform_section(self) -> np.ndarray:
-        """The shift | scale | clip section of every packed weight set ``[n_sets, 2 * n_in + 1]`` (a view)."""
-        off = sum(W.size + b.size for W, b in self.layers)
-        return self.params[:, off: off + 2 * self.n_in + 1]
+        """The shift | scale | clip section of every packed weight set ``[n_sets, 2 * n_in + 1]`` (a view; for an
+        ``on_device`` policy a host copy of that section alone: one device-to-host copy)."""
+        off = self.weight_floats
+        sec = self.params[:, off: off + 2 * self.n_in + 1]
+        return sec.cpu().numpy() if self._on_device else sec
 
     def device_params(self, device) -> torch.Tensor:
-        """The packed parameters on ``device`` (uploaded once per device)."""
+        """The packed parameters on ``device`` (uploaded once per device; an ``on_device`` policy returns its own
+        tensor, and raises on another device)."""
+        if self._on_device:
+            return self._own("params", self.params, device)
         return self._upload("params", self.params, device)
 
     def device_log_std(self, device) -> torch.Tensor:
         """``log_std`` ``[n_sets]`` float32 on ``device`` (uploaded once per device)."""
+        if self._on_device:
+            return self._own("log_std", self.log_std, device)
         return self._upload("log_std", self.log_std, device)
+
+    def _own(self, key: str, t: torch.Tensor, device) -> torch.Tensor:
+        dev = torch.device(device)
+        if dev.type != t.device.type or (dev.index is not None and dev.index != t.device.index):
+            raise ValueError(f"this policy's {key} live on {t.device}, the launch runs on {dev}")
+        return t
 
     def _upload(self, key: str, a: np.ndarray, device) -> torch.Tensor:
         dev = torch.device(device)

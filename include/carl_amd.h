@@ -541,6 +541,59 @@ typedef struct carl_gae {
 
 int carl_gae(const carl_gae_t* gae_host, void* stream);
 
+/* ---- evolution strategies on the device: perturb and gradient (additive; ABI version unchanged) ----
+ * The population side of the closed-loop rollout (ES, Salimans et al. 2017; ARS, Mania et al. 2018): a centre parameter
+ * vector -- one packed weight set, the layout above -- is perturbed into n_pairs antithetic pairs of weight sets, written
+ * straight into the [n_sets][carl_policy_set_floats()] block carl_policy_t::params points at (n_sets = 2 * n_pairs: set
+ * 2i is centre + sigma * z_i, set 2i + 1 is centre - sigma * z_i), and after the sets have been evaluated the gradient
+ * estimate sum_i weight[i] * z_i is rebuilt by REGENERATING z from its counter: the noise is never stored.  No reference
+ * counterpart (the reference has no population path: its caller builds one env and one agent, carl/envs/carl_env.py).
+ *
+ * Noise rule.  Parameter j of pair i takes its standard normal z_ij from the Philox4x32-10 block w with key `seed` and
+ * counter (j >> 1, i, generation, 0x40000000): even j uses (a, b) = (w.x, w.y), odd j uses (w.z, w.w), and
+ *   u1 = ((a >> 8) + 1) * 2^-24 in (0, 1],  u2 = (b >> 8) * 2^-24,  z = sqrtf(-2 logf(u1)) * cospif(2 u2)
+ * -- carl_policy_sampling_t's Gaussian rule: the device's accurate fp32 functions, every product rounded on its own
+ * (no fma).  z is a pure function of (seed, generation, i, j): it does not depend on the grid, on how a population is
+ * sharded or on the number of launches.  The last counter word keeps the stream apart from the engine's sub-streams
+ * (0, 1, 2 + elapsed) and from the action draws (0x80000000 | elapsed) even under a shared seed.  |z| <= 5.8
+ * (u1 >= 2^-24).
+ *
+ * carl_es_perturb: for j < n_noisy
+ *   params[2i][j] = center[j] + d,  params[2i + 1][j] = center[j] - d,  d = sigma * z_ij
+ * in fp32 with two roundings each (the product, then the sum; no fma), so NumPy float32 reproduces both from z exactly;
+ * for j in [n_noisy, set_floats) (the shift | scale | clip section and the padding) both sets receive center[j]'s bits
+ * unchanged (a NaN or infinite clip included).  noise[i][j] = z_ij for j < n_noisy when `noise` is not NULL (dense rows
+ * of n_noisy floats; for tests and diagnostics -- carl_es_gradient does not read it).  Every element of params is
+ * written and nothing beyond it.
+ *
+ * carl_es_gradient: grad[j] = sum_i weight[i] * z_ij for j < n_noisy, in this order: the pairs are cut into slices of
+ * carl_es_slice_pairs() consecutive pairs (the last one may be shorter); inside a slice p = +0.0f, then
+ * p = p + weight[i] * z_ij for its pairs in order (fp32, the product and the sum rounded separately, no fma); then
+ * g = +0.0f, g = g + p_s over the slices in order.  The result is a pure function of the inputs whatever the grid (no
+ * floating-point atomics), and a host that holds the noise carl_es_perturb wrote reproduces it bit for bit.  Only
+ * grad[0 .. n_noisy) is written.  No scratch buffer is needed.
+ *
+ * Validation, before anything is enqueued, CARL_ERR_INVALID_ARGUMENT each: a NULL struct, center, params, weight or
+ * grad; n_pairs < 1; set_floats <= 0 or not a multiple of 4; n_noisy outside 1 .. set_floats; sigma not finite or not
+ * positive; 2 * n_pairs * set_floats >= 2^31; params off a 16-byte boundary.  Both calls are stream-ordered and
+ * capturable; the library allocates nothing. */
+typedef struct carl_es {
+  uint64_t seed;        /* Philox key of the noise */
+  uint32_t generation;  /* counter word */
+  int32_t n_pairs;      /* >= 1; the population is 2 * n_pairs weight sets */
+  int32_t set_floats;   /* carl_policy_set_floats() of the shape: > 0, a multiple of 4 */
+  int32_t n_noisy;      /* leading floats of a set that receive noise (every W and b); 1 .. set_floats */
+  float sigma;          /* finite, > 0 */
+  int32_t reserved;
+} carl_es_t;
+
+int carl_es_perturb(const carl_es_t* es_host, const float* center /* DEVICE [set_floats] */,
+                    float* params /* DEVICE [2 * n_pairs][set_floats], 16-byte aligned */,
+                    float* noise /* DEVICE [n_pairs][n_noisy], nullable */, void* stream);
+int carl_es_gradient(const carl_es_t* es_host, const float* weight /* DEVICE [n_pairs] */,
+                     float* grad /* DEVICE [n_noisy] */, void* stream);
+int32_t carl_es_slice_pairs(void); /* pairs of one summation slice of carl_es_gradient (16) */
+
 /* ======================= Brax-locomotion families (spring backend) =======================
  * Replaces CARLBraxEnv + BraxGymWrapper/VectorGymWrapper + brax.spring.pipeline.step x
  * n_frames + brax.envs.<env>.step/reset (carl/envs/brax/carl_brax_env.py:115-336,

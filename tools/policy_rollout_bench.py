@@ -21,10 +21,17 @@
                    (b) VecEngine.gae against the torch reverse loop over the same columns.
                    Written to key "value" of --out.
 
+  --legs es        one ES generation, CartPole x --lanes, --lanes / 256 weight sets of 256 lanes, linear and 2x64 tanh,
+                   n_episodes = 1, max_steps = 500: (a) EvolutionStrategy.step against (b) the way to the same centre
+                   update without it -- NumPy noise, one MLPPolicy per member, stack, upload, evaluate_policy, read-back,
+                   NumPy ranks and sum -- both as a host clock around a generation that ends in a device synchronise;
+                   and the two new launches on their own (device events around 50 back-to-back launches).
+                   Written to key "es" of --out.
+
 Host timing with torch.cuda events around `--reps` launches after one warm-up launch; the median per launch is
 reported.  Kernel times belong to a separate `rocprofv3 --kernel-trace --stats` run of this script.
 
-  python tools/policy_rollout_bench.py [--lanes 65536] [--steps 1000] [--reps 5] [--legs rollout,evaluate] [--out FILE]
+  python tools/policy_rollout_bench.py [--lanes 65536] [--steps 1000] [--reps 5] [--legs rollout,evaluate,value,es] [--out FILE]
 
 --out FILE: a JSON file whose keys of the legs run ("results": rollout, "evaluate") are replaced, others kept.
 """
@@ -210,6 +217,91 @@ def value_leg(eng, n_in, steps, reps, block=64):
     return rows
 
 
+def host_generation(eng, tmpl, center, P, L, sigma, lr, rng, K, max_steps):
+    """one ES generation the way a caller writes it without carl_amd.es: everything around the launch on the host"""
+    N, n = tmpl.weight_floats, tmpl.n_in
+    z = rng.standard_normal((P // 2, N)).astype(np.float32)
+    sets = []
+    for i in range(P // 2):
+        for sign in (1.0, -1.0):
+            flat = center.copy()
+            flat[:N] += np.float32(sign * sigma) * z[i]
+            layers, off = [], 0
+            for W, b in tmpl.layers:
+                layers.append((flat[off: off + W.size].reshape(W.shape), flat[off + W.size: off + W.size + b.size]))
+                off += W.size + b.size
+            sets.append(MLPPolicy.for_env(eng, layers, tmpl.activation, flat[off: off + n], flat[off + n: off + 2 * n],
+                                          float(flat[off + 2 * n])))
+    pop = MLPPolicy.stack(sets, L)
+    eng.reset()
+    res = eng.evaluate_policy(pop, K, max_steps)
+    ret, ep = res["return"].cpu().numpy(), res["episodes"].cpu().numpy()
+    valid = np.arange(K)[:, None] < ep[None, :]
+    with np.errstate(invalid="ignore", divide="ignore"):
+        lane = np.where(valid, ret, 0).sum(0) / ep
+        has = (ep > 0).reshape(P, L)
+        fit = np.where(has, lane.reshape(P, L), 0).sum(1) / has.sum(1)
+    fit = np.where(has.any(1), fit, -np.inf).astype(np.float32)
+    rank = np.empty(P, np.int64)
+    rank[np.argsort(fit, kind="stable")] = np.arange(P)
+    u = rank.astype(np.float32) / np.float32(P - 1) - np.float32(0.5)
+    grad = (u[0::2] - u[1::2]) @ z
+    center[:N] += np.float32(lr / (P * sigma)) * grad
+    return center
+
+
+def es_leg(eng, n_in, reps, L=256, K=1, max_steps=500, sigma=0.1, lr=0.05):
+    import ctypes as C
+    import time
+
+    from carl_amd.es import EvolutionStrategy
+
+    def clock(fn):
+        fn()  # warm-up
+        torch.cuda.synchronize()
+        ts = []
+        for _ in range(reps):
+            t0 = time.perf_counter()
+            fn()
+            torch.cuda.synchronize()
+            ts.append(time.perf_counter() - t0)
+        return float(np.median(ts)), ts
+
+    rows, P = [], eng.n // L
+    for name, widths in {"linear": [], "mlp_2x64_tanh": [64, 64]}.items():
+        tmpl = MLPPolicy.from_sequential(eng, make_mlp(widths, n_in))
+        es = EvolutionStrategy(eng, tmpl, lanes_per_set=L, sigma=sigma, lr=lr, seed=0)
+        sec_a, ts_a = clock(lambda: es.step(n_episodes=K, max_steps=max_steps))
+        res = eng.alloc_policy_episodes(K)
+        eng.reset()
+        sec_e, _ = time_launches(lambda: eng.evaluate_policy(es.population, K, max_steps, out=res), reps)
+        state = {"center": tmpl.params[0].copy(), "rng": np.random.default_rng(0)}
+
+        def host_way():
+            state["center"] = host_generation(eng, tmpl, state["center"], P, L, sigma, lr, state["rng"], K, max_steps)
+
+        sec_b, ts_b = clock(host_way)
+        st = es.struct()
+        stream = torch.cuda.current_stream(eng.device).cuda_stream
+        weight = torch.randn(P // 2, device=eng.device)
+        grad = torch.empty(es.n_noisy, device=eng.device)
+        many = 50
+        sec_p, _ = time_launches(lambda: [_lib.check(eng.lib.carl_es_perturb(C.byref(st), es.center.data_ptr(),
+                                                                             es.population.params.data_ptr(), None, stream))
+                                          for _ in range(many)], reps)
+        sec_g, _ = time_launches(lambda: [_lib.check(eng.lib.carl_es_gradient(C.byref(st), weight.data_ptr(),
+                                                                              grad.data_ptr(), stream))
+                                          for _ in range(many)], reps)
+        r = {"config": f"es_{name}", "lanes": eng.n, "sets": P, "lanes_per_set": L, "n_episodes": K, "max_steps": max_steps,
+             "set_floats": es.set_floats, "n_noisy": es.n_noisy, "es_step_sec": sec_a, "host_generation_sec": sec_b,
+             "host_over_es_step": sec_b / sec_a, "evaluate_policy_launch_sec": sec_e,
+             "perturb_sec_per_launch_back_to_back": sec_p / many, "gradient_sec_per_launch_back_to_back": sec_g / many,
+             "perturb_bytes": 4 * es.set_floats * (P + 1), "reps_sec": {"es_step": ts_a, "host_generation": ts_b}}
+        rows.append(r)
+        print(json.dumps(r), flush=True)
+    return rows
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--lanes", type=int, default=65536)
@@ -229,6 +321,8 @@ def main():
         doc["evaluate"] = evaluate_leg(eng, n_in, T, args.reps)
     if "value" in legs:
         doc["value"] = value_leg(eng, n_in, T, args.reps)
+    if "es" in legs:
+        doc["es"] = es_leg(eng, n_in, args.reps)
     if "rollout" not in legs:
         return write(args.out, doc)
 
