@@ -317,3 +317,21 @@ EXPORTS.update({
     "carl_es_gradient": (C.c_int, [C.POINTER(Es), _vp, _vp, _vp]),
     "carl_es_slice_pairs": (C.c_int32, []),
 })
+
+
+# ---- input statistics inside the episodes launch (include/carl_amd.h: carl_policy_stats_t) --------------------
+class PolicyStats(C.Structure):
+    _fields_ = [("partial", _vp), ("partial_capacity", _i)]
+
+
+class PolicyRunningStats(C.Structure):
+    _fields_ = [("count", _vp), ("mean", _vp), ("m2", _vp)]
+
+
+EXPORTS.update({
+    "carl_policy_stats_workgroups": (C.c_int32, [C.c_int32]),
+    "carl_evaluate_policy_stats": (C.c_int, [C.POINTER(Batch), C.POINTER(Policy), C.POINTER(PolicySampling), C.c_int32,
+                                             C.c_int32, C.POINTER(PolicyEpisodes), C.POINTER(PolicyStats), _vp]),
+    "carl_policy_stats_merge": (C.c_int, [C.POINTER(Policy), C.POINTER(PolicyStats), C.c_int32, _vp, C.c_int32,
+                                          C.POINTER(PolicyRunningStats), C.c_double, C.c_double, _vp, C.c_int32, _vp]),
+})

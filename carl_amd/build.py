@@ -23,9 +23,12 @@ ARCH = "gfx950"
 # carl_policy.hip (the closed-loop rollout) and carl_policy_sample.hip (its sampled twins) instantiate the same device
 # templates as carl_amd.hip, and so does carl_policy_value.hip (the rollout with a critic, and GAE): same flags.
 # carl_es.hip (evolution strategies: perturb / gradient) shares Philox with them and takes the same flags.
+# carl_policy_stats.hip (the episodes launch gathering input statistics, and their merge) instantiates the episodes body
+# once more: same flags.
 SOURCES = {"carl_amd.hip": ["-fno-slp-vectorize"], "carl_brax.hip": ["-fno-slp-vectorize"],
            "carl_policy.hip": ["-fno-slp-vectorize"], "carl_policy_sample.hip": ["-fno-slp-vectorize"],
-           "carl_policy_value.hip": ["-fno-slp-vectorize"], "carl_es.hip": ["-fno-slp-vectorize"]}
+           "carl_policy_value.hip": ["-fno-slp-vectorize"], "carl_es.hip": ["-fno-slp-vectorize"],
+           "carl_policy_stats.hip": ["-fno-slp-vectorize"]}
 
 
 def _hipcc() -> str:

@@ -18,15 +18,20 @@ int policy_set_floats(const carl_policy_t* p) {
   if (p->n_in < 1 || p->n_in > CARL_POLICY_MAX_IN || p->n_out < 1 || p->n_out > 4 || p->n_hidden < 0 ||
       p->n_hidden > CARL_POLICY_MAX_HIDDEN)
     return -1;
-  int64_t total = 0, prev = p->n_in;
+  for (int l = 0; l < p->n_hidden; ++l)
+    if (p->width[l] < 1 || p->width[l] > CARL_POLICY_MAX_WIDTH) return -1;
+  const int64_t total = (int64_t)policy_transform_offset(p) + 2 * (int64_t)p->n_in + 1;
+  return (int)((total + 3) / 4 * 4);
+}
+
+int policy_transform_offset(const carl_policy_t* p) {
+  int total = 0, prev = p->n_in;  // (<= 32 x 64 + 64 x 64 + 4 x 64 + biases: far from 2^31)
   for (int l = 0; l <= p->n_hidden; ++l) {
-    const int64_t w = l < p->n_hidden ? p->width[l] : p->n_out;
-    if (l < p->n_hidden && (w < 1 || w > CARL_POLICY_MAX_WIDTH)) return -1;
+    const int w = l < p->n_hidden ? p->width[l] : p->n_out;
     total += w * prev + w;
     prev = w;
   }
-  total += 2 * (int64_t)p->n_in + 1;
-  return (int)((total + 3) / 4 * 4);
+  return total;
 }
 
 int policy_padded_hidden(const carl_policy_t* p) {

@@ -12,12 +12,9 @@
 #include "policy_host.hpp"
 #include "policy_kernels.hip.h"
 
-namespace {
+namespace carl_host {
 
-using carl_host::check_launch;
-using carl_host::fail;
-
-// what the sampled twins refuse on top of their deterministic twin's checks
+// what the sampled twins refuse on top of their deterministic twin's checks (policy_host.hpp)
 int check_sampling(const char* who, const carl_policy_sampling_t* smp, const carl_family_info_t& fi, bool log_prob_ok) {
   if (smp == nullptr) return fail(CARL_ERR_INVALID_ARGUMENT, "%s: sampling is NULL", who);
   if (!fi.action_is_discrete && smp->log_std == nullptr)
@@ -29,6 +26,14 @@ int check_sampling(const char* who, const carl_policy_sampling_t* smp, const car
     return fail(CARL_ERR_UNSUPPORTED, "%s: sampling->log_prob is not on a 16-byte boundary", who);
   return 0;
 }
+
+}  // namespace carl_host
+
+namespace {
+
+using carl_host::check_launch;
+using carl_host::check_sampling;
+using carl_host::fail;
 
 // a policy_rollout_sampled_kernel instance and the dynamic LDS it takes
 struct SampledKernel {

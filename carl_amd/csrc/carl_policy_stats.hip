@@ -1,0 +1,109 @@
+// carl_policy_stats.hip -- C-ABI entry points of the input statistics of the closed-loop rollout (include/carl_amd.h:
+// carl_evaluate_policy_stats, carl_policy_stats_merge) and their kernel dispatch.  A translation unit of its own, so that
+// every other unit's kernels compile exactly as they did; the validation is carl_policy.hip's and
+// carl_policy_sample.hip's (policy_host.hpp), the kernels are policy_stats_kernels.hip.h's.
+#include <hip/hip_runtime.h>
+
+#include <cmath>
+#include <cstdint>
+
+#include "../../include/carl_amd.h"
+#include "classic_control.hip.h"
+#include "host_common.hpp"
+#include "policy_host.hpp"
+#include "policy_stats_kernels.hip.h"
+
+namespace {
+
+using carl_host::check_launch;
+using carl_host::fail;
+
+int stats_workgroups(int32_t n_lanes) { return n_lanes <= 0 ? 0 : (n_lanes + carl::kPolicyLanes - 1) / carl::kPolicyLanes; }
+
+int check_stats(const char* who, const carl_policy_stats_t* stats, int n_workgroups) {
+  if (stats == nullptr || stats->partial == nullptr)
+    return fail(CARL_ERR_INVALID_ARGUMENT, "%s: stats / stats->partial is NULL", who);
+  if ((reinterpret_cast<uintptr_t>(stats->partial) & 15) != 0)
+    return fail(CARL_ERR_INVALID_ARGUMENT, "%s: stats->partial is not on a 16-byte boundary", who);
+  if (stats->partial_capacity < n_workgroups)
+    return fail(CARL_ERR_INVALID_ARGUMENT, "%s: stats->partial_capacity %d < %d workgroups (carl_policy_stats_workgroups)",
+                who, stats->partial_capacity, n_workgroups);
+  return 0;
+}
+
+// a policy_episodes_stats_kernel instance and the dynamic LDS it takes (the weight set and the waves' float64 sums)
+struct StatsKernel {
+  void (*fn)(carl_batch_t, carl_policy_t, int, carl_policy_episodes_t, int, int, carl_policy_sampling_t, double*);
+  size_t lds;
+};
+
+template <class Fam, int H>
+StatsKernel stats_kernel(bool sampled) {
+  const size_t lds = carl::policy_lds_bytes<Fam, H, true>() + carl::policy_stats_lds_bytes<Fam, H>();
+  if (sampled) return {carl::policy_episodes_stats_kernel<Fam, H, true>, lds};
+  return {carl::policy_episodes_stats_kernel<Fam, H, false>, lds};
+}
+
+template <class Fam>
+int launch_stats(const carl_batch_t* b, const carl_policy_t* p, const carl_policy_sampling_t* smp, int n_episodes,
+                 int max_steps, const carl_policy_episodes_t* out, double* partial, hipStream_t s) {
+  const char* who = "carl_evaluate_policy_stats";
+  const int H = carl_host::policy_padded_hidden(p);
+  const bool sampled = smp != nullptr;
+  const StatsKernel k = H == 0 ? stats_kernel<Fam, 0>(sampled) : H == 32 ? stats_kernel<Fam, 32>(sampled)
+                                                                 : stats_kernel<Fam, 64>(sampled);
+  if (int e = carl_host::ensure_dynamic_lds(reinterpret_cast<const void*>(k.fn), k.lds, who)) return e;
+  const carl_policy_sampling_t smp_r = sampled ? *smp : carl_policy_sampling_t{0, nullptr, nullptr};
+  hipLaunchKernelGGL(k.fn, dim3(stats_workgroups(b->n_lanes)), dim3(carl::kPolicyThreadsSummary), k.lds, s, *b, *p,
+                     carl_host::policy_set_floats(p), *out, n_episodes, max_steps, smp_r, partial);
+  return check_launch(who);
+}
+
+}  // namespace
+
+extern "C" {
+
+int32_t carl_policy_stats_workgroups(int32_t n_lanes) { return stats_workgroups(n_lanes); }
+
+int carl_evaluate_policy_stats(const carl_batch_t* batch, const carl_policy_t* policy_host,
+                               const carl_policy_sampling_t* sampling, int32_t n_episodes, int32_t max_steps,
+                               const carl_policy_episodes_t* episodes_out, const carl_policy_stats_t* stats, void* stream) {
+  const char* who = "carl_evaluate_policy_stats";
+  carl_family_info_t fi;
+  if (int e = carl_host::check_evaluate_policy(who, batch, policy_host, n_episodes, max_steps, episodes_out, &fi)) return e;
+  if (sampling != nullptr)
+    if (int e = carl_host::check_sampling(who, sampling, fi, false)) return e;
+  if (int e = check_stats(who, stats, stats_workgroups(batch->n_lanes))) return e;
+  if (batch->n_lanes == 0) return 0;
+  return carl_host::with_classic_family(batch, [&](auto fam) {
+    return launch_stats<decltype(fam)>(batch, policy_host, sampling, n_episodes, max_steps, episodes_out, stats->partial,
+                                       (hipStream_t)stream);
+  });
+}
+
+int carl_policy_stats_merge(const carl_policy_t* policy_host, const carl_policy_stats_t* stats, int32_t n_workgroups,
+                            const int32_t* steps, int32_t n_lanes, const carl_policy_running_stats_t* running, double eps,
+                            double min_std, float* params_out, int32_t n_write, void* stream) {
+  const char* who = "carl_policy_stats_merge";
+  if (policy_host == nullptr) return fail(CARL_ERR_INVALID_ARGUMENT, "%s: policy is NULL", who);
+  const int set_floats = carl_host::policy_set_floats(policy_host);
+  if (set_floats < 0) return fail(CARL_ERR_INVALID_ARGUMENT, "%s: the policy's shape is outside the limits", who);
+  if (policy_host->params == nullptr) return fail(CARL_ERR_INVALID_ARGUMENT, "%s: params is NULL", who);
+  if (n_workgroups < 0) return fail(CARL_ERR_INVALID_ARGUMENT, "%s: n_workgroups %d < 0", who, n_workgroups);
+  if (int e = check_stats(who, stats, n_workgroups)) return e;
+  if (n_lanes < 0) return fail(CARL_ERR_INVALID_ARGUMENT, "%s: n_lanes %d < 0", who, n_lanes);
+  if (steps == nullptr && n_lanes > 0) return fail(CARL_ERR_INVALID_ARGUMENT, "%s: steps is NULL", who);
+  if (running == nullptr || !running->count || !running->mean || !running->m2)
+    return fail(CARL_ERR_INVALID_ARGUMENT, "%s: running and its three arrays are required", who);
+  if (!std::isfinite(eps) || eps < 0.0) return fail(CARL_ERR_INVALID_ARGUMENT, "%s: eps %g is not finite and >= 0", who, eps);
+  if (!std::isfinite(min_std) || min_std < 0.0)
+    return fail(CARL_ERR_INVALID_ARGUMENT, "%s: min_std %g is not finite and >= 0", who, min_std);
+  if (n_write < 0) return fail(CARL_ERR_INVALID_ARGUMENT, "%s: n_write %d < 0", who, n_write);
+  const int p_shift = carl_host::policy_transform_offset(policy_host);
+  hipLaunchKernelGGL(carl::policy_stats_merge_kernel, dim3(1), dim3(carl::kStatsMergeThreads), 0, (hipStream_t)stream,
+                     stats->partial, n_workgroups, steps, n_lanes, policy_host->n_in, policy_host->params + p_shift,
+                     running->count, running->mean, running->m2, eps, min_std, params_out, n_write, set_floats, p_shift);
+  return check_launch(who);
+}
+
+}  // extern "C"

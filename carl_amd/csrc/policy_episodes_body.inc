@@ -1,7 +1,8 @@
 // policy_episodes_body.inc -- the body of policy_episodes_kernel and policy_episodes_sampled_kernel
 // (policy_kernels.hip.h), included textually inside each, as policy_rollout_body.inc.  In scope: Fam, H, the kernel
 // arguments b, pol, set_floats, ep, n_episodes, max_steps; `Pick` (ModePick / SampledPick without log-probabilities) and `pick`,
-// which chooses each step's action.
+// which chooses each step's action; `Stats` and `istats` (NoInputStats: nothing, or policy_stats_kernels.hip.h's InputStats,
+// which gathers the raw inputs' sums of every live lane-step).
   using L = PolicyLayout<Fam, H>;
   using Action = typename Fam::Action;
   constexpr int CHUNK = policy_chunk<Fam>();
@@ -16,6 +17,7 @@
   const uint64_t glane = (uint64_t)(b.lane_offset + lane);
   const size_t n = (size_t)b.n_lanes;
   __syncthreads();
+  if constexpr (Stats::kOn) istats.begin(wts + L::kFloats);
 
   LaneRegs<Fam> r{};
   load_staged_lane<Fam>(b, ctx, lane, active, r);
@@ -36,6 +38,7 @@
     for (int u = 0; u < n_u; ++u) {
       if (ballot(live) == 0ull) break;
       if (ballot(r.cidx != x_cidx) != 0ull) {
+        if constexpr (Stats::kOn) istats.flush_context(ctx, pol, wts, n_ctx, x_cidx);
 #pragma unroll
         for (int k = 0; k < Fam::F; ++k)
           if (k < n_ctx) x[k] = normalize_input(ctx.get(pol.ctx_rows[k], r.cidx), wts[L::kShift + k], wts[L::kScale + k], clip);
@@ -43,6 +46,7 @@
       }
       float o[Fam::D];
       Fam::observe(r.s, r.aux, o);
+      if constexpr (Stats::kOn) istats.add_step(live, o, wts);
 #pragma unroll
       for (int d = 0; d < Fam::D; ++d)
         x[Fam::F + d] = normalize_input(o[d], wts[L::kShift + Fam::F + d], wts[L::kScale + Fam::F + d], clip);
@@ -67,7 +71,9 @@
       }
       live = live && done_eps < n_episodes;
     }
+    if constexpr (Stats::kOn) istats.flush(ctx, pol, wts, n_ctx, x_cidx);
   }
+  if constexpr (Stats::kOn) istats.store(wts + L::kFloats, n_ctx, pol.n_in);
   if (active) {
     store_lane<Fam>(b, ctx, lane, r);
     ep.episodes[lane] = done_eps;

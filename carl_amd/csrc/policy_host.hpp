@@ -9,6 +9,8 @@
 namespace carl_host {
 // floats of one packed weight set (include/carl_amd.h), or -1 for a shape outside the limits
 int policy_set_floats(const carl_policy_t* p);
+// floats of a packed weight set before its shift | scale | clip section (every W and b); the shape is a valid one
+int policy_transform_offset(const carl_policy_t* p);
 // the instantiated hidden width a policy is padded to: 0 (a linear policy), 32, 64
 int policy_padded_hidden(const carl_policy_t* p);
 
@@ -18,6 +20,9 @@ int check_rollout_policy(const char* who, const carl_batch_t* batch, const carl_
                          int32_t n_steps, const carl_policy_summary_t* summary_out, carl_family_info_t* fi);
 int check_evaluate_policy(const char* who, const carl_batch_t* batch, const carl_policy_t* policy, int32_t n_episodes,
                           int32_t max_steps, const carl_policy_episodes_t* out, carl_family_info_t* fi);
+// what the sampled twins refuse on top of their deterministic twin's checks (defined in carl_policy_sample.hip);
+// log_prob_ok: the mode stores per-step columns
+int check_sampling(const char* who, const carl_policy_sampling_t* smp, const carl_family_info_t& fi, bool log_prob_ok);
 // a validated rollout without a step (n_lanes == 0 or n_steps == 0): zero the summary totals, if any
 int policy_rollout_without_steps(const char* who, const carl_batch_t* batch, const carl_policy_summary_t* summary_out,
                                  void* stream);

@@ -398,6 +398,13 @@ struct TermSink {
   __device__ __forceinline__ float* final_obs_ptr() const { return nullptr; }
 };
 
+// episodes mode without input statistics: the body's `if constexpr (Stats::kOn)` statements are discarded, no code
+// (policy_stats_kernels.hip.h: InputStats gathers them, in a kernel of its own)
+template <class Fam, int H>
+struct NoInputStats {
+  static constexpr bool kOn = false;
+};
+
 // Episodes mode (include/carl_amd.h: carl_evaluate_policy): the summary instantiation's layout -- 256 threads, four
 // compute waves, one weight set in LDS, no storer waves -- with a per-lane `live` predicate.  A lane is live while it
 // has finished fewer than K episodes and taken fewer than max_steps steps; the step runs through step_lane's
@@ -412,6 +419,8 @@ __global__ void __launch_bounds__(kPolicyThreadsSummary)
                            const carl_policy_episodes_t ep, const int n_episodes, const int max_steps) {
   using Pick = ModePick<Fam>;
   const Pick pick{};
+  using Stats = NoInputStats<Fam, H>;
+  [[maybe_unused]] Stats istats;
 #include "policy_episodes_body.inc"
 }
 
@@ -423,6 +432,8 @@ __global__ void __launch_bounds__(kPolicyThreadsSummary)
                                    const carl_policy_sampling_t smp) {
   using Pick = SampledPick<Fam, false>;
   const Pick pick = Pick::of(smp, pol);
+  using Stats = NoInputStats<Fam, H>;
+  [[maybe_unused]] Stats istats;
 #include "policy_episodes_body.inc"
 }
 

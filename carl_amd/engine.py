@@ -893,7 +893,7 @@ class VecEngine(LaneEngine):
                 for k, dt, rows in self._EPISODE_KEYS}
 
     def evaluate_policy(self, policy, n_episodes: int, max_steps: int, out: dict | None = None,
-                        deterministic: bool = True, sample_seed: int = 0) -> dict:
+                        deterministic: bool = True, sample_seed: int = 0, input_stats: bool = False) -> dict:
         """Run ``policy`` (``carl_amd.policy.MLPPolicy``) on every lane until the lane has finished ``n_episodes``
         episodes or taken ``max_steps`` steps, in ONE launch, from the current engine state (a running episode is counted
         with its full length; ``CARLEnv.evaluate_policy`` resets first).  Returns ``alloc_policy_episodes``' dict:
@@ -903,7 +903,12 @@ class VecEngine(LaneEngine):
         for the steps each lane took.  Needs ``auto_reset``.  ``carl_amd.policy.episode_stats`` reduces the result per
         context.  No host synchronisation.  ``deterministic=False``: sampled actions, as ``rollout_policy``'s (SB3's
         ``evaluate_policy(..., deterministic=False)``); the records are then those of a sampled transitions launch with
-        the same ``sample_seed``."""
+        the same ``sample_seed``.  ``input_stats=True``: the launch also gathers, for every live lane-step, the sums of
+        ``d = x_raw - shift`` and ``d * d`` of every policy input (include/carl_amd.h: carl_evaluate_policy_stats); the
+        result gains ``"input_partial"``, the float64 ``[workgroups, 2, 32]`` device tensor of per-workgroup sums that
+        ``carl_amd.policy.InputStats.update`` merges (with ``input_stats=False`` a reused ``out`` loses that key, so the
+        sums of an earlier launch are never merged beside this launch's ``steps``).  Records and engine state are the
+        same bits either way."""
         if policy.family != self.family or policy.obs_dim != self.D:
             raise ValueError(f"the policy was built for family {policy.family}, this engine runs family {self.family}")
         if not self.auto_reset:
@@ -927,6 +932,22 @@ class VecEngine(LaneEngine):
         pol = policy.struct(self.n, params.data_ptr())
         eps = _lib.PolicyEpisodes(*(_ptr(res[k]) for k, _, _ in self._EPISODE_KEYS))
         smp = self._sampling(policy, deterministic, sample_seed)
+        if input_stats:
+            n_wg = int(self.lib.carl_policy_stats_workgroups(self.n))
+            partial = res.get("input_partial")
+            if partial is None:
+                partial = res["input_partial"] = torch.empty((n_wg, 2, _lib.POLICY_MAX_IN), dtype=torch.float64,
+                                                             device=self.device)
+            if (partial.device != self.device or partial.dtype != torch.float64 or not partial.is_contiguous()
+                    or tuple(partial.shape) != (n_wg, 2, _lib.POLICY_MAX_IN)):
+                raise ValueError(f"evaluate_policy output 'input_partial' must be a contiguous torch.float64 "
+                                 f"[{n_wg}, 2, {_lib.POLICY_MAX_IN}] tensor on {self.device}")
+            st = _lib.PolicyStats(_ptr(partial), n_wg)
+            with torch.cuda.device(self.device):
+                _lib.check(self.lib.carl_evaluate_policy_stats(self._b_ref, C.byref(pol), None if smp is None else C.byref(smp),
+                                                               K, T, C.byref(eps), C.byref(st), self._stream()))
+            return res
+        res.pop("input_partial", None)  # a reused dict must not carry an earlier launch's sums beside this launch's steps
         with torch.cuda.device(self.device):
             if smp is None:
                 _lib.check(self.lib.carl_evaluate_policy(self._b_ref, C.byref(pol), K, T, C.byref(eps), self._stream()))

@@ -326,14 +326,15 @@ class CARLEnv(abc.ABC):
                                        value_net=value_net, bootstrap_truncated=bootstrap_truncated, gae=gae)
 
     def evaluate_policy(self, policy, n_episodes: int, max_steps: int, seed: int | None = None,
-                        deterministic: bool = True, sample_seed: int = 0) -> dict:
+                        deterministic: bool = True, sample_seed: int = 0, input_stats: bool = False) -> dict:
         """``n_episodes`` whole episodes of ``policy`` per lane (at most ``max_steps`` steps) in one launch:
-        ``reset(seed=seed)``, then ``VecEngine.evaluate_policy`` (sampled actions with ``deterministic=False``).
+        ``reset(seed=seed)``, then ``VecEngine.evaluate_policy`` (sampled actions with ``deterministic=False``;
+        ``input_stats=True``: the launch also gathers the policy inputs' sums, see there).
         ``carl_amd.policy.episode_stats`` reduces the result per context (mean / std return, as SB3's
         ``evaluate_policy`` reports them)."""
         self.reset(seed=seed)
         return self.env.evaluate_policy(policy, n_episodes, max_steps, deterministic=deterministic,
-                                        sample_seed=sample_seed)
+                                        sample_seed=sample_seed, input_stats=input_stats)
 
     def _views(self) -> dict:
         eng = self.env

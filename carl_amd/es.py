@@ -15,6 +15,12 @@ and no Python loop over the population:
 The noise is a pure function of (seed, generation, pair, parameter), like every other random stream here, so a
 generation does not depend on the GPU count or on how many launches it takes.
 
+Input normalisation (ARS V2): with ``normalize_inputs=True`` the evaluation launch also gathers the sums of every input
+every member visited (``evaluate_policy(..., input_stats=True)``), and after the centre has moved one more small launch
+merges them into the running mean and variance (``self.input_stats``, ``carl_amd.policy.InputStats``) and writes the
+shift and scale they imply into the centre's transform section.  The next generation's ``carl_es_perturb`` carries that
+section into every member, so the statistics of generation g act from generation g + 1.  Still no host synchronisation.
+
 Choosing contexts: with a static selector and a context count that divides ``lanes_per_set``, every member of the
 population is evaluated on every context once per episode slot -- the CARL question ES is asked here.
 
@@ -29,7 +35,7 @@ from typing import Callable
 import torch
 
 from carl_amd import _lib
-from carl_amd.policy import MLPPolicy, _engine_of
+from carl_amd.policy import InputStats, MLPPolicy, _engine_of
 
 
 def centered_rank_weights(fitness: torch.Tensor) -> torch.Tensor:
@@ -74,14 +80,16 @@ class EvolutionStrategy:
     ``fitness_shaping``: ``"centered_rank"``, ``"difference"`` or a callable ``fitness [P] -> weight [P / 2]`` (float32,
     on the device).  ``optimizer``: a factory ``lambda param: torch.optim.X([param], ...)``: it receives the noisy slice of
     the centre as a leaf tensor, and each step sets its ``.grad = -grad / (P * sigma)`` and calls ``step()`` instead of
-    the default update.
+    the default update.  ``normalize_inputs``: keep running statistics of the policy inputs and normalise the next
+    generation's inputs by them (module docstring); ``stats_eps`` / ``stats_min_std``: ``InputStats``' ``eps`` / ``min_std``.
 
     ``center``: the ``[set_floats]`` float32 device tensor of the packed centre (readable at any time; assign a tensor to
     replace its values).  ``generation``: starts at 0, one more per ``step``.  ``population``: the ``on_device`` policy
-    the members are written into."""
+    the members are written into.  ``input_stats``: the ``InputStats`` of ``normalize_inputs=True``, else None."""
 
     def __init__(self, env, policy: MLPPolicy, lanes_per_set: int = 256, sigma: float = 0.1, lr: float = 0.05, seed: int = 0,
-                 fitness_shaping: str | Callable = "centered_rank", optimizer: Callable | None = None):
+                 fitness_shaping: str | Callable = "centered_rank", optimizer: Callable | None = None,
+                 normalize_inputs: bool = False, stats_eps: float = 1e-8, stats_min_std: float = 1e-6):
         eng, cenv = _engine_of(env)
         if not eng.auto_reset:
             raise ValueError("EvolutionStrategy needs auto_reset=True (evaluate_policy counts whole episodes)")
@@ -120,6 +128,7 @@ class EvolutionStrategy:
         self._noisy = self._center[: self.n_noisy]  # (a view: the optimizer's parameter)
         self._opt = optimizer(self._noisy) if optimizer is not None else None
         self.lib = _lib.load()
+        self.input_stats = InputStats(policy, dev, stats_eps, stats_min_std) if normalize_inputs else None
 
     # ------------------------------------------------------------------ state
     @property
@@ -150,7 +159,7 @@ class EvolutionStrategy:
              sample_seed: int | None = None) -> dict:
         """One generation: perturb, reset, ``evaluate_policy`` (``n_episodes`` per lane, at most ``max_steps`` steps;
         sampled actions with ``deterministic=False``, keyed by ``sample_seed``, default the generation), fitness, shaping,
-        gradient, update.  Returns ``{"fitness" [P], "weight" [P / 2], "grad" [n_noisy], "result": evaluate_policy's
+        gradient, update (and, with ``normalize_inputs``, the statistics' merge into the centre).  Returns ``{"fitness" [P], "weight" [P / 2], "grad" [n_noisy], "result": evaluate_policy's
         dict}``, every value a device tensor.  No host synchronisation."""
         eng = self.engine
         es = self.struct()
@@ -158,12 +167,14 @@ class EvolutionStrategy:
         with torch.cuda.device(eng.device):
             _lib.check(self.lib.carl_es_perturb(C.byref(es), self._center.data_ptr(), self._params.data_ptr(), None, stream))
         seed = self.generation if sample_seed is None else int(sample_seed)
+        kw = dict(deterministic=deterministic, sample_seed=seed)
+        if self.input_stats is not None:
+            kw["input_stats"] = True
         if self._carl_env is not None:
-            res = self._carl_env.evaluate_policy(self.population, n_episodes, max_steps, deterministic=deterministic,
-                                                 sample_seed=seed)
+            res = self._carl_env.evaluate_policy(self.population, n_episodes, max_steps, **kw)
         else:
             eng.reset()
-            res = eng.evaluate_policy(self.population, n_episodes, max_steps, deterministic=deterministic, sample_seed=seed)
+            res = eng.evaluate_policy(self.population, n_episodes, max_steps, **kw)
         fitness = set_fitness(res, self.n_sets)
         weight = self._shape(fitness)
         if (not isinstance(weight, torch.Tensor) or weight.dtype != torch.float32 or weight.device != eng.device
@@ -179,5 +190,7 @@ class EvolutionStrategy:
         else:
             self._noisy.grad = grad * (-1.0 / scale)
             self._opt.step()
+        if self.input_stats is not None:  # the members still hold the shift this generation ran under
+            self.input_stats.update(res, self._center, n_write=1, policy=self.population, stream=stream)
         self.generation += 1
         return {"fitness": fitness, "weight": weight, "grad": grad, "result": res}

@@ -31,6 +31,11 @@ Weight sets made on the device: ``MLPPolicy.on_device(template, params, lanes_pe
 tensor ``[n_sets, set_floats]`` in the packed layout as a multi-set policy, with no host copy -- what an on-device
 producer of weight sets (``carl_amd.es.EvolutionStrategy``) hands to ``rollout_policy`` / ``evaluate_policy``.
 
+Input normalisation from the device: ``evaluate_policy(..., input_stats=True)`` gathers the sums of every input the
+lanes visited inside the launch, and ``InputStats`` keeps their running mean and variance on the device and writes the
+``shift`` / ``scale`` they imply into packed weight sets (include/carl_amd.h: carl_policy_stats_merge) -- ARS V2's state
+normalisation, which ``carl_amd.es.EvolutionStrategy(normalize_inputs=True)`` runs every generation.
+
 Out of scope: the Brax families, ``MixedVecEngine`` pairs, the gymnasium drop-in (``carl_amd.dropin``) and the
 multi-process helpers (``carl_amd.distributed``).
 """
@@ -364,6 +369,126 @@ class MLPPolicy:
             t = torch.as_tensor(a).to(dev).contiguous()
             self._dev[(key, dev)] = t
         return t
+
+
+class InputStats:
+    """Running count, mean and M2 (sum of squared deviations) of a policy's inputs, float64 on the device, merged from
+    ``evaluate_policy(..., input_stats=True)`` results by one small launch each (carl_policy_stats_merge) with no host
+    synchronisation.  ``template``: a policy of the shape the launches run (its context rows and layer sizes give the
+    input count and the offset of the transform section).  ``eps``: ``scale = 1 / sqrt(var + eps)``; ``min_std``: an input
+    whose variance is at most ``max(min_std^2, (2^-18 |mean|)^2)`` counts as constant and gets ``scale = 0``."""
+
+    def __init__(self, template: MLPPolicy, device, eps: float = 1e-8, min_std: float = 1e-6):
+        if not isinstance(template, MLPPolicy):
+            raise TypeError("InputStats: the template must be an MLPPolicy")
+        if not (0 <= eps < float("inf")) or not (0 <= min_std < float("inf")):
+            raise ValueError(f"eps {eps} / min_std {min_std}: finite and >= 0")
+        self.template, self.device = template, torch.device(device)
+        self.n_in, self.eps, self.min_std = template.n_in, float(eps), float(min_std)
+        self._count = torch.zeros(1, dtype=torch.int64, device=self.device)
+        self._mean = torch.zeros(_lib.POLICY_MAX_IN, dtype=torch.float64, device=self.device)
+        self._m2 = torch.zeros(_lib.POLICY_MAX_IN, dtype=torch.float64, device=self.device)
+
+    @property
+    def count(self) -> torch.Tensor:
+        """Lane-steps merged so far: an int64 ``[1]`` device tensor."""
+        return self._count
+
+    @property
+    def mean(self) -> torch.Tensor:
+        """``[n_in]`` float64 device tensor."""
+        return self._mean[: self.n_in]
+
+    @property
+    def var(self) -> torch.Tensor:
+        """``M2 / count`` (ddof 0, as VecNormalize), ``[n_in]`` float64 on the device; NaN before the first merge."""
+        return self._m2[: self.n_in] / self._count.to(torch.float64)
+
+    def update(self, result: dict, policy_or_block=None, n_write: int | None = None, policy: MLPPolicy | None = None,
+               stream: int | None = None) -> None:
+        """Merge one ``evaluate_policy(..., input_stats=True)`` result.  ``policy``: the policy that launch ran (default:
+        ``policy_or_block`` when that is a policy) -- the merge reads the shift the launch ran under from its weight set
+        0, so it must still hold it, and for a policy of several weight sets every set must have carried that same
+        shift during the launch (the sums are centred on it; nothing here can check this without a synchronisation --
+        ``EvolutionStrategy`` guarantees it, since the perturbation copies the centre's transform into every member).
+        Merge a result once: a second ``update`` of the same result counts its lane-steps twice.  ``policy_or_block``: an ``on_device`` policy, or a float32 device tensor of packed
+        weight sets (``[set_floats]`` or ``[n, set_floats]``), whose first ``n_write`` sets (default: all) receive the new
+        shift and scale; None: only the running state moves.  Stream-ordered on ``stream`` (default: the current one)."""
+        partial, steps = result.get("input_partial"), result["steps"]
+        if partial is None:
+            raise ValueError("InputStats.update: the result has no 'input_partial' (evaluate_policy(..., input_stats=True))")
+        block, ran = None, policy
+        if isinstance(policy_or_block, MLPPolicy):
+            if not policy_or_block._on_device:
+                raise ValueError("InputStats.update: a host-built policy is not written on the device (apply_to copies)")
+            block, ran = policy_or_block.params, policy_or_block if ran is None else ran
+        elif policy_or_block is not None:
+            block = policy_or_block
+        if ran is None:
+            raise ValueError("InputStats.update: policy= (the policy the launch ran) is needed to read its shift")
+        S = self.template.set_floats
+        if (ran.n_in != self.n_in or ran.weight_floats != self.template.weight_floats or ran.set_floats != S):
+            raise ValueError("InputStats.update: the policy's shape is not the template's")
+        n_blocks = 0
+        if block is not None:
+            if (not isinstance(block, torch.Tensor) or block.dtype != torch.float32 or block.device != self.device
+                    or not block.is_contiguous() or block.numel() % S or block.dim() not in (1, 2)
+                    or (block.dim() == 2 and block.shape[1] != S) or (block.dim() == 1 and block.numel() != S)):
+                raise ValueError(f"InputStats.update: the block must be a contiguous float32 [{S}] or [n, {S}] tensor on "
+                                 f"{self.device}")
+            n_blocks = block.numel() // S
+            n_write = n_blocks if n_write is None else int(n_write)
+            if not 0 <= n_write <= n_blocks:
+                raise ValueError(f"n_write {n_write} outside [0, {n_blocks}]")
+        params = ran.device_params(self.device)
+        pol = ran.struct(int(steps.numel()), params.data_ptr())
+        st = _lib.PolicyStats(partial.data_ptr(), int(partial.shape[0]))
+        run = _lib.PolicyRunningStats(self._count.data_ptr(), self._mean.data_ptr(), self._m2.data_ptr())
+        if stream is None:
+            stream = torch.cuda.current_stream(self.device).cuda_stream
+        with torch.cuda.device(self.device):
+            _lib.check(_lib.load().carl_policy_stats_merge(
+                C.byref(pol), C.byref(st), int(partial.shape[0]), steps.data_ptr(), int(steps.numel()), C.byref(run),
+                self.eps, self.min_std, None if block is None else block.data_ptr(), n_write if block is not None else 0,
+                stream))
+
+    def transform(self) -> tuple[np.ndarray, np.ndarray]:
+        """``(shift, scale)`` float32 ``[n_in]`` the running statistics imply, by the merge's rule, on the host (one
+        device-to-host copy)."""
+        host = torch.cat([self._count.to(torch.float64), self._mean, self._m2]).cpu().numpy()
+        n, mean, m2 = host[0], host[1: 1 + self.n_in], host[1 + _lib.POLICY_MAX_IN: 1 + _lib.POLICY_MAX_IN + self.n_in]
+        if n == 0:
+            raise ValueError("InputStats: nothing merged yet")
+        var = m2 / n
+        floor = np.maximum(self.min_std * self.min_std, (2.0 ** -18 * np.abs(mean)) ** 2)
+        with np.errstate(divide="ignore"):
+            scale = np.where(var <= floor, 0.0, 1.0 / np.sqrt(var + self.eps))
+        return mean.astype(np.float32), scale.astype(np.float32)
+
+    def apply_to(self, policy: MLPPolicy) -> MLPPolicy:
+        """A one-set host-built policy of ``policy``'s weights with the statistics' shift and scale (its clip is kept)."""
+        if policy._on_device or policy.n_sets != 1 or policy.n_in != self.n_in:
+            raise ValueError("InputStats.apply_to: a one-set host-built policy with the template's inputs")
+        shift, scale = self.transform()
+        flat = policy.params[0].copy()
+        off = policy.weight_floats
+        flat[off: off + self.n_in], flat[off + self.n_in: off + 2 * self.n_in] = shift, scale
+        return MLPPolicy.unpack(policy, flat)
+
+    def state_dict(self) -> dict:
+        """``{"count", "mean", "m2"}`` as host tensors (one copy each)."""
+        return {"count": self._count.cpu().clone(), "mean": self._mean[: self.n_in].cpu().clone(),
+                "m2": self._m2[: self.n_in].cpu().clone()}
+
+    def load_state_dict(self, state: dict) -> None:
+        count, mean, m2 = (torch.as_tensor(state[k]) for k in ("count", "mean", "m2"))
+        if count.numel() != 1 or mean.numel() != self.n_in or m2.numel() != self.n_in:
+            raise ValueError(f"InputStats.load_state_dict: count [1], mean / m2 [{self.n_in}]")
+        self._count.copy_(count.reshape(1).to(torch.int64))
+        self._mean.zero_()
+        self._m2.zero_()
+        self._mean[: self.n_in].copy_(mean.reshape(-1).to(torch.float64))
+        self._m2[: self.n_in].copy_(m2.reshape(-1).to(torch.float64))
 
 
 def episode_stats(result: dict, n_contexts: int | None = None) -> dict:

@@ -594,6 +594,88 @@ int carl_es_gradient(const carl_es_t* es_host, const float* weight /* DEVICE [n_
                      float* grad /* DEVICE [n_noisy] */, void* stream);
 int32_t carl_es_slice_pairs(void); /* pairs of one summation slice of carl_es_gradient (16) */
 
+/* ---- input statistics inside the episodes launch, and their running merge (additive; ABI version unchanged) ----
+ * What produces the shift and scale of the input transform above (SB3's VecNormalize; ARS V2, Mania et al. 2018: the
+ * mean and variance of every state every member of a population visited, applied to the next generation's inputs).
+ * In episodes mode no per-step output exists, so the sums are gathered inside the launch.  No reference counterpart.
+ *
+ * carl_evaluate_policy_stats is carl_evaluate_policy (sampling == NULL) or carl_evaluate_policy_sampled (sampling !=
+ * NULL): the records, the engine state and the bookkeeping are theirs bit for bit.  In addition, for every LIVE
+ * lane-step (the steps `episodes_out.steps` counts: a frozen lane and a padding lane add nothing) and every policy
+ * input i < n_in, in FlattenObservation order (the n_ctx context inputs, then the observation):
+ *     d_i = fp32(x_i - shift_i)       x_i the raw input, shift_i that of the lane's weight set: the first operation
+ *                                     of the input transform, before the scale and the clip
+ *     S1_i += d_i,  S2_i += d_i * d_i
+ * (the shifted-data algorithm: once the shift tracks the mean, the variance suffers no cancellation).  Workgroup w --
+ * lanes [256 w, 256 w + 256) -- writes its own sums to partial[w][0][i] (S1) and partial[w][1][i] (S2), float64,
+ * partial being [n_workgroups][2][CARL_POLICY_MAX_IN]; entries i >= n_in receive +0.0.  Every workgroup writes its slab
+ * in full, so nothing needs clearing, and max_steps == 0 writes zeros.  The number of lane-steps is not stored again:
+ * it is the sum of episodes_out.steps.
+ * Accuracy: for an observation input a lane adds in fp32 (S2 by one fma per step) over at most one chunk of 8 steps (4
+ * for Acrobot); the chunk partials are widened to float64, added across the wavefront in a fixed order and accumulated in
+ * float64 from there on.  So |S1_i - exact| <= 10 * 2^-24 * sum |d_i|, likewise S2_i against sum d_i^2.  A context
+ * input, constant while the lane stays in one context, enters as c * d_i and c * d_i * d_i formed in float64, c the
+ * lane's steps in that context since the last chunk boundary (<= 8): both products are exact, so a context input's
+ * sums carry float64 rounding only.  No floating-point atomics: the slabs are a fixed function of the launch's inputs,
+ * the same bits whatever the grid's schedule.
+ * Validation: everything carl_evaluate_policy (and, with `sampling`, carl_evaluate_policy_sampled) validates, in the
+ * same order with the same codes; then `stats` and stats->partial non-NULL, partial on a 16-byte boundary and
+ * partial_capacity >= carl_policy_stats_workgroups(n_lanes): CARL_ERR_INVALID_ARGUMENT before anything is enqueued. */
+typedef struct carl_policy_stats {
+  double* partial;          /* DEVICE [partial_capacity][2][CARL_POLICY_MAX_IN] float64 */
+  int32_t partial_capacity; /* workgroup slabs `partial` holds */
+} carl_policy_stats_t;
+
+int32_t carl_policy_stats_workgroups(int32_t n_lanes); /* slabs a launch over n_lanes writes (0 for n_lanes <= 0) */
+int carl_evaluate_policy_stats(const carl_batch_t* batch, const carl_policy_t* policy_host,
+                               const carl_policy_sampling_t* sampling /* NULL: deterministic */, int32_t n_episodes,
+                               int32_t max_steps, const carl_policy_episodes_t* episodes_out,
+                               const carl_policy_stats_t* stats, void* stream);
+
+/* The running statistics of a policy's inputs, on the device: count of lane-steps, mean[n_in], M2[n_in] (the sum of
+ * squared deviations from the mean).  All zero: nothing seen yet. */
+typedef struct carl_policy_running_stats {
+  int64_t* count; /* DEVICE [1] */
+  double* mean;   /* DEVICE [CARL_POLICY_MAX_IN] ([n_in] used) */
+  double* m2;     /* DEVICE [CARL_POLICY_MAX_IN] ([n_in] used) */
+} carl_policy_running_stats_t;
+
+/* Merge the slabs of one carl_evaluate_policy_stats launch into `running` and, when params_out is not NULL, write the
+ * transform the new statistics imply into n_write consecutive packed weight sets at params_out.  One small workgroup,
+ * every operation in float64, each rounded on its own (no fma):
+ *   n_b  = sum of steps[0 .. n_lanes) (int64);  n_b == 0: nothing is read further and nothing is written.
+ *   S1_i = 0.0; S1_i += partial[w][0][i] for w = 0 .. n_workgroups - 1 in order;  S2_i likewise from partial[w][1][i]
+ *   shift_i = policy_host->params[transform offset + i] of weight set 0 -- the shift the launch ran under; every
+ *             weight set of that launch must have carried the same shift
+ *   mean_b = (double)shift_i + S1_i / n_b;   M2_b = max(S2_i - S1_i * S1_i / n_b, 0)
+ *   count == 0:  mean_i = mean_b, M2_i = M2_b
+ *   else (Chan et al.):  n = count + n_b;  delta = mean_b - mean_i;
+ *                mean_i = mean_i + delta * (n_b / n);   M2_i = (M2_i + M2_b) + delta * delta * (count * n_b / n)
+ *   count = count + n_b
+ *   var = M2_i / count;   floor = max(min_std^2, (2^-18 * |mean_i|)^2)
+ *   scale_i = var <= floor ? 0 : 1 / sqrt(var + eps)
+ *   block k < n_write: params_out[k * set_floats + transform offset + i] = fp32(mean_i),
+ *                      params_out[k * set_floats + transform offset + n_in + i] = fp32(scale_i)
+ * with transform offset = the floats of every W and b of the shape (the packing rule above) and set_floats =
+ * carl_policy_set_floats().  Weights, biases, clip and the padding keep their bits.  An input whose variance is at
+ * or below the floor counts as CONSTANT and gets scale 0: the policy ignores it (ARS's convention).  The relative
+ * term is a derived bound, not a measurement: a constant fp32 input summed over a chunk of at most 8 steps carries at
+ * most about 8 * 2^-24 = 2^-21 of relative rounding, and 2^-18 leaves a factor of 8 over that.  (That is a bound on
+ * the SUMS.  The variance M2 / count = S2 / n - (S1 / n)^2 loses them to cancellation: a relative error r of S2 is a
+ * variance of r * mean^2, a deviation of sqrt(r) * |mean| -- 2^-12 |mean| for one fp32 rounding of d * d.  The floor
+ * therefore tells a constant input only because the context inputs' sums are formed exactly, see above: r is then a
+ * few float64 roundings per addition, far below 2^-36.  A constant OBSERVATION entry summed in fp32 is not detected.)
+ * params_out may be policy_host->params itself.  Validation, CARL_ERR_INVALID_ARGUMENT before anything is enqueued: a
+ * NULL policy_host, an invalid shape or NULL params; stats / stats->partial NULL; n_workgroups outside
+ * 0 .. partial_capacity; n_lanes < 0, or steps NULL with n_lanes > 0; `running` or one of its pointers NULL; eps or
+ * min_std negative or not finite; n_write < 0.
+ * Both calls are stream-ordered and capturable, never synchronise with the host and allocate nothing. */
+int carl_policy_stats_merge(const carl_policy_t* policy_host, const carl_policy_stats_t* stats, int32_t n_workgroups,
+                            const int32_t* steps /* DEVICE [n_lanes] */, int32_t n_lanes,
+                            const carl_policy_running_stats_t* running, double eps, double min_std,
+                            float* params_out /* DEVICE [n_write][set_floats], nullable */, int32_t n_write,
+                            void* stream);
+
 /* ======================= Brax-locomotion families (spring backend) =======================
  * Replaces CARLBraxEnv + BraxGymWrapper/VectorGymWrapper + brax.spring.pipeline.step x
  * n_frames + brax.envs.<env>.step/reset (carl/envs/brax/carl_brax_env.py:115-336,

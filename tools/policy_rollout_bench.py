@@ -28,10 +28,15 @@
                    and the two new launches on their own (device events around 50 back-to-back launches).
                    Written to key "es" of --out.
 
+  --legs stats     evaluate_policy(..., input_stats=True) against the same launch without statistics (the kernel of the
+                   parent commit: profiles/policy_stats_isa_identity.txt), CartPole x --lanes, K = 1, max_steps = 500, linear
+                   and 2x64 tanh, every launch from the same snapshot; and the merge launch (InputStats.update writing one
+                   block) on its own, device events around 50 back-to-back launches.  Written to key "stats" of --out.
+
 Host timing with torch.cuda events around `--reps` launches after one warm-up launch; the median per launch is
 reported.  Kernel times belong to a separate `rocprofv3 --kernel-trace --stats` run of this script.
 
-  python tools/policy_rollout_bench.py [--lanes 65536] [--steps 1000] [--reps 5] [--legs rollout,evaluate,value,es] [--out FILE]
+  python tools/policy_rollout_bench.py [--lanes 65536] [--steps 1000] [--reps 5] [--legs rollout,evaluate,value,es,stats] [--out FILE]
 
 --out FILE: a JSON file whose keys of the legs run ("results": rollout, "evaluate") are replaced, others kept.
 """
@@ -302,6 +307,44 @@ def es_leg(eng, n_in, reps, L=256, K=1, max_steps=500, sigma=0.1, lr=0.05):
     return rows
 
 
+def stats_leg(eng, n_in, reps, K=1, max_steps=500):
+    from carl_amd.policy import InputStats
+
+    rows = []
+    snap = eng.snapshot()
+    for name, widths in {"linear": [], "mlp_2x64_tanh": [64, 64]}.items():
+        tmpl = MLPPolicy.from_sequential(eng, make_mlp(widths, n_in))
+        block = torch.as_tensor(tmpl.params).to(eng.device).contiguous().clone()
+        pol = MLPPolicy.on_device(tmpl, block, (eng.n + 255) // 256 * 256)
+        res = eng.alloc_policy_episodes(K)
+        sec = {}
+        for key, kw in (("plain", {}), ("stats", {"input_stats": True})):
+            ts = []
+            for _ in range(reps + 1):  # (the first: warm-up)
+                eng.restore(snap)
+                torch.cuda.synchronize()
+                a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+                a.record()
+                eng.evaluate_policy(pol, K, max_steps, out=res, **kw)
+                b.record()
+                b.synchronize()
+                ts.append(a.elapsed_time(b) * 1e-3)
+            sec[key] = (float(np.median(ts[1:])), ts[1:])
+        lane_steps = int(res["steps"].to(torch.int64).sum())
+        stats = InputStats(tmpl, eng.device)
+        many = 50
+        sec_m, _ = time_launches(lambda: [stats.update(res, pol, n_write=1) for _ in range(many)], reps)
+        r = {"config": f"stats_{name}", "lanes": eng.n, "n_episodes": K, "max_steps": max_steps, "lane_steps": lane_steps,
+             "evaluate_policy_sec": sec["plain"][0], "evaluate_policy_stats_sec": sec["stats"][0],
+             "stats_over_plain": sec["stats"][0] / sec["plain"][0], "merge_sec_per_launch_back_to_back": sec_m / many,
+             "workgroups": int(res["input_partial"].shape[0]),
+             "reps_sec": {"plain": sec["plain"][1], "stats": sec["stats"][1]}}
+        rows.append(r)
+        print(json.dumps(r), flush=True)
+    eng.restore(snap)
+    return rows
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--lanes", type=int, default=65536)
@@ -323,6 +366,8 @@ def main():
         doc["value"] = value_leg(eng, n_in, T, args.reps)
     if "es" in legs:
         doc["es"] = es_leg(eng, n_in, args.reps)
+    if "stats" in legs:
+        doc["stats"] = stats_leg(eng, n_in, args.reps)
     if "rollout" not in legs:
         return write(args.out, doc)
 
