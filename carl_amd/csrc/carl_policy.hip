@@ -1,7 +1,8 @@
 // carl_policy.hip -- C-ABI entry points of the closed-loop rollout (include/carl_amd.h: carl_rollout_policy) and their
 // kernel dispatch.  A translation unit of its own: the kernels (policy_kernels.hip.h) instantiate the engine's device
 // templates anew, and the open-loop kernels of carl_amd.hip compile exactly as they did without them.  The host rules
-// of policy_host.hpp live here too; the sampled twins (carl_policy_sample.hip) call them.
+// of policy_host.hpp live here too; the other units of the closed-loop rollout call them.  The launch itself is
+// policy_launch.hpp's.
 #include <hip/hip_runtime.h>
 
 #include <cstdint>
@@ -11,6 +12,7 @@
 #include "host_common.hpp"
 #include "policy_host.hpp"
 #include "policy_kernels.hip.h"
+#include "policy_launch.hpp"
 
 namespace carl_host {
 
@@ -40,15 +42,31 @@ int policy_padded_hidden(const carl_policy_t* p) {
   return p->n_hidden == 0 ? 0 : wmax <= 32 ? 32 : 64;
 }
 
-namespace {
-
-int validate_policy(const carl_batch_t* b, const carl_policy_t* p, const carl_family_info_t& fi, const char* who) {
+int check_hidden_layers(const char* who, const carl_policy_t* p) {
   if (p->n_hidden < 0 || p->n_hidden > CARL_POLICY_MAX_HIDDEN)
     return fail(CARL_ERR_INVALID_ARGUMENT, "%s: n_hidden %d outside [0, %d]", who, p->n_hidden, CARL_POLICY_MAX_HIDDEN);
   for (int l = 0; l < p->n_hidden; ++l)
     if (p->width[l] < 1 || p->width[l] > CARL_POLICY_MAX_WIDTH)
       return fail(CARL_ERR_INVALID_ARGUMENT, "%s: hidden width[%d] = %d outside [1, %d]", who, l, p->width[l],
                   CARL_POLICY_MAX_WIDTH);
+  return 0;
+}
+
+int check_activation(const char* who, const carl_policy_t* p) {
+  if (p->activation < CARL_POLICY_IDENTITY || p->activation > CARL_POLICY_RELU)
+    return fail(CARL_ERR_INVALID_ARGUMENT, "%s: unknown activation %d", who, p->activation);
+  return 0;
+}
+
+int check_params(const char* who, const carl_policy_t* p) {
+  if (p->params == nullptr) return fail(CARL_ERR_INVALID_ARGUMENT, "%s: params is NULL", who);
+  return 0;
+}
+
+namespace {
+
+int validate_policy(const carl_batch_t* b, const carl_policy_t* p, const carl_family_info_t& fi, const char* who) {
+  if (int e = check_hidden_layers(who, p)) return e;
   if (p->n_ctx < 0 || p->n_ctx > fi.n_features)
     return fail(CARL_ERR_INVALID_ARGUMENT, "%s: n_ctx %d outside [0, F = %d]", who, p->n_ctx, fi.n_features);
   for (int k = 0; k < p->n_ctx; ++k)
@@ -63,8 +81,7 @@ int validate_policy(const carl_batch_t* b, const carl_policy_t* p, const carl_fa
                 fi.action_is_discrete ? "n_actions" : "one Box value");
   if (p->head != (fi.action_is_discrete ? CARL_POLICY_HEAD_ARGMAX : CARL_POLICY_HEAD_BOX))
     return fail(CARL_ERR_INVALID_ARGUMENT, "%s: head kind %d does not match the family's action space", who, p->head);
-  if (p->activation < CARL_POLICY_IDENTITY || p->activation > CARL_POLICY_RELU)
-    return fail(CARL_ERR_INVALID_ARGUMENT, "%s: unknown activation %d", who, p->activation);
+  if (int e = check_activation(who, p)) return e;
   if (p->n_sets < 1) return fail(CARL_ERR_INVALID_ARGUMENT, "%s: n_sets %d < 1", who, p->n_sets);
   if (p->lanes_per_set < carl::kPolicyLanes || p->lanes_per_set % carl::kPolicyLanes != 0)
     return fail(CARL_ERR_INVALID_ARGUMENT, "%s: lanes_per_set %d is not a positive multiple of %d (carl_policy_lane_quantum)",
@@ -72,8 +89,7 @@ int validate_policy(const carl_batch_t* b, const carl_policy_t* p, const carl_fa
   if ((int64_t)p->n_sets * p->lanes_per_set < b->n_lanes)
     return fail(CARL_ERR_INVALID_ARGUMENT, "%s: %d sets x %d lanes do not cover %d lanes", who, p->n_sets,
                 p->lanes_per_set, b->n_lanes);
-  if (p->params == nullptr) return fail(CARL_ERR_INVALID_ARGUMENT, "%s: params is NULL", who);
-  return 0;
+  return check_params(who, p);
 }
 
 // transitions mode: the staged layout of carl_rollout (see include/carl_amd.h: carl_step_io_t::row_pitch)
@@ -93,18 +109,24 @@ int validate_io(const carl_batch_t* b, const carl_step_io_t* io, const carl_fami
   return 0;
 }
 
-}  // namespace
-
-int check_rollout_policy(const char* who, const carl_batch_t* batch, const carl_policy_t* policy_host,
-                         const carl_step_io_t* io, int32_t n_steps, const carl_policy_summary_t* summary_out,
-                         carl_family_info_t* fi) {
+// what every closed-loop entry point checks first; `fi`: the batch family's info
+int check_batch_and_policy(const char* who, const carl_batch_t* batch, const carl_policy_t* policy_host,
+                           carl_family_info_t* fi) {
   if (batch == nullptr || policy_host == nullptr) return fail(CARL_ERR_INVALID_ARGUMENT, "%s: batch / policy is NULL", who);
   if (batch->family >= CARL_N_FAMILIES)
     return fail(CARL_ERR_INVALID_ARGUMENT, "%s: family %d is a Brax family -- the closed-loop rollout covers the "
                 "classic-control families only", who, batch->family);
   if (int e = validate_batch(batch, who)) return e;
   if (int e = carl_family_info(batch->family, fi)) return e;
-  if (int e = validate_policy(batch, policy_host, *fi, who)) return e;
+  return validate_policy(batch, policy_host, *fi, who);
+}
+
+}  // namespace
+
+int check_rollout_policy(const char* who, const carl_batch_t* batch, const carl_policy_t* policy_host,
+                         const carl_step_io_t* io, int32_t n_steps, const carl_policy_summary_t* summary_out,
+                         carl_family_info_t* fi) {
+  if (int e = check_batch_and_policy(who, batch, policy_host, fi)) return e;
   if (n_steps < 0) return fail(CARL_ERR_INVALID_ARGUMENT, "%s: n_steps %d < 0", who, n_steps);
   if (io == nullptr) {
     if (summary_out == nullptr || !summary_out->episodes || !summary_out->return_sum || !summary_out->length_sum)
@@ -137,14 +159,7 @@ int policy_rollout_without_steps(const char* who, const carl_batch_t* batch, con
 int check_evaluate_policy(const char* who, const carl_batch_t* batch, const carl_policy_t* policy_host,
                           int32_t n_episodes, int32_t max_steps, const carl_policy_episodes_t* out,
                           carl_family_info_t* fi) {
-  if (batch == nullptr || policy_host == nullptr)
-    return fail(CARL_ERR_INVALID_ARGUMENT, "%s: batch / policy is NULL", who);
-  if (batch->family >= CARL_N_FAMILIES)
-    return fail(CARL_ERR_INVALID_ARGUMENT, "%s: family %d is a Brax family -- the closed-loop rollout covers the "
-                "classic-control families only", who, batch->family);
-  if (int e = validate_batch(batch, who)) return e;
-  if (int e = carl_family_info(batch->family, fi)) return e;
-  if (int e = validate_policy(batch, policy_host, *fi, who)) return e;
+  if (int e = check_batch_and_policy(who, batch, policy_host, fi)) return e;
   if (out == nullptr || !out->episodes || !out->steps || !out->ret || !out->length || !out->context_id ||
       !out->terminated)
     return fail(CARL_ERR_INVALID_ARGUMENT, "%s: out and all six of its arrays are required", who);
@@ -164,65 +179,36 @@ int check_evaluate_policy(const char* who, const carl_batch_t* batch, const carl
 
 namespace {
 
-using carl_host::check_launch;
-using carl_host::fail;
-
-// a policy_rollout_kernel instance and the dynamic LDS it takes
-struct PolicyKernel {
-  void (*fn)(carl_batch_t, carl_step_io_t, carl_policy_t, int, carl_policy_summary_t, int);
-  size_t lds;
-};
-
-template <class Fam, int H>
-PolicyKernel policy_kernel(bool summary) {
-  if (summary) return {carl::policy_rollout_kernel<Fam, H, true>, carl::policy_lds_bytes<Fam, H, true>()};
-  return {carl::policy_rollout_kernel<Fam, H, false>, carl::policy_lds_bytes<Fam, H, false>()};
-}
+using carl_host::launch_policy_kernel;
+using carl_host::PolicyKernel;
+using carl_host::with_padded_hidden;
 
 template <class Fam>
 int launch_policy(const carl_batch_t* b, const carl_policy_t* p, const carl_step_io_t* io, int n_steps,
                   const carl_policy_summary_t* sum, hipStream_t s) {
   const bool summary = io == nullptr;
-  const int H = carl_host::policy_padded_hidden(p);
-  const PolicyKernel k = H == 0 ? policy_kernel<Fam, 0>(summary) : H == 32 ? policy_kernel<Fam, 32>(summary)
-                                                                  : policy_kernel<Fam, 64>(summary);
   static_assert(carl::policy_lds_bytes<Fam, 64, false>() + carl::static_lds_bytes<Fam>() <= carl::kCuLdsBytes,
                 "the closed-loop rollout's LDS does not fit a compute unit");
-  if (int e = carl_host::ensure_dynamic_lds(reinterpret_cast<const void*>(k.fn), k.lds, "carl_rollout_policy")) return e;
-  carl_step_io_t io_r{};
-  if (!summary) {
-    io_r = *io;
-    io_r.row_pitch = io->row_pitch > 0 ? io->row_pitch : b->n_lanes;  // the kernel reads the pitch as given: never 0
-  }
-  const carl_policy_summary_t sum_r = sum != nullptr ? *sum : carl_policy_summary_t{nullptr, nullptr, nullptr};
-  const int grid = (b->n_lanes + carl::kPolicyLanes - 1) / carl::kPolicyLanes;
+  const auto k = with_padded_hidden(carl_host::policy_padded_hidden(p), [&](auto h) {
+    constexpr int H = decltype(h)::value;
+    if (summary) return PolicyKernel{carl::policy_rollout_kernel<Fam, H, true>, carl::policy_lds_bytes<Fam, H, true>()};
+    return PolicyKernel{carl::policy_rollout_kernel<Fam, H, false>, carl::policy_lds_bytes<Fam, H, false>()};
+  });
   const int threads = summary ? carl::kPolicyThreadsSummary : carl::kPolicyThreadsTransitions;
-  hipLaunchKernelGGL(k.fn, dim3(grid), dim3(threads), k.lds, s, *b, io_r, *p, carl_host::policy_set_floats(p), sum_r, n_steps);
-  return check_launch("carl_rollout_policy");
-}
-
-// a policy_episodes_kernel instance and the dynamic LDS it takes (summary mode's: the weight set alone)
-struct EpisodesKernel {
-  void (*fn)(carl_batch_t, carl_policy_t, int, carl_policy_episodes_t, int, int);
-  size_t lds;
-};
-
-template <class Fam, int H>
-EpisodesKernel episodes_kernel() {
-  return {carl::policy_episodes_kernel<Fam, H>, carl::policy_lds_bytes<Fam, H, true>()};
+  return launch_policy_kernel("carl_rollout_policy", k, b->n_lanes, threads, s, *b, carl_host::launch_io(b, io), *p,
+                              carl_host::policy_set_floats(p), carl_host::launch_summary(sum), n_steps);
 }
 
 template <class Fam>
 int launch_episodes(const carl_batch_t* b, const carl_policy_t* p, int n_episodes, int max_steps,
                     const carl_policy_episodes_t* out, hipStream_t s) {
-  const int H = carl_host::policy_padded_hidden(p);
-  const EpisodesKernel k = H == 0 ? episodes_kernel<Fam, 0>() : H == 32 ? episodes_kernel<Fam, 32>()
-                                                               : episodes_kernel<Fam, 64>();
-  if (int e = carl_host::ensure_dynamic_lds(reinterpret_cast<const void*>(k.fn), k.lds, "carl_evaluate_policy")) return e;
-  const int grid = (b->n_lanes + carl::kPolicyLanes - 1) / carl::kPolicyLanes;
-  hipLaunchKernelGGL(k.fn, dim3(grid), dim3(carl::kPolicyThreadsSummary), k.lds, s, *b, *p, carl_host::policy_set_floats(p), *out,
-                     n_episodes, max_steps);
-  return check_launch("carl_evaluate_policy");
+  // summary mode's LDS: the weight set alone
+  const auto k = with_padded_hidden(carl_host::policy_padded_hidden(p), [](auto h) {
+    constexpr int H = decltype(h)::value;
+    return PolicyKernel{carl::policy_episodes_kernel<Fam, H>, carl::policy_lds_bytes<Fam, H, true>()};
+  });
+  return launch_policy_kernel("carl_evaluate_policy", k, b->n_lanes, carl::kPolicyThreadsSummary, s, *b, *p,
+                              carl_host::policy_set_floats(p), *out, n_episodes, max_steps);
 }
 
 }  // namespace

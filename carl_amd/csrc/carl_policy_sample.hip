@@ -1,7 +1,8 @@
 // carl_policy_sample.hip -- C-ABI entry points of the closed-loop rollout with sampled actions (include/carl_amd.h:
 // carl_rollout_policy_sampled, carl_evaluate_policy_sampled) and their kernel dispatch.  A translation unit of its own,
 // so that the deterministic kernels of carl_policy.hip compile exactly as they did; the validation is carl_policy.hip's
-// (policy_host.hpp), the kernels are the same bodies with SampledPick choosing the action (policy_kernels.hip.h).
+// (policy_host.hpp), the launch path policy_launch.hpp's, the kernels are the same bodies with SampledPick choosing the
+// action (policy_kernels.hip.h).  The sampling checks of every unit (policy_host.hpp: check_sampling) live here.
 #include <hip/hip_runtime.h>
 
 #include <cstdint>
@@ -11,17 +12,20 @@
 #include "host_common.hpp"
 #include "policy_host.hpp"
 #include "policy_kernels.hip.h"
+#include "policy_launch.hpp"
 
 namespace carl_host {
 
-// what the sampled twins refuse on top of their deterministic twin's checks (policy_host.hpp)
-int check_sampling(const char* who, const carl_policy_sampling_t* smp, const carl_family_info_t& fi, bool log_prob_ok) {
+int check_sampling(const char* who, const carl_policy_sampling_t* smp, const carl_family_info_t& fi, LogProb log_prob) {
   if (smp == nullptr) return fail(CARL_ERR_INVALID_ARGUMENT, "%s: sampling is NULL", who);
   if (!fi.action_is_discrete && smp->log_std == nullptr)
     return fail(CARL_ERR_INVALID_ARGUMENT, "%s: a Box family needs sampling->log_std ([n_sets] on the device)", who);
-  if (!log_prob_ok && smp->log_prob != nullptr)
+  if (log_prob == LogProb::kRefused && smp->log_prob != nullptr)
     return fail(CARL_ERR_INVALID_ARGUMENT, "%s: sampling->log_prob is a transitions-mode output (io != NULL); this mode "
                 "stores nothing per step", who);
+  if (log_prob == LogProb::kRequired && smp->log_prob == nullptr)
+    return fail(CARL_ERR_INVALID_ARGUMENT, "%s: a sampled launch with a critic stores the log-probabilities: "
+                "sampling->log_prob is NULL", who);
   if ((reinterpret_cast<uintptr_t>(smp->log_prob) & 15) != 0)  // (drained in 16-byte pieces, as io->action)
     return fail(CARL_ERR_UNSUPPORTED, "%s: sampling->log_prob is not on a 16-byte boundary", who);
   return 0;
@@ -31,71 +35,41 @@ int check_sampling(const char* who, const carl_policy_sampling_t* smp, const car
 
 namespace {
 
-using carl_host::check_launch;
 using carl_host::check_sampling;
-using carl_host::fail;
-
-// a policy_rollout_sampled_kernel instance and the dynamic LDS it takes
-struct SampledKernel {
-  void (*fn)(carl_batch_t, carl_step_io_t, carl_policy_t, int, carl_policy_summary_t, int, carl_policy_sampling_t);
-  size_t lds;
-};
-
-template <class Fam, int H>
-SampledKernel sampled_kernel(bool summary, bool logp) {
-  using carl::policy_lds_bytes;
-  if (summary) return {carl::policy_rollout_sampled_kernel<Fam, H, true, false>, policy_lds_bytes<Fam, H, true>()};
-  if (logp) return {carl::policy_rollout_sampled_kernel<Fam, H, false, true>, policy_lds_bytes<Fam, H, false, true>()};
-  return {carl::policy_rollout_sampled_kernel<Fam, H, false, false>, policy_lds_bytes<Fam, H, false>()};
-}
+using carl_host::launch_policy_kernel;
+using carl_host::LogProb;
+using carl_host::PolicyKernel;
+using carl_host::with_padded_hidden;
 
 template <class Fam>
 int launch_sampled(const carl_batch_t* b, const carl_policy_t* p, const carl_policy_sampling_t* smp,
                    const carl_step_io_t* io, int n_steps, const carl_policy_summary_t* sum, hipStream_t s) {
   const bool summary = io == nullptr, logp = smp->log_prob != nullptr;
-  const int H = carl_host::policy_padded_hidden(p);
-  const SampledKernel k = H == 0 ? sampled_kernel<Fam, 0>(summary, logp) : H == 32 ? sampled_kernel<Fam, 32>(summary, logp)
-                                                                          : sampled_kernel<Fam, 64>(summary, logp);
   static_assert(carl::policy_lds_bytes<Fam, 64, false, true>() + carl::static_lds_bytes<Fam>() <= carl::kCuLdsBytes,
                 "the sampled rollout's LDS (the log_prob column included) does not fit a compute unit");
-  if (int e = carl_host::ensure_dynamic_lds(reinterpret_cast<const void*>(k.fn), k.lds, "carl_rollout_policy_sampled"))
-    return e;
-  carl_step_io_t io_r{};
-  if (!summary) {
-    io_r = *io;
-    io_r.row_pitch = io->row_pitch > 0 ? io->row_pitch : b->n_lanes;  // the kernel reads the pitch as given: never 0
-  }
-  const carl_policy_summary_t sum_r = sum != nullptr ? *sum : carl_policy_summary_t{nullptr, nullptr, nullptr};
-  const int grid = (b->n_lanes + carl::kPolicyLanes - 1) / carl::kPolicyLanes;
+  const auto k = with_padded_hidden(carl_host::policy_padded_hidden(p), [&](auto h) {
+    constexpr int H = decltype(h)::value;
+    using carl::policy_lds_bytes;
+    if (summary) return PolicyKernel{carl::policy_rollout_sampled_kernel<Fam, H, true, false>, policy_lds_bytes<Fam, H, true>()};
+    if (logp)
+      return PolicyKernel{carl::policy_rollout_sampled_kernel<Fam, H, false, true>, policy_lds_bytes<Fam, H, false, true>()};
+    return PolicyKernel{carl::policy_rollout_sampled_kernel<Fam, H, false, false>, policy_lds_bytes<Fam, H, false>()};
+  });
   const int threads = summary ? carl::kPolicyThreadsSummary : carl::kPolicyThreadsTransitions;
-  hipLaunchKernelGGL(k.fn, dim3(grid), dim3(threads), k.lds, s, *b, io_r, *p, carl_host::policy_set_floats(p), sum_r,
-                     n_steps, *smp);
-  return check_launch("carl_rollout_policy_sampled");
-}
-
-// a policy_episodes_sampled_kernel instance and the dynamic LDS it takes (the weight set alone)
-struct SampledEpisodesKernel {
-  void (*fn)(carl_batch_t, carl_policy_t, int, carl_policy_episodes_t, int, int, carl_policy_sampling_t);
-  size_t lds;
-};
-
-template <class Fam, int H>
-SampledEpisodesKernel sampled_episodes_kernel() {
-  return {carl::policy_episodes_sampled_kernel<Fam, H>, carl::policy_lds_bytes<Fam, H, true>()};
+  return launch_policy_kernel("carl_rollout_policy_sampled", k, b->n_lanes, threads, s, *b, carl_host::launch_io(b, io), *p,
+                              carl_host::policy_set_floats(p), carl_host::launch_summary(sum), n_steps, *smp);
 }
 
 template <class Fam>
 int launch_sampled_episodes(const carl_batch_t* b, const carl_policy_t* p, const carl_policy_sampling_t* smp,
                             int n_episodes, int max_steps, const carl_policy_episodes_t* out, hipStream_t s) {
-  const int H = carl_host::policy_padded_hidden(p);
-  const SampledEpisodesKernel k = H == 0 ? sampled_episodes_kernel<Fam, 0>() : H == 32 ? sampled_episodes_kernel<Fam, 32>()
-                                                                              : sampled_episodes_kernel<Fam, 64>();
-  if (int e = carl_host::ensure_dynamic_lds(reinterpret_cast<const void*>(k.fn), k.lds, "carl_evaluate_policy_sampled"))
-    return e;
-  const int grid = (b->n_lanes + carl::kPolicyLanes - 1) / carl::kPolicyLanes;
-  hipLaunchKernelGGL(k.fn, dim3(grid), dim3(carl::kPolicyThreadsSummary), k.lds, s, *b, *p,
-                     carl_host::policy_set_floats(p), *out, n_episodes, max_steps, *smp);
-  return check_launch("carl_evaluate_policy_sampled");
+  // the LDS: the weight set alone
+  const auto k = with_padded_hidden(carl_host::policy_padded_hidden(p), [](auto h) {
+    constexpr int H = decltype(h)::value;
+    return PolicyKernel{carl::policy_episodes_sampled_kernel<Fam, H>, carl::policy_lds_bytes<Fam, H, true>()};
+  });
+  return launch_policy_kernel("carl_evaluate_policy_sampled", k, b->n_lanes, carl::kPolicyThreadsSummary, s, *b, *p,
+                              carl_host::policy_set_floats(p), *out, n_episodes, max_steps, *smp);
 }
 
 }  // namespace
@@ -108,7 +82,7 @@ int carl_rollout_policy_sampled(const carl_batch_t* batch, const carl_policy_t* 
   const char* who = "carl_rollout_policy_sampled";
   carl_family_info_t fi;
   if (int e = carl_host::check_rollout_policy(who, batch, policy_host, io, n_steps, summary_out, &fi)) return e;
-  if (int e = check_sampling(who, sampling, fi, io != nullptr)) return e;
+  if (int e = check_sampling(who, sampling, fi, io != nullptr ? LogProb::kOptional : LogProb::kRefused)) return e;
   if (batch->n_lanes == 0 || n_steps == 0) return carl_host::policy_rollout_without_steps(who, batch, summary_out, stream);
   return carl_host::with_classic_family(batch, [&](auto fam) {
     return launch_sampled<decltype(fam)>(batch, policy_host, sampling, io, n_steps, summary_out, (hipStream_t)stream);
@@ -121,7 +95,7 @@ int carl_evaluate_policy_sampled(const carl_batch_t* batch, const carl_policy_t*
   const char* who = "carl_evaluate_policy_sampled";
   carl_family_info_t fi;
   if (int e = carl_host::check_evaluate_policy(who, batch, policy_host, n_episodes, max_steps, out, &fi)) return e;
-  if (int e = check_sampling(who, sampling, fi, false)) return e;
+  if (int e = check_sampling(who, sampling, fi, LogProb::kRefused)) return e;
   if (batch->n_lanes == 0) return 0;
   return carl_host::with_classic_family(batch, [&](auto fam) {
     return launch_sampled_episodes<decltype(fam)>(batch, policy_host, sampling, n_episodes, max_steps, out,

@@ -1,7 +1,8 @@
 // carl_policy_stats.hip -- C-ABI entry points of the input statistics of the closed-loop rollout (include/carl_amd.h:
 // carl_evaluate_policy_stats, carl_policy_stats_merge) and their kernel dispatch.  A translation unit of its own, so that
 // every other unit's kernels compile exactly as they did; the validation is carl_policy.hip's and
-// carl_policy_sample.hip's (policy_host.hpp), the kernels are policy_stats_kernels.hip.h's.
+// carl_policy_sample.hip's (policy_host.hpp), the launch path policy_launch.hpp's, the kernels are
+// policy_stats_kernels.hip.h's.
 #include <hip/hip_runtime.h>
 
 #include <cmath>
@@ -12,13 +13,12 @@
 #include "host_common.hpp"
 #include "policy_host.hpp"
 #include "policy_stats_kernels.hip.h"
+#include "policy_launch.hpp"
 
 namespace {
 
 using carl_host::check_launch;
 using carl_host::fail;
-
-int stats_workgroups(int32_t n_lanes) { return n_lanes <= 0 ? 0 : (n_lanes + carl::kPolicyLanes - 1) / carl::kPolicyLanes; }
 
 int check_stats(const char* who, const carl_policy_stats_t* stats, int n_workgroups) {
   if (stats == nullptr || stats->partial == nullptr)
@@ -31,39 +31,27 @@ int check_stats(const char* who, const carl_policy_stats_t* stats, int n_workgro
   return 0;
 }
 
-// a policy_episodes_stats_kernel instance and the dynamic LDS it takes (the weight set and the waves' float64 sums)
-struct StatsKernel {
-  void (*fn)(carl_batch_t, carl_policy_t, int, carl_policy_episodes_t, int, int, carl_policy_sampling_t, double*);
-  size_t lds;
-};
-
-template <class Fam, int H>
-StatsKernel stats_kernel(bool sampled) {
-  const size_t lds = carl::policy_lds_bytes<Fam, H, true>() + carl::policy_stats_lds_bytes<Fam, H>();
-  if (sampled) return {carl::policy_episodes_stats_kernel<Fam, H, true>, lds};
-  return {carl::policy_episodes_stats_kernel<Fam, H, false>, lds};
-}
-
 template <class Fam>
 int launch_stats(const carl_batch_t* b, const carl_policy_t* p, const carl_policy_sampling_t* smp, int n_episodes,
                  int max_steps, const carl_policy_episodes_t* out, double* partial, hipStream_t s) {
-  const char* who = "carl_evaluate_policy_stats";
-  const int H = carl_host::policy_padded_hidden(p);
   const bool sampled = smp != nullptr;
-  const StatsKernel k = H == 0 ? stats_kernel<Fam, 0>(sampled) : H == 32 ? stats_kernel<Fam, 32>(sampled)
-                                                                 : stats_kernel<Fam, 64>(sampled);
-  if (int e = carl_host::ensure_dynamic_lds(reinterpret_cast<const void*>(k.fn), k.lds, who)) return e;
-  const carl_policy_sampling_t smp_r = sampled ? *smp : carl_policy_sampling_t{0, nullptr, nullptr};
-  hipLaunchKernelGGL(k.fn, dim3(stats_workgroups(b->n_lanes)), dim3(carl::kPolicyThreadsSummary), k.lds, s, *b, *p,
-                     carl_host::policy_set_floats(p), *out, n_episodes, max_steps, smp_r, partial);
-  return check_launch(who);
+  const auto k = carl_host::with_padded_hidden(carl_host::policy_padded_hidden(p), [&](auto h) {
+    constexpr int H = decltype(h)::value;
+    // the weight set and the waves' float64 sums
+    const size_t lds = carl::policy_lds_bytes<Fam, H, true>() + carl::policy_stats_lds_bytes<Fam, H>();
+    if (sampled) return carl_host::PolicyKernel{carl::policy_episodes_stats_kernel<Fam, H, true>, lds};
+    return carl_host::PolicyKernel{carl::policy_episodes_stats_kernel<Fam, H, false>, lds};
+  });
+  return carl_host::launch_policy_kernel("carl_evaluate_policy_stats", k, b->n_lanes, carl::kPolicyThreadsSummary, s, *b, *p,
+                                         carl_host::policy_set_floats(p), *out, n_episodes, max_steps,
+                                         carl_host::launch_sampling(smp), partial);
 }
 
 }  // namespace
 
 extern "C" {
 
-int32_t carl_policy_stats_workgroups(int32_t n_lanes) { return stats_workgroups(n_lanes); }
+int32_t carl_policy_stats_workgroups(int32_t n_lanes) { return carl_host::policy_workgroups(n_lanes); }
 
 int carl_evaluate_policy_stats(const carl_batch_t* batch, const carl_policy_t* policy_host,
                                const carl_policy_sampling_t* sampling, int32_t n_episodes, int32_t max_steps,
@@ -72,8 +60,8 @@ int carl_evaluate_policy_stats(const carl_batch_t* batch, const carl_policy_t* p
   carl_family_info_t fi;
   if (int e = carl_host::check_evaluate_policy(who, batch, policy_host, n_episodes, max_steps, episodes_out, &fi)) return e;
   if (sampling != nullptr)
-    if (int e = carl_host::check_sampling(who, sampling, fi, false)) return e;
-  if (int e = check_stats(who, stats, stats_workgroups(batch->n_lanes))) return e;
+    if (int e = carl_host::check_sampling(who, sampling, fi, carl_host::LogProb::kRefused)) return e;
+  if (int e = check_stats(who, stats, carl_host::policy_workgroups(batch->n_lanes))) return e;
   if (batch->n_lanes == 0) return 0;
   return carl_host::with_classic_family(batch, [&](auto fam) {
     return launch_stats<decltype(fam)>(batch, policy_host, sampling, n_episodes, max_steps, episodes_out, stats->partial,

@@ -540,6 +540,12 @@ class LaneEngine:
         return out
 
 
+def _check_policy_family(eng, policy) -> None:
+    """ValueError unless ``policy`` was built for the family and observation of ``eng`` (the closed-loop launches)."""
+    if policy.family != eng.family or policy.obs_dim != eng.D:
+        raise ValueError(f"the policy was built for family {policy.family}, this engine runs family {eng.family}")
+
+
 class VecEngine(LaneEngine):
     """N lanes of one env family on one device.
 
@@ -697,6 +703,22 @@ class VecEngine(LaneEngine):
         s.log_prob = _ptr(log_prob)
         return s
 
+    def _policy_call(self, fn, *args) -> None:
+        """One closed-loop C call ``fn(batch, *args, stream)`` on the current stream, its error code raised."""
+        with torch.cuda.device(self.device):
+            _lib.check(fn(self._b_ref, *args, self._stream()))
+
+    def _policy_columns(self, out: dict, keys, T: int, dtype=torch.float32) -> None:
+        """Each of ``out[keys]`` a ``[>= T, N]`` ``dtype`` column in rows of ``out``'s pitch on this device: allocated
+        where absent, ValueError otherwise (every dtype before any row layout)."""
+        P = self._out_pitch(out)
+        for k in keys:
+            if k not in out:
+                out[k] = torch.empty((T, P), dtype=dtype, device=self.device)[:, : self.n]
+            elif out[k].dtype != dtype:
+                raise ValueError(f"rollout_policy '{k}' buffer must be {dtype}")
+        self._check_rows("rollout_policy", out, keys, P, T, self.device)
+
     def rollout_policy(self, policy, n_steps: int, out: dict | None = None, mode: str = "transitions",
                        final_obs: bool = False, deterministic: bool = True, sample_seed: int = 0,
                        log_prob: bool = False, *, value_net=None, bootstrap_truncated: bool = True,
@@ -723,8 +745,7 @@ class VecEngine(LaneEngine):
         A sampled launch with a critic always returns ``"log_prob"``.  Everything else the launch writes keeps its bits.
         ``gae=(gamma, lam)`` adds ``"advantage"`` and ``"return"`` ``[T, N]`` from one ``carl_gae`` launch on the same
         stream (``VecEngine.gae`` of the launch's own columns)."""
-        if policy.family != self.family or policy.obs_dim != self.D:
-            raise ValueError(f"the policy was built for family {policy.family}, this engine runs family {self.family}")
+        _check_policy_family(self, policy)
         if gae is not None and value_net is None:
             raise ValueError("gae=(gamma, lam) needs value_net: advantages are computed from the critic's values")
         if value_net is not None:
@@ -744,6 +765,13 @@ class VecEngine(LaneEngine):
         pol = policy.struct(self.n, params.data_ptr())
         if log_prob and deterministic:
             raise ValueError("log_prob=True: sampled launches only (deterministic=False)")
+
+        def launch(smp, io, summ):  # the deterministic entry point or its sampled twin
+            if smp is None:
+                self._policy_call(self.lib.carl_rollout_policy, C.byref(pol), io, T, summ)
+            else:
+                self._policy_call(self.lib.carl_rollout_policy_sampled, C.byref(pol), C.byref(smp), io, T, summ)
+
         if mode == "summary":
             if final_obs:
                 raise ValueError("final_obs: transitions mode only (a summary launch stores nothing per step)")
@@ -755,65 +783,38 @@ class VecEngine(LaneEngine):
                 if t.device != self.device or not t.is_contiguous() or t.numel() != self.n or t.element_size() != 4:
                     raise ValueError(f"summary output '{k}' must be a contiguous 4-byte [{self.n}] tensor on {self.device}")
             summ = _lib.PolicySummary(_ptr(res["episodes"]), _ptr(res["return_sum"]), _ptr(res["length_sum"]))
-            smp = self._sampling(policy, deterministic, sample_seed)
-            with torch.cuda.device(self.device):
-                if smp is None:
-                    _lib.check(self.lib.carl_rollout_policy(self._b_ref, C.byref(pol), None, T, C.byref(summ),
-                                                            self._stream()))
-                else:
-                    _lib.check(self.lib.carl_rollout_policy_sampled(self._b_ref, C.byref(pol), C.byref(smp), None, T,
-                                                                    C.byref(summ), self._stream()))
+            launch(self._sampling(policy, deterministic, sample_seed), None, C.byref(summ))
             return res
         if mode != "transitions":
             raise ValueError(f"mode {mode!r}: 'transitions' or 'summary'")
         if out is None:
             out = self.alloc_rollout(T, final_obs=final_obs)
-            adt = torch.int32 if self.info.action_is_discrete else torch.float32
-            out["action"] = torch.empty((T, self._out_pitch(out)), dtype=adt, device=self.device)[:, : self.n]
+            self._policy_columns(out, ("action",), T, torch.int32 if self.info.action_is_discrete else torch.float32)
         if value_net is not None and not deterministic:
             log_prob = True  # (a sampled launch with a critic always stores the log-probabilities)
-        if log_prob and "log_prob" not in out:
-            out["log_prob"] = torch.empty((T, self._out_pitch(out)), dtype=torch.float32, device=self.device)[:, : self.n]
         io = self._rollout_io(None, None, out, T)
-        lp = out.get("log_prob") if log_prob else None
-        if lp is not None:
-            if lp.dtype != torch.float32:
-                raise ValueError("rollout_policy 'log_prob' buffer must be torch.float32")
-            self._check_rows("rollout_policy", {"log_prob": lp}, ("log_prob",), self._out_pitch(out), T, self.device)
-        smp = self._sampling(policy, deterministic, sample_seed, lp)
-        if value_net is not None:
-            P = self._out_pitch(out)
-            cols = ("value", "boot_value") if bootstrap_truncated else ("value",)
-            for k in cols:
-                if k not in out:
-                    out[k] = torch.empty((T, P), dtype=torch.float32, device=self.device)[:, : self.n]
-                elif out[k].dtype != torch.float32:
-                    raise ValueError(f"rollout_policy '{k}' buffer must be torch.float32")
-            self._check_rows("rollout_policy", {k: out[k] for k in cols}, cols, P, T, self.device)
-            if "last_value" not in out:
-                out["last_value"] = torch.empty(self.n, dtype=torch.float32, device=self.device)
-            lv = out["last_value"]
-            if lv.dtype != torch.float32 or lv.device != self.device or tuple(lv.shape) != (self.n,) or not lv.is_contiguous():
-                raise ValueError(f"rollout_policy 'last_value' must be a contiguous float32 [{self.n}] tensor on {self.device}")
-            cparams = value_net.device_params(self.device)
-            crit = value_net.struct(self.n, cparams.data_ptr())
-            vout = _lib.PolicyValue(_ptr(out["value"]), _ptr(lv), _ptr(out["boot_value"]) if bootstrap_truncated else None)
-            with torch.cuda.device(self.device):
-                _lib.check(self.lib.carl_rollout_policy_valued(self._b_ref, C.byref(pol), C.byref(crit),
-                                                               None if smp is None else C.byref(smp), C.byref(io), T, None,
-                                                               C.byref(vout), self._stream()))
-            if gae is not None:
-                res = self.gae(out["reward"][:T], out["value"][:T], out["terminated"][:T], out["truncated"][:T], lv, gamma,
-                               lam, boot_value=out["boot_value"][:T] if bootstrap_truncated else None,
-                               out={k: out[k] for k in ("advantage", "return") if k in out} or None)
-                out["advantage"], out["return"] = res["advantage"], res["return"]
+        if log_prob:
+            self._policy_columns(out, ("log_prob",), T)
+        smp = self._sampling(policy, deterministic, sample_seed, out["log_prob"] if log_prob else None)
+        if value_net is None:
+            launch(smp, C.byref(io), None)
             return out
-        with torch.cuda.device(self.device):
-            if smp is None:
-                _lib.check(self.lib.carl_rollout_policy(self._b_ref, C.byref(pol), C.byref(io), T, None, self._stream()))
-            else:
-                _lib.check(self.lib.carl_rollout_policy_sampled(self._b_ref, C.byref(pol), C.byref(smp), C.byref(io), T,
-                                                                None, self._stream()))
+        self._policy_columns(out, ("value", "boot_value") if bootstrap_truncated else ("value",), T)
+        if "last_value" not in out:
+            out["last_value"] = torch.empty(self.n, dtype=torch.float32, device=self.device)
+        lv = out["last_value"]
+        if lv.dtype != torch.float32 or lv.device != self.device or tuple(lv.shape) != (self.n,) or not lv.is_contiguous():
+            raise ValueError(f"rollout_policy 'last_value' must be a contiguous float32 [{self.n}] tensor on {self.device}")
+        cparams = value_net.device_params(self.device)
+        crit = value_net.struct(self.n, cparams.data_ptr())
+        vout = _lib.PolicyValue(_ptr(out["value"]), _ptr(lv), _ptr(out["boot_value"]) if bootstrap_truncated else None)
+        self._policy_call(self.lib.carl_rollout_policy_valued, C.byref(pol), C.byref(crit),
+                          None if smp is None else C.byref(smp), C.byref(io), T, None, C.byref(vout))
+        if gae is not None:
+            res = self.gae(out["reward"][:T], out["value"][:T], out["terminated"][:T], out["truncated"][:T], lv, gamma,
+                           lam, boot_value=out["boot_value"][:T] if bootstrap_truncated else None,
+                           out={k: out[k] for k in ("advantage", "return") if k in out} or None)
+            out["advantage"], out["return"] = res["advantage"], res["return"]
         return out
 
     def _check_value_net(self, policy, value_net) -> None:
@@ -909,8 +910,7 @@ class VecEngine(LaneEngine):
         ``carl_amd.policy.InputStats.update`` merges (with ``input_stats=False`` a reused ``out`` loses that key, so the
         sums of an earlier launch are never merged beside this launch's ``steps``).  Records and engine state are the
         same bits either way."""
-        if policy.family != self.family or policy.obs_dim != self.D:
-            raise ValueError(f"the policy was built for family {policy.family}, this engine runs family {self.family}")
+        _check_policy_family(self, policy)
         if not self.auto_reset:
             raise ValueError("evaluate_policy needs auto_reset=True: without it a finished lane reports done on every "
                              "later step")
@@ -932,6 +932,7 @@ class VecEngine(LaneEngine):
         pol = policy.struct(self.n, params.data_ptr())
         eps = _lib.PolicyEpisodes(*(_ptr(res[k]) for k, _, _ in self._EPISODE_KEYS))
         smp = self._sampling(policy, deterministic, sample_seed)
+        tail = (K, T, C.byref(eps))
         if input_stats:
             n_wg = int(self.lib.carl_policy_stats_workgroups(self.n))
             partial = res.get("input_partial")
@@ -943,17 +944,14 @@ class VecEngine(LaneEngine):
                 raise ValueError(f"evaluate_policy output 'input_partial' must be a contiguous torch.float64 "
                                  f"[{n_wg}, 2, {_lib.POLICY_MAX_IN}] tensor on {self.device}")
             st = _lib.PolicyStats(_ptr(partial), n_wg)
-            with torch.cuda.device(self.device):
-                _lib.check(self.lib.carl_evaluate_policy_stats(self._b_ref, C.byref(pol), None if smp is None else C.byref(smp),
-                                                               K, T, C.byref(eps), C.byref(st), self._stream()))
+            self._policy_call(self.lib.carl_evaluate_policy_stats, C.byref(pol), None if smp is None else C.byref(smp),
+                              *tail, C.byref(st))
             return res
         res.pop("input_partial", None)  # a reused dict must not carry an earlier launch's sums beside this launch's steps
-        with torch.cuda.device(self.device):
-            if smp is None:
-                _lib.check(self.lib.carl_evaluate_policy(self._b_ref, C.byref(pol), K, T, C.byref(eps), self._stream()))
-            else:
-                _lib.check(self.lib.carl_evaluate_policy_sampled(self._b_ref, C.byref(pol), C.byref(smp), K, T,
-                                                                 C.byref(eps), self._stream()))
+        if smp is None:
+            self._policy_call(self.lib.carl_evaluate_policy, C.byref(pol), *tail)
+        else:
+            self._policy_call(self.lib.carl_evaluate_policy_sampled, C.byref(pol), C.byref(smp), *tail)
         return res
 
     def rollout_variant(self) -> int:

@@ -97,6 +97,67 @@ def c_policy(**kw):
     return p
 
 
+# What the entry points answer c_batch(**batch_kw) with c_policy(**pol_kw), by the case names of the refusal tests: the
+# whole message after "<entry point>: ".  Every closed-loop entry point runs these checks first and words them alike.
+REFUSALS = {
+    "width over the limit": b"hidden width[0] = 65 outside [1, 64]",
+    "width zero": b"hidden width[1] = 0 outside [1, 64]",
+    "too many layers": b"n_hidden 3 outside [0, 2]",
+    "discrete head width": b"head width 3, the family needs 2 (n_actions)",
+    "Box head width": b"head width 2, the family needs 1 (one Box value)",
+    "Brax family": b"family 5 is a Brax family -- the closed-loop rollout covers the classic-control families only",
+    "lanes_per_set not a multiple": b"lanes_per_set 300 is not a positive multiple of 256 (carl_policy_lane_quantum)",
+    "lanes_per_set zero": b"lanes_per_set 0 is not a positive multiple of 256 (carl_policy_lane_quantum)",
+    "sets do not cover": b"3 sets x 256 lanes do not cover 1000 lanes",
+    "context row >= F": b"ctx_rows[1] = 8 is not a context-table row (F = 8)",
+    "context row < 0": b"ctx_rows[0] = -1 is not a context-table row (F = 8)",
+    "n_in mismatch": b"n_in 7 != n_ctx 2 + obs_dim 4",
+    "head kind": b"head kind 1 does not match the family's action space",
+    "activation": b"unknown activation 7",
+    "no params": b"params is NULL",
+    "context observation feature >= F": b"ctx_obs_feat[0] = 8 out of range",
+    "no contexts": b"n_contexts 0 / ctx_stride 4 invalid",
+}
+# the sampling checks, in the order every entry point with a carl_policy_sampling_t runs them
+SAMPLING_NULL = b"sampling is NULL"
+SAMPLING_LOG_STD = b"a Box family needs sampling->log_std ([n_sets] on the device)"
+SAMPLING_LOG_PROB_REFUSED = (b"sampling->log_prob is a transitions-mode output (io != NULL); this mode stores nothing per "
+                             b"step")
+SAMPLING_LOG_PROB_REQUIRED = b"a sampled launch with a critic stores the log-probabilities: sampling->log_prob is NULL"
+SAMPLING_LOG_PROB_UNALIGNED = b"sampling->log_prob is not on a 16-byte boundary"
+# (batch_kw, pol_kw, the REFUSALS case reported): two arguments spoilt at once, the earlier check answers
+FIRST_OF_TWO = [
+    ({"family": _lib.CARL_N_FAMILIES}, {"params": None}, "Brax family"),
+    ({"n_contexts": 0}, {"n_hidden": 3}, "no contexts"),
+    ({}, {"n_hidden": 3, "n_out": 3}, "too many layers"),
+    ({}, {"width": (65, 64), "activation": 7}, "width over the limit"),
+    ({}, {"n_out": 3, "activation": 7}, "discrete head width"),
+    ({}, {"activation": 7, "lanes_per_set": 300}, "activation"),
+    ({}, {"activation": 7, "params": None}, "activation"),
+    ({}, {"lanes_per_set": 256, "n_sets": 3, "params": None}, "sets do not cover"),
+]
+
+
+def c_io(**kw):
+    """A carl_step_io_t in the staged layout for c_batch() (int32 actions, rows of 1008 lanes), kw: the fields to spoil"""
+    io = _lib.StepIO()
+    io.action, io.obs, io.reward, io.terminated, io.truncated = 0x1000, 0x1000, 0x1000, 0x1000, 0x1000
+    io.action_dtype, io.row_pitch = _lib.ACTION_I32, 1008
+    for k, v in kw.items():
+        setattr(io, k, v)
+    return io
+
+
+def check_first_of_two(who, call):
+    """``call(b, p)`` -> the entry point's code for that batch and policy (its other arguments valid, or spoilt where a
+    later check would answer); asserts for every FIRST_OF_TWO case that the earlier check's whole message comes back"""
+    lib = _lib.load()
+    for batch_kw, pol_kw, case in FIRST_OF_TWO:
+        code = call(c_batch(flags=_lib.FLAG_AUTORESET, **batch_kw), c_policy(**pol_kw))
+        assert code == _lib.ERR_INVALID_ARGUMENT, (who, case)
+        assert lib.carl_last_error() == who + b": " + REFUSALS[case], (who, case, lib.carl_last_error())
+
+
 # ---------------------------------------------------------------- engines
 def defaults(family):
     return np.array([float(f.default_value) for f in FAMILIES[family].get_context_features().values()])

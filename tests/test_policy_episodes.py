@@ -9,8 +9,8 @@ import pytest
 import torch
 
 from carl_amd import _lib
-from carl_amd.policy import episode_stats
-from policy_cases import HEADER, c_batch, c_policy
+from carl_amd.policy import MLPPolicy, episode_stats
+from policy_cases import HEADER, REFUSALS, c_batch, c_policy, check_first_of_two, fake_engine, rand_layers
 
 
 def test_episodes_struct_layout_matches_c(tmp_path):
@@ -63,6 +63,23 @@ def test_c_entry_point_validates_batch_and_policy(case, batch_kw, pol_kw, msg):
     assert _call(b, p) == _lib.ERR_INVALID_ARGUMENT, case
     err = _lib.load().carl_last_error()
     assert msg in err and err.startswith(b"carl_evaluate_policy"), (case, err)
+    assert err == b"carl_evaluate_policy: " + REFUSALS[case]
+
+
+def test_c_entry_point_reports_the_earlier_of_two_bad_arguments():
+    """the batch / policy checks in their order, and all of them before the output struct and the counts"""
+    lib = _lib.load()
+    for out in (None, _eps(steps=None)):
+        check_first_of_two(b"carl_evaluate_policy", lambda b, p: _call(b, p, K=0, T=-1, out=out))
+    assert lib.carl_evaluate_policy(None, C.byref(c_policy(params=None)), 0, -1, None, None) == _lib.ERR_INVALID_ARGUMENT
+    assert lib.carl_last_error() == b"carl_evaluate_policy: batch / policy is NULL"
+    assert lib.carl_evaluate_policy(C.byref(c_batch(family=_lib.CARL_N_FAMILIES)), None, 0, -1, None, None) == -1
+    assert lib.carl_last_error() == b"carl_evaluate_policy: batch / policy is NULL"
+    # past the shared checks: the output struct before the counts, the counts before the auto-reset flag
+    assert _call(c_batch(), c_policy(), K=0, out=None) == _lib.ERR_INVALID_ARGUMENT
+    assert lib.carl_last_error() == b"carl_evaluate_policy: out and all six of its arrays are required"
+    assert _call(c_batch(), c_policy(), K=0, T=-1) == _lib.ERR_INVALID_ARGUMENT
+    assert lib.carl_last_error() == b"carl_evaluate_policy: n_episodes 0 < 1"
 
 
 @pytest.mark.parametrize("field", ["episodes", "steps", "ret", "length", "context_id", "terminated"])
@@ -98,6 +115,41 @@ def test_out_of_scope_engines_refuse():
         object.__new__(BraxVecEngine).evaluate_policy(None, 1, 1)
     with pytest.raises(NotImplementedError):
         object.__new__(MixedVecEngine).evaluate_policy(None, 1, 1)
+
+
+def test_python_refuses_bad_output_buffers_in_their_order():
+    """the whole messages of evaluate_policy's own refusals on an engine that is never launched, and which of two answers"""
+    rng = np.random.default_rng(0)
+    eng = fake_engine()
+    eng.device, eng.b = torch.device("cpu"), c_batch(flags=_lib.FLAG_AUTORESET)
+    pol = MLPPolicy.for_env(eng, rand_layers(rng, [eng.F + eng.D, 8, 2]))
+    other = fake_engine(_lib.MOUNTAINCAR)
+    stranger = MLPPolicy.for_env(other, rand_layers(rng, [other.F + other.D, 3]))
+    K, n = 2, eng.n
+
+    def out(**kw):
+        o = {k: torch.empty((K, n) if rows else (n,), dtype=dt) for k, dt, rows in eng._EPISODE_KEYS}
+        o.update(kw)
+        return o
+
+    bad_first = torch.empty(n, dtype=torch.int64)
+    for args, kw, msg in [
+            ((stranger, 0, -1), {}, f"the policy was built for family {_lib.MOUNTAINCAR}, this engine runs family {_lib.CARTPOLE}"),
+            ((pol, 0, -1), {}, "n_episodes 0 < 1"),
+            ((pol, K, -1), {"out": out(episodes=bad_first)}, "max_steps -1 < 0"),
+            ((pol, K, 5), {"out": out(episodes=bad_first, length=torch.empty((K, n)))},
+             f"evaluate_policy output 'episodes' must be a contiguous torch.int32 [{n}] tensor on cpu"),
+            ((pol, K, 5), {"out": out(length=torch.empty((K, n), dtype=torch.int32).t().contiguous().t(),
+                                      terminated=torch.empty((K, n), dtype=torch.bool))},
+             f"evaluate_policy output 'length' must be a contiguous torch.int32 [{K}, {n}] tensor on cpu"),
+            ((pol, K, 5), {"out": out(terminated=torch.empty((K + 1, n), dtype=torch.uint8))},
+             f"evaluate_policy output 'terminated' must be a contiguous torch.uint8 [{K}, {n}] tensor on cpu")]:
+        with pytest.raises(ValueError) as e:
+            eng.evaluate_policy(*args, **kw)
+        assert str(e.value) == msg
+    with pytest.raises(ValueError) as e:
+        eng.rollout_policy(stranger, 4, gae=(0.9, 0.9))  # (gae without value_net: refused after the family)
+    assert str(e.value) == f"the policy was built for family {_lib.MOUNTAINCAR}, this engine runs family {_lib.CARTPOLE}"
 
 
 # ---------------------------------------------------------------- episode_stats

@@ -11,7 +11,7 @@ import torch
 from carl_amd import _lib
 from carl_amd.envs import CARLCartPole
 from carl_amd.policy import MLPPolicy
-from policy_cases import HEADER, c_batch, fake_engine, c_policy, rand_layers
+from policy_cases import HEADER, REFUSALS, c_batch, c_io, c_policy, check_first_of_two, fake_engine, rand_layers
 
 CP_NAMES = list(CARLCartPole.get_context_features())  # table order of the CartPole family
 
@@ -155,6 +155,26 @@ def test_c_entry_point_refuses(case, batch_kw, pol_kw, msg):
     summ = _lib.PolicySummary(0x3000, 0x3000, 0x3000)
     assert lib.carl_rollout_policy(C.byref(b), C.byref(p), None, 10, C.byref(summ), None) == _lib.ERR_INVALID_ARGUMENT, case
     assert msg in lib.carl_last_error(), (case, lib.carl_last_error())
+    assert lib.carl_last_error() == b"carl_rollout_policy: " + REFUSALS[case]
+
+
+def test_c_entry_point_reports_the_earlier_of_two_bad_arguments():
+    """the batch / policy checks in their order, and all of them before n_steps, io and the summary"""
+    lib = _lib.load()
+    for io in (None, c_io(action_dtype=_lib.ACTION_I64)):
+        check_first_of_two(b"carl_rollout_policy", lambda b, p: lib.carl_rollout_policy(
+            C.byref(b), C.byref(p), None if io is None else C.byref(io), -1, None, None))
+    assert lib.carl_rollout_policy(None, C.byref(c_policy(params=None)), None, -1, None, None) == _lib.ERR_INVALID_ARGUMENT
+    assert lib.carl_last_error() == b"carl_rollout_policy: batch / policy is NULL"
+    assert lib.carl_rollout_policy(C.byref(c_batch(family=_lib.CARL_N_FAMILIES)), None, None, -1, None, None) == -1
+    assert lib.carl_last_error() == b"carl_rollout_policy: batch / policy is NULL"
+    # past the shared checks: n_steps before the summary, the io before the auto-reset a summary needs
+    b, p = c_batch(), c_policy()
+    assert lib.carl_rollout_policy(C.byref(b), C.byref(p), None, -1, None, None) == _lib.ERR_INVALID_ARGUMENT
+    assert lib.carl_last_error() == b"carl_rollout_policy: n_steps -1 < 0"
+    summ = _lib.PolicySummary(0x3000, 0x3000, 0x3000)
+    assert lib.carl_rollout_policy(C.byref(b), C.byref(p), C.byref(c_io(row_pitch=999)), 10, C.byref(summ), None) == -1
+    assert lib.carl_last_error() == b"carl_rollout_policy: io.row_pitch 999 < n_lanes 1000"
 
 
 def test_c_entry_point_refuses_bad_io_and_summary():

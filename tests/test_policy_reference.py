@@ -166,6 +166,14 @@ def test_summary_without_auto_reset_is_refused():
     summ = _lib.PolicySummary(0x3000, 0x3000, 0x3000)
     assert lib.carl_rollout_policy(C.byref(b), C.byref(p), None, 10, C.byref(summ), None) == _lib.ERR_UNSUPPORTED
     assert b"CARL_FLAG_AUTORESET" in lib.carl_last_error()
+    assert lib.carl_last_error() == (
+        b"carl_rollout_policy: a summary needs CARL_FLAG_AUTORESET (without auto-reset a finished lane reports done on "
+        b"every later step, and its episode would be counted on each of them)")
+    # the last check of all: a policy without params is refused for that, with or without the flag
+    p.params = None
+    assert lib.carl_rollout_policy(C.byref(b), C.byref(p), None, 10, C.byref(summ), None) == _lib.ERR_INVALID_ARGUMENT
+    assert lib.carl_last_error() == b"carl_rollout_policy: params is NULL"
+    p.params = 0x2000
     for n_steps, n_lanes in ((0, 1000), (10, 0)):  # (the no-step shortcut too)
         b.n_lanes = n_lanes
         assert lib.carl_rollout_policy(C.byref(b), C.byref(p), None, n_steps, C.byref(summ), None) == _lib.ERR_UNSUPPORTED

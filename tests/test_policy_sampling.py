@@ -13,7 +13,8 @@ import sampling_ref as SR
 from carl_amd import _lib
 from carl_amd.policy import MLPPolicy
 from oracle import oracle as O
-from policy_cases import HEADER, c_batch, fake_engine, c_policy, rand_layers
+from policy_cases import (HEADER, SAMPLING_LOG_PROB_REFUSED, SAMPLING_LOG_PROB_UNALIGNED, SAMPLING_LOG_STD,
+                          SAMPLING_NULL, c_batch, c_io, c_policy, check_first_of_two, fake_engine, rand_layers)
 
 
 def test_sampling_struct_layout_matches_c(tmp_path):
@@ -97,6 +98,51 @@ def test_sampled_entry_points_refuse_bad_sampling():
     assert lib.carl_rollout_policy_sampled(C.byref(b), C.byref(p), C.byref(_lib.PolicySampling(1, None, 0x4004)),
                                            C.byref(io), 10, None, None) == _lib.ERR_UNSUPPORTED
     assert b"16-byte" in lib.carl_last_error()
+
+
+def test_sampled_entry_points_word_the_sampling_checks_alike_and_in_one_order():
+    """the whole message of every sampling check under both entry points' names, and which of two spoilt fields answers:
+    sampling NULL, then log_std, then a log_prob where none is stored, then its alignment"""
+    lib = _lib.load()
+    summ = _lib.PolicySummary(0x3000, 0x3000, 0x3000)
+    bp, pp = _flags(c_batch(family=_lib.PENDULUM)), c_policy(n_in=5, n_out=1, head=_lib.POLICY_HEAD_BOX)
+    bd, pd = _flags(c_batch()), c_policy()
+    io_f = c_io(action_dtype=_lib.ACTION_F32)
+
+    def rollout(b, p, smp, io=None):
+        return lib.carl_rollout_policy_sampled(C.byref(b), C.byref(p), None if smp is None else C.byref(smp),
+                                               None if io is None else C.byref(io), 10, None if io else C.byref(summ), None)
+
+    def evaluate(b, p, smp, io=None):
+        return lib.carl_evaluate_policy_sampled(C.byref(b), C.byref(p), None if smp is None else C.byref(smp), 2, 10,
+                                                C.byref(_episodes()), None)
+
+    S = _lib.PolicySampling
+    for who, fn in ((b"carl_rollout_policy_sampled: ", rollout), (b"carl_evaluate_policy_sampled: ", evaluate)):
+        for b, p, smp, code, msg in [
+                (bp, pp, None, -1, SAMPLING_NULL),
+                (bp, pp, S(1, None, None), -1, SAMPLING_LOG_STD),
+                (bp, pp, S(1, None, 0x4004), -1, SAMPLING_LOG_STD),  # log_std before either log_prob check
+                (bp, pp, S(1, 0x6000, 0x4004), -1, SAMPLING_LOG_PROB_REFUSED),  # a column refused before its alignment
+                (bd, pd, S(1, None, 0x4000), -1, SAMPLING_LOG_PROB_REFUSED)]:
+            assert fn(b, p, smp) == code
+            assert lib.carl_last_error() == who + msg
+    # transitions mode stores the column: log_std first, then the alignment
+    who = b"carl_rollout_policy_sampled: "
+    assert rollout(bp, pp, S(1, None, 0x4004), io_f) == _lib.ERR_INVALID_ARGUMENT
+    assert lib.carl_last_error() == who + SAMPLING_LOG_STD
+    assert rollout(bp, pp, S(1, 0x6000, 0x4004), io_f) == _lib.ERR_UNSUPPORTED
+    assert lib.carl_last_error() == who + SAMPLING_LOG_PROB_UNALIGNED
+    assert rollout(bd, pd, S(1, None, 0x4008), c_io()) == _lib.ERR_UNSUPPORTED
+    assert lib.carl_last_error() == who + SAMPLING_LOG_PROB_UNALIGNED
+    # the deterministic twin's checks answer before any sampling check (sampling NULL, or a misaligned log_prob)
+    for smp in (None, S(1, None, 0x4004)):
+        check_first_of_two(b"carl_rollout_policy_sampled", lambda b, p: rollout(b, p, smp))
+        check_first_of_two(b"carl_evaluate_policy_sampled", lambda b, p: evaluate(b, p, smp))
+    assert rollout(bd, pd, None, c_io(row_pitch=999)) == _lib.ERR_INVALID_ARGUMENT
+    assert lib.carl_last_error() == who + b"io.row_pitch 999 < n_lanes 1000"
+    assert lib.carl_evaluate_policy_sampled(C.byref(bd), C.byref(pd), None, 0, 10, C.byref(_episodes()), None) == -1
+    assert lib.carl_last_error() == b"carl_evaluate_policy_sampled: n_episodes 0 < 1"
 
 
 def test_python_refusals():

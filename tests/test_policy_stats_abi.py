@@ -7,7 +7,8 @@ import subprocess
 import pytest
 
 from carl_amd import _lib
-from policy_cases import HEADER, c_batch, c_policy
+from policy_cases import (HEADER, REFUSALS, SAMPLING_LOG_PROB_REFUSED, SAMPLING_LOG_STD,
+                          c_batch, c_policy, check_first_of_two)
 
 PTR = 0x10000  # a 16-byte-aligned "device pointer" that is never dereferenced: every call here is refused first
 
@@ -79,6 +80,31 @@ def test_evaluate_stats_validates_what_evaluate_policy_validates(case, batch_kw,
     assert _call(b, p, stats=None) == want, case
     err = lib.carl_last_error()
     assert msg in err and err.startswith(b"carl_evaluate_policy_stats:"), (case, err)
+    assert err == b"carl_evaluate_policy_stats: " + REFUSALS[case]
+
+
+def test_evaluate_stats_reports_the_earlier_of_two_bad_arguments():
+    """the batch / policy checks in their order before everything else (sampling, output struct, counts and stats spoilt
+    too); then the sampling checks, whole and in their order, before the stats checks"""
+    lib = _lib.load()
+    who = b"carl_evaluate_policy_stats: "
+    for smp in (None, _lib.PolicySampling(1, None, PTR + 4)):
+        check_first_of_two(who[:-2], lambda b, p: _call(b, p, smp=smp, K=0, T=-1, out=None, stats=None))
+    assert lib.carl_evaluate_policy_stats(None, C.byref(c_policy(params=None)), None, 0, -1, None, None, None) == -1
+    assert lib.carl_last_error() == who + b"batch / policy is NULL"
+    bp = c_batch(family=_lib.PENDULUM, flags=_lib.FLAG_AUTORESET)
+    pp = c_policy(n_in=5, n_out=1, head=_lib.POLICY_HEAD_BOX)
+    for smp, b, p, code, msg in [
+            (_lib.PolicySampling(1, None, PTR + 4), bp, pp, _lib.ERR_INVALID_ARGUMENT, SAMPLING_LOG_STD),
+            (_lib.PolicySampling(1, None, PTR), bp, pp, _lib.ERR_INVALID_ARGUMENT, SAMPLING_LOG_STD),
+            (_lib.PolicySampling(1, PTR, PTR + 4), bp, pp, _lib.ERR_INVALID_ARGUMENT, SAMPLING_LOG_PROB_REFUSED),
+            (_lib.PolicySampling(1, None, PTR + 4), c_batch(flags=_lib.FLAG_AUTORESET), c_policy(), _lib.ERR_INVALID_ARGUMENT,
+             SAMPLING_LOG_PROB_REFUSED)]:
+        assert _call(b, p, smp=smp, stats=None) == code
+        assert lib.carl_last_error() == who + msg
+    # the evaluate checks before the sampling checks
+    assert _call(bp, pp, smp=_lib.PolicySampling(1, None, None), K=0, stats=None) == _lib.ERR_INVALID_ARGUMENT
+    assert lib.carl_last_error() == who + b"n_episodes 0 < 1"
 
 
 def test_evaluate_stats_refusals_in_order():

@@ -10,7 +10,8 @@ import pytest
 import value_cases as VC
 from carl_amd import _lib
 from carl_amd.policy import MLPPolicy
-from policy_cases import HEADER, c_batch, c_policy, fake_engine, rand_layers
+from policy_cases import (HEADER, SAMPLING_LOG_PROB_REQUIRED, SAMPLING_LOG_PROB_UNALIGNED, SAMPLING_LOG_STD, c_batch, c_io,
+                          c_policy, check_first_of_two, fake_engine, rand_layers)
 
 
 def fake(family=_lib.CARTPOLE, auto_reset=True):
@@ -149,6 +150,114 @@ def test_c_entry_points_refuse_on_the_host():
     for f in ("reward", "value", "last_value", "terminated", "truncated", "advantage", "ret"):
         setattr(g, f, 0x1000)
     assert lib.carl_gae(C.byref(g), None) == 0  # nothing to do: nothing enqueued
+
+
+def test_valued_entry_point_words_the_shared_checks_as_before_and_in_their_order():
+    """the whole message of the checks the critic shares with the actor and of the sampling checks, and which of two
+    spoilt arguments answers"""
+    lib = _lib.load()
+    who = b"carl_rollout_policy_valued: "
+    S = _lib.PolicySampling
+
+    def crit(n_in=6, **kw):
+        c = c_policy(n_in=n_in, n_out=1, head=_lib.POLICY_HEAD_BOX, width=(16, 8), activation=_lib.POLICY_RELU)
+        for k, v in kw.items():
+            setattr(c, k, v)
+        return c
+
+    def call(b, p, c, smp=None, io="default", out="default"):
+        io = c_io() if io == "default" else io
+        out = _lib.PolicyValue(0x4000, 0x5000, None) if out == "default" else out
+        return lib.carl_rollout_policy_valued(C.byref(b), C.byref(p), None if c is None else C.byref(c),
+                                              None if smp is None else C.byref(smp), None if io is None else C.byref(io),
+                                              4, None, None if out is None else C.byref(out), None)
+
+    b, p = c_batch(), c_policy()
+    wide = crit()
+    wide.width[0] = 65
+    for c, msg in [(crit(n_hidden=3), b"critic: n_hidden 3 outside [0, 2]"),
+                   (wide, b"critic: hidden width[0] = 65 outside [1, 64]"),
+                   (crit(activation=7), b"critic: unknown activation 7"),
+                   (crit(params=None), b"critic: params is NULL"),
+                   # two at once: the critic's checks in their order
+                   (crit(n_hidden=3, n_out=2), b"critic: n_hidden 3 outside [0, 2]"),
+                   (crit(n_out=2, n_in=5), b"critic: head width 2, a value network has 1"),
+                   (crit(n_in=5, activation=7), b"critic: n_in 5 / n_ctx 2, the actor has 6 / 2 (the critic reads the "
+                                                b"actor's inputs)"),
+                   (crit(activation=7, lanes_per_set=2048), b"critic: unknown activation 7"),
+                   (crit(activation=7, params=None), b"critic: unknown activation 7"),
+                   (crit(lanes_per_set=2048, params=None), b"critic: 1 sets x 2048 lanes, the actor has 1 x 1024"),
+                   (None, b"critic is NULL")]:
+        assert call(b, p, c, out=None) == _lib.ERR_INVALID_ARGUMENT  # (the critic before the value outputs)
+        assert lib.carl_last_error() == who + msg
+    # io NULL answers before a bad critic, a NULL batch / policy before that, the actor's own checks after it
+    assert call(b, p, crit(n_hidden=3), io=None) == _lib.ERR_INVALID_ARGUMENT
+    assert lib.carl_last_error() == who + b"io is NULL -- transitions mode only (a summary has no use for values)"
+    assert lib.carl_rollout_policy_valued(None, C.byref(p), None, None, None, 4, None, None, None) == -1
+    assert lib.carl_last_error() == who + b"batch / policy is NULL"
+    # the sampling checks: after the actor's, before the critic's; log_std, then the required column, then its alignment
+    bp = c_batch(family=_lib.PENDULUM)
+    pp, cp, io_f = c_policy(n_in=5, n_out=1, head=_lib.POLICY_HEAD_BOX), crit(n_in=5), c_io(action_dtype=_lib.ACTION_F32)
+    for smp, code, msg in [(S(1, None, 0x4004), -1, SAMPLING_LOG_STD), (S(1, None, None), -1, SAMPLING_LOG_STD),
+                           (S(1, 0x6000, None), -1, SAMPLING_LOG_PROB_REQUIRED),
+                           (S(1, 0x6000, 0x4004), _lib.ERR_UNSUPPORTED, SAMPLING_LOG_PROB_UNALIGNED)]:
+        assert call(bp, pp, crit(n_in=5, n_hidden=3), smp, io_f) == code
+        assert lib.carl_last_error() == who + msg
+    assert call(b, p, None, S(1, None, None)) == _lib.ERR_INVALID_ARGUMENT
+    assert lib.carl_last_error() == who + SAMPLING_LOG_PROB_REQUIRED
+    assert call(bp, pp, cp, S(1, None, None), c_io(action_dtype=_lib.ACTION_F32, row_pitch=999)) == -1
+    assert lib.carl_last_error() == who + b"io.row_pitch 999 < n_lanes 1000"
+    for smp in (None, S(1, None, 0x4004)):
+        check_first_of_two(who[:-2], lambda b, p: call(b, p, crit(n_hidden=3), smp, out=None))
+
+
+def test_rollout_policy_refuses_bad_columns_in_their_order():
+    """the dtype and row refusals of the per-step columns, whole, and which of two bad columns answers: the launch's
+    own buffers (action first), then log_prob, then every critic column's dtype before any critic column's rows"""
+    import torch
+
+    rng = np.random.default_rng(3)
+    eng = fake()
+    eng.device = torch.device("cpu")
+    a, c = pair(eng, rng)
+    T, n, P = 4, eng.n, 1008
+
+    def col(dtype=torch.float32, rows=T, pitch=P):
+        return torch.empty((rows, pitch), dtype=dtype)[:, :n]
+
+    def out(**kw):
+        o = {"obs": torch.empty((T, P, eng.D))[:, :n], "reward": col(), "terminated": col(torch.uint8),
+             "truncated": col(torch.uint8), "action": col(torch.int32)}
+        o.update(kw)
+        return o
+
+    def rows(k, t):
+        return (f"rollout_policy output '{k}': shape {tuple(t.shape)} / strides {tuple(t.stride())} do not form "
+                f"[>= {T}, {n}] rows of one common pitch ({P} lanes)")
+
+    short, dense, f64 = col(rows=T - 1), col(pitch=n), col(torch.float64)
+    cases = [
+        (dict(deterministic=False, log_prob=True), out(action=col(torch.int64), log_prob=f64),
+         "rollout_policy 'action' buffer must be torch.int32 for this family"),
+        (dict(deterministic=False, log_prob=True), out(action=col(torch.int32, pitch=n), log_prob=f64),
+         rows("action", col(torch.int32, pitch=n))),
+        (dict(deterministic=False, log_prob=True), out(log_prob=f64), "rollout_policy 'log_prob' buffer must be torch.float32"),
+        (dict(deterministic=False, log_prob=True), out(log_prob=short), rows("log_prob", short)),
+        (dict(deterministic=False, log_prob=True), out(log_prob=dense), rows("log_prob", dense)),
+        (dict(deterministic=False, value_net=c), out(log_prob=f64, value=f64),
+         "rollout_policy 'log_prob' buffer must be torch.float32"),
+        (dict(value_net=c), out(log_prob=f64, value=f64), "rollout_policy 'value' buffer must be torch.float32"),
+        (dict(value_net=c), out(value=short, boot_value=f64), "rollout_policy 'boot_value' buffer must be torch.float32"),
+        (dict(value_net=c), out(value=short, boot_value=dense), rows("value", short)),
+        (dict(value_net=c), out(value=col(), boot_value=dense), rows("boot_value", dense)),
+        (dict(value_net=c, bootstrap_truncated=False), out(value=dense, boot_value=f64), rows("value", dense)),
+        (dict(value_net=c), out(value=col(), boot_value=col(), last_value=torch.empty(n, dtype=torch.float64)),
+         f"rollout_policy 'last_value' must be a contiguous float32 [{n}] tensor on cpu"),
+    ]
+    for kw, o, msg in cases:
+        with pytest.raises(ValueError) as e:
+            eng.rollout_policy(a, T, out=o, **kw)
+        assert str(e.value) == msg, (kw, str(e.value))
 
 
 def test_new_struct_layouts_match_the_header(tmp_path):
