@@ -1,7 +1,9 @@
 """carl_es_perturb / carl_es_gradient on the GPU against the host reference written from the header (es_ref.py): the noise
 within the project's bound for the device's Gaussian expression of the float64 z, everything after the noise bit for
 bit -- the perturbation (two roundings, antithetic, the tail's bits), the gradient in the header's summation order --
-canaries behind every output, and the stream's dependence on seed, generation and pair."""
+canaries behind every output, and the stream's dependence on seed, generation and pair.  Pair counts up to two slices
+and a bit, and then across the rounds of the gradient kernel's slice loop (one round: 8 slices), at parameter counts
+around a workgroup's 64; an entry of the gradient does not depend on how many parameters the launch has."""
 import ctypes as C
 
 import numpy as np
@@ -138,6 +140,102 @@ def test_gradient_is_the_header_sum(device, n_noisy):
             got = gradient(es, w, device)
             want = ER.gradient_ref(w, z, sl)
             np.testing.assert_array_equal(bits(got), bits(want))
+
+
+# ---------------------------------------------------------------- past one round of the gradient's slice loop
+# es_kernels.hip.h: a workgroup of es_gradient_kernel sums kEsGradSlices = 8 slices side by side, so one trip of its s0
+# loop covers 8 * carl_es_slice_pairs() pairs; beyond that it goes round again and carries `total` across the trips.
+GRAD_SLICES = 8  # kEsGradSlices (not exported)
+ROUND_COUNTS = {"R-1": lambda R, s: R - 1, "R": lambda R, s: R, "R+1": lambda R, s: R + 1,  # the round boundary
+                "R+s+3": lambda R, s: R + s + 3,   # a second round of two slices, the last one ragged
+                "2R": lambda R, s: 2 * R,          # exactly two full rounds
+                "2R+1": lambda R, s: 2 * R + 1}    # a third round of one slice holding one pair
+# a workgroup owns 64 parameters: below, at and above one workgroup, and three of them with one parameter in the last
+ROUND_N_NOISY = [26, 63, 64, 65, 129]
+ROUND_CASES = [(n, c) for n in ROUND_N_NOISY for c in ROUND_COUNTS] + [(4417, "R+s+3")]
+
+
+def round_pairs(count):
+    s = slice_pairs()
+    return ROUND_COUNTS[count](GRAD_SLICES * s, s), GRAD_SLICES * s
+
+
+def round_weights(n_pairs, R, rng):
+    """the three weight vectors of test_gradient_is_the_header_sum, one with its inf in a pair of the second round (the
+    last pair where there is no second round), and one with an inf in each of the first two rounds: wherever the two z
+    have opposite signs the total is inf - inf"""
+    weights = [rng.normal(size=n_pairs).astype(np.float32)]
+    w = rng.normal(size=n_pairs).astype(np.float32)
+    w[rng.random(n_pairs) < 0.4] = 0.0
+    w[::3] = -np.abs(w[::3])
+    weights.append(w)
+    w = rng.normal(size=n_pairs).astype(np.float32)
+    w[n_pairs // 2] = np.inf
+    weights.append(w)
+    second = R + (n_pairs - R) // 2 if n_pairs > R else n_pairs - 1
+    w = rng.normal(size=n_pairs).astype(np.float32)
+    w[second] = np.inf
+    weights.append(w)
+    w = rng.normal(size=n_pairs).astype(np.float32)
+    w[3], w[second] = np.inf, np.inf
+    weights.append(w)
+    return weights, second
+
+
+def assert_same_floats(got, want):
+    """bit for bit; a NaN must be a NaN at the same index (its sign and payload are the adder's, not the header's)"""
+    nan = np.isnan(want)
+    np.testing.assert_array_equal(np.isnan(got), nan)
+    np.testing.assert_array_equal(bits(got)[~nan], bits(want)[~nan])
+
+
+@pytest.mark.parametrize("n_noisy, count", ROUND_CASES, ids=[f"{n}-{c}" for n, c in ROUND_CASES])
+def test_rounds_of_the_gradient_loop(device, n_noisy, count):
+    n_pairs, R = round_pairs(count)
+    k = list(ROUND_COUNTS).index(count)
+    S = set_floats_of(n_noisy, True)
+    rng = np.random.default_rng(1000 * n_noisy + k)
+    gen = [0, 7, 2**32 - 1][k % 3]
+    es = es_struct(n_pairs, S, n_noisy, sigma=[0.1, 0.02, 1.5][k % 3], generation=gen)
+    center = center_of(S, n_noisy, rng)
+    params, z = perturb(es, center, device)
+    if n_noisy == 26:  # (the host Philox dominates the cost: the noise bound at one width only)
+        z64 = ER.z64(SEED, gen, n_pairs, n_noisy)
+        err = np.abs(z.astype(np.float64) - z64)
+        assert (err <= SR.gaussian_z_bound(z64)).all(), (n_pairs, float((err / SR.gaussian_z_bound(z64)).max()))
+    assert np.isfinite(z).all() and np.abs(z).max() <= 5.8
+    np.testing.assert_array_equal(bits(params), bits(ER.perturb_ref(center, z, es.sigma)))
+    np.testing.assert_array_equal(bits(params[:, n_noisy:]), np.tile(bits(center[n_noisy:]), (2 * n_pairs, 1)))
+    weights, second = round_weights(n_pairs, R, rng)
+    sl = slice_pairs()
+    for i, w in enumerate(weights):
+        got = gradient(es, w, device)
+        want = ER.gradient_ref(w, z, sl)
+        assert_same_floats(got, want)
+        if i < 2:
+            assert np.isfinite(want).all()
+        elif i < 4:  # one inf weight: every entry is +-inf by the sign of that pair's z, none is NaN
+            at = n_pairs // 2 if i == 2 else second
+            assert np.isinf(want).all() and (np.signbit(want) == np.signbit(z[at])).all()
+        elif second != 3 and n_noisy >= 26:  # inf - inf wherever the two pairs' z differ in sign, and only there
+            np.testing.assert_array_equal(np.isnan(want), np.signbit(z[3]) != np.signbit(z[second]))
+            assert np.isnan(want).any() and not np.isnan(want).all()
+
+
+@pytest.mark.parametrize("count", ["R+s+3", "2R+1"])
+def test_an_entry_does_not_depend_on_the_grid(device, count):
+    """the counter holds the parameter index, not the launch's shape: the first 26 entries of a three-workgroup launch
+    (n_noisy = 129) are the one-workgroup launch (n_noisy = 26) of the same seed, generation, pairs and weights"""
+    n_pairs, R = round_pairs(count)
+    S = set_floats_of(129, True)
+    rng = np.random.default_rng(77)
+    center = center_of(S, 129, rng)
+    wide, narrow = es_struct(n_pairs, S, 129, generation=5), es_struct(n_pairs, S, 26, generation=5)
+    _, z_wide = perturb(wide, center, device)
+    _, z_narrow = perturb(narrow, center, device)
+    np.testing.assert_array_equal(bits(z_wide[:, :26]), bits(z_narrow))
+    for w in round_weights(n_pairs, R, rng)[0]:
+        assert_same_floats(gradient(wide, w, device)[:26], gradient(narrow, w, device))
 
 
 def test_stream_depends_on_seed_generation_and_pair(device):

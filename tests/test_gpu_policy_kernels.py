@@ -10,8 +10,8 @@ from carl_amd import _lib
 from carl_amd.policy import MLPPolicy
 from oracle import oracle as O
 from policy_cases import (ACTS, CTX_MODES, HIDDEN_SHAPES, OPTIONS, STEP_TYPES, first_layer_pre, host_summary, make_engine,
-                          make_policy, n_outputs, saturate_units)
-from policy_checks import STATS, check_deterministic_launch, deterministic_launch_shape_case
+                          make_policy, n_outputs, saturate_units, stacked_policy)
+from policy_checks import STATS, check_actions, check_deterministic_launch, deterministic_launch_shape_case
 
 pytestmark = pytest.mark.gpu
 
@@ -144,6 +144,24 @@ def test_each_lane_uses_its_own_weight_set(step_type, lanes_per_set):
             for _ in range(n_sets)]
     pol = MLPPolicy.stack(sets, lanes_per_set)
     check_deterministic_launch(eng, pol, 21, sets=np.arange(n) // lanes_per_set)
+
+
+def test_258_weight_sets():
+    """a population-sized block: workgroup w stages weight set lane_base / lanes_per_set = w for w up to 257, over two
+    chunks of steps (8 + 1); relu, so every action is compared bit for bit.  The negative control: the same actions
+    against each lane's neighbouring set do not pass"""
+    n_sets, lanes_per_set, T = 258, 256, 9
+    n = n_sets * lanes_per_set
+    eng = make_engine(_lib.CARTPOLE, n, seed=258)
+    pol = stacked_policy(eng, n_sets, lanes_per_set, np.random.default_rng(258))
+    assert pol.n_sets == n_sets and pol.activation == "relu"
+    assert np.unique(pol.params, axis=0).shape[0] == n_sets  # the sets are distinct
+    sets = np.arange(n) // lanes_per_set
+    out, x = check_deterministic_launch(eng, pol, T, sets=sets)
+    acts = out["action"][:T].cpu().numpy()
+    assert 0.2 < acts.mean() < 0.8  # (both actions occur: a wrong set is visible)
+    with pytest.raises(AssertionError):
+        check_actions(pol, x, acts, (sets + 1) % n_sets)
 
 
 # ---------------------------------------------------------------- d. engine options

@@ -75,6 +75,34 @@ def test_an_empty_launch_changes_nothing():
     assert new["count"] == 0 and sh is None
 
 
+def test_the_reference_merge_stays_inside_the_exact_bound(capsys):
+    """SR.merge (the header's operations in float64) against the pooled mean and M2 of integer data in exact rational
+    arithmetic, over one to three successive merges of up to 257 slabs: inside the bound derived from the operation list
+    (test_gpu_policy_stats_merge.py's docstring; SR.exact_merge) on every case.  The exact recursion itself is checked
+    against the plain sums of everything merged."""
+    worst = [0.0, 0.0]
+    cases = SR.exact_cases()
+    assert len(cases) == 120
+    for n_in, launches, (tot_n, tot_x, tot_xx) in cases:
+        st, ex = SR.fresh(n_in), SR.exact_fresh(n_in)
+        for partial, steps, shift in launches:
+            assert np.isnan(partial[:, :, n_in:]).all()
+            n_b = int(steps.astype(np.int64).sum())
+            st, _, _ = SR.merge(st, partial, n_b, shift)
+            ex = SR.exact_merge(ex, partial, n_b, shift)
+            r = SR.exact_ratio(ex, st["mean"], st["m2"])
+            assert max(r) <= 1.0, (n_in, r)
+            worst = [max(a, b) for a, b in zip(worst, r)]
+            assert st["count"] == ex["count"] and np.all(st["m2"] >= 0)
+        assert ex["count"] == tot_n
+        for i in range(n_in):
+            assert ex["mean"][i] == SR.Fraction(tot_x[i], tot_n)
+            assert ex["m2"][i] == tot_xx[i] - SR.Fraction(tot_x[i] * tot_x[i], tot_n)
+    with capsys.disabled():
+        print(f"\nstats_ref.merge against exact arithmetic: worst |err| / bound {worst[0]:.3f} (mean), {worst[1]:.3f} (M2)")
+    assert min(worst) > 0.01  # (the bound is of the error's order: a bound a hundred times too wide would check little)
+
+
 @pytest.mark.parametrize("widths", [()] + HIDDEN_SHAPES, ids=str)
 @pytest.mark.parametrize("family", [_lib.CARTPOLE, _lib.PENDULUM])
 def test_offsets_agree_with_the_packing(family, widths):
