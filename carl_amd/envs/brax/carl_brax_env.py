@@ -120,15 +120,7 @@ class CARLBraxEnv(CARLEnv):
             sys_table.goal_mode = 1 if goal_mode else 0
             models.apply_viscosity_rule(sys_table, names, viscosity)  # "reference": viscosity overwrites ang_damping (:278-279)
             if mass_check != "off":  # per-env clamp of the effective mass ratio (carl_brax_ctx_map_t::mass_ratio_floor)
-                from carl_amd.envs.brax.feature_tables import (COMBINED_FLOOR_SCALE, DEFAULT_MASS_RATIO_FLOOR,
-                                                               MASS_RATIO_FLOOR)
-
-                floors = MASS_RATIO_FLOOR.get(self.env_name, {})
-                scale = COMBINED_FLOOR_SCALE.get(self.env_name, 2.0)
-                cm = sys_table.ctx
-                for k in range(cm.n_mass):
-                    cm.mass_ratio_floor[k] = floors.get(names[cm.mass_row[k]], DEFAULT_MASS_RATIO_FLOOR)
-                    cm.mass_ratio_floor_multi[k] = min(1.0, scale * cm.mass_ratio_floor[k])
+                models.wire_mass_floors(sys_table, names, self.env_name)
             n_auto = batch_size > 1
             env = BraxVecEngine(
                 sys_table, len(names),

@@ -22,7 +22,8 @@ import math
 import numpy as np
 
 from carl_amd import _lib
-from carl_amd.envs.brax.feature_tables import masses
+from carl_amd.envs.brax.feature_tables import (COMBINED_FLOOR_SCALE, DEFAULT_MASS_RATIO_FLOOR, MASS_RATIO_FLOOR,
+                                               masses)
 
 
 def _axis_quat(axis) -> tuple[float, float, float, float]:
@@ -154,6 +155,19 @@ def _wire_context(s, feature_names, reference_compat, link_ids, mass_defaults):
             k = m.n_mass
             m.mass_row[k], m.mass_link[k], m.mass_nominal[k] = i, link_ids[link], float(mass_defaults[name])
             m.n_mass = k + 1
+
+
+def wire_mass_floors(s, feature_names, env_name: str) -> None:
+    """The per-env clamp of the effective mass ratio (``carl_brax_ctx_map_t::mass_ratio_floor`` / ``_multi``): every mass
+    feature's measured single floor (``feature_tables.MASS_RATIO_FLOOR``; ``DEFAULT_MASS_RATIO_FLOOR`` where none was
+    measured), and for an env with two or more light links that floor times the family's ``COMBINED_FLOOR_SCALE``, capped
+    at the default mass."""
+    floors = MASS_RATIO_FLOOR.get(env_name, {})
+    scale = COMBINED_FLOOR_SCALE.get(env_name, 2.0)
+    cm = s.ctx
+    for k in range(cm.n_mass):
+        cm.mass_ratio_floor[k] = floors.get(feature_names[cm.mass_row[k]], DEFAULT_MASS_RATIO_FLOOR)
+        cm.mass_ratio_floor_multi[k] = min(1.0, scale * cm.mass_ratio_floor[k])
 
 
 def apply_viscosity_rule(s, feature_names, rule: str) -> None:

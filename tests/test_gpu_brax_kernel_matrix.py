@@ -1,7 +1,11 @@
 """Every Brax kernel instance against the float64 oracle (oracle/brax_spring.c through oracle/brax.py), per lane.
 
 carl_brax.hip's `kBraxKernels` holds 29 (class, width) entries: 40 `brax_kernel<MODE, MULTI, K, TASK, PLANAR, F32>`
-functions, 11 reset + 29 step.  tests/brax_kernel_cases.py names one representative model per class (and
+functions, 11 reset + 29 step.  This file pins WHICH kernel runs and checks its physics on contexts that vary gravity and
+friction only, every mass at its default, under the static selector: no env changes context inside a launch.  What
+`load_ctx` does with the other columns -- elasticity, angular damping, joint stiffness, the link masses and their
+stability clamp -- and with a context that changes on an in-launch reset is checked per instance by
+tests/test_gpu_brax_context_matrix.py.  tests/brax_kernel_cases.py names one representative model per class (and
 tests/test_brax_kernel_table.py holds that table against the library), beside a back-half Halfcheetah on the planar
 kernels (joint anchors off their parent's z axis, which Hopper's are not) and the float32 shapes bench.py times; here
 every (case, width) is pinned through
@@ -33,7 +37,7 @@ import numpy as np
 import pytest
 import torch
 
-from brax_kernel_cases import CASES, EXTRA_CASES, FP32, GENERIC, build
+from brax_kernel_cases import CASES, EXTRA_CASES, FP32, GENERIC, GROUND_CONTACT, build, touch_down
 from brax_parity_util import Parity, assert_parity, rel_err, step_both
 from oracle import brax as B
 from oracle import oracle as O
@@ -46,8 +50,6 @@ COUNTERS = ("state", "elapsed", "ctx_idx", "episode", "n_calls", "ep_return", "e
             "last_length")
 ALL = CASES + EXTRA_CASES
 BY_LABEL = {c.label: c for c in ALL}
-# models that stand on the ground from reset on
-GROUND_CONTACT = {"one_leg_ant", "hopper", "back_half_cheetah", "ant", "humanoid"}
 
 
 def _rows(rng, n, default, names):
@@ -72,23 +74,8 @@ def _engine(case, s, names, rows, n, device, **kw):
 
 
 def _touch_down(eng):
-    """Lower every even env of a model that stands on the ground until its lowest collision sphere is 5 mm deep.  Hopper
-    and Humanoid start above the ground and need longer than a TimeLimit of 4 to reach it; this puts the contact path
-    into the window (the odd envs keep their reset pose, and the envs that auto-reset start from the reset pose)."""
-    s = eng.sys
-    st = eng.state64()  # [N, L, 13]: position 3, rotation (w, x, y, z), linear and angular velocity
-    link = torch.as_tensor(np.array(s.coll_link[: s.n_coll]), device=st.device)
-    # a sphere's offset from its link's centre of mass, in the link frame (the state holds the COM)
-    off = torch.as_tensor(np.array([[s.coll_pos[k][j] - s.com[s.coll_link[k]][j] for j in range(3)]
-                                    for k in range(s.n_coll)]), dtype=torch.float64, device=st.device)
-    rad = torch.as_tensor(np.array(s.coll_radius[: s.n_coll]), dtype=torch.float64, device=st.device)
-    p, q = st[:, link, :3], st[:, link, 3:7]
-    w, u = q[..., 0], q[..., 1:]  # sphere centre = p + R off, R off = off + 2 w (u x off) + 2 u x (u x off)
-    uxo = torch.cross(u, off.expand_as(u), dim=-1)
-    z = p[..., 2] + off[:, 2] + 2 * (w * uxo[..., 2] + torch.cross(u, uxo, dim=-1)[..., 2])
-    gap = (z - rad).amin(1) - float(s.plane_z)  # [N]: height of the lowest sphere's bottom above the ground
-    st[0::2, :, 2] -= (gap[0::2] + 0.005)[:, None]
-    eng.set_state64(st)
+    """the envs of a model that stands on the ground, half of them lowered 5 mm into it (brax_kernel_cases.touch_down)"""
+    eng.set_state64(touch_down(eng.sys, eng.state64().cpu().numpy()))
 
 
 def _assert_f32_parity(par: Parity, label):
