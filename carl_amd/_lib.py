@@ -287,6 +287,24 @@ EXPORTS.update({
 })
 
 
+# ---- closed-loop rollout of the Brax families (include/carl_amd.h: carl_brax_rollout_policy) ------------------------
+class BraxLaunchShape(C.Structure):
+    """carl_brax_launch_shape_t: the shape of a carl_brax_rollout_policy launch (carl_brax_policy_launch_shape; host logic)"""
+    _fields_ = [("grid", _i), ("waves_per_workgroup", _i), ("lanes_per_env", _i), ("reserved", _i),
+                ("lds_bytes", C.c_int64)]
+
+
+EXPORTS.update({
+    "carl_brax_rollout_policy": (C.c_int, [C.POINTER(Batch), _vp, C.POINTER(BraxSys), _vp, C.POINTER(Policy),
+                                           C.POINTER(StepIO), C.c_int32, C.POINTER(PolicySummary), _vp]),
+    "carl_brax_policy_set_floats": (C.c_int32, [C.POINTER(Policy)]),
+    "carl_brax_policy_launch_shape": (C.c_int, [C.POINTER(Batch), C.POINTER(BraxSys), C.POINTER(Policy), C.c_int32,
+                                                C.POINTER(BraxLaunchShape)]),
+    "carl_brax_launch_shape": (C.c_int, [C.POINTER(Batch), C.POINTER(BraxSys), C.c_int32, C.c_int32,
+                                         C.POINTER(BraxLaunchShape)]),
+})
+
+
 # ---- a critic in the closed-loop launch, and GAE (include/carl_amd.h: carl_policy_value_t, carl_gae_t) ----------
 class PolicyValue(C.Structure):
     _fields_ = [("value", _vp), ("last_value", _vp), ("boot_value", _vp)]

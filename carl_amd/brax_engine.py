@@ -33,6 +33,11 @@ _BRAX_FAMILY = -1  # ``carl_batch_t.family`` of a Brax batch: none of the built-
 class BraxVecEngine(LaneEngine):
     # optional buffers (None: not built): BraxWalkerGoalWrapper state, the first_state auto-reset's copy, the branch record
     goal_pos = success = first_state = branch_sig = None
+    # the last row of the open-loop ``rollout`` that ran since ``obs`` was last written: ``rollout`` stores observations in
+    # its own ``[T, N, D]`` output, so ``obs`` is stale after it until ``_flush_obs`` (``rollout_policy`` starts from ``obs``).
+    # A VIEW of the caller's output, read when the next ``rollout_policy`` / ``snapshot`` / masked ``reset`` runs: it keeps
+    # that output alive until then, and what the caller does to it in between is what gets read (``rollout``'s docstring)
+    _obs_pending = None
     _SNAPSHOT = LaneEngine._SNAPSHOT + ("goal_pos", "success", "first_state", "branch_sig")
 
     def __init__(self, sys_table: _lib.BraxSys, n_features: int, ctx_table, n_lanes: int, device="cuda", *,
@@ -163,8 +168,12 @@ class BraxVecEngine(LaneEngine):
                              f"rows of {int(r.stride(0))} lanes")
         return self.n
 
-    def alloc_rollout(self, n_steps: int, final_obs: bool = False, branch_record: bool = False) -> dict:
+    def alloc_rollout(self, n_steps: int, final_obs: bool = False, branch_record: bool = False,
+                      action: bool = False) -> dict:
+        """``action=True``: plus ``"action"`` ``[T, N, n_act]`` float32, the column ``rollout_policy`` writes."""
         out = super().alloc_rollout(n_steps, final_obs)
+        if action:
+            out["action"] = torch.empty((n_steps, self.n, self.sys.n_act), dtype=torch.float32, device=self.device)
         if branch_record:
             out["branch_sig"] = torch.zeros((n_steps, self.n, 2), dtype=torch.int32, device=self.device)
         if self.sys.goal_mode:
@@ -187,12 +196,51 @@ class BraxVecEngine(LaneEngine):
 
     def step(self, action):
         self._shape_for(1)
+        self._obs_pending = None  # (the step writes every lane's observation)
         return super().step(action)
 
+    def reset(self, mask: torch.Tensor | None = None) -> torch.Tensor:
+        if mask is None:
+            self._obs_pending = None
+        else:
+            self._flush_obs()  # (a masked reset writes the masked lanes' observations only)
+        return super().reset(mask)
+
+    def snapshot(self) -> dict:
+        self._flush_obs()
+        return super().snapshot()
+
+    def restore(self, snap: dict) -> None:
+        super().restore(snap)
+        self._obs_pending = None
+
+    def _flush_obs(self) -> None:
+        """``obs`` <- the current observation, where an open-loop ``rollout`` left it in its own output"""
+        if self._obs_pending is not None:
+            self.obs.copy_(self._obs_pending)
+            self._obs_pending = None
+
     def rollout(self, actions, out: dict | None = None) -> dict:
-        self._shape_for(int(actions.shape[0]))
-        if not self.sys.goal_mode:
-            return super().rollout(actions, out)
+        """``LaneEngine.rollout``.  The kernel does not write ``obs``; the engine remembers the last row of the returned
+        ``"obs"`` instead and copies it into ``obs`` when it is next needed (``rollout_policy``, ``snapshot``, a masked
+        ``reset``) -- a rollout loop pays no copy.  Until then that row must still hold what this call wrote: a caller who
+        normalises ``out["obs"]`` in place, reuses ``out`` for another launch, or replays a ``torch.cuda.graph`` that
+        captured this call (the replay does not pass through here) hands the current observation over itself, with
+        ``set_current_obs``, before ``rollout_policy``."""
+        T = int(actions.shape[0])
+        self._shape_for(T)
+        res = self._rollout_goal(actions, out) if self.sys.goal_mode else super().rollout(actions, out)
+        if T > 0:
+            self._obs_pending = res["obs"][T - 1]  # (a view: no copy unless a closed-loop launch follows)
+        return res
+
+    def set_current_obs(self, obs: torch.Tensor) -> None:
+        """``obs`` <- ``obs`` ``[N, D]``, every env's current observation, for a caller whose last ``rollout`` output no
+        longer holds it (``rollout``'s docstring); ``rollout_policy`` then starts from it."""
+        self.obs.copy_(obs)
+        self._obs_pending = None
+
+    def _rollout_goal(self, actions, out: dict | None) -> dict:
         if out is None:
             out = self.alloc_rollout(int(actions.shape[0]))
         self.b.success = out["success"].data_ptr()  # [T][N] for the duration of this launch
@@ -270,11 +318,75 @@ class BraxVecEngine(LaneEngine):
     def reset_indexed(self, idx, count):
         raise NotImplementedError("Brax families reset through a lane mask (reset(mask)) or in-kernel auto-reset")
 
-    def rollout_policy(self, *args, **kwargs):
-        raise NotImplementedError(f"{type(self).__name__}: the closed-loop rollout covers the classic-control "
-                                  "families only")
+    # ------------------------------------------------------------------ closed-loop rollout
+    def alloc_policy_summary(self) -> dict:
+        """Per-lane totals of a summary-mode ``rollout_policy``: ``episodes`` / ``length_sum`` int32, ``return_sum``
+        float32, ``[N]`` each."""
+        z = lambda dt: torch.zeros(self.n, dtype=dt, device=self.device)  # noqa: E731
+        return {"episodes": z(torch.int32), "return_sum": z(torch.float32), "length_sum": z(torch.int32)}
 
-    evaluate_policy = rollout_policy
+    def rollout_policy(self, policy, n_steps: int, out: dict | None = None, mode: str = "transitions") -> dict:
+        """``n_steps`` steps in ONE launch, each env's action computed inside the rollout kernel by ``policy`` (a
+        ``carl_amd.brax_policy.BraxMLPPolicy``) from the env's current context and observation (include/carl_amd.h:
+        carl_brax_rollout_policy).  ``mode="transitions"``: ``rollout``'s dict (``alloc_rollout(T, action=True)`` layout)
+        with ``"action"`` ``[T, N, n_act]`` float32, the actions each step took -- ``rollout`` of those actions from the
+        same engine state gives the same bits.  ``mode="summary"``: no per-step output; ``{"episodes", "return_sum",
+        "length_sum"}`` per lane, needs ``auto_reset``.  The launch starts from ``obs`` -- the observation ``reset`` and
+        ``step`` leave there; after an open-loop ``rollout`` its last row is copied in first, read from that rollout's
+        output as it is NOW (``rollout``'s docstring: a caller who changed it calls ``set_current_obs``) -- and leaves
+        every env's last observation in ``obs``.  No host synchronisation."""
+        from carl_amd.brax_policy import BraxMLPPolicy
+
+        if not isinstance(policy, BraxMLPPolicy):
+            raise TypeError(f"{type(self).__name__}.rollout_policy takes a carl_amd.brax_policy.BraxMLPPolicy, not "
+                            f"{type(policy).__name__}")
+        if policy.obs_dim != self.D or policy.n_out != self.sys.n_act:
+            raise ValueError(f"the policy was built for {policy.obs_dim} observations and {policy.n_out} actuators, this "
+                             f"engine's model has {self.D} and {self.sys.n_act}")
+        if mode not in ("transitions", "summary"):
+            raise ValueError(f"mode {mode!r}: 'transitions' or 'summary'")
+        T = int(n_steps)
+        if mode == "summary":
+            if not self.auto_reset:
+                raise ValueError("mode='summary' needs auto_reset=True: without it a finished lane reports done on every "
+                                 "later step, and the totals would count its episode on each of them")
+            res = self.alloc_policy_summary() if out is None else out
+            for k, dt in (("episodes", torch.int32), ("return_sum", torch.float32), ("length_sum", torch.int32)):
+                t = res.get(k)
+                if (t is None or t.device != self.device or t.dtype != dt or tuple(t.shape) != (self.n,)
+                        or not t.is_contiguous()):
+                    raise ValueError(f"rollout_policy summary '{k}' must be a contiguous {dt} [{self.n}] tensor on "
+                                     f"{self.device}")
+            io, summ = None, C.byref(_lib.PolicySummary(*(_ptr(res[k]) for k in ("episodes", "return_sum", "length_sum"))))
+        else:
+            res = self.alloc_rollout(T, action=True) if out is None else out
+            a = res.get("action")
+            if (a is None or a.dtype != torch.float32 or a.device != self.device or a.dim() != 3 or a.shape[0] < T
+                    or tuple(a.shape[1:]) != (self.n, self.sys.n_act) or not a.is_contiguous()):
+                raise ValueError(f"rollout_policy output needs a contiguous float32 'action' [>= {T}, {self.n}, "
+                                 f"{self.sys.n_act}] buffer on {self.device}")
+            io, summ = C.byref(self._rollout_io(a, _lib.ACTION_F32, res, T)), None
+        # (after ``autotune``: the width that was fastest for the OPEN-loop rollout of this length class.  The closed loop
+        # has 164 more LDS rows per env and another instruction mix; whether its best width differs is not measured)
+        self._shape_for(T)
+        self._flush_obs()
+        params = policy.device_params(self.device)
+        pol = policy.struct(self.n, params.data_ptr())
+        goal = self.sys.goal_mode and mode == "transitions"
+        if goal:
+            self.b.success = res["success"].data_ptr()  # [T][N] for the duration of this launch
+        try:
+            with torch.cuda.device(self.device):
+                _lib.check(self.lib.carl_brax_rollout_policy(C.byref(self.b), _ptr(self.sys_dev), C.byref(self.sys),
+                                                             _ptr(self.obs), C.byref(pol), io, T, summ, self._stream()))
+        finally:
+            if goal:
+                self.b.success = self.success.data_ptr()
+        return res
+
+    def evaluate_policy(self, *args, **kwargs):
+        raise NotImplementedError(f"{type(self).__name__}: the episodes mode of the closed-loop rollout covers the "
+                                  "classic-control families only")
 
     def reset_done(self):
         return self.reset((self.terminated | self.truncated))

@@ -1,0 +1,60 @@
+"""A small fp32 MLP evaluated inside the Brax rollout kernel (include/carl_amd.h: carl_brax_rollout_policy).
+
+``BraxMLPPolicy`` is ``carl_amd.policy.MLPPolicy`` for the Brax families: the same packed weight sets, built by the same
+code, the same input vector -- ``FlattenObservation(env)``: the visible context values, then the observation -- and the
+same arithmetic on the device.  What differs is where its sizes come from: a Brax engine is a model table, not one of the
+built-in families, so the head width is the model's actuator count (``n_act`` Box outputs, which the env clips as it
+clips an action given to ``step``) and the observation width the model's ``obs_dim``, both read from the engine.
+``BraxVecEngine.rollout_policy`` / ``CARLBraxEnv.rollout_policy`` run it for T steps in one launch.
+
+At most ``CARL_POLICY_MAX_IN`` = 32 inputs: Humanoid's and HumanoidStandup's 244 observations do not fit.  Out of scope
+here: sampled actions and log-probabilities, value networks and GAE, input statistics, the episodes mode
+(``evaluate_policy``), ``carl_amd.es.EvolutionStrategy`` and ``MixedVecEngine``.
+"""
+from __future__ import annotations
+
+from typing import Sequence
+
+from carl_amd.policy import MLPPolicy, flattened_context_rows
+
+
+def _brax_engine_of(env):
+    """(BraxVecEngine, CARLBraxEnv or None) of what the caller passes"""
+    from carl_amd.brax_engine import BraxVecEngine
+
+    carl_env, eng = None, env
+    if not isinstance(env, BraxVecEngine) and isinstance(getattr(env, "env", None), BraxVecEngine):
+        carl_env, eng = env, env.env
+    if not isinstance(eng, BraxVecEngine):
+        raise TypeError(f"BraxMLPPolicy: {type(env).__name__} is not a CARLBraxEnv or BraxVecEngine (the classic-control "
+                        "families take carl_amd.policy.MLPPolicy)")
+    return eng, carl_env
+
+
+class BraxMLPPolicy(MLPPolicy):
+    """One or more weight sets of one MLP shape for one Brax model (see the module docstring).  ``info``: the engine's
+    info record (``BraxVecEngine.info``); the other parameters are ``MLPPolicy``'s."""
+
+    def __init__(self, info, ctx_rows: Sequence[int], layers: Sequence, activation: str = "tanh", input_shift=None,
+                 input_scale=None, input_clip: float | None = None, context_names: Sequence | None = None):
+        from carl_amd.brax_engine import _BRAX_FAMILY
+
+        super().__init__(_BRAX_FAMILY, info.obs_dim, ctx_rows, layers, activation, input_shift, input_scale, input_clip,
+                         context_names, None, "policy", info=info)
+
+    @staticmethod
+    def _box_outputs(info) -> int:
+        return int(info.action_dim)  # one output per actuator
+
+    @classmethod
+    def for_env(cls, env, layers: Sequence, activation: str = "tanh", input_shift=None, input_scale=None,
+                input_clip: float | None = None, context_features: Sequence | None = None) -> "BraxMLPPolicy":
+        """A policy for ``env`` (a ``CARLBraxEnv`` or ``BraxVecEngine``) from explicit ``(W [out, in], b [out])`` arrays,
+        hidden layers first, the head (``n_act`` outputs) last; ``context_features`` as ``MLPPolicy.for_env``'s."""
+        eng, _ = _brax_engine_of(env)
+        rows, names = flattened_context_rows(env, context_features, _brax_engine_of)
+        return cls(eng.info, rows, layers, activation, input_shift, input_scale, input_clip, names)
+
+    @staticmethod
+    def unpack(template, packed, log_std=None):
+        raise NotImplementedError("BraxMLPPolicy: unpack (input statistics) is out of scope for the Brax families")

@@ -395,6 +395,19 @@ __host__ __device__ inline Layout layout_of(const carl_brax_sys_t& s) {
   return Layout::make(s.n_links, s.n_dof, io_rows_of(s), overlay ? s.n_q + s.n_dof : -1);
 }
 
+// The closed-loop rollout (Group::run, MODE 2) adds rows per env behind layout_of's, for that mode only: the policy's
+// transformed inputs (CARL_POLICY_MAX_IN = 32), the activations of its two hidden layers (2 x CARL_POLICY_MAX_WIDTH = 64)
+// and the env's summary totals (3, rounded to 4).  layout_of itself -- what modes 0 and 1 allocate -- is unchanged.
+constexpr int kPolicyXRows = 32, kPolicyHRows = 64, kPolicySumRows = 4;
+constexpr int kPolicyRows = kPolicyXRows + 2 * kPolicyHRows + kPolicySumRows;
+__host__ __device__ inline Layout policy_layout_of(const carl_brax_sys_t& s) {
+  Layout l = layout_of(s);
+  l.total += kPolicyRows;  // rows [layout_of(s).total, total)
+  return l;
+}
+// run()'s policy argument in modes 0 and 1: none
+struct NoPolicy {};
+
 // tree topology derived from the model table once per workgroup
 struct Topo {
   uint8_t child_begin[CARL_BRAX_MAX_LINKS + 1], child_idx[CARL_BRAX_MAX_LINKS];
@@ -2179,12 +2192,18 @@ static __device__ __forceinline__ void write_ctx_obs(const carl_batch_t& b, cons
 }
 
 // mode 0: reset (mask optional), mode 1: n_steps env steps (1 = per call, T = fused rollout)
+// mode 2: mode 1 closed loop (include/carl_amd.h: carl_brax_rollout_policy; compiled from carl_brax_policy.hip alone).  At
+// the top of a step the env's io rows hold its current observation; the env's lanes evaluate the policy `pol`
+// (brax_policy_kernels.hip.h) on it in place and leave the action in those rows, where mode 1 puts the action it was fed.
+// io.action is an OUTPUT; with io.obs == NULL (summary mode) no per-step record is stored at all.  A fragment starts from
+// the env's observation in pol.cur_obs [N][obs_dim] and leaves its last one there, ordered between the two wavefronts of
+// a split group by the head_done release / acquire like the state record.
 // F32 (MODE 1, CARL_FLAG_BRAX_FP32): the n_frames substeps of an env step run their pose algebra in float32.
-template <int MODE, bool MULTI, bool TASK, bool PLANAR = false, bool F32 = false>
+template <int MODE, bool MULTI, bool TASK, bool PLANAR = false, bool F32 = false, class Pol = NoPolicy>
 static __device__ __forceinline__ void run(const carl_batch_t& b, const carl_brax_sys_t* __restrict__ sys_dev,
                                            const Prepared& prep, const carl_step_io_t& io,
                                            const uint8_t* __restrict__ mask, float* __restrict__ reset_obs,
-                                           const int n_steps) {
+                                           const int n_steps, [[maybe_unused]] const Pol& pol = Pol()) {
   __shared__ carl_brax_sys_t s;
   __shared__ Topo tp;
   __shared__ Packed pk;
@@ -2248,7 +2267,8 @@ static __device__ __forceinline__ void run(const carl_batch_t& b, const carl_bra
   // point at the last env's column, own no link (sub beyond every loop bound) and are never active
   const int tid = (int)threadIdx.x & (kLanes - 1), wave = (int)threadIdx.x >> 6;
   const bool lane_ok = tid < kEnvs * kSub;
-  const Layout lay = layout_of(s);
+  const Layout lay = MODE == 2 ? policy_layout_of(s) : layout_of(s);
+  [[maybe_unused]] const int pol_rows = lay.total - kPolicyRows;  // MODE 2: where the policy's rows begin (policy_layout_of)
   char* const my_lds = reinterpret_cast<char*>(lds_dyn) + (size_t)wave * lay.bytes(kEnvs);  // this wavefront's slice
   const Lds m{my_lds, reinterpret_cast<float*>(my_lds + lay.rows_offset(kEnvs)), lay,
               lane_ok ? tid / kSub : kEnvs - 1, lane_ok ? tid % kSub : kLanes};
@@ -2355,12 +2375,23 @@ static __device__ __forceinline__ void run(const carl_batch_t& b, const carl_bra
       r.pos_x = b.goal_pos[env];
       r.pos_y = b.goal_pos[n + env];
     }
+    if constexpr (MODE == 2) {
+      // the observation the fragment's first step acts on; the env's summary totals so far (0 at the launch's start)
+      record_in(pol.cur_obs, (size_t)env, s.obs_dim, m, active);
+      if (lead && pol.sum.episodes != nullptr) {
+        const int k = pol_rows + kPolicyXRows + 2 * kPolicyHRows;
+        m.atu(k) = t_lo > 0 ? (uint32_t)pol.sum.episodes[env] : 0u;
+        m.at(k + 1) = t_lo > 0 ? pol.sum.return_sum[env] : 0.0f;
+        m.atu(k + 2) = t_lo > 0 ? (uint32_t)pol.sum.length_sum[env] : 0u;
+      }
+    }
     prof.mark(kProfLoad);
     // The env's action record of step t + 1 is fetched while step t computes (two registers per lane: every shipped
     // model has n_act <= 2 kSub) -- a load issued at the step's own start costs the wavefront one HBM round trip per env
     // step before anything can begin.  Models with more actuators per lane take the direct path.
     const int n_act = __builtin_amdgcn_readfirstlane(s.n_act);
-    const bool act_prefetch = n_act <= 2 * kSub;
+    const bool act_prefetch = MODE != 2 && n_act <= 2 * kSub;  // (MODE 2 reads no action)
+    const bool per_step = MODE != 2 || io.obs != nullptr;      // MODE 2, summary mode: no per-step record (wavefront-uniform)
     const float* const act_env = static_cast<const float*>(io.action) + (size_t)env * n_act;
     const size_t act_step = n * (size_t)n_act;
     const int ak0 = m.sub, ak1 = m.sub + kSub;
@@ -2386,6 +2417,11 @@ static __device__ __forceinline__ void run(const carl_batch_t& b, const carl_bra
       // The env's episode scalars (identical in all its lanes) wait in LDS until the reward needs them: a dozen registers
       // per lane that the substeps and observe need more.
       if (lead) stash_put(m, r);
+      if constexpr (MODE == 2) {
+        // the policy on the observation in the io rows -> the action in the io rows, and in row t of io.action
+        pol.template act<kSub>(m, pol_rows, b, r.cidx, env, active, s.obs_dim, n_act,
+                per_step ? const_cast<float*>(static_cast<const float*>(io.action)) + (step_off + (size_t)env) * n_act : nullptr);
+      } else
       if (act_prefetch) {
         if (active) {
           if (ak0 < n_act) m.at(m.lay.io + ak0) = a_next0;
@@ -2538,11 +2574,11 @@ static __device__ __forceinline__ void run(const carl_batch_t& b, const carl_bra
         const bool ok = cur <= r.goal_radius;
         terminated = terminated | ok;
         reward = fmaxf(0.0f, prev - cur);
-        if (lead && b.success != nullptr) b.success[step_off + env] = (uint8_t)ok;
+        if (lead && per_step && b.success != nullptr) b.success[step_off + env] = (uint8_t)ok;
       }
       r.ep_return += reward;
       const bool done = active && (terminated | truncated);
-      if (lead) {
+      if (lead && per_step) {
         io.reward[step_off + env] = reward;
         io.terminated[step_off + env] = (uint8_t)terminated;
         io.truncated[step_off + env] = (uint8_t)truncated;
@@ -2558,6 +2594,14 @@ static __device__ __forceinline__ void run(const carl_batch_t& b, const carl_bra
             if (b.last_length) b.last_length[env] = fin_len;
           }
           r.n_new_episodes += 1;
+          if constexpr (MODE == 2) {
+            if (m.sub == 0 && pol.sum.episodes != nullptr) {  // the env's totals: fp32 return sum in step order
+              const int k = pol_rows + kPolicyXRows + 2 * kPolicyHRows;
+              m.atu(k) += 1u;
+              m.at(k + 1) += fin_ret;
+              m.atu(k + 2) += (uint32_t)fin_len;
+            }
+          }
         }
         log_finished(b, done && m.sub == 0, genv, fin_ret, fin_len);
         if (b.flags & CARL_FLAG_AUTORESET) {
@@ -2597,9 +2641,18 @@ static __device__ __forceinline__ void run(const carl_batch_t& b, const carl_bra
         }
       }
       prof.mark(kProfDone);
-      record_out(io.obs + step_off * s.obs_dim, (size_t)env, s.obs_dim, m, active);
+      record_out(io.obs + step_off * s.obs_dim, (size_t)env, s.obs_dim, m, active && per_step);
       phase_sync();  // the next step's actions overwrite the io rows
       prof.mark(kProfOutput);
+    }
+    if constexpr (MODE == 2) {
+      record_out(pol.cur_obs, (size_t)env, s.obs_dim, m, active);  // the env's current observation (the io rows hold it)
+      if (lead && pol.sum.episodes != nullptr) {
+        const int k = pol_rows + kPolicyXRows + 2 * kPolicyHRows;
+        pol.sum.episodes[env] = (int32_t)m.atu(k);
+        pol.sum.return_sum[env] = m.at(k + 1);
+        pol.sum.length_sum[env] = (int32_t)m.atu(k + 2);
+      }
     }
     if (active) {
       record_store(b.state + (size_t)env * S, m, s.n_links, true);

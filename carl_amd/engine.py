@@ -80,6 +80,7 @@ class CapturedStep:
             return self.eng.step(self.action)
         self.graph.replay()
         e = self.eng
+        e._obs_pending = None  # (BraxVecEngine: the replayed steps wrote every lane's observation)
         return e.obs, e.reward, e.terminated, e.truncated
 
 
@@ -93,6 +94,7 @@ class LaneEngine:
     subclass's ``CARL_FLAG_*`` bits; every other parameter is described at ``VecEngine``."""
 
     # every buffer a launch can change (snapshot / restore); a subclass appends its own, None = not built
+    _obs_pending = None  # (BraxVecEngine: where the current observation is when ``obs`` does not hold it)
     _SNAPSHOT = ("state", "elapsed", "ctx_idx", "episode", "n_calls", "ep_return", "last_return", "last_length",
                  "episodes_done", "obs", "reward", "terminated", "truncated", "done", "final_obs", "ctx_obs", "fin_count")
 

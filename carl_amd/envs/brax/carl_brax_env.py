@@ -330,6 +330,12 @@ class CARLBraxEnv(CARLEnv):
             info["success"] = 0 if self._scalar_api else torch.zeros_like(self.env.success)
         return self._with_goal_text(obs, info.get("context_id")), info
 
+    def rollout_policy(self, policy, n_steps: int, out: dict | None = None, mode: str = "transitions") -> dict:
+        """``n_steps`` closed-loop steps of every env in one launch, actions computed inside the rollout kernel by
+        ``policy`` (``carl_amd.brax_policy.BraxMLPPolicy.for_env(self, ...)``): ``BraxVecEngine.rollout_policy`` of this
+        env's engine.  The host selector object is not consulted."""
+        return self.env.rollout_policy(policy, n_steps, out=out, mode=mode)
+
     @classmethod
     def get_default_context(cls) -> Context:
         """Default context without goal features (reference: :308-324)."""

@@ -36,8 +36,9 @@ lanes visited inside the launch, and ``InputStats`` keeps their running mean and
 ``shift`` / ``scale`` they imply into packed weight sets (include/carl_amd.h: carl_policy_stats_merge) -- ARS V2's state
 normalisation, which ``carl_amd.es.EvolutionStrategy(normalize_inputs=True)`` runs every generation.
 
-Out of scope: the Brax families, ``MixedVecEngine`` pairs, the gymnasium drop-in (``carl_amd.dropin``) and the
-multi-process helpers (``carl_amd.distributed``).
+Out of scope: ``MixedVecEngine`` pairs, the gymnasium drop-in (``carl_amd.dropin``) and the
+multi-process helpers (``carl_amd.distributed``).  The Brax families have a class and a launch of their own:
+``carl_amd.brax_policy.BraxMLPPolicy`` (same packing, through this class) and ``BraxVecEngine.rollout_policy``.
 """
 from __future__ import annotations
 
@@ -69,11 +70,12 @@ def _engine_of(env):
     return eng, carl_env
 
 
-def flattened_context_rows(env, features: Sequence | None = None) -> tuple[list[int], list]:
+def flattened_context_rows(env, features: Sequence | None = None, engine_of=None) -> tuple[list[int], list]:
     """Context-table rows (and their names, or rows for a bare engine) of the context part of ``FlattenObservation(env)``,
     in its order.  ``features``: a subset to use instead (names for a ``CARLEnv``, table rows for a ``VecEngine``), each of
-    which must be a context value the engine makes visible; ``[]``: the policy sees the observation only."""
-    eng, cenv = _engine_of(env)
+    which must be a context value the engine makes visible; ``[]``: the policy sees the observation only.  ``engine_of``:
+    what resolves (and refuses) ``env`` (default: the classic-control rule)."""
+    eng, cenv = (engine_of or _engine_of)(env)
     visible = list(eng.ctx_obs_rows)
     if cenv is None:
         rows = visible if features is None else [int(f) for f in features]
@@ -98,8 +100,10 @@ class MLPPolicy:
 
     def __init__(self, family: int, obs_dim: int, ctx_rows: Sequence[int], layers: Sequence, activation: str = "tanh",
                  input_shift=None, input_scale=None, input_clip: float | None = None, context_names: Sequence | None = None,
-                 log_std=None, head: str = "policy"):
-        info = _lib.family_info(int(family))
+                 log_std=None, head: str = "policy", info=None):
+        """``info``: the family's info record (default: ``carl_family_info(family)``; a subclass for engines that are
+        not built-in families passes its engine's)."""
+        info = _lib.family_info(int(family)) if info is None else info
         self.family, self.obs_dim = int(family), int(obs_dim)
         self.ctx_rows = [int(r) for r in ctx_rows]
         self.context_names = list(context_names) if context_names is not None else list(self.ctx_rows)
@@ -132,7 +136,7 @@ class MLPPolicy:
             raise ValueError(f"hidden widths {self.widths}: at most {_lib.POLICY_MAX_HIDDEN} layers of width <= "
                              f"{_lib.POLICY_MAX_WIDTH}")
         self.n_out = self.layers[-1][0].shape[0]
-        want = 1 if head == "value" else int(info.n_actions) if self.discrete else 1
+        want = 1 if head == "value" else int(info.n_actions) if self.discrete else self._box_outputs(info)
         if self.n_out != want:
             kind = "a value network has one output" if head == "value" else "n_actions" if self.discrete else "Box"
             raise ValueError(f"head width {self.n_out}: this family needs {want} ({kind})")
@@ -154,6 +158,11 @@ class MLPPolicy:
         self.lanes_per_set = None  # one set: every lane
         self._on_device = False  # on_device(): params is the caller's device tensor, never copied
         self._dev = {}
+
+    @staticmethod
+    def _box_outputs(info) -> int:
+        """head width of a Box family's policy"""
+        return 1
 
     # ------------------------------------------------------------------ construction
     @classmethod
@@ -210,14 +219,14 @@ class MLPPolicy:
             raise ValueError("stack(): a policy whose parameters live on the device (on_device) is not stacked on the host")
         if head is not None and any(p.head != head for p in policies):
             raise ValueError(f"stack(head={head!r}): every weight set must have that head")
-        key = lambda p: (p.family, p.ctx_rows, p.obs_dim, [W.shape for W, _ in p.layers], p.activation, p.head)  # noqa: E731
+        key = lambda p: (type(p), p.family, p.ctx_rows, p.obs_dim, [W.shape for W, _ in p.layers], p.activation, p.head)  # noqa: E731
         for p in policies[1:]:
             if key(p) != key(p0):
                 raise ValueError("stack(): every weight set must have the same family, inputs, shape and activation")
         q = _lib.load().carl_policy_lane_quantum()
         if lanes_per_set <= 0 or lanes_per_set % q:
             raise ValueError(f"lanes_per_set {lanes_per_set} is not a positive multiple of {q}")
-        out = object.__new__(MLPPolicy)
+        out = object.__new__(type(p0))
         out.__dict__.update(p0.__dict__)
         out.params = np.concatenate([p.params for p in policies], axis=0)
         out.log_std = np.concatenate([p.log_std for p in policies])
@@ -262,7 +271,7 @@ class MLPPolicy:
             if (not isinstance(ls, torch.Tensor) or ls.device != params.device or ls.dtype != torch.float32
                     or tuple(ls.shape) != (n_sets,) or not ls.is_contiguous()):
                 raise ValueError(f"on_device(): log_std must be a contiguous float32 [{n_sets}] tensor on {params.device}")
-        out = object.__new__(MLPPolicy)
+        out = object.__new__(type(template))
         out.__dict__.update(template.__dict__)
         out.params, out.log_std = params, ls
         out.lanes_per_set = int(lanes_per_set)

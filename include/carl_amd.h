@@ -1,5 +1,7 @@
 /* carl_amd.h -- C ABI of the MI355X batched step/reset engine for CARL's
- * contextual classic-control (and Brax-locomotion) families.
+ * contextual classic-control (and Brax-locomotion) families: reset / step / fused open-loop rollout for both, and the
+ * closed-loop rollout with a policy network on the device (carl_rollout_policy and its sampled / valued / episodes / ES
+ * forms for the classic-control families; carl_brax_rollout_policy, deterministic transitions and summary, for Brax).
  *
  * The reference (automl/CARL v1.1.1) has NO FFI on this path: its boundary is a
  * Python protocol, "the object CARLEnv wraps" (SURVEY.md section 8b).  This header
@@ -324,7 +326,9 @@ int32_t carl_done_compact_scratch_elems(int32_t n);
  * for every lane at every step instead, and that step takes the action it yields: the workload of evaluating a
  * trained agent over a context set (the reference's examples/carl_with_sb3.py trains a policy on
  * FlattenObservation(env); carl/envs/carl_env.py:276-305 builds what it sees).  Classic-control families only: a
- * Brax batch (family >= CARL_N_FAMILIES) is refused, and so are the pair launch (carl_rollout_pair) and the
+ * Brax batch (family >= CARL_N_FAMILIES) is refused here -- the Brax families have carl_brax_rollout_policy, a mode of
+ * their own rollout kernel, further down; the episodes mode, sampling, the critic, ES and the input statistics below
+ * stay classic-control only -- and so are the pair launch (carl_rollout_pair) and the
  * narrow action formats -- the kernel writes the actions it takes, it reads none.
  *
  * The policy's input is what FlattenObservation(env) yields for a lane:
@@ -887,6 +891,54 @@ int carl_brax_model_is_planar(const carl_brax_sys_t* sys_host);
  * that every group-step is run exactly once, in step order, and that no hand-over can wait on a later one). */
 int carl_brax_fragment_plan(int32_t n_groups, int32_t n_workgroups, int32_t waves_per_workgroup, int32_t n_steps,
                             int32_t workgroup, int32_t wave, int32_t* fragments_out, int32_t cap);
+
+/* ---- closed-loop rollout of the Brax families (additive; ABI version unchanged) ----
+ * carl_rollout_policy refuses a Brax batch; this is its Brax counterpart, a mode of the rollout kernel itself: T steps of
+ * every env in ONE launch, each step's action computed on the device by `policy_host` from the env's current context and
+ * observation.  No reference counterpart: the reference steps the env per Python call and its caller runs the policy
+ * between the calls (carl/envs/carl_env.py:321-342, examples/carl_with_sb3.py).
+ * The policy is a carl_policy_t as carl_rollout_policy specifies it -- the same input vector
+ *   x = [ctx_table[ctx_rows[0]][c], ..., ctx_table[ctx_rows[n_ctx - 1]][c], obs_0, ..., obs_{obs_dim - 1}]
+ * (c: the env's CURRENT context, after any auto-reset of the previous step), the same transform, layers, activations and
+ * arithmetic (explicit fma, input order, bias first; tanh as described there), the same packed parameters -- with
+ *   head == CARL_POLICY_HEAD_BOX, n_out == sys.n_act (the action is the head's n_act outputs as they come; the env clips
+ *   them exactly as it clips actions given to carl_brax_rollout), n_in == n_ctx + sys.obs_dim <= CARL_POLICY_MAX_IN
+ *   (Humanoid's and HumanoidStandup's 244 observations are refused), every ctx_rows[k] one of batch.ctx_obs_feat,
+ *   lanes_per_set a positive multiple of carl_policy_lane_quantum() with n_sets * lanes_per_set >= n_lanes (env l uses
+ *   set l / lanes_per_set), params on a 16-byte boundary, carl_brax_policy_set_floats() floats per set
+ *   (carl_policy_set_floats limits n_out to 4).
+ * `obs` [n_lanes][obs_dim] (DEVICE) holds every env's current observation when the launch starts -- what carl_brax_reset
+ * and carl_brax_step leave in their obs arrays -- and every env's last observation when it ends.
+ *  - transitions mode (io != NULL): everything carl_brax_rollout writes (dense rows), with io->action [T][n_lanes][n_act]
+ *    float32 an OUTPUT: row t holds the actions step t took.  carl_brax_rollout of those actions from the same engine
+ *    state gives the same bits, and the same engine state.
+ *  - summary mode (io == NULL): no per-step stores; summary_out (required) receives each env's totals as
+ *    carl_rollout_policy defines them.  A summary (in either mode) needs CARL_FLAG_AUTORESET, else CARL_ERR_UNSUPPORTED.
+ * The batch, the model and io are checked as carl_brax_rollout checks them.  CARL_FLAG_BRAX_FP32 is refused with
+ * CARL_ERR_UNSUPPORTED; both auto-reset modes and the goal wrapper work as in carl_brax_rollout.  Out of scope: sampled
+ * actions and log-probabilities, critics and GAE, input statistics, an episodes mode. */
+int carl_brax_rollout_policy(const carl_batch_t* batch, const carl_brax_sys_t* sys_dev, const carl_brax_sys_t* sys_host,
+                             float* obs, const carl_policy_t* policy_host, const carl_step_io_t* io, int32_t n_steps,
+                             const carl_policy_summary_t* summary_out, void* stream);
+/* floats per packed weight set of a Brax policy's shape (n_out up to CARL_BRAX_MAX_ACT); -1 for an invalid shape */
+int32_t carl_brax_policy_set_floats(const carl_policy_t* policy_host);
+/* The shape carl_brax_rollout_policy launches for this batch, model and step count (host only, no device access beyond the
+ * compute-unit count of the current device; 256 where there is none): with n_groups = ceil(n_lanes / (64 / lanes_per_env))
+ * it is what carl_brax_fragment_plan takes. */
+typedef struct carl_brax_launch_shape {
+  int32_t grid;                /* workgroups */
+  int32_t waves_per_workgroup; /* wavefronts per workgroup */
+  int32_t lanes_per_env;       /* lanes that share an env (64 / lanes_per_env envs per wavefront) */
+  int32_t reserved;
+  int64_t lds_bytes;           /* dynamic LDS per workgroup */
+} carl_brax_launch_shape_t;
+int carl_brax_policy_launch_shape(const carl_batch_t* batch, const carl_brax_sys_t* sys_host, const carl_policy_t* policy_host,
+                                  int32_t n_steps, carl_brax_launch_shape_t* out);
+/* The same for the launches of carl_brax_reset (step == 0; n_steps ignored), carl_brax_step (step != 0, n_steps == 1) and
+ * carl_brax_rollout (step != 0): the closed-loop launch of the same batch has the same lanes_per_env, and each wavefront's
+ * slice of lds_bytes is larger by the policy's rows alone. */
+int carl_brax_launch_shape(const carl_batch_t* batch, const carl_brax_sys_t* sys_host, int32_t step, int32_t n_steps,
+                           carl_brax_launch_shape_t* out);
 
 /* ======================= context sets on the device =======================
  * Replaces ContextSampler.sample_contexts (carl/context/sampler.py:45-61: per-feature draws from
