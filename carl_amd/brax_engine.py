@@ -11,7 +11,7 @@ from dataclasses import dataclass
 import torch
 
 from carl_amd import _lib
-from carl_amd.engine import LaneEngine, _ptr
+from carl_amd.engine import LaneEngine, VecEngine, _ptr
 
 
 @dataclass
@@ -325,6 +325,17 @@ class BraxVecEngine(LaneEngine):
         z = lambda dt: torch.zeros(self.n, dtype=dt, device=self.device)  # noqa: E731
         return {"episodes": z(torch.int32), "return_sum": z(torch.float32), "length_sum": z(torch.int32)}
 
+    def _check_policy(self, policy, what: str) -> None:
+        """the policy / model checks of the closed-loop launches (``rollout_policy``, ``evaluate_episodes``)"""
+        from carl_amd.brax_policy import BraxMLPPolicy
+
+        if not isinstance(policy, BraxMLPPolicy):
+            raise TypeError(f"{type(self).__name__}.{what} takes a carl_amd.brax_policy.BraxMLPPolicy, not "
+                            f"{type(policy).__name__}")
+        if policy.obs_dim != self.D or policy.n_out != self.sys.n_act:
+            raise ValueError(f"the policy was built for {policy.obs_dim} observations and {policy.n_out} actuators, this "
+                             f"engine's model has {self.D} and {self.sys.n_act}")
+
     def rollout_policy(self, policy, n_steps: int, out: dict | None = None, mode: str = "transitions") -> dict:
         """``n_steps`` steps in ONE launch, each env's action computed inside the rollout kernel by ``policy`` (a
         ``carl_amd.brax_policy.BraxMLPPolicy``) from the env's current context and observation (include/carl_amd.h:
@@ -335,14 +346,7 @@ class BraxVecEngine(LaneEngine):
         ``step`` leave there; after an open-loop ``rollout`` its last row is copied in first, read from that rollout's
         output as it is NOW (``rollout``'s docstring: a caller who changed it calls ``set_current_obs``) -- and leaves
         every env's last observation in ``obs``.  No host synchronisation."""
-        from carl_amd.brax_policy import BraxMLPPolicy
-
-        if not isinstance(policy, BraxMLPPolicy):
-            raise TypeError(f"{type(self).__name__}.rollout_policy takes a carl_amd.brax_policy.BraxMLPPolicy, not "
-                            f"{type(policy).__name__}")
-        if policy.obs_dim != self.D or policy.n_out != self.sys.n_act:
-            raise ValueError(f"the policy was built for {policy.obs_dim} observations and {policy.n_out} actuators, this "
-                             f"engine's model has {self.D} and {self.sys.n_act}")
+        self._check_policy(policy, "rollout_policy")
         if mode not in ("transitions", "summary"):
             raise ValueError(f"mode {mode!r}: 'transitions' or 'summary'")
         T = int(n_steps)
@@ -385,8 +389,62 @@ class BraxVecEngine(LaneEngine):
         return res
 
     def evaluate_policy(self, *args, **kwargs):
-        raise NotImplementedError(f"{type(self).__name__}: the episodes mode of the closed-loop rollout covers the "
-                                  "classic-control families only")
+        raise NotImplementedError(f"{type(self).__name__}: evaluate_policy (sampling, input statistics) covers the "
+                                  "classic-control families only; the episodes mode of the Brax closed-loop rollout is "
+                                  "evaluate_episodes")
+
+    _EPISODE_KEYS = VecEngine._EPISODE_KEYS  # (key, dtype, per-episode rows): the result is VecEngine.evaluate_policy's
+
+    def alloc_policy_episodes(self, n_episodes: int) -> dict:
+        """Output buffers of ``evaluate_episodes``, as ``VecEngine.alloc_policy_episodes``: ``episodes`` / ``steps`` int32
+        ``[N]``; ``return`` float32, ``length`` / ``context_id`` int32, ``terminated`` uint8, ``[n_episodes, N]`` each.
+        The launch writes every element."""
+        K = int(n_episodes)
+        if K < 1:
+            raise ValueError(f"n_episodes {K} < 1")
+        return {k: torch.empty((K, self.n) if rows else (self.n,), dtype=dt, device=self.device)
+                for k, dt, rows in self._EPISODE_KEYS}
+
+    def evaluate_episodes(self, policy, n_episodes: int, max_steps: int, out: dict | None = None) -> dict:
+        """Run ``policy`` (a ``BraxMLPPolicy``, deterministic) on every env until the env has finished ``n_episodes``
+        episodes or taken ``max_steps`` steps, in ONE launch, from the current engine state (include/carl_amd.h:
+        carl_brax_evaluate_policy; a running episode is counted with its full length, ``CARLBraxEnv.evaluate_episodes``
+        resets first).  Returns ``alloc_policy_episodes``' dict -- the keys, dtypes and shapes of
+        ``VecEngine.evaluate_policy``'s result, so ``carl_amd.policy.episode_stats`` and ``carl_amd.es.set_fitness`` take
+        it as it is: ``episodes`` / ``steps`` per env, and per env and episode k < ``episodes`` its fp32 ``return``,
+        ``length``, the ``context_id`` it ran in and whether it ``terminated`` (NaN / 0 / -1 / 0 beyond).  An env stops at
+        the step that ends its last episode, that step's auto-reset applied (its stored state is the start of the next
+        episode), or at ``max_steps``, mid-episode; its records and its state are those of a transitions-mode
+        ``rollout_policy`` of as many steps, bit for bit, and a wavefront stops stepping once none of its envs is live.
+        The launch starts from ``obs`` and leaves every env's current observation there, as ``rollout_policy`` does.
+        Needs ``auto_reset``.  No host synchronisation."""
+        self._check_policy(policy, "evaluate_episodes")
+        if not self.auto_reset:
+            raise ValueError("evaluate_episodes needs auto_reset=True: without it a finished lane reports done on every "
+                             "later step")
+        K, T = int(n_episodes), int(max_steps)
+        if K < 1:
+            raise ValueError(f"n_episodes {K} < 1")
+        if T < 0:
+            raise ValueError(f"max_steps {T} < 0")
+        if K * self.n >= 1 << 31:
+            raise ValueError(f"{K} episodes x {self.n} lanes: more than 2^31 - 1 records")
+        res = self.alloc_policy_episodes(K) if out is None else out
+        for k, dt, rows in self._EPISODE_KEYS:
+            t = res.get(k)
+            shape = (K, self.n) if rows else (self.n,)
+            if t is None or t.device != self.device or t.dtype != dt or tuple(t.shape) != shape or not t.is_contiguous():
+                raise ValueError(f"evaluate_episodes output '{k}' must be a contiguous {dt} {list(shape)} tensor on "
+                                 f"{self.device}")
+        self._shape_for(T)  # (as rollout_policy: the width autotune found for the open loop of this length class)
+        self._flush_obs()
+        params = policy.device_params(self.device)
+        pol = policy.struct(self.n, params.data_ptr())
+        eps = _lib.PolicyEpisodes(*(_ptr(res[k]) for k, _, _ in self._EPISODE_KEYS))
+        with torch.cuda.device(self.device):
+            _lib.check(self.lib.carl_brax_evaluate_policy(C.byref(self.b), _ptr(self.sys_dev), C.byref(self.sys),
+                                                          _ptr(self.obs), C.byref(pol), K, T, C.byref(eps), self._stream()))
+        return res
 
     def reset_done(self):
         return self.reset((self.terminated | self.truncated))

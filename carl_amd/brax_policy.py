@@ -7,13 +7,18 @@ built-in families, so the head width is the model's actuator count (``n_act`` Bo
 clips an action given to ``step``) and the observation width the model's ``obs_dim``, both read from the engine.
 ``BraxVecEngine.rollout_policy`` / ``CARLBraxEnv.rollout_policy`` run it for T steps in one launch.
 
+``BraxVecEngine.evaluate_episodes`` / ``CARLBraxEnv.evaluate_episodes`` run it for whole episodes -- K per env, each env
+stopping at its K-th episode end -- and ``carl_amd.es.EvolutionStrategy`` takes it as its template.
+
 At most ``CARL_POLICY_MAX_IN`` = 32 inputs: Humanoid's and HumanoidStandup's 244 observations do not fit.  Out of scope
-here: sampled actions and log-probabilities, value networks and GAE, input statistics, the episodes mode
-(``evaluate_policy``), ``carl_amd.es.EvolutionStrategy`` and ``MixedVecEngine``.
+here: sampled actions and log-probabilities, value networks and GAE, input statistics (``evaluate_policy`` stays the
+classic-control families') and ``MixedVecEngine``.
 """
 from __future__ import annotations
 
 from typing import Sequence
+
+import numpy as np
 
 from carl_amd.policy import MLPPolicy, flattened_context_rows
 
@@ -41,6 +46,7 @@ class BraxMLPPolicy(MLPPolicy):
 
         super().__init__(_BRAX_FAMILY, info.obs_dim, ctx_rows, layers, activation, input_shift, input_scale, input_clip,
                          context_names, None, "policy", info=info)
+        self._info = info  # (unpack builds its result through this constructor)
 
     @staticmethod
     def _box_outputs(info) -> int:
@@ -56,5 +62,24 @@ class BraxMLPPolicy(MLPPolicy):
         return cls(eng.info, rows, layers, activation, input_shift, input_scale, input_clip, names)
 
     @staticmethod
-    def unpack(template, packed, log_std=None):
-        raise NotImplementedError("BraxMLPPolicy: unpack (input statistics) is out of scope for the Brax families")
+    def unpack(template, packed, log_std=None) -> "BraxMLPPolicy":
+        """A one-set host policy of ``template``'s model, inputs, shape and activation from one packed weight set
+        ``[set_floats]`` (host floats): the inverse of the packing, bit for bit, its shift | scale | clip section included
+        (``MLPPolicy.unpack`` for a Brax template; ``EvolutionStrategy.policy()`` reads the centre through it).  A
+        ``log_std`` is refused: the Brax closed loop samples nothing."""
+        if not isinstance(template, BraxMLPPolicy):
+            raise TypeError(f"BraxMLPPolicy.unpack: the template is a {type(template).__name__}, not a BraxMLPPolicy")
+        if log_std is not None:
+            raise NotImplementedError("BraxMLPPolicy: log_std (sampled actions) is out of scope for the Brax families")
+        if template._on_device or template.n_sets != 1:
+            raise ValueError("unpack(): the template must be a one-set host-built BraxMLPPolicy")
+        flat = np.ascontiguousarray(np.asarray(packed, dtype=np.float32).reshape(-1))
+        if flat.size != template.set_floats:
+            raise ValueError(f"unpack(): {flat.size} floats, the template's weight set has {template.set_floats}")
+        layers, off = [], 0
+        for W, b in template.layers:
+            layers.append((flat[off: off + W.size].reshape(W.shape), flat[off + W.size: off + W.size + b.size]))
+            off += W.size + b.size
+        n = template.n_in
+        return BraxMLPPolicy(template._info, template.ctx_rows, layers, template.activation, flat[off: off + n],
+                             flat[off + n: off + 2 * n], flat[off + 2 * n], template.context_names)

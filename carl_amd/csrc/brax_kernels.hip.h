@@ -405,8 +405,11 @@ __host__ __device__ inline Layout policy_layout_of(const carl_brax_sys_t& s) {
   l.total += kPolicyRows;  // rows [layout_of(s).total, total)
   return l;
 }
-// run()'s policy argument in modes 0 and 1: none
-struct NoPolicy {};
+// run()'s policy argument in modes 0 and 1: none.  kEpisodes: the policy type selects the episodes variant of MODE 2
+// (brax_episodes_kernels.hip.h: BraxEpisodesPolicy).
+struct NoPolicy {
+  static constexpr bool kEpisodes = false;
+};
 
 // tree topology derived from the model table once per workgroup
 struct Topo {
@@ -2198,6 +2201,14 @@ static __device__ __forceinline__ void write_ctx_obs(const carl_batch_t& b, cons
 // io.action is an OUTPUT; with io.obs == NULL (summary mode) no per-step record is stored at all.  A fragment starts from
 // the env's observation in pol.cur_obs [N][obs_dim] and leaves its last one there, ordered between the two wavefronts of
 // a split group by the head_done release / acquire like the state record.
+// mode 2 with Pol::kEpisodes (include/carl_amd.h: carl_brax_evaluate_policy; compiled from carl_brax_episodes.hip alone):
+// n_steps is max_steps and an env is LIVE while it has finished fewer than pol.n_episodes episodes of this launch.  At the
+// step that ends its last episode the env FREEZES: after that step's auto-reset everything a fragment end stores for it is
+// stored at once (the step loop is left for the fragment-end stores, which store the envs that froze, and entered again while
+// an env is live), and nothing of it is stored again -- its lanes go on computing in LDS, where it stays a real env (it
+// keeps resetting there), with every global write under `live`.  The wavefront leaves the step loop for good once none of
+// its envs is live.  A tail fragment learns what the head left from pol.ep.episodes [env] in HBM, as the summary
+// totals are handed over; every way out of the step loop falls through to the fragment's stores and the head_done release.
 // F32 (MODE 1, CARL_FLAG_BRAX_FP32): the n_frames substeps of an env step run their pose algebra in float32.
 template <int MODE, bool MULTI, bool TASK, bool PLANAR = false, bool F32 = false, class Pol = NoPolicy>
 static __device__ __forceinline__ void run(const carl_batch_t& b, const carl_brax_sys_t* __restrict__ sys_dev,
@@ -2276,6 +2287,8 @@ static __device__ __forceinline__ void run(const carl_batch_t& b, const carl_bra
   const int S = CARL_BRAX_LINK_RECORD * s.n_links;  // floats of the env's record in HBM
   const bool goal = s.goal_mode != 0 && b.goal_pos != nullptr;
   const int n_waves = (int)blockDim.x >> 6;
+  constexpr bool EP = Pol::kEpisodes;
+  static_assert(!EP || MODE == 2, "the episodes mode is a variant of the closed-loop rollout");
 
   if constexpr (MODE == 0) {
     const int gwave = (int)blockIdx.x * n_waves + wave;  // global wavefront = group of kEnvs envs
@@ -2361,6 +2374,14 @@ static __device__ __forceinline__ void run(const carl_batch_t& b, const carl_bra
         __builtin_amdgcn_s_sleep(16);
       __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");
     }
+    // episodes mode: the episodes the env has yet to finish (0: it froze at the last step and is to be stored; -1: frozen
+    // and stored, or no env); what the head fragment left is in HBM
+    [[maybe_unused]] int ep_left = -1;
+    if constexpr (EP) {
+      if (active) ep_left = pol.n_episodes - (t_lo > 0 ? pol.ep.episodes[env] : 0);
+      ep_left = ep_left > 0 ? ep_left : -1;
+    }
+    if (!EP || ballot(ep_left > 0) != 0ull) {  // (a tail fragment whose group is all frozen: that load and nothing else)
     LaneState r{};
     if (active) {
       r.cidx = b.ctx_idx[env];
@@ -2378,6 +2399,7 @@ static __device__ __forceinline__ void run(const carl_batch_t& b, const carl_bra
     if constexpr (MODE == 2) {
       // the observation the fragment's first step acts on; the env's summary totals so far (0 at the launch's start)
       record_in(pol.cur_obs, (size_t)env, s.obs_dim, m, active);
+      if constexpr (!EP)
       if (lead && pol.sum.episodes != nullptr) {
         const int k = pol_rows + kPolicyXRows + 2 * kPolicyHRows;
         m.atu(k) = t_lo > 0 ? (uint32_t)pol.sum.episodes[env] : 0u;
@@ -2402,7 +2424,13 @@ static __device__ __forceinline__ void run(const carl_batch_t& b, const carl_bra
     }
     const Lds& m_launch = m;
     const int env_frag = env;
-    for (int t = t_lo; t < t_hi; ++t) {
+    // Episodes mode: the fragment's steps run in one or more passes of the step loop.  A pass ends with the step at which
+    // an env freezes (or with the fragment's last step), the envs that froze -- at the fragment's last step also the ones
+    // still live -- are stored below exactly as a fragment end stores an env, and the next pass goes on from the rows and
+    // registers as they are: the stores stay outside the step loop, where the other modes have them.
+    [[maybe_unused]] int t_next = t_lo;    // the first step of the next pass = the steps the stored envs have taken
+    do {
+    for (int t = EP ? t_next : t_lo; t < t_hi; ++t) {
       // Every LDS address of the step is derived from an opaque copy of the lane's coordinates: as loop invariants the
       // compiler hoisted dozens of them (row addresses of the staging, tau, mass and stash rows ...) out of the step
       // loop, ran out of registers and reloaded them from scratch memory all through the step.
@@ -2578,6 +2606,7 @@ static __device__ __forceinline__ void run(const carl_batch_t& b, const carl_bra
       }
       r.ep_return += reward;
       const bool done = active && (terminated | truncated);
+      [[maybe_unused]] const bool live = ep_left > 0;  // episodes mode: the env's global writes of this step happen
       if (lead && per_step) {
         io.reward[step_off + env] = reward;
         io.terminated[step_off + env] = (uint8_t)terminated;
@@ -2589,11 +2618,23 @@ static __device__ __forceinline__ void run(const carl_batch_t& b, const carl_bra
         const float fin_ret = r.ep_return;
         const int fin_len = r.elapsed;
         if (done) {
-          if (m.sub == 0) {
+          if (m.sub == 0 && (!EP || live)) {
             if (b.last_return) b.last_return[env] = fin_ret;
             if (b.last_length) b.last_length[env] = fin_len;
           }
           r.n_new_episodes += 1;
+          if constexpr (EP) {
+            if (live) {  // the episode's record, in the env's next slot (r.cidx: still the context the episode ran in)
+              if (m.sub == 0) {
+                const size_t at = (size_t)(pol.n_episodes - ep_left) * n + env;
+                pol.ep.ret[at] = fin_ret;
+                pol.ep.length[at] = fin_len;
+                pol.ep.context_id[at] = r.cidx;
+                pol.ep.terminated[at] = (uint8_t)terminated;
+              }
+              ep_left -= 1;
+            }
+          } else
           if constexpr (MODE == 2) {
             if (m.sub == 0 && pol.sum.episodes != nullptr) {  // the env's totals: fp32 return sum in step order
               const int k = pol_rows + kPolicyXRows + 2 * kPolicyHRows;
@@ -2603,7 +2644,7 @@ static __device__ __forceinline__ void run(const carl_batch_t& b, const carl_bra
             }
           }
         }
-        log_finished(b, done && m.sub == 0, genv, fin_ret, fin_len);
+        log_finished(b, done && m.sub == 0 && (!EP || live), genv, fin_ret, fin_len);
         if (b.flags & CARL_FLAG_AUTORESET) {
           if (io.final_obs != nullptr)  // terminal observation, done envs only
             record_out(io.final_obs + step_off * s.obs_dim, (size_t)env, s.obs_dim, m, done);
@@ -2634,7 +2675,7 @@ static __device__ __forceinline__ void run(const carl_batch_t& b, const carl_bra
             r.elapsed = 0;
             r.ep_return = 0.0f;
             r.n_new_calls += 1;
-            write_ctx_obs(b, m, n, env, r.cidx);
+            if (!EP || live) write_ctx_obs(b, m, n, env, r.cidx);
           }
           }
           observe<MULTI, TASK, kSlides>(s, pk, m, done, true);
@@ -2644,7 +2685,56 @@ static __device__ __forceinline__ void run(const carl_batch_t& b, const carl_bra
       record_out(io.obs + step_off * s.obs_dim, (size_t)env, s.obs_dim, m, active && per_step);
       phase_sync();  // the next step's actions overwrite the io rows
       prof.mark(kProfOutput);
+      if constexpr (EP) {
+        t_next = t + 1;
+        if (ballot(ep_left == 0) != 0ull) break;  // an env's last episode ended at this step (wave-uniform: on to the stores)
+      }
     }
+    if constexpr (EP) {
+      // who is stored now, t_next steps into the launch: the envs that froze at the last step, and at the fragment's end the
+      // envs still live.  A slot the env did not fill is written once the launch is over for it (t_next == T).
+      const bool who = ep_left == 0 || (t_next == t_hi && ep_left > 0);
+      // (the stores sit inside the loop of passes: as the step does, they take opaque copies of the lane's coordinates, or the
+      // compiler hoists their addresses out of that loop and keeps them in registers, and in scratch, through every step)
+      Lds m_store = m_launch;
+      int env_store = env_frag;
+      asm volatile("" : "+v"(m_store.sub), "+v"(m_store.env), "+v"(env_store));
+      const Lds& m = m_store;
+      const int env = env_store;
+      record_out(pol.cur_obs, (size_t)env, s.obs_dim, m, who);
+      // (the records' counters in a block of their own, not inside `if (who)` below: nested there, the gfx950 back end of
+      // ROCm's clang stops at an instruction it built itself -- "V_CMP_NE_U32 0, $src_shared_base": illegal operand)
+      if (who && m.sub == 0) {
+        const int fin = pol.n_episodes - ep_left;  // (ep_left >= 0 here)
+        pol.ep.episodes[env] = fin;
+        pol.ep.steps[env] = t_next;
+        if (t_next == T)
+          for (int k = fin; k < pol.n_episodes; ++k) {
+            const size_t at = (size_t)k * n + env;
+            pol.ep.ret[at] = __builtin_nanf("");
+            pol.ep.length[at] = 0;
+            pol.ep.context_id[at] = -1;
+            pol.ep.terminated[at] = 0;
+          }
+      }
+      if (who) {
+        record_store(b.state + (size_t)env * S, m, s.n_links, true);
+        if (m.sub == 0) {
+          b.elapsed[env] = r.elapsed;
+          b.ep_return[env] = r.ep_return;
+          if (goal) {
+            b.goal_pos[env] = r.pos_x;
+            b.goal_pos[n + env] = r.pos_y;
+          }
+          if (r.n_new_episodes != 0 && b.episodes_done != nullptr) b.episodes_done[env] += r.n_new_episodes;
+          if (r.n_new_calls != 0) {
+            b.ctx_idx[env] = r.cidx;
+            b.episode[env] = r.episode;
+            b.n_calls[env] += r.n_new_calls;
+          }
+        }
+      }
+    } else {
     if constexpr (MODE == 2) {
       record_out(pol.cur_obs, (size_t)env, s.obs_dim, m, active);  // the env's current observation (the io rows hold it)
       if (lead && pol.sum.episodes != nullptr) {
@@ -2671,6 +2761,11 @@ static __device__ __forceinline__ void run(const carl_batch_t& b, const carl_bra
         }
       }
     }
+    }
+    if constexpr (EP) ep_left = ep_left == 0 ? -1 : ep_left;  // (stored)
+    // (the next pass, while the fragment has steps left and an env of the wavefront is live: wave-uniform)
+    } while (EP && t_next < t_hi && ballot(ep_left > 0) != 0ull);
+    }  // (the fragment's body; the hand-over below is outside it: a skipped release would hang the next wavefront)
     if (signal_head) {  // the group continues in the next wavefront: everything above is in memory before the flag
       __builtin_amdgcn_fence(__ATOMIC_RELEASE, "agent");
       if (tid == 0) __hip_atomic_store(&head_done[wave], 1, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_WORKGROUP);

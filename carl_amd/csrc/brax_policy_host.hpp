@@ -1,0 +1,104 @@
+// brax_policy_host.hpp -- host-side checks of the closed-loop entry points of the Brax families, shared by their two
+// translation units (carl_brax_policy.hip: carl_brax_rollout_policy; carl_brax_episodes.hip: carl_brax_evaluate_policy):
+// the packed size of a policy's shape, the kernel class of a closed-loop launch, the policy's validation against the batch
+// and the model, and the launch shape.  Host code only; the kernels are each unit's own.
+#pragma once
+
+#include <cstdint>
+
+#include "../../include/carl_amd.h"
+#include "brax_launch.hpp"
+#include "host_common.hpp"
+#include "policy_host.hpp"
+
+namespace carl_host {
+namespace brax {
+
+inline int brax_policy_floats(const carl_policy_t* p) {
+  if (p->n_in < 1 || p->n_in > CARL_POLICY_MAX_IN || p->n_out < 1 || p->n_out > CARL_BRAX_MAX_ACT || p->n_hidden < 0 ||
+      p->n_hidden > CARL_POLICY_MAX_HIDDEN)
+    return -1;
+  for (int l = 0; l < p->n_hidden; ++l)
+    if (p->width[l] < 1 || p->width[l] > CARL_POLICY_MAX_WIDTH) return -1;
+  const int64_t total = (int64_t)carl_host::policy_transform_offset(p) + 2 * (int64_t)p->n_in + 1;
+  return (int)((total + 3) / 4 * 4);
+}
+
+// the class of a closed-loop launch, or the refusal of CARL_FLAG_BRAX_FP32
+inline int policy_class(const char* who, const carl_batch_t* b, const carl_brax_sys_t* sh, BraxClass* c) {
+  if (b->flags & CARL_FLAG_BRAX_FP32)
+    return fail(CARL_ERR_UNSUPPORTED, "%s: CARL_FLAG_BRAX_FP32 is not built for the closed-loop rollout (the float64 "
+                "kernel classes only)", who);
+  *c = brax_class(sh, b->flags, true);
+  return 0;
+}
+
+inline int validate_policy(const char* who, const carl_batch_t* b, const carl_brax_sys_t* sh, const carl_policy_t* p) {
+  if (int e = carl_host::check_hidden_layers(who, p)) return e;
+  if (p->n_ctx < 0 || p->n_ctx > CARL_POLICY_MAX_IN)
+    return fail(CARL_ERR_INVALID_ARGUMENT, "%s: n_ctx %d outside [0, %d]", who, p->n_ctx, CARL_POLICY_MAX_IN);
+  if (p->n_ctx + sh->obs_dim > CARL_POLICY_MAX_IN)
+    return fail(CARL_ERR_INVALID_ARGUMENT, "%s: %d context inputs + %d observations are more than CARL_POLICY_MAX_IN = %d "
+                "policy inputs (Humanoid-size observations are out of scope)", who, p->n_ctx, sh->obs_dim, CARL_POLICY_MAX_IN);
+  // a Brax batch does not say how many rows its context table has: a policy sees the rows the batch makes visible
+  for (int k = 0; k < p->n_ctx; ++k) {
+    bool visible = false;
+    for (int j = 0; j < b->n_ctx_obs && j < CARL_MAX_CTX_OBS; ++j) visible |= b->ctx_obs_feat[j] == p->ctx_rows[k];
+    if (p->ctx_rows[k] < 0 || !visible)
+      return fail(CARL_ERR_INVALID_ARGUMENT, "%s: ctx_rows[%d] = %d is not one of the batch's observed context rows "
+                  "(ctx_obs_feat)", who, k, p->ctx_rows[k]);
+  }
+  if (p->n_in != p->n_ctx + sh->obs_dim)
+    return fail(CARL_ERR_INVALID_ARGUMENT, "%s: n_in %d != n_ctx %d + obs_dim %d", who, p->n_in, p->n_ctx, sh->obs_dim);
+  if (p->n_out != sh->n_act)
+    return fail(CARL_ERR_INVALID_ARGUMENT, "%s: head width %d, the model has %d actuators", who, p->n_out, sh->n_act);
+  if (p->head != CARL_POLICY_HEAD_BOX)
+    return fail(CARL_ERR_INVALID_ARGUMENT, "%s: head kind %d: the Brax families take Box actions (CARL_POLICY_HEAD_BOX)", who,
+                p->head);
+  if (int e = carl_host::check_activation(who, p)) return e;
+  if (p->n_sets < 1) return fail(CARL_ERR_INVALID_ARGUMENT, "%s: n_sets %d < 1", who, p->n_sets);
+  const int q = carl_policy_lane_quantum();
+  if (p->lanes_per_set < q || p->lanes_per_set % q != 0)
+    return fail(CARL_ERR_INVALID_ARGUMENT, "%s: lanes_per_set %d is not a positive multiple of %d (carl_policy_lane_quantum)",
+                who, p->lanes_per_set, q);
+  if ((int64_t)p->n_sets * p->lanes_per_set < b->n_lanes)
+    return fail(CARL_ERR_INVALID_ARGUMENT, "%s: %d sets x %d lanes do not cover %d lanes", who, p->n_sets, p->lanes_per_set,
+                b->n_lanes);
+  if (int e = carl_host::check_params(who, p)) return e;
+  if (reinterpret_cast<uintptr_t>(p->params) % 16 != 0)
+    return fail(CARL_ERR_INVALID_ARGUMENT, "%s: params must start on a 16-byte boundary (weight rows are read 16 bytes at a time)",
+                who);
+  return 0;
+}
+
+// What both entry points check first, in this order: the batch and the model, policy / obs non-NULL, the kernel class
+// (CARL_FLAG_BRAX_FP32 is refused), the policy.
+inline int validate_closed_loop(const char* who, const carl_batch_t* batch, const carl_brax_sys_t* sys_dev,
+                                const carl_brax_sys_t* sys_host, const float* obs, const carl_policy_t* policy_host,
+                                BraxClass* c) {
+  if (int e = validate_brax(batch, sys_dev, sys_host, who)) return e;
+  if (policy_host == nullptr || obs == nullptr) return fail(CARL_ERR_INVALID_ARGUMENT, "%s: policy / obs is NULL", who);
+  if (int e = policy_class(who, batch, sys_host, c)) return e;
+  return validate_policy(who, batch, sys_host, policy_host);
+}
+
+// The shape of a closed-loop launch of n_steps (episodes mode: max_steps) steps, and its kernel out of the unit's table
+// `tab` (entries with a class `c`, a width `k` and a kernel `kern`): one rule for both entry points, whose tables hold the
+// same (class, width) instances (tests/test_brax_episodes_abi.py), so carl_brax_policy_launch_shape answers for both.
+template <class Entry, size_t N>
+int policy_launch(const Entry (&tab)[N], const carl_batch_t* batch, const carl_brax_sys_t* sys_host, const BraxClass& c,
+                  int n_steps, const char* who, BraxShape* shape, decltype(Entry::kern)* kern) {
+  if (int e = brax_launch_shape(tab, batch, sys_host, c, true, n_steps, true, who, shape)) return e;
+  if (kern == nullptr) return 0;  // (the shape alone)
+  *kern = nullptr;
+  for (const Entry& e : tab)
+    if (same_class(e.c, c) && e.k == shape->K) *kern = e.kern;
+  if (*kern == nullptr) return fail(CARL_ERR_UNSUPPORTED, "%s: no kernel for %d lanes per env", who, shape->K);
+  if (shape->lds_bytes > 48 * 1024) {
+    if (int e = carl_host::ensure_dynamic_lds(reinterpret_cast<const void*>(*kern), shape->lds_bytes, who)) return e;
+  }
+  return 0;
+}
+
+}  // namespace brax
+}  // namespace carl_host

@@ -28,6 +28,7 @@ namespace carl {
 namespace brax {
 
 struct BraxPolicy {
+  static constexpr bool kEpisodes = false;  // (run(): not the episodes variant -- brax_episodes_kernels.hip.h)
   carl_policy_t p;            // validated by the host (carl_brax_policy.hip)
   int set_floats;             // floats per packed weight set
   carl_policy_summary_t sum;  // per-env totals; all NULL: none

@@ -1,0 +1,101 @@
+// carl_brax_episodes.hip -- C-ABI entry point of the episodes mode of the Brax closed-loop rollout (include/carl_amd.h:
+// carl_brax_evaluate_policy) and its kernel dispatch.  A translation unit of its own, as carl_brax_policy.hip is: the
+// kernels are the Pol::kEpisodes variant of MODE 2 of brax_kernels.hip.h's run(), instantiated here and nowhere else, so
+// that every other unit -- carl_brax_policy.hip included -- compiles exactly as it did without them
+// (profiles/brax_episodes_isa_identity.txt).  The batch, model and policy checks and the launch rule are the closed-loop
+// rollout's (brax_launch.hpp, brax_policy_host.hpp).  Same flags as carl_brax_policy.hip (carl_amd/build.py).
+#include <hip/hip_runtime.h>
+
+#include <cstdint>
+
+#include "../../include/carl_amd.h"
+#include "brax_episodes_kernels.hip.h"
+#include "brax_launch.hpp"
+#include "brax_policy_host.hpp"
+#include "host_common.hpp"
+
+namespace {
+
+using carl_host::check_launch;
+using carl_host::fail;
+using carl_host::brax::BraxClass;
+using carl_host::brax::BraxShape;
+
+// Every instantiated brax_episodes_kernel<MULTI, K, TASK, PLANAR>: carl_brax_policy.hip's kBraxPolicyKernels, entry for
+// entry (tests/test_brax_episodes_abi.py holds the two tables together; carl_brax_policy_launch_shape answers for both).
+using brax_episodes_kern_t = void (*)(carl_batch_t, const carl_brax_sys_t*, carl::brax::Prepared, carl_step_io_t,
+                                      carl::brax::BraxEpisodesPolicy, int);
+struct BraxEpisodesKernel {
+  BraxClass c;
+  int k;
+  brax_episodes_kern_t kern;
+};
+#define CARL_BRAX_EPISODES(MULTI, K, TASK, PLANAR) \
+  {{MULTI, TASK, PLANAR, false}, K, carl::brax::brax_episodes_kernel<MULTI, K, TASK, PLANAR>}
+const BraxEpisodesKernel kBraxEpisodesKernels[] = {
+    // lean
+    CARL_BRAX_EPISODES(false, 4, false, false), CARL_BRAX_EPISODES(false, 7, false, false),
+    CARL_BRAX_EPISODES(false, 8, false, false), CARL_BRAX_EPISODES(false, 9, false, false),
+    CARL_BRAX_EPISODES(false, 16, false, false),
+    // multi-hinge
+    CARL_BRAX_EPISODES(true, 2, false, false), CARL_BRAX_EPISODES(true, 11, false, false),
+    CARL_BRAX_EPISODES(true, 16, false, false),
+    // general: reach / push task models and anisotropic inertia
+    CARL_BRAX_EPISODES(true, 4, true, false), CARL_BRAX_EPISODES(true, 8, true, false), CARL_BRAX_EPISODES(true, 16, true, false),
+    // planar
+    CARL_BRAX_EPISODES(false, 4, false, true), CARL_BRAX_EPISODES(false, 7, false, true),
+    CARL_BRAX_EPISODES(false, 8, false, true), CARL_BRAX_EPISODES(false, 9, false, true),
+    CARL_BRAX_EPISODES(false, 16, false, true),
+};
+#undef CARL_BRAX_EPISODES
+
+static_assert(sizeof(carl_batch_t) + sizeof(carl::brax::Prepared) + sizeof(carl_step_io_t) + sizeof(carl::brax::BraxEpisodesPolicy) + 64 <= 4096,
+              "the episodes kernel's arguments do not fit the 4 KiB kernel-argument segment");
+
+}  // namespace
+
+extern "C" {
+
+int carl_brax_evaluate_policy(const carl_batch_t* batch, const carl_brax_sys_t* sys_dev, const carl_brax_sys_t* sys_host,
+                              float* obs, const carl_policy_t* policy_host, int32_t n_episodes, int32_t max_steps,
+                              const carl_policy_episodes_t* out, void* stream) {
+  const char* who = "carl_brax_evaluate_policy";
+  BraxClass c;
+  if (int e = carl_host::brax::validate_closed_loop(who, batch, sys_dev, sys_host, obs, policy_host, &c)) return e;
+  if (out == nullptr || !out->episodes || !out->steps || !out->ret || !out->length || !out->context_id || !out->terminated)
+    return fail(CARL_ERR_INVALID_ARGUMENT, "%s: out and its six arrays must not be NULL", who);
+  if (n_episodes < 1) return fail(CARL_ERR_INVALID_ARGUMENT, "%s: n_episodes %d < 1", who, n_episodes);
+  if (max_steps < 0) return fail(CARL_ERR_INVALID_ARGUMENT, "%s: max_steps %d < 0", who, max_steps);
+  if ((int64_t)n_episodes * batch->n_lanes >= (int64_t)1 << 31)
+    return fail(CARL_ERR_INVALID_ARGUMENT, "%s: %d episodes x %d lanes: more than 2^31 - 1 records", who, n_episodes,
+                batch->n_lanes);
+  if (!(batch->flags & CARL_FLAG_AUTORESET))
+    return fail(CARL_ERR_UNSUPPORTED, "%s: needs CARL_FLAG_AUTORESET (without auto-reset a finished lane reports done on "
+                "every later step, and its episode would be counted on each of them)", who);
+  if (batch->n_lanes == 0) return 0;
+  if (max_steps == 0) {
+    hipLaunchKernelGGL(carl::brax::brax_episodes_empty_kernel, dim3((batch->n_lanes + 255) / 256), dim3(256), 0,
+                       (hipStream_t)stream, *out, (int)batch->n_lanes, (int)n_episodes);
+    return check_launch(who);
+  }
+
+  BraxShape shape;
+  brax_episodes_kern_t kern = nullptr;
+  if (int e = carl_host::brax::policy_launch(kBraxEpisodesKernels, batch, sys_host, c, max_steps, who, &shape, &kern)) return e;
+  carl::brax::BraxEpisodesPolicy pol{};
+  pol.p = *policy_host;
+  pol.set_floats = carl_host::brax::brax_policy_floats(policy_host);
+  pol.sum = carl_policy_summary_t{nullptr, nullptr, nullptr};
+  pol.cur_obs = obs;
+  pol.ep = *out;
+  pol.n_episodes = n_episodes;
+  carl::brax::Prepared prep{};
+  carl::brax::build_topo_host(*sys_host, prep.topo);
+  carl::brax::build_packed_host(*sys_host, prep.topo, prep.packed);
+  // (no per-step record: the all-NULL io is run()'s summary mode)
+  hipLaunchKernelGGL(kern, dim3(shape.grid), dim3(carl::brax::kLanes * shape.W), shape.lds_bytes, (hipStream_t)stream, *batch,
+                     sys_dev, prep, carl_step_io_t{}, pol, (int)max_steps);
+  return check_launch(who);
+}
+
+}  // extern "C"

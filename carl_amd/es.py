@@ -24,8 +24,13 @@ section into every member, so the statistics of generation g act from generation
 Choosing contexts: with a static selector and a context count that divides ``lanes_per_set``, every member of the
 population is evaluated on every context once per episode slot -- the CARL question ES is asked here.
 
-Out of scope, and refused as ``carl_amd.policy`` refuses them: the Brax families, ``MixedVecEngine`` pairs, the
-gymnasium drop-in.
+The Brax families: with a ``carl_amd.brax_policy.BraxMLPPolicy`` template on a ``CARLBraxEnv`` or ``BraxVecEngine`` the
+same sequence runs over the Brax closed loop -- step 2 is ``evaluate_episodes`` (include/carl_amd.h:
+carl_brax_evaluate_policy: exactly K whole episodes per env, each env stopping at its K-th episode end), the other
+launches do not depend on the family.  Deterministic actions only, and no ``normalize_inputs``: sampling and input
+statistics for the Brax families are separate work.
+
+Out of scope, and refused as ``carl_amd.policy`` refuses them: ``MixedVecEngine`` pairs, the gymnasium drop-in.
 """
 from __future__ import annotations
 
@@ -35,6 +40,7 @@ from typing import Callable
 import torch
 
 from carl_amd import _lib
+from carl_amd.brax_policy import BraxMLPPolicy, _brax_engine_of
 from carl_amd.policy import InputStats, MLPPolicy, _engine_of
 
 
@@ -71,7 +77,8 @@ _SHAPING = {"centered_rank": centered_rank_weights, "difference": difference_wei
 
 
 class EvolutionStrategy:
-    """One ES generation per ``step`` on a classic-control ``CARLEnv`` or ``VecEngine`` with ``auto_reset``.
+    """One ES generation per ``step`` on a classic-control ``CARLEnv`` or ``VecEngine`` with ``auto_reset`` -- or, with a
+    ``BraxMLPPolicy`` template, on a ``CARLBraxEnv`` or ``BraxVecEngine`` (module docstring).
 
     ``policy``: a one-set ``MLPPolicy`` for ``env`` -- the shape, the inputs and the starting centre (its shift | scale |
     clip section is carried into every member unchanged).  The population is ``P = n_lanes // lanes_per_set`` weight sets,
@@ -90,14 +97,22 @@ class EvolutionStrategy:
     def __init__(self, env, policy: MLPPolicy, lanes_per_set: int = 256, sigma: float = 0.1, lr: float = 0.05, seed: int = 0,
                  fitness_shaping: str | Callable = "centered_rank", optimizer: Callable | None = None,
                  normalize_inputs: bool = False, stats_eps: float = 1e-8, stats_min_std: float = 1e-6):
-        eng, cenv = _engine_of(env)
+        brax = isinstance(policy, BraxMLPPolicy)  # the template's type picks the closed loop: every other one the classic
+        if brax and normalize_inputs:
+            raise NotImplementedError("EvolutionStrategy: normalize_inputs (input statistics) is out of scope for the Brax "
+                                      "families")
+        eng, cenv = _brax_engine_of(env) if brax else _engine_of(env)
         if not eng.auto_reset:
             raise ValueError("EvolutionStrategy needs auto_reset=True (evaluate_policy counts whole episodes)")
         if not isinstance(policy, MLPPolicy) or policy._on_device or policy.n_sets != 1 or policy.lanes_per_set is not None:
             raise ValueError("EvolutionStrategy: the template must be a one-set host-built MLPPolicy")
         if policy.head != "policy":
             raise ValueError("EvolutionStrategy: the template must have head='policy'")
-        if policy.family != eng.family or policy.obs_dim != eng.D:
+        if brax:
+            if policy.obs_dim != eng.D or policy.n_out != eng.sys.n_act:
+                raise ValueError(f"the policy was built for {policy.obs_dim} observations and {policy.n_out} actuators, "
+                                 f"this engine's model has {eng.D} and {eng.sys.n_act}")
+        elif policy.family != eng.family or policy.obs_dim != eng.D:
             raise ValueError(f"the policy was built for family {policy.family}, this engine runs family {eng.family}")
         L = int(lanes_per_set)
         q = int(_lib.load().carl_policy_lane_quantum())
@@ -115,7 +130,7 @@ class EvolutionStrategy:
         if not callable(fitness_shaping) and fitness_shaping not in _SHAPING:
             raise ValueError(f"fitness_shaping {fitness_shaping!r}: one of {sorted(_SHAPING)} or a callable")
         self.env, self.engine, self._carl_env = env, eng, cenv
-        self.template = policy
+        self.template, self._brax = policy, brax
         self.lanes_per_set, self.n_sets, self.n_pairs = L, P, P // 2
         self.sigma, self.lr, self.seed = float(sigma), float(lr), int(seed) & (2**64 - 1)
         self.set_floats, self.n_noisy = policy.set_floats, policy.weight_floats
@@ -144,7 +159,7 @@ class EvolutionStrategy:
 
     def policy(self) -> MLPPolicy:
         """The centre as a one-set host ``MLPPolicy`` (one device-to-host copy)."""
-        return MLPPolicy.unpack(self.template, self._center.cpu().numpy())
+        return (BraxMLPPolicy if self._brax else MLPPolicy).unpack(self.template, self._center.cpu().numpy())
 
     def struct(self, generation: int | None = None) -> "_lib.Es":
         """The ``carl_es_t`` of a generation (default: the next ``step``'s)."""
@@ -160,21 +175,32 @@ class EvolutionStrategy:
         """One generation: perturb, reset, ``evaluate_policy`` (``n_episodes`` per lane, at most ``max_steps`` steps;
         sampled actions with ``deterministic=False``, keyed by ``sample_seed``, default the generation), fitness, shaping,
         gradient, update (and, with ``normalize_inputs``, the statistics' merge into the centre).  Returns ``{"fitness" [P], "weight" [P / 2], "grad" [n_noisy], "result": evaluate_policy's
-        dict}``, every value a device tensor.  No host synchronisation."""
+        dict}``, every value a device tensor.  No host synchronisation.  A Brax template: ``evaluate_episodes`` in place
+        of ``evaluate_policy``, ``deterministic=True`` only (``sample_seed`` has nothing to key)."""
         eng = self.engine
+        if self._brax and not deterministic:
+            raise ValueError("EvolutionStrategy.step: deterministic=False (sampled actions) is out of scope for the Brax "
+                             "families")
         es = self.struct()
         stream = eng._stream()
         with torch.cuda.device(eng.device):
             _lib.check(self.lib.carl_es_perturb(C.byref(es), self._center.data_ptr(), self._params.data_ptr(), None, stream))
-        seed = self.generation if sample_seed is None else int(sample_seed)
-        kw = dict(deterministic=deterministic, sample_seed=seed)
-        if self.input_stats is not None:
-            kw["input_stats"] = True
-        if self._carl_env is not None:
-            res = self._carl_env.evaluate_policy(self.population, n_episodes, max_steps, **kw)
+        if self._brax:
+            if self._carl_env is not None:
+                res = self._carl_env.evaluate_episodes(self.population, n_episodes, max_steps)
+            else:
+                eng.reset()
+                res = eng.evaluate_episodes(self.population, n_episodes, max_steps)
         else:
-            eng.reset()
-            res = eng.evaluate_policy(self.population, n_episodes, max_steps, **kw)
+            seed = self.generation if sample_seed is None else int(sample_seed)
+            kw = dict(deterministic=deterministic, sample_seed=seed)
+            if self.input_stats is not None:
+                kw["input_stats"] = True
+            if self._carl_env is not None:
+                res = self._carl_env.evaluate_policy(self.population, n_episodes, max_steps, **kw)
+            else:
+                eng.reset()
+                res = eng.evaluate_policy(self.population, n_episodes, max_steps, **kw)
         fitness = set_fitness(res, self.n_sets)
         weight = self._shape(fitness)
         if (not isinstance(weight, torch.Tensor) or weight.dtype != torch.float32 or weight.device != eng.device

@@ -1,7 +1,8 @@
 /* carl_amd.h -- C ABI of the MI355X batched step/reset engine for CARL's
  * contextual classic-control (and Brax-locomotion) families: reset / step / fused open-loop rollout for both, and the
  * closed-loop rollout with a policy network on the device (carl_rollout_policy and its sampled / valued / episodes / ES
- * forms for the classic-control families; carl_brax_rollout_policy, deterministic transitions and summary, for Brax).
+ * forms for the classic-control families; carl_brax_rollout_policy, deterministic transitions and summary, and
+ * carl_brax_evaluate_policy, whole episodes, for Brax).
  *
  * The reference (automl/CARL v1.1.1) has NO FFI on this path: its boundary is a
  * Python protocol, "the object CARLEnv wraps" (SURVEY.md section 8b).  This header
@@ -916,10 +917,37 @@ int carl_brax_fragment_plan(int32_t n_groups, int32_t n_workgroups, int32_t wave
  *    carl_rollout_policy defines them.  A summary (in either mode) needs CARL_FLAG_AUTORESET, else CARL_ERR_UNSUPPORTED.
  * The batch, the model and io are checked as carl_brax_rollout checks them.  CARL_FLAG_BRAX_FP32 is refused with
  * CARL_ERR_UNSUPPORTED; both auto-reset modes and the goal wrapper work as in carl_brax_rollout.  Out of scope: sampled
- * actions and log-probabilities, critics and GAE, input statistics, an episodes mode. */
+ * actions and log-probabilities, critics and GAE, input statistics (the episodes mode is carl_brax_evaluate_policy). */
 int carl_brax_rollout_policy(const carl_batch_t* batch, const carl_brax_sys_t* sys_dev, const carl_brax_sys_t* sys_host,
                              float* obs, const carl_policy_t* policy_host, const carl_step_io_t* io, int32_t n_steps,
                              const carl_policy_summary_t* summary_out, void* stream);
+/* Episodes mode of carl_brax_rollout_policy (additive; ABI version unchanged): carl_evaluate_policy's semantics for the
+ * Brax families, a variant of the same rollout kernel.  No reference counterpart: the reference evaluates a policy by
+ * stepping the env per Python call until `done` (carl/envs/carl_env.py:321-342; examples/carl_with_sb3.py runs SB3's
+ * evaluate_policy over it).
+ * Every env runs `policy_host` (as carl_brax_rollout_policy, deterministic) until it has finished n_episodes episodes or
+ * taken max_steps steps in this launch, whichever comes first.  An env is LIVE until then.  At the step that ends its
+ * n_episodes-th episode that step's auto-reset is applied as always (both auto-reset modes, the goal wrapper, the push
+ * task's goal placement) and the env FREEZES: its state record, elapsed, ep_return, ctx_idx, episode, n_calls, the
+ * episodes_done increment, goal_pos and its current observation in `obs` are stored then -- the start of the next episode,
+ * as per-call stepping leaves it -- and nothing of it is stored afterwards (last_return / last_length, the finished-episode
+ * log and ctx_obs included).  An env that reaches max_steps first stops there, mid-episode, exactly as
+ * carl_brax_rollout_policy of max_steps steps leaves it.  An env's records and its stored state are bit-identical to its
+ * first episodes in, and to its state after as many steps of, a transitions-mode carl_brax_rollout_policy from the same
+ * engine state.  Episodes are counted from the current state: one already running is reported with its full length and
+ * return.  A wavefront leaves the step loop once none of its envs is live.
+ * `out` is carl_evaluate_policy's: slot k of an env holds ret (the fp32 ep_return at the episode's end, summed in step
+ * order), length, context_id (ctx_idx before the step that ended it) and terminated; episodes [env] and steps [env] are
+ * written for every env, and every slot at or beyond episodes [env] as NaN / 0 / -1 / 0, so nothing needs clearing.
+ * Validation: everything carl_brax_rollout_policy checks, in its order (batch, model, policy / obs, the refusal of
+ * CARL_FLAG_BRAX_FP32, the policy); then out and its six arrays non-NULL, n_episodes >= 1, max_steps >= 0 and n_episodes *
+ * n_lanes < 2^31.  A failure returns CARL_ERR_INVALID_ARGUMENT before anything is enqueued; without CARL_FLAG_AUTORESET
+ * the call returns CARL_ERR_UNSUPPORTED.  n_lanes == 0 enqueues nothing; max_steps == 0 fills every output and steps
+ * nothing.  No host synchronisation: stream-ordered and capturable.  The launch has the shape
+ * carl_brax_policy_launch_shape reports for n_steps = max_steps. */
+int carl_brax_evaluate_policy(const carl_batch_t* batch, const carl_brax_sys_t* sys_dev, const carl_brax_sys_t* sys_host,
+                              float* obs, const carl_policy_t* policy_host, int32_t n_episodes, int32_t max_steps,
+                              const carl_policy_episodes_t* out, void* stream);
 /* floats per packed weight set of a Brax policy's shape (n_out up to CARL_BRAX_MAX_ACT); -1 for an invalid shape */
 int32_t carl_brax_policy_set_floats(const carl_policy_t* policy_host);
 /* The shape carl_brax_rollout_policy launches for this batch, model and step count (host only, no device access beyond the

@@ -33,10 +33,19 @@
                    and 2x64 tanh, every launch from the same snapshot; and the merge launch (InputStats.update writing one
                    block) on its own, device events around 50 back-to-back launches.  Written to key "stats" of --out.
 
+  --legs brax_es   the episodes mode of the Brax closed loop and ES on it (runs on its own engines; --lanes is not used):
+                   (a) BraxVecEngine.evaluate_episodes, K = 1, against summary-mode rollout_policy of S and of 1 000 steps,
+                       Ant x 32 768 and Hopper x 32 768, 2x64 tanh, static selector, for TimeLimit = max_steps = 1 000
+                       (S = 1 000) and TimeLimit 100 with max_steps = 1 000 (S = 100): every env stops by step S.  State
+                       restored before each launch; device events; the median of --reps after a warm-up.
+                   (b) one EvolutionStrategy generation, Ant x 32 768 in sets of 256 (P = 128), TimeLimit 100, max_steps
+                       1 000: a host clock around step() that ends in a device synchronise, beside the evaluate_episodes
+                       launch alone.  Written to key "brax_es" of --out.
+
 Host timing with torch.cuda events around `--reps` launches after one warm-up launch; the median per launch is
 reported.  Kernel times belong to a separate `rocprofv3 --kernel-trace --stats` run of this script.
 
-  python tools/policy_rollout_bench.py [--lanes 65536] [--steps 1000] [--reps 5] [--legs rollout,evaluate,value,es,stats] [--out FILE]
+  python tools/policy_rollout_bench.py [--lanes 65536] [--steps 1000] [--reps 5] [--legs rollout,evaluate,value,es,stats,brax_es] [--out FILE]
 
 --out FILE: a JSON file whose keys of the legs run ("results": rollout, "evaluate") are replaced, others kept.
 """
@@ -345,6 +354,97 @@ def stats_leg(eng, n_in, reps, K=1, max_steps=500):
     return rows
 
 
+def brax_es_leg(reps, n=32768, L=256, long_steps=1000):
+    import time
+
+    from carl_amd.brax_engine import BraxVecEngine
+    from carl_amd.brax_policy import BraxMLPPolicy
+    from carl_amd import envs as E
+    from carl_amd.envs.brax.models import SYSTEMS
+    from carl_amd.es import EvolutionStrategy
+
+    def engine(cls, time_limit):
+        feats = cls.get_context_features()
+        names = list(feats)
+        row = np.array([[float(f.default_value) for f in feats.values()]])
+        eng = BraxVecEngine(SYSTEMS[cls.env_name](names), len(names), row, n, "cuda", selector=_lib.SEL_STATIC, seed=0,
+                            ctx_obs_rows=[], max_episode_steps=time_limit)
+        eng.reset()
+        return eng
+
+    def policy(eng, seed=0):
+        rng = np.random.default_rng(seed)
+        dims = [eng.D, 64, 64, eng.sys.n_act]
+        layers = [((rng.normal(size=(o, i)) / np.sqrt(i)).astype(np.float32), np.zeros(o, np.float32))
+                  for i, o in zip(dims[:-1], dims[1:])]
+        return BraxMLPPolicy.for_env(eng, layers, "tanh")
+
+    def launched_width(eng, pol):
+        """lanes per env of the launch (carl_brax_policy_launch_shape answers for both closed-loop entry points)"""
+        import ctypes as C
+
+        shape = _lib.BraxLaunchShape()
+        st = pol.struct(eng.n, pol.device_params(eng.device).data_ptr())
+        _lib.check(eng.lib.carl_brax_policy_launch_shape(C.byref(eng.b), C.byref(eng.sys), C.byref(st), long_steps,
+                                                         C.byref(shape)))
+        return int(shape.lanes_per_env)
+
+    def timed(eng, snap, fn):
+        ts = []
+        for _ in range(reps + 1):  # (the first: warm-up)
+            eng.restore(snap)
+            torch.cuda.synchronize()
+            a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            a.record()
+            fn()
+            b.record()
+            b.synchronize()
+            ts.append(a.elapsed_time(b) * 1e-3)
+        return float(np.median(ts[1:])), ts[1:]
+
+    rows = []
+    for model, cls in (("ant", E.CARLBraxAnt), ("hopper", E.CARLBraxHopper)):
+        for S in (long_steps, 100):
+            eng = engine(cls, S)
+            pol = policy(eng)
+            snap = eng.snapshot()
+            res, summ = eng.alloc_policy_episodes(1), eng.alloc_policy_summary()
+            sec_e, ts_e = timed(eng, snap, lambda: eng.evaluate_episodes(pol, 1, long_steps, out=res))
+            steps = res["steps"].to(torch.int64)
+            assert int(steps.max()) <= S and int(res["episodes"].min()) == 1
+            sec_s, ts_s = timed(eng, snap, lambda: eng.rollout_policy(pol, S, out=summ, mode="summary"))
+            sec_l, ts_l = (sec_s, ts_s) if S == long_steps else timed(
+                eng, snap, lambda: eng.rollout_policy(pol, long_steps, out=summ, mode="summary"))
+            r = {"config": f"brax_episodes_{model}_timelimit_{S}", "envs": n, "n_episodes": 1, "max_steps": long_steps,
+                 "time_limit": S, "lanes_per_env": launched_width(eng, pol), "env_steps_taken": int(steps.sum()),
+                 "longest_env_steps": int(steps.max()), "mean_env_steps": float(steps.double().mean()),
+                 "evaluate_episodes_sec": sec_e, f"summary_{S}_steps_sec": sec_s, f"summary_{long_steps}_steps_sec": sec_l,
+                 "episodes_over_summary_S_steps": sec_e / sec_s, "episodes_over_summary_1000_steps": sec_e / sec_l,
+                 "reps_sec": {"evaluate_episodes": ts_e, "summary_S": ts_s, "summary_long": ts_l}}
+            rows.append(r)
+            print(json.dumps(r), flush=True)
+    eng = engine(E.CARLBraxAnt, 100)
+    es = EvolutionStrategy(eng, policy(eng), lanes_per_set=L, sigma=0.1, lr=0.05, seed=0)
+    ts = []
+    for _ in range(reps + 1):
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        es.step(n_episodes=1, max_steps=long_steps)
+        torch.cuda.synchronize()
+        ts.append(time.perf_counter() - t0)
+    eng.reset()
+    snap = eng.snapshot()
+    res = eng.alloc_policy_episodes(1)
+    sec_e, ts_e = timed(eng, snap, lambda: eng.evaluate_episodes(es.population, 1, long_steps, out=res))
+    r = {"config": "brax_es_ant_2x64_tanh", "envs": n, "sets": es.n_sets, "lanes_per_set": L, "n_episodes": 1,
+         "max_steps": long_steps, "time_limit": 100, "set_floats": es.set_floats, "n_noisy": es.n_noisy,
+         "es_step_sec": float(np.median(ts[1:])), "evaluate_episodes_launch_sec": sec_e,
+         "reps_sec": {"es_step": ts[1:], "evaluate_episodes": ts_e}}
+    rows.append(r)
+    print(json.dumps(r), flush=True)
+    return rows
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--lanes", type=int, default=65536)
@@ -355,6 +455,8 @@ def main():
     ap.add_argument("--sampled", action="store_true")
     args = ap.parse_args()
     legs = set(args.legs.split(","))
+    if legs == {"brax_es"}:  # (its own engines: the CartPole engine below is not built)
+        return write(args.out, {"brax_es": brax_es_leg(args.reps)})
     n, T = args.lanes, args.steps
     eng = make_engine(n)
     n_in = len(eng.ctx_obs_rows) + eng.D
@@ -368,6 +470,8 @@ def main():
         doc["es"] = es_leg(eng, n_in, args.reps)
     if "stats" in legs:
         doc["stats"] = stats_leg(eng, n_in, args.reps)
+    if "brax_es" in legs:
+        doc["brax_es"] = brax_es_leg(args.reps)
     if "rollout" not in legs:
         return write(args.out, doc)
 
