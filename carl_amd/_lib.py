@@ -354,4 +354,10 @@ EXPORTS.update({
                                              C.c_int32, C.POINTER(PolicyEpisodes), C.POINTER(PolicyStats), _vp]),
     "carl_policy_stats_merge": (C.c_int, [C.POINTER(Policy), C.POINTER(PolicyStats), C.c_int32, _vp, C.c_int32,
                                           C.POINTER(PolicyRunningStats), C.c_double, C.c_double, _vp, C.c_int32, _vp]),
+    # the Brax families' (carl_brax_evaluate_policy gathering the sums; one slab per wavefront of the launch)
+    "carl_brax_policy_stats_slabs": (C.c_int32, [C.POINTER(Batch), C.POINTER(BraxSys), C.POINTER(Policy), C.c_int32]),
+    "carl_brax_evaluate_policy_stats": (C.c_int, [C.POINTER(Batch), _vp, C.POINTER(BraxSys), _vp, C.POINTER(Policy), C.c_int32,
+                                                  C.c_int32, C.POINTER(PolicyEpisodes), C.POINTER(PolicyStats), _vp]),
+    "carl_brax_policy_stats_merge": (C.c_int, [C.POINTER(Policy), C.POINTER(PolicyStats), C.c_int32, _vp, C.c_int32,
+                                               C.POINTER(PolicyRunningStats), C.c_double, C.c_double, _vp, C.c_int32, _vp]),
 })

@@ -405,7 +405,8 @@ class BraxVecEngine(LaneEngine):
         return {k: torch.empty((K, self.n) if rows else (self.n,), dtype=dt, device=self.device)
                 for k, dt, rows in self._EPISODE_KEYS}
 
-    def evaluate_episodes(self, policy, n_episodes: int, max_steps: int, out: dict | None = None) -> dict:
+    def evaluate_episodes(self, policy, n_episodes: int, max_steps: int, out: dict | None = None,
+                          input_stats: bool = False) -> dict:
         """Run ``policy`` (a ``BraxMLPPolicy``, deterministic) on every env until the env has finished ``n_episodes``
         episodes or taken ``max_steps`` steps, in ONE launch, from the current engine state (include/carl_amd.h:
         carl_brax_evaluate_policy; a running episode is counted with its full length, ``CARLBraxEnv.evaluate_episodes``
@@ -417,7 +418,12 @@ class BraxVecEngine(LaneEngine):
         episode), or at ``max_steps``, mid-episode; its records and its state are those of a transitions-mode
         ``rollout_policy`` of as many steps, bit for bit, and a wavefront stops stepping once none of its envs is live.
         The launch starts from ``obs`` and leaves every env's current observation there, as ``rollout_policy`` does.
-        Needs ``auto_reset``.  No host synchronisation."""
+        Needs ``auto_reset``.  No host synchronisation.  ``input_stats=True``: the launch also gathers, for every live
+        env-step, the sums of ``d = x_raw - shift`` and ``d * d`` of every policy input (include/carl_amd.h:
+        carl_brax_evaluate_policy_stats); the result gains ``"input_partial"``, the float64 ``[slabs, 2, 32]`` device tensor
+        of per-wavefront sums (``carl_brax_policy_stats_slabs`` of them) that ``carl_amd.policy.InputStats.update`` merges,
+        as ``VecEngine.evaluate_policy``'s does; with ``input_stats=False`` a reused ``out`` loses that key.  Records and
+        engine state are the same bits either way."""
         self._check_policy(policy, "evaluate_episodes")
         if not self.auto_reset:
             raise ValueError("evaluate_episodes needs auto_reset=True: without it a finished lane reports done on every "
@@ -441,9 +447,26 @@ class BraxVecEngine(LaneEngine):
         params = policy.device_params(self.device)
         pol = policy.struct(self.n, params.data_ptr())
         eps = _lib.PolicyEpisodes(*(_ptr(res[k]) for k, _, _ in self._EPISODE_KEYS))
+        head = (C.byref(self.b), _ptr(self.sys_dev), C.byref(self.sys), _ptr(self.obs), C.byref(pol), K, T, C.byref(eps))
+        if input_stats:
+            n_slabs = int(self.lib.carl_brax_policy_stats_slabs(C.byref(self.b), C.byref(self.sys), C.byref(pol), T))
+            if n_slabs < 0:
+                raise ValueError("evaluate_episodes: this batch and model have no closed-loop launch shape")
+            shape = (n_slabs, 2, _lib.POLICY_MAX_IN)
+            partial = res.get("input_partial")
+            if partial is None:
+                partial = res["input_partial"] = torch.empty(shape, dtype=torch.float64, device=self.device)
+            if (partial.device != self.device or partial.dtype != torch.float64 or not partial.is_contiguous()
+                    or tuple(partial.shape) != shape):
+                raise ValueError(f"evaluate_episodes output 'input_partial' must be a contiguous torch.float64 "
+                                 f"{list(shape)} tensor on {self.device}")
+            st = _lib.PolicyStats(_ptr(partial), n_slabs)
+            with torch.cuda.device(self.device):
+                _lib.check(self.lib.carl_brax_evaluate_policy_stats(*head, C.byref(st), self._stream()))
+            return res
+        res.pop("input_partial", None)  # a reused dict must not carry an earlier launch's sums beside this launch's steps
         with torch.cuda.device(self.device):
-            _lib.check(self.lib.carl_brax_evaluate_policy(C.byref(self.b), _ptr(self.sys_dev), C.byref(self.sys),
-                                                          _ptr(self.obs), C.byref(pol), K, T, C.byref(eps), self._stream()))
+            _lib.check(self.lib.carl_brax_evaluate_policy(*head, self._stream()))
         return res
 
     def reset_done(self):

@@ -8,11 +8,13 @@ clips an action given to ``step``) and the observation width the model's ``obs_d
 ``BraxVecEngine.rollout_policy`` / ``CARLBraxEnv.rollout_policy`` run it for T steps in one launch.
 
 ``BraxVecEngine.evaluate_episodes`` / ``CARLBraxEnv.evaluate_episodes`` run it for whole episodes -- K per env, each env
-stopping at its K-th episode end -- and ``carl_amd.es.EvolutionStrategy`` takes it as its template.
+stopping at its K-th episode end -- and ``carl_amd.es.EvolutionStrategy`` takes it as its template.  With
+``input_stats=True`` that launch also gathers the sums of every input every env visited; ``carl_amd.policy.InputStats``
+with a ``BraxMLPPolicy`` template merges them into running statistics on the device (ARS V2's normalisation).
 
 At most ``CARL_POLICY_MAX_IN`` = 32 inputs: Humanoid's and HumanoidStandup's 244 observations do not fit.  Out of scope
-here: sampled actions and log-probabilities, value networks and GAE, input statistics (``evaluate_policy`` stays the
-classic-control families') and ``MixedVecEngine``.
+here: sampled actions and log-probabilities, value networks and GAE (``evaluate_policy`` stays the classic-control
+families') and ``MixedVecEngine``.
 """
 from __future__ import annotations
 
@@ -39,6 +41,8 @@ def _brax_engine_of(env):
 class BraxMLPPolicy(MLPPolicy):
     """One or more weight sets of one MLP shape for one Brax model (see the module docstring).  ``info``: the engine's
     info record (``BraxVecEngine.info``); the other parameters are ``MLPPolicy``'s."""
+
+    _STATS_MERGE = "carl_brax_policy_stats_merge"  # (n_out up to the model's actuators: the Brax packing rule)
 
     def __init__(self, info, ctx_rows: Sequence[int], layers: Sequence, activation: str = "tanh", input_shift=None,
                  input_scale=None, input_clip: float | None = None, context_names: Sequence | None = None):

@@ -25,21 +25,5 @@ brax_episodes_kernel(const carl_batch_t b, const carl_brax_sys_t* __restrict__ s
   Group<K>::template run<2, MULTI, TASK, PLANAR, false, BraxEpisodesPolicy>(b, sys_dev, prep, io, nullptr, nullptr, max_steps, pol);
 }
 
-// max_steps == 0: nothing is stepped and no episode finishes, but every output is still written
-__global__ void __launch_bounds__(256) brax_episodes_empty_kernel(const carl_policy_episodes_t ep, const int n_lanes,
-                                                                  const int n_episodes) {
-  const int env = (int)(blockIdx.x * blockDim.x + threadIdx.x);
-  if (env >= n_lanes) return;
-  ep.episodes[env] = 0;
-  ep.steps[env] = 0;
-  for (int k = 0; k < n_episodes; ++k) {
-    const size_t at = (size_t)k * (size_t)n_lanes + (size_t)env;
-    ep.ret[at] = __builtin_nanf("");
-    ep.length[at] = 0;
-    ep.context_id[at] = -1;
-    ep.terminated[at] = 0;
-  }
-}
-
 }  // namespace brax
 }  // namespace carl

@@ -406,9 +406,11 @@ __host__ __device__ inline Layout policy_layout_of(const carl_brax_sys_t& s) {
   return l;
 }
 // run()'s policy argument in modes 0 and 1: none.  kEpisodes: the policy type selects the episodes variant of MODE 2
-// (brax_episodes_kernels.hip.h: BraxEpisodesPolicy).
+// (brax_episodes_kernels.hip.h: BraxEpisodesPolicy); kStats: its variant that also gathers input statistics
+// (brax_stats_kernels.hip.h: BraxStatsPolicy).
 struct NoPolicy {
   static constexpr bool kEpisodes = false;
+  static constexpr bool kStats = false;
 };
 
 // tree topology derived from the model table once per workgroup
@@ -2209,6 +2211,9 @@ static __device__ __forceinline__ void write_ctx_obs(const carl_batch_t& b, cons
 // keeps resetting there), with every global write under `live`.  The wavefront leaves the step loop for good once none of
 // its envs is live.  A tail fragment learns what the head left from pol.ep.episodes [env] in HBM, as the summary
 // totals are handed over; every way out of the step loop falls through to the fragment's stores and the head_done release.
+// the episodes mode with Pol::kStats (include/carl_amd.h: carl_brax_evaluate_policy_stats; compiled from
+// carl_brax_policy_stats.hip alone): the policy is called with the env's liveness and the wavefront's two float64 sums,
+// which it adds the live envs' raw inputs to (brax_stats_kernels.hip.h), and the sums are stored once behind the fragment loop.
 // F32 (MODE 1, CARL_FLAG_BRAX_FP32): the n_frames substeps of an env step run their pose algebra in float32.
 template <int MODE, bool MULTI, bool TASK, bool PLANAR = false, bool F32 = false, class Pol = NoPolicy>
 static __device__ __forceinline__ void run(const carl_batch_t& b, const carl_brax_sys_t* __restrict__ sys_dev,
@@ -2289,6 +2294,8 @@ static __device__ __forceinline__ void run(const carl_batch_t& b, const carl_bra
   const int n_waves = (int)blockDim.x >> 6;
   constexpr bool EP = Pol::kEpisodes;
   static_assert(!EP || MODE == 2, "the episodes mode is a variant of the closed-loop rollout");
+  constexpr bool ST = Pol::kStats;
+  static_assert(!ST || EP, "input statistics are gathered in the episodes mode");
 
   if constexpr (MODE == 0) {
     const int gwave = (int)blockIdx.x * n_waves + wave;  // global wavefront = group of kEnvs envs
@@ -2361,6 +2368,8 @@ static __device__ __forceinline__ void run(const carl_batch_t& b, const carl_bra
     }
     Prof prof;
     prof.start();
+    // statistics variant: the wavefront's float64 sums of the input its lane owns, over all its fragments
+    [[maybe_unused]] double st_s1 = 0.0, st_s2 = 0.0;
     for (int fi = 0; fi < n_frag; ++fi) {
     const Fragment frag = fragment_of(piece, T, fi);
     const int grp = frag.grp, t_lo = frag.t_lo, t_hi = frag.t_hi;
@@ -2445,6 +2454,10 @@ static __device__ __forceinline__ void run(const carl_batch_t& b, const carl_bra
       // The env's episode scalars (identical in all its lanes) wait in LDS until the reward needs them: a dozen registers
       // per lane that the substeps and observe need more.
       if (lead) stash_put(m, r);
+      if constexpr (ST) {
+        // the policy as below, gathering the raw inputs of the envs that are live at this step (no per-step record)
+        pol.template act_stats<kSub>(m, pol_rows, b, r.cidx, env, active, ep_left > 0, tid, s.obs_dim, n_act, st_s1, st_s2);
+      } else
       if constexpr (MODE == 2) {
         // the policy on the observation in the io rows -> the action in the io rows, and in row t of io.action
         pol.template act<kSub>(m, pol_rows, b, r.cidx, env, active, s.obs_dim, n_act,
@@ -2773,6 +2786,7 @@ static __device__ __forceinline__ void run(const carl_batch_t& b, const carl_bra
     phase_sync();  // the next fragment reloads this wavefront's rows
     prof.mark(kProfStore);
     }  // fragments
+    if constexpr (ST) pol.store_stats(((int)blockIdx.x * n_waves + wave), tid, st_s1, st_s2);  // (a wavefront without a fragment: zeros)
     prof.flush(tid == 0);
   }
 }

@@ -82,6 +82,22 @@ inline int validate_closed_loop(const char* who, const carl_batch_t* batch, cons
   return validate_policy(who, batch, sys_host, policy_host);
 }
 
+// What the episodes entry points (carl_brax_evaluate_policy, carl_brax_evaluate_policy_stats) check after that, in this order.
+inline int validate_episodes(const char* who, const carl_batch_t* batch, int32_t n_episodes, int32_t max_steps,
+                             const carl_policy_episodes_t* out) {
+  if (out == nullptr || !out->episodes || !out->steps || !out->ret || !out->length || !out->context_id || !out->terminated)
+    return fail(CARL_ERR_INVALID_ARGUMENT, "%s: out and its six arrays must not be NULL", who);
+  if (n_episodes < 1) return fail(CARL_ERR_INVALID_ARGUMENT, "%s: n_episodes %d < 1", who, n_episodes);
+  if (max_steps < 0) return fail(CARL_ERR_INVALID_ARGUMENT, "%s: max_steps %d < 0", who, max_steps);
+  if ((int64_t)n_episodes * batch->n_lanes >= (int64_t)1 << 31)
+    return fail(CARL_ERR_INVALID_ARGUMENT, "%s: %d episodes x %d lanes: more than 2^31 - 1 records", who, n_episodes,
+                batch->n_lanes);
+  if (!(batch->flags & CARL_FLAG_AUTORESET))
+    return fail(CARL_ERR_UNSUPPORTED, "%s: needs CARL_FLAG_AUTORESET (without auto-reset a finished lane reports done on "
+                "every later step, and its episode would be counted on each of them)", who);
+  return 0;
+}
+
 // The shape of a closed-loop launch of n_steps (episodes mode: max_steps) steps, and its kernel out of the unit's table
 // `tab` (entries with a class `c`, a width `k` and a kernel `kern`): one rule for both entry points, whose tables hold the
 // same (class, width) instances (tests/test_brax_episodes_abi.py), so carl_brax_policy_launch_shape answers for both.

@@ -27,8 +27,14 @@
 namespace carl {
 namespace brax {
 
+// act()'s tap on the raw inputs: none.  brax_stats_kernels.hip.h has the one that gathers input statistics.
+struct NoInputTap {
+  static constexpr bool kOn = false;
+};
+
 struct BraxPolicy {
   static constexpr bool kEpisodes = false;  // (run(): not the episodes variant -- brax_episodes_kernels.hip.h)
+  static constexpr bool kStats = false;     // (nor its statistics variant -- brax_stats_kernels.hip.h)
   carl_policy_t p;            // validated by the host (carl_brax_policy.hip)
   int set_floats;             // floats per packed weight set
   carl_policy_summary_t sum;  // per-env totals; all NULL: none
@@ -85,9 +91,11 @@ struct BraxPolicy {
 
   // The env's io rows hold its observation [obs_dim]: leave its action [n_act] there, and in action_out[0, n_act) when
   // that is not NULL.  `rows`: the first of the env's policy rows; cidx: the env's current context.  Wavefront-uniform call.
-  template <int kSub, class LdsT>
+  // `tap` (Tap::kOn): sees every raw input beside its shift where the first phase normalises it, marks the env before that
+  // phase's hand-over and gathers behind it, while h2 and the summary-total rows are still dead.
+  template <int kSub, class LdsT, class Tap = NoInputTap>
   __device__ __forceinline__ void act(const LdsT& m, int rows, const carl_batch_t& b, int cidx, int env, bool active,
-                                      int obs_dim, int n_act, float* __restrict__ action_out) const {
+                                      int obs_dim, int n_act, float* __restrict__ action_out, const Tap& tap = Tap()) const {
     const int X = rows, H1 = rows + kPolicyXRows, H2 = H1 + kPolicyHRows;
     const int n_in = p.n_in, n_ctx = p.n_ctx, nh = p.n_hidden;
     const int w0 = nh > 0 ? p.width[0] : 0, w1 = nh > 1 ? p.width[1] : 0;
@@ -102,13 +110,20 @@ struct BraxPolicy {
     if (active) {
       const float clip = w[p_clip];
       for (int k = 0; k < n_ctx; ++k)  // (wavefront-uniform k: the row index is a scalar load from the kernel arguments)
-        if (m.sub == k % kSub)
-          m.at(X + k) = normalize_input(b.ctx_table[(size_t)p.ctx_rows[k] * b.ctx_stride + cidx], w[p_shift + k],
-                                        w[p_scale + k], clip);
-      for (int d = m.sub; d < obs_dim; d += kSub)
-        m.at(X + n_ctx + d) = normalize_input(m.at(m.lay.io + d), w[p_shift + n_ctx + d], w[p_scale + n_ctx + d], clip);
+        if (m.sub == k % kSub) {
+          const float raw = b.ctx_table[(size_t)p.ctx_rows[k] * b.ctx_stride + cidx];
+          m.at(X + k) = normalize_input(raw, w[p_shift + k], w[p_scale + k], clip);
+          if constexpr (Tap::kOn) tap.put(m, H2 + k, raw, w[p_shift + k]);
+        }
+      for (int d = m.sub; d < obs_dim; d += kSub) {
+        const float raw = m.at(m.lay.io + d);
+        m.at(X + n_ctx + d) = normalize_input(raw, w[p_shift + n_ctx + d], w[p_scale + n_ctx + d], clip);
+        if constexpr (Tap::kOn) tap.put(m, H2 + n_ctx + d, raw, w[p_shift + n_ctx + d]);
+      }
     }
+    if constexpr (Tap::kOn) tap.mark(m, H2 + kPolicyHRows);
     Group<kSub>::phase_sync();
+    if constexpr (Tap::kOn) tap.template gather<kSub>(m, H2, H2 + kPolicyHRows, n_in);
     if (nh == 0) {
       layer<kSub, false>(m, w, p_w0, p_b0, n_in, n_act, X, m.lay.io, active, action_out);
     } else {

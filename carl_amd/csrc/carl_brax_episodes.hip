@@ -14,6 +14,29 @@
 #include "brax_policy_host.hpp"
 #include "host_common.hpp"
 
+namespace carl {
+namespace brax {
+
+// max_steps == 0: nothing is stepped and no episode finishes, but every output is still written.  (Defined in this unit,
+// not in the kernels' header: carl_brax_policy_stats.hip includes that header and calls the entry point below instead.)
+__global__ void __launch_bounds__(256) brax_episodes_empty_kernel(const carl_policy_episodes_t ep, const int n_lanes,
+                                                                  const int n_episodes) {
+  const int env = (int)(blockIdx.x * blockDim.x + threadIdx.x);
+  if (env >= n_lanes) return;
+  ep.episodes[env] = 0;
+  ep.steps[env] = 0;
+  for (int k = 0; k < n_episodes; ++k) {
+    const size_t at = (size_t)k * (size_t)n_lanes + (size_t)env;
+    ep.ret[at] = __builtin_nanf("");
+    ep.length[at] = 0;
+    ep.context_id[at] = -1;
+    ep.terminated[at] = 0;
+  }
+}
+
+}  // namespace brax
+}  // namespace carl
+
 namespace {
 
 using carl_host::check_launch;
@@ -62,16 +85,7 @@ int carl_brax_evaluate_policy(const carl_batch_t* batch, const carl_brax_sys_t* 
   const char* who = "carl_brax_evaluate_policy";
   BraxClass c;
   if (int e = carl_host::brax::validate_closed_loop(who, batch, sys_dev, sys_host, obs, policy_host, &c)) return e;
-  if (out == nullptr || !out->episodes || !out->steps || !out->ret || !out->length || !out->context_id || !out->terminated)
-    return fail(CARL_ERR_INVALID_ARGUMENT, "%s: out and its six arrays must not be NULL", who);
-  if (n_episodes < 1) return fail(CARL_ERR_INVALID_ARGUMENT, "%s: n_episodes %d < 1", who, n_episodes);
-  if (max_steps < 0) return fail(CARL_ERR_INVALID_ARGUMENT, "%s: max_steps %d < 0", who, max_steps);
-  if ((int64_t)n_episodes * batch->n_lanes >= (int64_t)1 << 31)
-    return fail(CARL_ERR_INVALID_ARGUMENT, "%s: %d episodes x %d lanes: more than 2^31 - 1 records", who, n_episodes,
-                batch->n_lanes);
-  if (!(batch->flags & CARL_FLAG_AUTORESET))
-    return fail(CARL_ERR_UNSUPPORTED, "%s: needs CARL_FLAG_AUTORESET (without auto-reset a finished lane reports done on "
-                "every later step, and its episode would be counted on each of them)", who);
+  if (int e = carl_host::brax::validate_episodes(who, batch, n_episodes, max_steps, out)) return e;
   if (batch->n_lanes == 0) return 0;
   if (max_steps == 0) {
     hipLaunchKernelGGL(carl::brax::brax_episodes_empty_kernel, dim3((batch->n_lanes + 255) / 256), dim3(256), 0,

@@ -35,4 +35,8 @@ int check_sampling(const char* who, const carl_policy_sampling_t* smp, const car
 // a validated rollout without a step (n_lanes == 0 or n_steps == 0): zero the summary totals, if any
 int policy_rollout_without_steps(const char* who, const carl_batch_t* batch, const carl_policy_summary_t* summary_out,
                                  void* stream);
+// the statistics output of an episodes launch that gathers input statistics, or of their merge (defined in
+// carl_policy_stats.hip): stats and stats->partial not NULL, partial on a 16-byte boundary, room for n_slabs slabs.
+// `slabs`: what a slab is called and which function counts them, for the message
+int check_policy_stats(const char* who, const carl_policy_stats_t* stats, int n_slabs, const char* slabs);
 }  // namespace carl_host

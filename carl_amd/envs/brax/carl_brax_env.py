@@ -336,12 +336,14 @@ class CARLBraxEnv(CARLEnv):
         env's engine.  The host selector object is not consulted."""
         return self.env.rollout_policy(policy, n_steps, out=out, mode=mode)
 
-    def evaluate_episodes(self, policy, n_episodes: int, max_steps: int, seed: int | None = None) -> dict:
+    def evaluate_episodes(self, policy, n_episodes: int, max_steps: int, seed: int | None = None,
+                          input_stats: bool = False) -> dict:
         """``n_episodes`` whole episodes of ``policy`` per env (at most ``max_steps`` steps) in one launch:
-        ``reset(seed=seed)``, then ``BraxVecEngine.evaluate_episodes``.  ``carl_amd.policy.episode_stats`` reduces the
-        result per context (mean / std return, as SB3's ``evaluate_policy`` reports them)."""
+        ``reset(seed=seed)``, then ``BraxVecEngine.evaluate_episodes`` (``input_stats=True``: the launch also gathers the
+        policy inputs' sums, see there).  ``carl_amd.policy.episode_stats`` reduces the result per context (mean / std
+        return, as SB3's ``evaluate_policy`` reports them)."""
         self.reset(seed=seed)
-        return self.env.evaluate_episodes(policy, n_episodes, max_steps)
+        return self.env.evaluate_episodes(policy, n_episodes, max_steps, input_stats=input_stats)
 
     @classmethod
     def get_default_context(cls) -> Context:

@@ -20,6 +20,9 @@ every member visited (``evaluate_policy(..., input_stats=True)``), and after the
 merges them into the running mean and variance (``self.input_stats``, ``carl_amd.policy.InputStats``) and writes the
 shift and scale they imply into the centre's transform section.  The next generation's ``carl_es_perturb`` carries that
 section into every member, so the statistics of generation g act from generation g + 1.  Still no host synchronisation.
+``input_stats=`` takes a ready ``InputStats`` for the template's shape in the place of a fresh one -- the statistics of a
+checkpoint (``InputStats.load_state_dict``), to resume a run where it stopped -- and is the one route for both families;
+``normalize_inputs=True`` is the classic-control shorthand that builds one.
 
 Choosing contexts: with a static selector and a context count that divides ``lanes_per_set``, every member of the
 population is evaluated on every context once per episode slot -- the CARL question ES is asked here.
@@ -27,8 +30,10 @@ population is evaluated on every context once per episode slot -- the CARL quest
 The Brax families: with a ``carl_amd.brax_policy.BraxMLPPolicy`` template on a ``CARLBraxEnv`` or ``BraxVecEngine`` the
 same sequence runs over the Brax closed loop -- step 2 is ``evaluate_episodes`` (include/carl_amd.h:
 carl_brax_evaluate_policy: exactly K whole episodes per env, each env stopping at its K-th episode end), the other
-launches do not depend on the family.  Deterministic actions only, and no ``normalize_inputs``: sampling and input
-statistics for the Brax families are separate work.
+launches do not depend on the family.  Input normalisation runs through ``input_stats=InputStats(template, device)``:
+the launch is then ``evaluate_episodes(..., input_stats=True)`` (carl_brax_evaluate_policy_stats) and the merge
+carl_brax_policy_stats_merge, in the same places.  Deterministic actions only: sampling for the Brax families is separate
+work.
 
 Out of scope, and refused as ``carl_amd.policy`` refuses them: ``MixedVecEngine`` pairs, the gymnasium drop-in.
 """
@@ -89,18 +94,24 @@ class EvolutionStrategy:
     the centre as a leaf tensor, and each step sets its ``.grad = -grad / (P * sigma)`` and calls ``step()`` instead of
     the default update.  ``normalize_inputs``: keep running statistics of the policy inputs and normalise the next
     generation's inputs by them (module docstring); ``stats_eps`` / ``stats_min_std``: ``InputStats``' ``eps`` / ``min_std``.
+    ``input_stats``: an ``InputStats`` built for this template's shape on the engine's device, fresh or loaded from a
+    checkpoint, to the same effect -- either family; giving both is an error.
 
     ``center``: the ``[set_floats]`` float32 device tensor of the packed centre (readable at any time; assign a tensor to
     replace its values).  ``generation``: starts at 0, one more per ``step``.  ``population``: the ``on_device`` policy
-    the members are written into.  ``input_stats``: the ``InputStats`` of ``normalize_inputs=True``, else None."""
+    the members are written into.  ``input_stats``: the ``InputStats`` given, or built by ``normalize_inputs=True``, else None."""
 
     def __init__(self, env, policy: MLPPolicy, lanes_per_set: int = 256, sigma: float = 0.1, lr: float = 0.05, seed: int = 0,
                  fitness_shaping: str | Callable = "centered_rank", optimizer: Callable | None = None,
-                 normalize_inputs: bool = False, stats_eps: float = 1e-8, stats_min_std: float = 1e-6):
+                 normalize_inputs: bool = False, stats_eps: float = 1e-8, stats_min_std: float = 1e-6,
+                 input_stats: InputStats | None = None):
         brax = isinstance(policy, BraxMLPPolicy)  # the template's type picks the closed loop: every other one the classic
         if brax and normalize_inputs:
-            raise NotImplementedError("EvolutionStrategy: normalize_inputs (input statistics) is out of scope for the Brax "
-                                      "families")
+            raise NotImplementedError("EvolutionStrategy: normalize_inputs=True builds the statistics of a classic-control "
+                                      "template; for the Brax families pass input_stats=InputStats(template, device)")
+        if normalize_inputs and input_stats is not None:
+            raise ValueError("EvolutionStrategy: normalize_inputs=True builds an InputStats, input_stats= brings one: give "
+                             "one of the two")
         eng, cenv = _brax_engine_of(env) if brax else _engine_of(env)
         if not eng.auto_reset:
             raise ValueError("EvolutionStrategy needs auto_reset=True (evaluate_policy counts whole episodes)")
@@ -129,6 +140,15 @@ class EvolutionStrategy:
             raise ValueError(f"sigma {sigma}: finite and positive")
         if not callable(fitness_shaping) and fitness_shaping not in _SHAPING:
             raise ValueError(f"fitness_shaping {fitness_shaping!r}: one of {sorted(_SHAPING)} or a callable")
+        dev = eng.device
+        if input_stats is not None:
+            t = input_stats.template if isinstance(input_stats, InputStats) else None
+            at = input_stats.device if t is not None else None  # ("cuda" without an index: the engine's)
+            if (t is None or type(t) is not type(policy) or t.n_in != policy.n_in or t.weight_floats != policy.weight_floats
+                    or t.set_floats != policy.set_floats or at.type != dev.type
+                    or (at.index is not None and dev.index is not None and at.index != dev.index)):
+                raise ValueError(f"input_stats: an InputStats built for a {type(policy).__name__} of this template's shape "
+                                 f"({policy.n_in} inputs, {policy.set_floats} floats per weight set) on {dev}")
         self.env, self.engine, self._carl_env = env, eng, cenv
         self.template, self._brax = policy, brax
         self.lanes_per_set, self.n_sets, self.n_pairs = L, P, P // 2
@@ -136,14 +156,13 @@ class EvolutionStrategy:
         self.set_floats, self.n_noisy = policy.set_floats, policy.weight_floats
         self.generation = 0
         self._shape = fitness_shaping if callable(fitness_shaping) else _SHAPING[fitness_shaping]
-        dev = eng.device
         self._center = torch.as_tensor(policy.params[0]).to(dev).contiguous().clone()
         self._params = torch.empty((P, self.set_floats), dtype=torch.float32, device=dev)
         self.population = MLPPolicy.on_device(policy, self._params, L)
         self._noisy = self._center[: self.n_noisy]  # (a view: the optimizer's parameter)
         self._opt = optimizer(self._noisy) if optimizer is not None else None
         self.lib = _lib.load()
-        self.input_stats = InputStats(policy, dev, stats_eps, stats_min_std) if normalize_inputs else None
+        self.input_stats = InputStats(policy, dev, stats_eps, stats_min_std) if normalize_inputs else input_stats
 
     # ------------------------------------------------------------------ state
     @property
@@ -174,7 +193,7 @@ class EvolutionStrategy:
              sample_seed: int | None = None) -> dict:
         """One generation: perturb, reset, ``evaluate_policy`` (``n_episodes`` per lane, at most ``max_steps`` steps;
         sampled actions with ``deterministic=False``, keyed by ``sample_seed``, default the generation), fitness, shaping,
-        gradient, update (and, with ``normalize_inputs``, the statistics' merge into the centre).  Returns ``{"fitness" [P], "weight" [P / 2], "grad" [n_noisy], "result": evaluate_policy's
+        gradient, update (and, with ``input_stats``, the statistics' merge into the centre).  Returns ``{"fitness" [P], "weight" [P / 2], "grad" [n_noisy], "result": evaluate_policy's
         dict}``, every value a device tensor.  No host synchronisation.  A Brax template: ``evaluate_episodes`` in place
         of ``evaluate_policy``, ``deterministic=True`` only (``sample_seed`` has nothing to key)."""
         eng = self.engine
@@ -186,11 +205,12 @@ class EvolutionStrategy:
         with torch.cuda.device(eng.device):
             _lib.check(self.lib.carl_es_perturb(C.byref(es), self._center.data_ptr(), self._params.data_ptr(), None, stream))
         if self._brax:
+            kw = dict(input_stats=True) if self.input_stats is not None else {}
             if self._carl_env is not None:
-                res = self._carl_env.evaluate_episodes(self.population, n_episodes, max_steps)
+                res = self._carl_env.evaluate_episodes(self.population, n_episodes, max_steps, **kw)
             else:
                 eng.reset()
-                res = eng.evaluate_episodes(self.population, n_episodes, max_steps)
+                res = eng.evaluate_episodes(self.population, n_episodes, max_steps, **kw)
         else:
             seed = self.generation if sample_seed is None else int(sample_seed)
             kw = dict(deterministic=deterministic, sample_seed=seed)

@@ -98,6 +98,8 @@ def flattened_context_rows(env, features: Sequence | None = None, engine_of=None
 class MLPPolicy:
     """One or more weight sets of one MLP shape, for one env family (see the module docstring)."""
 
+    _STATS_MERGE = "carl_policy_stats_merge"  # the C entry point InputStats merges this packing rule's policies through
+
     def __init__(self, family: int, obs_dim: int, ctx_rows: Sequence[int], layers: Sequence, activation: str = "tanh",
                  input_shift=None, input_scale=None, input_clip: float | None = None, context_names: Sequence | None = None,
                  log_std=None, head: str = "policy", info=None):
@@ -384,7 +386,8 @@ class InputStats:
     """Running count, mean and M2 (sum of squared deviations) of a policy's inputs, float64 on the device, merged from
     ``evaluate_policy(..., input_stats=True)`` results by one small launch each (carl_policy_stats_merge) with no host
     synchronisation.  ``template``: a policy of the shape the launches run (its context rows and layer sizes give the
-    input count and the offset of the transform section).  ``eps``: ``scale = 1 / sqrt(var + eps)``; ``min_std``: an input
+    input count and the offset of the transform section; a ``BraxMLPPolicy`` template takes
+    ``evaluate_episodes(..., input_stats=True)`` results and merges through carl_brax_policy_stats_merge).  ``eps``: ``scale = 1 / sqrt(var + eps)``; ``min_std``: an input
     whose variance is at most ``max(min_std^2, (2^-18 |mean|)^2)`` counts as constant and gets ``scale = 0``."""
 
     def __init__(self, template: MLPPolicy, device, eps: float = 1e-8, min_std: float = 1e-6):
@@ -456,7 +459,7 @@ class InputStats:
         if stream is None:
             stream = torch.cuda.current_stream(self.device).cuda_stream
         with torch.cuda.device(self.device):
-            _lib.check(_lib.load().carl_policy_stats_merge(
+            _lib.check(getattr(_lib.load(), type(self.template)._STATS_MERGE)(
                 C.byref(pol), C.byref(st), int(partial.shape[0]), steps.data_ptr(), int(steps.numel()), C.byref(run),
                 self.eps, self.min_std, None if block is None else block.data_ptr(), n_write if block is not None else 0,
                 stream))
@@ -475,14 +478,15 @@ class InputStats:
         return mean.astype(np.float32), scale.astype(np.float32)
 
     def apply_to(self, policy: MLPPolicy) -> MLPPolicy:
-        """A one-set host-built policy of ``policy``'s weights with the statistics' shift and scale (its clip is kept)."""
+        """A one-set host-built policy of ``policy``'s weights (and of its type) with the statistics' shift and scale (its
+        clip is kept)."""
         if policy._on_device or policy.n_sets != 1 or policy.n_in != self.n_in:
             raise ValueError("InputStats.apply_to: a one-set host-built policy with the template's inputs")
         shift, scale = self.transform()
         flat = policy.params[0].copy()
         off = policy.weight_floats
         flat[off: off + self.n_in], flat[off + self.n_in: off + 2 * self.n_in] = shift, scale
-        return MLPPolicy.unpack(policy, flat)
+        return type(policy).unpack(policy, flat)
 
     def state_dict(self) -> dict:
         """``{"count", "mean", "m2"}`` as host tensors (one copy each)."""

@@ -917,7 +917,8 @@ int carl_brax_fragment_plan(int32_t n_groups, int32_t n_workgroups, int32_t wave
  *    carl_rollout_policy defines them.  A summary (in either mode) needs CARL_FLAG_AUTORESET, else CARL_ERR_UNSUPPORTED.
  * The batch, the model and io are checked as carl_brax_rollout checks them.  CARL_FLAG_BRAX_FP32 is refused with
  * CARL_ERR_UNSUPPORTED; both auto-reset modes and the goal wrapper work as in carl_brax_rollout.  Out of scope: sampled
- * actions and log-probabilities, critics and GAE, input statistics (the episodes mode is carl_brax_evaluate_policy). */
+ * actions and log-probabilities, critics and GAE (the episodes mode is carl_brax_evaluate_policy, its input statistics
+ * carl_brax_evaluate_policy_stats). */
 int carl_brax_rollout_policy(const carl_batch_t* batch, const carl_brax_sys_t* sys_dev, const carl_brax_sys_t* sys_host,
                              float* obs, const carl_policy_t* policy_host, const carl_step_io_t* io, int32_t n_steps,
                              const carl_policy_summary_t* summary_out, void* stream);
@@ -948,6 +949,54 @@ int carl_brax_rollout_policy(const carl_batch_t* batch, const carl_brax_sys_t* s
 int carl_brax_evaluate_policy(const carl_batch_t* batch, const carl_brax_sys_t* sys_dev, const carl_brax_sys_t* sys_host,
                               float* obs, const carl_policy_t* policy_host, int32_t n_episodes, int32_t max_steps,
                               const carl_policy_episodes_t* out, void* stream);
+/* ---- input statistics inside the Brax episodes launch (additive; ABI version unchanged) ----
+ * carl_evaluate_policy_stats for the Brax families: what ARS V2 needs to normalise these models' inputs.  No reference
+ * counterpart.
+ * carl_brax_evaluate_policy_stats is carl_brax_evaluate_policy: the records, the engine state and `obs` are its, bit for
+ * bit, and the launch has its shape.  In addition it gathers what carl_evaluate_policy_stats gathers, word for word: for
+ * every LIVE env-step (the steps out.steps counts: a frozen env that computes along in a live wavefront, an env past the end
+ * of the batch and a wavefront's spare lanes add nothing) and every policy input i < n_in, in FlattenObservation order,
+ *     d_i = fp32(x_i - shift_i),   S1_i += d_i,  S2_i += d_i * d_i
+ * with x_i the raw input the policy acted on at that step (the context value of the env's current context, or the
+ * observation before the step) and shift_i that of the env's own weight set.  One float64 slab [2][CARL_POLICY_MAX_IN] per
+ * WAVEFRONT of the launch, partial[workgroup * waves_per_workgroup + wave] (carl_brax_policy_launch_shape): the wavefront's
+ * sums over all the (group, step range) fragments it ran, written once and in full, +0.0 at and beyond n_in and in the
+ * slab of a wavefront that ran nothing, so nothing needs clearing.  The number of env-steps is the sum of out.steps.
+ * Accuracy, from the operation list: d_i is one fp32 subtraction, the contract's own; it and its square are widened to
+ * float64 exactly (the square of an fp32 value has at most 48 significant bits).  At every step a wavefront takes, lane i
+ * adds the terms of its at most 64 / lanes_per_env envs in env order into a float64 step sum that starts at +0.0, then adds
+ * the step sum to the slab's running float64 sum.  Nothing is added in fp32.  With u = 2^-53, a slab entry that took s
+ * wavefront-steps has |S1_i - exact| <= (s + 64 / lanes_per_env) * u * sum |d_i| and likewise S2_i against sum d_i^2
+ * (recursive summation, first order in u) -- for EVERY input, context and observation alike: float64 rounding only, below
+ * the classic entry point's 10 * 2^-24 bound by a factor of 2^28 / s.  carl_brax_policy_stats_merge's constant rule needs
+ * the relative error of the sums well under 2^-36: guaranteed (at most 2^-39) for s <= 2^14 - 32 wavefront-steps per
+ * slab, i.e. (groups per wavefront) * max_steps <= 16 352 -- up to 523 264 env-steps per wavefront at 2 lanes per env,
+ * 114 464 at 9; beyond that the bound grows linearly with s and the rule's margin shrinks with it.  No floating-point
+ * atomics, no workgroup barrier: the slabs are a fixed function of the launch's inputs and shape, the same bits on every
+ * repetition from the same state.
+ * Validation: everything carl_brax_evaluate_policy checks, in its order and with its codes; then `stats` and
+ * stats->partial non-NULL, partial on a 16-byte boundary and partial_capacity >= carl_brax_policy_stats_slabs(batch,
+ * sys_host, policy_host, max_steps): CARL_ERR_INVALID_ARGUMENT before anything is enqueued.  n_lanes == 0 enqueues nothing.
+ * max_steps == 0 fills the records as carl_brax_evaluate_policy does and writes every slab as zeros. */
+int carl_brax_evaluate_policy_stats(const carl_batch_t* batch, const carl_brax_sys_t* sys_dev, const carl_brax_sys_t* sys_host,
+                                    float* obs, const carl_policy_t* policy_host, int32_t n_episodes, int32_t max_steps,
+                                    const carl_policy_episodes_t* out, const carl_policy_stats_t* stats, void* stream);
+/* The slabs that launch writes: grid * waves_per_workgroup of carl_brax_policy_launch_shape for n_steps = max_steps; for
+ * max_steps == 0, where nothing is launched over the envs, the count of max_steps == 1.  Host only (as
+ * carl_brax_policy_launch_shape).  0 for n_lanes <= 0; -1 for a NULL argument, max_steps < 0, a model table out of range,
+ * CARL_FLAG_BRAX_FP32 or a model without a launch shape. */
+int32_t carl_brax_policy_stats_slabs(const carl_batch_t* batch, const carl_brax_sys_t* sys_host, const carl_policy_t* policy_host,
+                                     int32_t max_steps);
+/* carl_policy_stats_merge for the slabs of carl_brax_evaluate_policy_stats: the same kernel, arithmetic, constant rule and
+ * validation list, with n_slabs in the place of n_workgroups and the packing rule of the Brax families -- set_floats =
+ * carl_brax_policy_set_floats() (n_out up to CARL_BRAX_MAX_ACT; carl_policy_stats_merge refuses such a shape), the
+ * transform offset the floats of every W and b.  Stream-ordered and capturable like the launch above; neither call
+ * synchronises with the host or allocates. */
+int carl_brax_policy_stats_merge(const carl_policy_t* policy_host, const carl_policy_stats_t* stats, int32_t n_slabs,
+                                 const int32_t* steps /* DEVICE [n_lanes] */, int32_t n_lanes,
+                                 const carl_policy_running_stats_t* running, double eps, double min_std,
+                                 float* params_out /* DEVICE [n_write][set_floats], nullable */, int32_t n_write,
+                                 void* stream);
 /* floats per packed weight set of a Brax policy's shape (n_out up to CARL_BRAX_MAX_ACT); -1 for an invalid shape */
 int32_t carl_brax_policy_set_floats(const carl_policy_t* policy_host);
 /* The shape carl_brax_rollout_policy launches for this batch, model and step count (host only, no device access beyond the

@@ -42,10 +42,19 @@
                        1 000: a host clock around step() that ends in a device synchronise, beside the evaluate_episodes
                        launch alone.  Written to key "brax_es" of --out.
 
+  --legs brax_stats  input statistics inside the Brax episodes launch (runs on its own engine; --lanes is not used), brax_es's
+                   set-up: Ant x 32 768, 2x64 tanh, K = 1, TimeLimit 100, max_steps 1 000.  evaluate_episodes(...,
+                   input_stats=True) against evaluate_episodes without it (the kernel of the parent commit:
+                   profiles/brax_stats_isa_identity.txt) in the same process, state restored before each launch, device
+                   events, the two sides interleaved; and one normalised EvolutionStrategy generation (merge included)
+                   against one unnormalised, a host clock around step() that ends in a device synchronise.  The median of
+                   --reps after a warm-up (the launches: of two interleaved runs of --reps per side).  Written to key
+                   "brax_stats" of --out.
+
 Host timing with torch.cuda events around `--reps` launches after one warm-up launch; the median per launch is
 reported.  Kernel times belong to a separate `rocprofv3 --kernel-trace --stats` run of this script.
 
-  python tools/policy_rollout_bench.py [--lanes 65536] [--steps 1000] [--reps 5] [--legs rollout,evaluate,value,es,stats,brax_es] [--out FILE]
+  python tools/policy_rollout_bench.py [--lanes 65536] [--steps 1000] [--reps 5] [--legs rollout,evaluate,value,es,stats,brax_es,brax_stats] [--out FILE]
 
 --out FILE: a JSON file whose keys of the legs run ("results": rollout, "evaluate") are replaced, others kept.
 """
@@ -354,30 +363,56 @@ def stats_leg(eng, n_in, reps, K=1, max_steps=500):
     return rows
 
 
+def brax_bench_engine(cls, n, time_limit):
+    """the Brax legs' engine: the model's default context, static selector, no context inputs"""
+    from carl_amd.brax_engine import BraxVecEngine
+    from carl_amd.envs.brax.models import SYSTEMS
+
+    feats = cls.get_context_features()
+    names = list(feats)
+    row = np.array([[float(f.default_value) for f in feats.values()]])
+    eng = BraxVecEngine(SYSTEMS[cls.env_name](names), len(names), row, n, "cuda", selector=_lib.SEL_STATIC, seed=0,
+                        ctx_obs_rows=[], max_episode_steps=time_limit)
+    eng.reset()
+    return eng
+
+
+def brax_bench_policy(eng, seed=0):
+    """the Brax legs' policy: 2 x 64 tanh"""
+    from carl_amd.brax_policy import BraxMLPPolicy
+
+    rng = np.random.default_rng(seed)
+    dims = [eng.D, 64, 64, eng.sys.n_act]
+    layers = [((rng.normal(size=(o, i)) / np.sqrt(i)).astype(np.float32), np.zeros(o, np.float32))
+              for i, o in zip(dims[:-1], dims[1:])]
+    return BraxMLPPolicy.for_env(eng, layers, "tanh")
+
+
+def timed_from_snapshot(eng, snap, fn, reps):
+    """device events around fn(), the state restored before each launch: (median of `reps` after a warm-up, the reps)"""
+    ts = []
+    for _ in range(reps + 1):  # (the first: warm-up)
+        eng.restore(snap)
+        torch.cuda.synchronize()
+        a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        a.record()
+        fn()
+        b.record()
+        b.synchronize()
+        ts.append(a.elapsed_time(b) * 1e-3)
+    return float(np.median(ts[1:])), ts[1:]
+
+
 def brax_es_leg(reps, n=32768, L=256, long_steps=1000):
     import time
 
-    from carl_amd.brax_engine import BraxVecEngine
-    from carl_amd.brax_policy import BraxMLPPolicy
     from carl_amd import envs as E
-    from carl_amd.envs.brax.models import SYSTEMS
     from carl_amd.es import EvolutionStrategy
 
     def engine(cls, time_limit):
-        feats = cls.get_context_features()
-        names = list(feats)
-        row = np.array([[float(f.default_value) for f in feats.values()]])
-        eng = BraxVecEngine(SYSTEMS[cls.env_name](names), len(names), row, n, "cuda", selector=_lib.SEL_STATIC, seed=0,
-                            ctx_obs_rows=[], max_episode_steps=time_limit)
-        eng.reset()
-        return eng
+        return brax_bench_engine(cls, n, time_limit)
 
-    def policy(eng, seed=0):
-        rng = np.random.default_rng(seed)
-        dims = [eng.D, 64, 64, eng.sys.n_act]
-        layers = [((rng.normal(size=(o, i)) / np.sqrt(i)).astype(np.float32), np.zeros(o, np.float32))
-                  for i, o in zip(dims[:-1], dims[1:])]
-        return BraxMLPPolicy.for_env(eng, layers, "tanh")
+    policy = brax_bench_policy
 
     def launched_width(eng, pol):
         """lanes per env of the launch (carl_brax_policy_launch_shape answers for both closed-loop entry points)"""
@@ -390,17 +425,7 @@ def brax_es_leg(reps, n=32768, L=256, long_steps=1000):
         return int(shape.lanes_per_env)
 
     def timed(eng, snap, fn):
-        ts = []
-        for _ in range(reps + 1):  # (the first: warm-up)
-            eng.restore(snap)
-            torch.cuda.synchronize()
-            a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-            a.record()
-            fn()
-            b.record()
-            b.synchronize()
-            ts.append(a.elapsed_time(b) * 1e-3)
-        return float(np.median(ts[1:])), ts[1:]
+        return timed_from_snapshot(eng, snap, fn, reps)
 
     rows = []
     for model, cls in (("ant", E.CARLBraxAnt), ("hopper", E.CARLBraxHopper)):
@@ -445,6 +470,54 @@ def brax_es_leg(reps, n=32768, L=256, long_steps=1000):
     return rows
 
 
+def brax_stats_leg(reps, n=32768, L=256, max_steps=1000, time_limit=100):
+    """the statistics launch against the episodes launch, and a normalised ES generation (merge included) against an
+    unnormalised one: brax_es_leg's set-up (Ant, 2 x 64 tanh, K = 1), every launch from the same state"""
+    import time
+
+    from carl_amd import envs as E
+    from carl_amd.es import EvolutionStrategy
+    from carl_amd.policy import InputStats
+
+    eng = brax_bench_engine(E.CARLBraxAnt, n, time_limit)
+    pol = brax_bench_policy(eng)
+    snap = eng.snapshot()
+    plain, with_stats = eng.alloc_policy_episodes(1), eng.alloc_policy_episodes(1)
+    eng.evaluate_episodes(pol, 1, max_steps, out=with_stats, input_stats=True)  # (allocates the slabs once)
+    # interleaved A, B, A, B: a drift of the clock over the run lands on both sides
+    ts_p, ts_s = [], []
+    for _ in range(2):
+        ts_p += timed_from_snapshot(eng, snap, lambda: eng.evaluate_episodes(pol, 1, max_steps, out=plain), reps)[1]
+        ts_s += timed_from_snapshot(
+            eng, snap, lambda: eng.evaluate_episodes(pol, 1, max_steps, out=with_stats, input_stats=True), reps)[1]
+    sec_p, sec_s = float(np.median(ts_p)), float(np.median(ts_s))
+    assert torch.equal(plain["steps"], with_stats["steps"])
+
+    def generation(es):
+        ts = []
+        for _ in range(reps + 1):  # (the first: warm-up)
+            torch.cuda.synchronize()
+            t0 = time.perf_counter()
+            es.step(n_episodes=1, max_steps=max_steps)
+            torch.cuda.synchronize()
+            ts.append(time.perf_counter() - t0)
+        return float(np.median(ts[1:])), ts[1:]
+
+    tmpl = brax_bench_policy(eng)
+    gen_p, tg_p = generation(EvolutionStrategy(eng, tmpl, lanes_per_set=L, sigma=0.1, lr=0.05, seed=0))
+    gen_s, tg_s = generation(EvolutionStrategy(eng, tmpl, lanes_per_set=L, sigma=0.1, lr=0.05, seed=0,
+                                               input_stats=InputStats(tmpl, eng.device)))
+    r = {"config": "brax_stats_ant_2x64_tanh", "envs": n, "lanes_per_set": L, "n_episodes": 1, "max_steps": max_steps,
+         "time_limit": time_limit, "slabs": int(with_stats["input_partial"].shape[0]),
+         "env_steps_taken": int(plain["steps"].to(torch.int64).sum()),
+         "evaluate_episodes_sec": sec_p, "evaluate_episodes_input_stats_sec": sec_s, "input_stats_over_plain": sec_s / sec_p,
+         "es_step_sec": gen_p, "es_step_normalised_sec": gen_s, "normalised_over_plain": gen_s / gen_p,
+         "reps_sec": {"evaluate_episodes": ts_p, "evaluate_episodes_input_stats": ts_s, "es_step": tg_p,
+                      "es_step_normalised": tg_s}}
+    print(json.dumps(r), flush=True)
+    return [r]
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--lanes", type=int, default=65536)
@@ -455,8 +528,9 @@ def main():
     ap.add_argument("--sampled", action="store_true")
     args = ap.parse_args()
     legs = set(args.legs.split(","))
-    if legs == {"brax_es"}:  # (its own engines: the CartPole engine below is not built)
-        return write(args.out, {"brax_es": brax_es_leg(args.reps)})
+    if legs <= {"brax_es", "brax_stats"}:  # (their own engines: the CartPole engine below is not built)
+        return write(args.out, {k: leg(args.reps) for k, leg in (("brax_es", brax_es_leg), ("brax_stats", brax_stats_leg))
+                                if k in legs})
     n, T = args.lanes, args.steps
     eng = make_engine(n)
     n_in = len(eng.ctx_obs_rows) + eng.D
@@ -472,6 +546,8 @@ def main():
         doc["stats"] = stats_leg(eng, n_in, args.reps)
     if "brax_es" in legs:
         doc["brax_es"] = brax_es_leg(args.reps)
+    if "brax_stats" in legs:
+        doc["brax_stats"] = brax_stats_leg(args.reps)
     if "rollout" not in legs:
         return write(args.out, doc)
 
