@@ -1,8 +1,8 @@
 // brax_launch.hpp -- host-side rules of the Brax entry points, shared by their translation units (carl_brax.hip: reset /
-// step / open-loop rollout; carl_brax_policy.hip: the closed-loop rollout): the batch / model / io checks, the kernel class
-// of a model, the lanes-per-env rule and the launch shape (workgroups, wavefronts per workgroup, dynamic LDS).  A kernel
-// table is whatever array of entries with a class `c` and a width `k` the unit instantiates; the rules are templates
-// over it, so that each unit instantiates its own kernels only.
+// step / open-loop rollout; the closed-loop units through brax_policy_host.hpp): the batch / model / io checks, the kernel
+// class of a model, the lanes-per-env rule, the launch shape (workgroups, wavefronts per workgroup, dynamic LDS) and the
+// kernels' Prepared argument.  A kernel table is whatever array of entries with a class `c` and a width `k` the unit
+// instantiates; the rules are templates over it, so that each unit instantiates its own kernels only.
 #pragma once
 
 #include <hip/hip_runtime.h>
@@ -285,6 +285,15 @@ int brax_launch_shape(const Entry (&tab)[N], const carl_batch_t* b, const carl_b
   }
   *out = BraxShape{K, W, grid, wave_bytes, (size_t)W * wave_bytes};
   return 0;
+}
+
+// What every Brax kernel takes by value beside the model: its topology and derived per-link constants, built on the host
+// at every launch (microseconds).
+inline carl::brax::Prepared make_prepared(const carl_brax_sys_t* sh) {
+  carl::brax::Prepared prep{};
+  carl::brax::build_topo_host(*sh, prep.topo);
+  carl::brax::build_packed_host(*sh, prep.topo, prep.packed);
+  return prep;
 }
 
 inline int validate_brax_io(const carl_step_io_t* io, const char* who) {

@@ -1,7 +1,9 @@
-// brax_policy_host.hpp -- host-side checks of the closed-loop entry points of the Brax families, shared by their two
-// translation units (carl_brax_policy.hip: carl_brax_rollout_policy; carl_brax_episodes.hip: carl_brax_evaluate_policy):
-// the packed size of a policy's shape, the kernel class of a closed-loop launch, the policy's validation against the batch
-// and the model, and the launch shape.  Host code only; the kernels are each unit's own.
+// brax_policy_host.hpp -- the host side of the closed-loop entry points of the Brax families, shared by their three
+// translation units (carl_brax_policy.hip: carl_brax_rollout_policy; carl_brax_episodes.hip: carl_brax_evaluate_policy;
+// carl_brax_policy_stats.hip: carl_brax_evaluate_policy_stats): the packed size of a policy's shape, the kernel class of a
+// closed-loop launch, the policy's validation against the batch and the model, the list of kernel instances and the entry
+// type of a unit's table of them, the kernels' policy argument, the launch shape and the launch.  Host code only; the
+// kernels are each unit's own: every table is one expansion of the list with the unit's kernel template.
 #pragma once
 
 #include <cstdint>
@@ -71,7 +73,7 @@ inline int validate_policy(const char* who, const carl_batch_t* b, const carl_br
   return 0;
 }
 
-// What both entry points check first, in this order: the batch and the model, policy / obs non-NULL, the kernel class
+// What every entry point checks first, in this order: the batch and the model, policy / obs non-NULL, the kernel class
 // (CARL_FLAG_BRAX_FP32 is refused), the policy.
 inline int validate_closed_loop(const char* who, const carl_batch_t* batch, const carl_brax_sys_t* sys_dev,
                                 const carl_brax_sys_t* sys_host, const float* obs, const carl_policy_t* policy_host,
@@ -98,9 +100,54 @@ inline int validate_episodes(const char* who, const carl_batch_t* batch, int32_t
   return 0;
 }
 
+// Every instantiated closed-loop kernel<MULTI, K, TASK, PLANAR>, of each of the three variants: the non-F32 step classes
+// of carl_brax.hip's kBraxKernels, at the widths it has for them (tests/test_brax_policy_abi.py holds the list against
+// that table).  A unit's table is `#define X(M, K, T, P) {{M, T, P, false}, K, its_kernel<M, K, T, P>},` around one
+// expansion.
+#define CARL_BRAX_CLOSED_LOOP_INSTANCES(X)                                                                      \
+  /* lean */                                                                                                    \
+  X(false, 4, false, false) X(false, 7, false, false) X(false, 8, false, false) X(false, 9, false, false)       \
+  X(false, 16, false, false)                                                                                    \
+  /* multi-hinge */                                                                                             \
+  X(true, 2, false, false) X(true, 11, false, false) X(true, 16, false, false)                                  \
+  /* general: reach / push task models and anisotropic inertia */                                               \
+  X(true, 4, true, false) X(true, 8, true, false) X(true, 16, true, false)                                      \
+  /* planar */                                                                                                  \
+  X(false, 4, false, true) X(false, 7, false, true) X(false, 8, false, true) X(false, 9, false, true)           \
+  X(false, 16, false, true)
+
+// An entry of a unit's table; Pol: the kernels' policy argument (carl::brax::BraxPolicy or a variant of it).
+template <class Pol>
+struct ClosedLoopKernel {
+  static_assert(sizeof(carl_batch_t) + sizeof(carl::brax::Prepared) + sizeof(carl_step_io_t) + sizeof(Pol) + 64 <= 4096,
+                "the closed-loop kernel's arguments do not fit the 4 KiB kernel-argument segment");
+  BraxClass c;
+  int k;
+  void (*kern)(carl_batch_t, const carl_brax_sys_t*, carl::brax::Prepared, carl_step_io_t, Pol, int);
+};
+
+// The kernels' policy argument, level by level.  BraxPolicy's fields, of it or a variant `Pol` of it: no summary.
+template <class Pol>
+Pol make_policy(const carl_policy_t* policy_host, float* obs) {
+  Pol pol{};
+  pol.p = *policy_host;
+  pol.set_floats = brax_policy_floats(policy_host);
+  pol.sum = carl_policy_summary_t{nullptr, nullptr, nullptr};
+  pol.cur_obs = obs;
+  return pol;
+}
+// BraxEpisodesPolicy's on top of them.
+template <class Pol>
+Pol make_episodes_policy(const carl_policy_t* policy_host, float* obs, const carl_policy_episodes_t* out, int32_t n_episodes) {
+  Pol pol = make_policy<Pol>(policy_host, obs);
+  pol.ep = *out;
+  pol.n_episodes = n_episodes;
+  return pol;
+}
+
 // The shape of a closed-loop launch of n_steps (episodes mode: max_steps) steps, and its kernel out of the unit's table
-// `tab` (entries with a class `c`, a width `k` and a kernel `kern`): one rule for both entry points, whose tables hold the
-// same (class, width) instances (tests/test_brax_episodes_abi.py), so carl_brax_policy_launch_shape answers for both.
+// `tab`: one rule for every entry point, whose tables hold the same (class, width) instances, so
+// carl_brax_policy_launch_shape answers for all of them.
 template <class Entry, size_t N>
 int policy_launch(const Entry (&tab)[N], const carl_batch_t* batch, const carl_brax_sys_t* sys_host, const BraxClass& c,
                   int n_steps, const char* who, BraxShape* shape, decltype(Entry::kern)* kern) {
@@ -114,6 +161,21 @@ int policy_launch(const Entry (&tab)[N], const carl_batch_t* batch, const carl_b
     if (int e = carl_host::ensure_dynamic_lds(reinterpret_cast<const void*>(*kern), shape->lds_bytes, who)) return e;
   }
   return 0;
+}
+
+// The launch of every closed-loop entry point: n_steps (episodes mode: max_steps) > 0 steps of a batch with lanes.
+// io_v all NULL: no per-step record (run()'s summary mode).
+template <class Pol, size_t N>
+int launch_closed_loop(const ClosedLoopKernel<Pol> (&tab)[N], const carl_batch_t* batch, const carl_brax_sys_t* sys_dev,
+                       const carl_brax_sys_t* sys_host, const BraxClass& c, int n_steps, const carl_step_io_t& io_v,
+                       const Pol& pol, void* stream, const char* who) {
+  BraxShape shape;
+  decltype(ClosedLoopKernel<Pol>::kern) kern = nullptr;
+  if (int e = policy_launch(tab, batch, sys_host, c, n_steps, who, &shape, &kern)) return e;
+  const carl::brax::Prepared prep = make_prepared(sys_host);
+  hipLaunchKernelGGL(kern, dim3(shape.grid), dim3(carl::brax::kLanes * shape.W), shape.lds_bytes, (hipStream_t)stream, *batch,
+                     sys_dev, prep, io_v, pol, n_steps);
+  return check_launch(who);
 }
 
 }  // namespace brax

@@ -90,9 +90,7 @@ int launch_brax(const carl_batch_t* b, const carl_brax_sys_t* sd, const carl_bra
   }
   carl_step_io_t io_v{};
   if (io != nullptr) io_v = *io;
-  carl::brax::Prepared prep{};  // topology + derived per-link constants, host-side (microseconds)
-  carl::brax::build_topo_host(*sh, prep.topo);
-  carl::brax::build_packed_host(*sh, prep.topo, prep.packed);
+  const carl::brax::Prepared prep = carl_host::brax::make_prepared(sh);
   hipLaunchKernelGGL(kern, dim3(grid), dim3(carl::brax::kLanes * W), sh_bytes, st, *b, sd, prep, io_v, mask, reset_obs,
                      n_steps);
   return check_launch(who);

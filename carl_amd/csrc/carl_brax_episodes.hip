@@ -1,9 +1,9 @@
 // carl_brax_episodes.hip -- C-ABI entry point of the episodes mode of the Brax closed-loop rollout (include/carl_amd.h:
-// carl_brax_evaluate_policy) and its kernel dispatch.  A translation unit of its own, as carl_brax_policy.hip is: the
+// carl_brax_evaluate_policy) and its kernel table.  A translation unit of its own, as carl_brax_policy.hip is: the
 // kernels are the Pol::kEpisodes variant of MODE 2 of brax_kernels.hip.h's run(), instantiated here and nowhere else, so
 // that every other unit -- carl_brax_policy.hip included -- compiles exactly as it did without them
-// (profiles/brax_episodes_isa_identity.txt).  The batch, model and policy checks and the launch rule are the closed-loop
-// rollout's (brax_launch.hpp, brax_policy_host.hpp).  Same flags as carl_brax_policy.hip (carl_amd/build.py).
+// (profiles/brax_episodes_isa_identity.txt).  The checks, the list of instances and the launch are the three closed-loop
+// units' (brax_launch.hpp, brax_policy_host.hpp).  Same flags as carl_brax_policy.hip (carl_amd/build.py).
 #include <hip/hip_runtime.h>
 
 #include <cstdint>
@@ -40,40 +40,13 @@ __global__ void __launch_bounds__(256) brax_episodes_empty_kernel(const carl_pol
 namespace {
 
 using carl_host::check_launch;
-using carl_host::fail;
 using carl_host::brax::BraxClass;
-using carl_host::brax::BraxShape;
 
-// Every instantiated brax_episodes_kernel<MULTI, K, TASK, PLANAR>: carl_brax_policy.hip's kBraxPolicyKernels, entry for
-// entry (tests/test_brax_episodes_abi.py holds the two tables together; carl_brax_policy_launch_shape answers for both).
-using brax_episodes_kern_t = void (*)(carl_batch_t, const carl_brax_sys_t*, carl::brax::Prepared, carl_step_io_t,
-                                      carl::brax::BraxEpisodesPolicy, int);
-struct BraxEpisodesKernel {
-  BraxClass c;
-  int k;
-  brax_episodes_kern_t kern;
-};
-#define CARL_BRAX_EPISODES(MULTI, K, TASK, PLANAR) \
-  {{MULTI, TASK, PLANAR, false}, K, carl::brax::brax_episodes_kernel<MULTI, K, TASK, PLANAR>}
-const BraxEpisodesKernel kBraxEpisodesKernels[] = {
-    // lean
-    CARL_BRAX_EPISODES(false, 4, false, false), CARL_BRAX_EPISODES(false, 7, false, false),
-    CARL_BRAX_EPISODES(false, 8, false, false), CARL_BRAX_EPISODES(false, 9, false, false),
-    CARL_BRAX_EPISODES(false, 16, false, false),
-    // multi-hinge
-    CARL_BRAX_EPISODES(true, 2, false, false), CARL_BRAX_EPISODES(true, 11, false, false),
-    CARL_BRAX_EPISODES(true, 16, false, false),
-    // general: reach / push task models and anisotropic inertia
-    CARL_BRAX_EPISODES(true, 4, true, false), CARL_BRAX_EPISODES(true, 8, true, false), CARL_BRAX_EPISODES(true, 16, true, false),
-    // planar
-    CARL_BRAX_EPISODES(false, 4, false, true), CARL_BRAX_EPISODES(false, 7, false, true),
-    CARL_BRAX_EPISODES(false, 8, false, true), CARL_BRAX_EPISODES(false, 9, false, true),
-    CARL_BRAX_EPISODES(false, 16, false, true),
-};
-#undef CARL_BRAX_EPISODES
-
-static_assert(sizeof(carl_batch_t) + sizeof(carl::brax::Prepared) + sizeof(carl_step_io_t) + sizeof(carl::brax::BraxEpisodesPolicy) + 64 <= 4096,
-              "the episodes kernel's arguments do not fit the 4 KiB kernel-argument segment");
+// Every instantiated brax_episodes_kernel<MULTI, K, TASK, PLANAR>.
+#define X(M, K, T, P) {{M, T, P, false}, K, carl::brax::brax_episodes_kernel<M, K, T, P>},
+const carl_host::brax::ClosedLoopKernel<carl::brax::BraxEpisodesPolicy> kBraxEpisodesKernels[] = {
+    CARL_BRAX_CLOSED_LOOP_INSTANCES(X)};
+#undef X
 
 }  // namespace
 
@@ -93,23 +66,10 @@ int carl_brax_evaluate_policy(const carl_batch_t* batch, const carl_brax_sys_t* 
     return check_launch(who);
   }
 
-  BraxShape shape;
-  brax_episodes_kern_t kern = nullptr;
-  if (int e = carl_host::brax::policy_launch(kBraxEpisodesKernels, batch, sys_host, c, max_steps, who, &shape, &kern)) return e;
-  carl::brax::BraxEpisodesPolicy pol{};
-  pol.p = *policy_host;
-  pol.set_floats = carl_host::brax::brax_policy_floats(policy_host);
-  pol.sum = carl_policy_summary_t{nullptr, nullptr, nullptr};
-  pol.cur_obs = obs;
-  pol.ep = *out;
-  pol.n_episodes = n_episodes;
-  carl::brax::Prepared prep{};
-  carl::brax::build_topo_host(*sys_host, prep.topo);
-  carl::brax::build_packed_host(*sys_host, prep.topo, prep.packed);
-  // (no per-step record: the all-NULL io is run()'s summary mode)
-  hipLaunchKernelGGL(kern, dim3(shape.grid), dim3(carl::brax::kLanes * shape.W), shape.lds_bytes, (hipStream_t)stream, *batch,
-                     sys_dev, prep, carl_step_io_t{}, pol, (int)max_steps);
-  return check_launch(who);
+  const carl::brax::BraxEpisodesPolicy pol =
+      carl_host::brax::make_episodes_policy<carl::brax::BraxEpisodesPolicy>(policy_host, obs, out, n_episodes);
+  return carl_host::brax::launch_closed_loop(kBraxEpisodesKernels, batch, sys_dev, sys_host, c, max_steps, carl_step_io_t{}, pol,
+                                             stream, who);
 }
 
 }  // extern "C"

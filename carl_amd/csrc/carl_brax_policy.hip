@@ -1,10 +1,10 @@
 // carl_brax_policy.hip -- C-ABI entry points of the closed-loop rollout of the Brax families (include/carl_amd.h:
-// carl_brax_rollout_policy) and their kernel dispatch.  A translation unit of its own: the kernels are MODE 2 of
+// carl_brax_rollout_policy) and their kernel table.  A translation unit of its own: the kernels are MODE 2 of
 // brax_kernels.hip.h's run(), instantiated here and nowhere else, so that the reset / step / rollout kernels of
 // carl_brax.hip compile exactly as they did without them (profiles/brax_policy_isa_identity.txt).  The batch, model and io
 // checks and the launch-shape rule are carl_brax.hip's (brax_launch.hpp); the network's shape rules are the classic
-// closed-loop rollout's (policy_host.hpp); the policy's checks and the launch rule are shared with the episodes mode's unit
-// (brax_policy_host.hpp; carl_brax_episodes.hip).  Same flags as carl_brax.hip (carl_amd/build.py).
+// closed-loop rollout's (policy_host.hpp); the policy's checks, the list of instances and the launch are the three
+// closed-loop units' (brax_policy_host.hpp).  Same flags as carl_brax.hip (carl_amd/build.py).
 #include <hip/hip_runtime.h>
 
 #include <cstdint>
@@ -18,43 +18,16 @@
 
 namespace {
 
-using carl_host::check_launch;
 using carl_host::fail;
 using carl_host::brax::BraxClass;
 using carl_host::brax::BraxShape;
 using carl_host::brax::brax_policy_floats;
 using carl_host::brax::policy_class;
 
-// Every instantiated brax_policy_kernel<MULTI, K, TASK, PLANAR>: the non-F32 step classes of carl_brax.hip's kBraxKernels,
-// at the widths it has for them (tests/test_brax_policy_abi.py holds the two tables together).
-using brax_policy_kern_t = void (*)(carl_batch_t, const carl_brax_sys_t*, carl::brax::Prepared, carl_step_io_t,
-                                    carl::brax::BraxPolicy, int);
-struct BraxPolicyKernel {
-  BraxClass c;
-  int k;
-  brax_policy_kern_t kern;
-};
-#define CARL_BRAX_POLICY(MULTI, K, TASK, PLANAR) \
-  {{MULTI, TASK, PLANAR, false}, K, carl::brax::brax_policy_kernel<MULTI, K, TASK, PLANAR>}
-const BraxPolicyKernel kBraxPolicyKernels[] = {
-    // lean
-    CARL_BRAX_POLICY(false, 4, false, false), CARL_BRAX_POLICY(false, 7, false, false),
-    CARL_BRAX_POLICY(false, 8, false, false), CARL_BRAX_POLICY(false, 9, false, false),
-    CARL_BRAX_POLICY(false, 16, false, false),
-    // multi-hinge
-    CARL_BRAX_POLICY(true, 2, false, false), CARL_BRAX_POLICY(true, 11, false, false),
-    CARL_BRAX_POLICY(true, 16, false, false),
-    // general: reach / push task models and anisotropic inertia
-    CARL_BRAX_POLICY(true, 4, true, false), CARL_BRAX_POLICY(true, 8, true, false), CARL_BRAX_POLICY(true, 16, true, false),
-    // planar
-    CARL_BRAX_POLICY(false, 4, false, true), CARL_BRAX_POLICY(false, 7, false, true),
-    CARL_BRAX_POLICY(false, 8, false, true), CARL_BRAX_POLICY(false, 9, false, true),
-    CARL_BRAX_POLICY(false, 16, false, true),
-};
-#undef CARL_BRAX_POLICY
-
-static_assert(sizeof(carl_batch_t) + sizeof(carl::brax::Prepared) + sizeof(carl_step_io_t) + sizeof(carl::brax::BraxPolicy) + 64 <= 4096,
-              "the closed-loop kernel's arguments do not fit the 4 KiB kernel-argument segment");
+// Every instantiated brax_policy_kernel<MULTI, K, TASK, PLANAR>.
+#define X(M, K, T, P) {{M, T, P, false}, K, carl::brax::brax_policy_kernel<M, K, T, P>},
+const carl_host::brax::ClosedLoopKernel<carl::brax::BraxPolicy> kBraxPolicyKernels[] = {CARL_BRAX_CLOSED_LOOP_INSTANCES(X)};
+#undef X
 
 bool summary_complete(const carl_policy_summary_t* s) { return s->episodes && s->return_sum && s->length_sum; }
 
@@ -103,19 +76,11 @@ int carl_brax_rollout_policy(const carl_batch_t* batch, const carl_brax_sys_t* s
                 "reports done on every later step, and its episode would be counted on each of them)", who);
   if (batch->n_lanes == 0 || n_steps == 0) return carl_host::policy_rollout_without_steps(who, batch, summary_out, stream);
 
-  BraxShape shape;
-  brax_policy_kern_t kern = nullptr;
-  if (int e = carl_host::brax::policy_launch(kBraxPolicyKernels, batch, sys_host, c, n_steps, who, &shape, &kern)) return e;
   carl_step_io_t io_v{};
   if (io != nullptr) io_v = *io;
-  carl::brax::BraxPolicy pol{*policy_host, brax_policy_floats(policy_host), carl_policy_summary_t{nullptr, nullptr, nullptr}, obs};
+  carl::brax::BraxPolicy pol = carl_host::brax::make_policy<carl::brax::BraxPolicy>(policy_host, obs);
   if (summary_out != nullptr) pol.sum = *summary_out;
-  carl::brax::Prepared prep{};
-  carl::brax::build_topo_host(*sys_host, prep.topo);
-  carl::brax::build_packed_host(*sys_host, prep.topo, prep.packed);
-  hipLaunchKernelGGL(kern, dim3(shape.grid), dim3(carl::brax::kLanes * shape.W), shape.lds_bytes, (hipStream_t)stream, *batch,
-                     sys_dev, prep, io_v, pol, (int)n_steps);
-  return check_launch(who);
+  return carl_host::brax::launch_closed_loop(kBraxPolicyKernels, batch, sys_dev, sys_host, c, n_steps, io_v, pol, stream, who);
 }
 
 }  // extern "C"

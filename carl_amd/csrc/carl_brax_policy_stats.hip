@@ -1,11 +1,11 @@
 // carl_brax_policy_stats.hip -- C-ABI entry points of the input statistics of the Brax closed-loop rollout
-// (include/carl_amd.h: carl_brax_evaluate_policy_stats, carl_brax_policy_stats_slabs) and their kernel dispatch.  A
+// (include/carl_amd.h: carl_brax_evaluate_policy_stats, carl_brax_policy_stats_slabs) and their kernel table.  A
 // translation unit of its own, as carl_brax_episodes.hip is: the kernels are the Pol::kStats variant of the episodes mode
 // of brax_kernels.hip.h's run(), instantiated here and nowhere else, so that every other unit -- carl_brax_episodes.hip
-// included -- compiles exactly as it did without them (profiles/brax_stats_isa_identity.txt).  The checks and the launch
-// rule are the episodes entry point's (brax_launch.hpp, brax_policy_host.hpp), the check of the statistics output is
-// carl_evaluate_policy_stats' (policy_host.hpp); the merge, carl_brax_policy_stats_merge, sits beside the kernel it calls
-// in carl_policy_stats.hip.  Same flags as carl_brax_episodes.hip (carl_amd/build.py).
+// included -- compiles exactly as it did without them (profiles/brax_stats_isa_identity.txt).  The checks, the list of
+// instances and the launch are the three closed-loop units' (brax_launch.hpp, brax_policy_host.hpp), the check of the
+// statistics output is carl_evaluate_policy_stats' (policy_host.hpp); the merge, carl_brax_policy_stats_merge, sits beside
+// the kernel it calls in carl_policy_stats.hip.  Same flags as carl_brax_episodes.hip (carl_amd/build.py).
 #include <hip/hip_runtime.h>
 
 #include <cstdint>
@@ -22,41 +22,15 @@ using carl_host::check_launch;
 using carl_host::brax::BraxClass;
 using carl_host::brax::BraxShape;
 
-// Every instantiated brax_episodes_stats_kernel<MULTI, K, TASK, PLANAR>: carl_brax_episodes.hip's kBraxEpisodesKernels,
-// entry for entry (tests/test_brax_stats_abi.py holds the tables together).
-using brax_stats_kern_t = void (*)(carl_batch_t, const carl_brax_sys_t*, carl::brax::Prepared, carl_step_io_t,
-                                   carl::brax::BraxStatsPolicy, int);
-struct BraxStatsKernel {
-  BraxClass c;
-  int k;
-  brax_stats_kern_t kern;
-};
-#define CARL_BRAX_STATS(MULTI, K, TASK, PLANAR) \
-  {{MULTI, TASK, PLANAR, false}, K, carl::brax::brax_episodes_stats_kernel<MULTI, K, TASK, PLANAR>}
-const BraxStatsKernel kBraxStatsKernels[] = {
-    // lean
-    CARL_BRAX_STATS(false, 4, false, false), CARL_BRAX_STATS(false, 7, false, false),
-    CARL_BRAX_STATS(false, 8, false, false), CARL_BRAX_STATS(false, 9, false, false),
-    CARL_BRAX_STATS(false, 16, false, false),
-    // multi-hinge
-    CARL_BRAX_STATS(true, 2, false, false), CARL_BRAX_STATS(true, 11, false, false),
-    CARL_BRAX_STATS(true, 16, false, false),
-    // general: reach / push task models and anisotropic inertia
-    CARL_BRAX_STATS(true, 4, true, false), CARL_BRAX_STATS(true, 8, true, false), CARL_BRAX_STATS(true, 16, true, false),
-    // planar
-    CARL_BRAX_STATS(false, 4, false, true), CARL_BRAX_STATS(false, 7, false, true),
-    CARL_BRAX_STATS(false, 8, false, true), CARL_BRAX_STATS(false, 9, false, true),
-    CARL_BRAX_STATS(false, 16, false, true),
-};
-#undef CARL_BRAX_STATS
-
-static_assert(sizeof(carl_batch_t) + sizeof(carl::brax::Prepared) + sizeof(carl_step_io_t) + sizeof(carl::brax::BraxStatsPolicy) + 64 <= 4096,
-              "the statistics kernel's arguments do not fit the 4 KiB kernel-argument segment");
+// Every instantiated brax_episodes_stats_kernel<MULTI, K, TASK, PLANAR>.
+#define X(M, K, T, P) {{M, T, P, false}, K, carl::brax::brax_episodes_stats_kernel<M, K, T, P>},
+const carl_host::brax::ClosedLoopKernel<carl::brax::BraxStatsPolicy> kBraxStatsKernels[] = {CARL_BRAX_CLOSED_LOOP_INSTANCES(X)};
+#undef X
 
 // the launch shape of max_steps steps; a launch of no step has the slabs of a launch of one
 int stats_shape(const char* who, const carl_batch_t* batch, const carl_brax_sys_t* sys_host, const BraxClass& c, int max_steps,
-                BraxShape* shape, brax_stats_kern_t* kern) {
-  return carl_host::brax::policy_launch(kBraxStatsKernels, batch, sys_host, c, max_steps > 0 ? max_steps : 1, who, shape, kern);
+                BraxShape* shape) {
+  return carl_host::brax::policy_launch(kBraxStatsKernels, batch, sys_host, c, max_steps > 0 ? max_steps : 1, who, shape, nullptr);
 }
 
 }  // namespace
@@ -71,7 +45,7 @@ int32_t carl_brax_policy_stats_slabs(const carl_batch_t* batch, const carl_brax_
   if (batch->n_lanes <= 0) return 0;
   BraxShape shape;
   if (stats_shape("carl_brax_policy_stats_slabs", batch, sys_host, carl_host::brax::brax_class(sys_host, batch->flags, true),
-                  max_steps, &shape, nullptr))
+                  max_steps, &shape))
     return -1;
   return shape.grid * shape.W;
 }
@@ -86,7 +60,7 @@ int carl_brax_evaluate_policy_stats(const carl_batch_t* batch, const carl_brax_s
   // (the shape alone first: the refusals below come before anything touches the device, the kernel's LDS limit included)
   BraxShape shape{};
   if (batch->n_lanes > 0)
-    if (int e = stats_shape(who, batch, sys_host, c, max_steps, &shape, nullptr)) return e;
+    if (int e = stats_shape(who, batch, sys_host, c, max_steps, &shape)) return e;
   const int n_slabs = shape.grid * shape.W;
   if (int e = carl_host::check_policy_stats(who, stats, n_slabs, "slabs (carl_brax_policy_stats_slabs)")) return e;
   if (batch->n_lanes == 0) return 0;
@@ -99,23 +73,11 @@ int carl_brax_evaluate_policy_stats(const carl_batch_t* batch, const carl_brax_s
     return check_launch(who);
   }
 
-  brax_stats_kern_t kern = nullptr;
-  if (int e = stats_shape(who, batch, sys_host, c, max_steps, &shape, &kern)) return e;
-  carl::brax::BraxStatsPolicy pol{};
-  pol.p = *policy_host;
-  pol.set_floats = carl_host::brax::brax_policy_floats(policy_host);
-  pol.sum = carl_policy_summary_t{nullptr, nullptr, nullptr};
-  pol.cur_obs = obs;
-  pol.ep = *out;
-  pol.n_episodes = n_episodes;
+  carl::brax::BraxStatsPolicy pol =
+      carl_host::brax::make_episodes_policy<carl::brax::BraxStatsPolicy>(policy_host, obs, out, n_episodes);
   pol.partial = stats->partial;
-  carl::brax::Prepared prep{};
-  carl::brax::build_topo_host(*sys_host, prep.topo);
-  carl::brax::build_packed_host(*sys_host, prep.topo, prep.packed);
-  // (no per-step record: the all-NULL io is run()'s summary mode)
-  hipLaunchKernelGGL(kern, dim3(shape.grid), dim3(carl::brax::kLanes * shape.W), shape.lds_bytes, (hipStream_t)stream, *batch,
-                     sys_dev, prep, carl_step_io_t{}, pol, (int)max_steps);
-  return check_launch(who);
+  return carl_host::brax::launch_closed_loop(kBraxStatsKernels, batch, sys_dev, sys_host, c, max_steps, carl_step_io_t{}, pol,
+                                             stream, who);
 }
 
 }  // extern "C"

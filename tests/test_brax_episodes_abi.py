@@ -1,63 +1,31 @@
 """Host side of the episodes mode of the Brax closed-loop rollout (include/carl_amd.h: carl_brax_evaluate_policy):
 everything that runs before a HIP call.  The entry point's refusals by their messages (fake device pointers: nothing is
-enqueued), its kernel table against carl_brax_policy.hip's entry for entry, BraxMLPPolicy.unpack against the packing, and
-the Python refusals of BraxVecEngine.evaluate_episodes and of EvolutionStrategy with a Brax template on fake engines."""
+enqueued), BraxMLPPolicy.unpack against the packing, and the Python refusals of BraxVecEngine.evaluate_episodes and of
+EvolutionStrategy with a Brax template on fake engines.  (Its kernel table: test_brax_policy_abi.py, with the other two.)"""
 import ctypes as C
-import os
-import re
+import functools
 
 import numpy as np
 import pytest
 import torch
 
+import brax_policy_abi_util as U
 import brax_policy_cases as BP
+from brax_policy_abi_util import (ant_policy as _ant_policy, batch as _batch, episodes_out as _out,
+                                  fake_brax_engine as _fake_brax_engine, info as _info, policy as _policy)
 from carl_amd import _lib
 from carl_amd import es as ES
-from carl_amd.brax_engine import _BRAX_FAMILY, BraxVecEngine, _BraxInfo
 from carl_amd.brax_policy import BraxMLPPolicy
 from carl_amd.policy import MLPPolicy
-from policy_cases import c_batch, fake_engine, rand_layers
+from policy_cases import fake_engine, rand_layers
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-WHO = b"carl_brax_evaluate_policy: "
-
-
-def _batch(n=1000, **kw):
-    kw.setdefault("n_ctx_obs", 2)
-    kw.setdefault("ctx_obs_feat", (0, 1))
-    kw.setdefault("flags", _lib.FLAG_AUTORESET)
-    return c_batch(family=_BRAX_FAMILY, n=n, **kw)
-
-
-def _policy(s, **kw):
-    """a valid carl_policy_t for _batch() and model `s` (2 context inputs, 2 x 64 tanh), kw: the fields to spoil"""
-    p = _lib.Policy()
-    p.n_ctx, p.n_hidden, p.n_out = 2, 2, s.n_act
-    p.n_in = 2 + s.obs_dim
-    p.ctx_rows[0], p.ctx_rows[1] = 0, 1
-    p.width[0], p.width[1] = 64, 64
-    p.activation, p.head, p.n_sets, p.lanes_per_set, p.params = _lib.POLICY_TANH, _lib.POLICY_HEAD_BOX, 1, 1024, 0x2000
-    for k, v in kw.items():
-        setattr(p, k, v)
-    return p
-
-
-def _out(**kw):
-    out = _lib.PolicyEpisodes(0x3000, 0x3000, 0x3000, 0x3000, 0x3000, 0x3000)
-    for k, v in kw.items():
-        setattr(out, k, v)
-    return out
+_refused = functools.partial(U.refused, b"carl_brax_evaluate_policy: ")
 
 
 def _call(b, s, p, out="all", n_episodes=2, max_steps=10, obs=0x5000):
     out = _out() if out == "all" else out
     return _lib.load().carl_brax_evaluate_policy(C.byref(b), 0x4000, C.byref(s), obs, C.byref(p), n_episodes, max_steps,
                                                  None if out is None else C.byref(out), None)
-
-
-def _refused(code, msg, want=_lib.ERR_INVALID_ARGUMENT):
-    err = _lib.load().carl_last_error()
-    assert code == want and err == WHO + msg, (code, err)
 
 
 def test_refusals_by_their_messages():
@@ -99,31 +67,6 @@ def test_refusals_by_their_messages():
     assert _call(_batch(n=0), ant, _policy(ant), max_steps=0) == 0
 
 
-def _entries(path, table, macro):
-    with open(os.path.join(ROOT, "carl_amd", "csrc", path)) as f:
-        src = f.read()
-    body = re.search(r"const \w+ " + table + r"\[\] = \{(.*?)\n\};", src, re.S).group(1)
-    return re.findall(macro + r"\((\w+), (\d+), (\w+), (\w+)\)", re.sub(r"//[^\n]*", "", body))
-
-
-def test_kernel_table_is_the_closed_loop_table_entry_for_entry():
-    """carl_brax_episodes.hip instantiates one episodes kernel per closed-loop kernel, in the same order: the launch-shape
-    rule picks a width out of either table, and carl_brax_policy_launch_shape answers for both entry points"""
-    want = _entries("carl_brax_policy.hip", "kBraxPolicyKernels", "CARL_BRAX_POLICY")
-    got = _entries("carl_brax_episodes.hip", "kBraxEpisodesKernels", "CARL_BRAX_EPISODES")
-    assert got == want and len(got) == 16 and len(set(got)) == 16
-    with open(os.path.join(ROOT, "carl_amd", "csrc", "carl_brax_policy.hip")) as f:
-        src = f.read()  # the closed-loop unit instantiates nothing of the episodes mode
-        assert "brax_episodes_kernel" not in src and "BraxEpisodesPolicy" not in src
-    from carl_amd.build import SOURCES
-
-    assert SOURCES["carl_brax_episodes.hip"] == SOURCES["carl_brax_policy.hip"]
-
-
-def _info(obs_dim, n_act, n_features=8):
-    return _BraxInfo(0, obs_dim, n_features, n_act, 0, 0, 1000, -1.0, 1.0)
-
-
 @pytest.mark.parametrize("widths,act", BP.NETWORKS)
 def test_unpack_is_the_inverse_of_the_packing(widths, act):
     rng = np.random.default_rng(5)
@@ -155,17 +98,6 @@ def test_unpack_is_the_inverse_of_the_packing(widths, act):
         BraxMLPPolicy.unpack(tmpl, packed, log_std=-0.5)
     with pytest.raises(TypeError, match="not a BraxMLPPolicy"):
         BraxMLPPolicy.unpack(MLPPolicy(_lib.PENDULUM, 3, rows, BP.make_layers(rng, 5, widths, 1), act), packed)
-
-
-def _fake_brax_engine(auto_reset=True, n=1024):
-    eng = object.__new__(BraxVecEngine)
-    eng.b = _lib.Batch()  # (auto_reset is a flag of the batch)
-    eng.D, eng.sys, eng.n, eng.auto_reset, eng.device = 27, BP.build_model("ant")[0], n, auto_reset, torch.device("cpu")
-    return eng
-
-
-def _ant_policy(rng, widths=(8,)):
-    return BraxMLPPolicy(_info(27, 8), [], BP.make_layers(rng, 27, widths, 8), "relu")
 
 
 def test_python_refusals_of_evaluate_episodes_before_any_launch():

@@ -1,44 +1,25 @@
 """Host side of the Brax closed-loop rollout (include/carl_amd.h: carl_brax_rollout_policy): everything that runs before
 a HIP call.  Refusals by their messages, BraxMLPPolicy's packing against MLPPolicy's and against the layout written out
-by hand, the launch-shape query, the closed-loop kernel table against carl_brax.hip's, and that the shape rule it shares
-with reset / step / rollout (brax_launch.hpp) still answers for those what it did: OPEN_SHAPES holds what
+by hand, the launch-shape query, the one list of closed-loop kernel instances (brax_policy_host.hpp) against
+carl_brax.hip's table and against the three units that expand it, and that the shape rule it shares with reset / step /
+rollout (brax_launch.hpp) still answers for those what it did: OPEN_SHAPES holds what
 carl_brax_launch_shape must report for them, recorded from the launches of the commit before the rule moved."""
 import ctypes as C
-import os
+import functools
 import re
 
 import numpy as np
 import pytest
 
+import brax_policy_abi_util as U
 import brax_policy_cases as BP
+from brax_policy_abi_util import batch as _batch, info as _info, policy as _policy
 from carl_amd import _lib
-from carl_amd.brax_engine import _BRAX_FAMILY, _BraxInfo
 from carl_amd.brax_policy import BraxMLPPolicy
 from carl_amd.policy import MLPPolicy
-from policy_cases import c_batch, fake_engine, rand_layers
+from policy_cases import fake_engine, rand_layers
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-WHO = b"carl_brax_rollout_policy: "
-
-
-def _batch(n=1000, **kw):
-    kw.setdefault("n_ctx_obs", 2)
-    kw.setdefault("ctx_obs_feat", (0, 1))
-    kw.setdefault("flags", _lib.FLAG_AUTORESET)
-    return c_batch(family=_BRAX_FAMILY, n=n, **kw)
-
-
-def _policy(s, **kw):
-    """a valid carl_policy_t for _batch() and model `s` (2 context inputs, 2 x 64 tanh), kw: the fields to spoil"""
-    p = _lib.Policy()
-    p.n_ctx, p.n_hidden, p.n_out = 2, 2, s.n_act
-    p.n_in = 2 + s.obs_dim
-    p.ctx_rows[0], p.ctx_rows[1] = 0, 1
-    p.width[0], p.width[1] = 64, 64
-    p.activation, p.head, p.n_sets, p.lanes_per_set, p.params = _lib.POLICY_TANH, _lib.POLICY_HEAD_BOX, 1, 1024, 0x2000
-    for k, v in kw.items():
-        setattr(p, k, v)
-    return p
+_refused = functools.partial(U.refused, b"carl_brax_rollout_policy: ", want=None)
 
 
 def _io():
@@ -53,11 +34,6 @@ def _call(b, s, p, io=None, summary=True, n_steps=10):
     return _lib.load().carl_brax_rollout_policy(C.byref(b), 0x4000, C.byref(s), 0x5000, C.byref(p),
                                                 None if io is None else C.byref(io), n_steps,
                                                 C.byref(summ) if summary else None, None)
-
-
-def _refused(code, msg):
-    err = _lib.load().carl_last_error()
-    assert code != 0 and err == WHO + msg, (code, err)
 
 
 def test_refusals_by_their_messages():
@@ -127,10 +103,6 @@ def test_the_pinned_refusals_of_the_classic_entry_points_stay():
         BraxMLPPolicy.for_env(fake_engine(_lib.CARTPOLE, [0, 3]), rand_layers(rng, [6, 2]))
 
 
-def _info(obs_dim, n_act, n_features=8):
-    return _BraxInfo(0, obs_dim, n_features, n_act, 0, 0, 1000, -1.0, 1.0)
-
-
 @pytest.mark.parametrize("widths,act", BP.NETWORKS)
 def test_packs_the_bytes_mlp_policy_packs(widths, act):
     """for a shape both classes take -- Pendulum's: 3 observations, one Box output -- the same packed block, struct
@@ -170,26 +142,58 @@ def test_packs_the_bytes_mlp_policy_packs(widths, act):
         BraxMLPPolicy(_info(244, 17), rows, BP.make_layers(rng, 246, widths, 17), act)
 
 
-def _entries(path, table, pattern):
-    with open(os.path.join(ROOT, "carl_amd", "csrc", path)) as f:
-        src = f.read()
-    body = re.search(r"const \w+ " + table + r"\[\] = \{(.*?)\n\};", src, re.S).group(1)
-    return re.findall(pattern, re.sub(r"//[^\n]*", "", body))
+def _open_loop_entries(pattern):
+    body = re.search(r"const \w+ kBraxKernels\[\] = \{(.*?)\n\};", U.source("carl_brax.hip", comments=False), re.S).group(1)
+    return re.findall(pattern, body)
+
+
+def _instance_list():
+    """the (MULTI, K, TASK, PLANAR) of CARL_BRAX_CLOSED_LOOP_INSTANCES in its order, read off brax_policy_host.hpp"""
+    body = re.search(r"#define CARL_BRAX_CLOSED_LOOP_INSTANCES\(X\)((?:[^\n]*\\\n)+[^\n]*)", U.source("brax_policy_host.hpp"))
+    return re.findall(r"X\((\w+), (\d+), (\w+), (\w+)\)", body.group(1))
 
 
 def test_kernel_table_is_the_float64_step_classes_of_the_open_loop_table():
-    """carl_brax_policy.hip instantiates the non-F32 step classes of carl_brax.hip's kBraxKernels at the same widths, and
-    the models of the GPU test reach every one of them"""
+    """the one list of closed-loop instances holds 16 distinct ones: the non-F32 step classes of carl_brax.hip's
+    kBraxKernels at the same widths, and the models of the GPU test reach every one of them"""
     b = lambda v: v == "true"  # noqa: E731
-    want = {(b(m), b(t), False, int(k)) for m, k, t in _entries("carl_brax.hip", "kBraxKernels",
-                                                                  r"CARL_BRAX\((\w+), (\d+), (\w+)\)")}
-    want |= {(b(m), False, b(p), int(k)) for m, k, p, f in _entries("carl_brax.hip", "kBraxKernels",
-                                                                     r"CARL_BRAX_STEP\((\w+), (\d+), (\w+), (\w+)\)") if not b(f)}
-    got = {(b(m), b(t), b(p), int(k)) for m, k, t, p in _entries("carl_brax_policy.hip", "kBraxPolicyKernels",
-                                                                 r"CARL_BRAX_POLICY\((\w+), (\d+), (\w+), (\w+)\)")}
+    want = {(b(m), b(t), False, int(k)) for m, k, t in _open_loop_entries(r"CARL_BRAX\((\w+), (\d+), (\w+)\)")}
+    want |= {(b(m), False, b(p), int(k)) for m, k, p, f in _open_loop_entries(r"CARL_BRAX_STEP\((\w+), (\d+), (\w+), (\w+)\)")
+             if not b(f)}
+    listed = _instance_list()
+    assert len(listed) == 16 and len(set(listed)) == 16
+    got = {(b(m), b(t), b(p), int(k)) for m, k, t, p in listed}
     assert got == want and len(got) == 16
     reached = {(*BP.MODELS[m], w) for m, w in BP.instance_cases()}
     assert reached == got
+
+
+UNITS = {"carl_brax_policy.hip": "brax_policy_kernel", "carl_brax_episodes.hip": "brax_episodes_kernel",
+         "carl_brax_policy_stats.hip": "brax_episodes_stats_kernel"}
+
+
+def test_each_unit_expands_the_instance_list_once_with_its_own_kernel():
+    """every unit's table is one expansion of the list, entry by entry its own kernel template at the entry's parameters
+    (so the three tables hold the same instances in the same order: the launch-shape rule picks a width out of any of
+    them, and carl_brax_policy_launch_shape answers for all three entry points); nothing else in a unit instantiates a
+    closed-loop kernel or writes an instance out, and no unit names anything of the variants stacked on it"""
+    for unit, kernel in UNITS.items():
+        src = U.source(unit, comments=False)
+        table = re.search(r"#define X\(M, K, T, P\) \{\{M, T, P, false\}, K, carl::brax::(\w+)<M, K, T, P>\},\n"
+                          r"const [\w:<>]+ \w+\[\] = \{\s*CARL_BRAX_CLOSED_LOOP_INSTANCES\(X\)\};\n#undef X\n", src)
+        assert table is not None and table.group(1) == kernel, unit
+        rest = src.replace(table.group(0), "")
+        assert "CARL_BRAX_CLOSED_LOOP_INSTANCES" not in rest, unit
+        assert not re.search(r"brax_(policy|episodes|episodes_stats)_kernel\s*<", rest), unit
+        assert not re.search(r"\((true|false), \d+, (true|false), (true|false)\)", rest), unit
+    src = U.source("carl_brax_policy.hip")  # the closed-loop unit instantiates nothing of the episodes mode
+    assert "brax_episodes_kernel" not in src and "BraxEpisodesPolicy" not in src
+    for unit in ("carl_brax_episodes.hip", "carl_brax_policy.hip", "carl_brax.hip"):
+        src = U.source(unit)  # the other Brax units instantiate nothing of the statistics variant
+        assert "brax_episodes_stats_kernel" not in src and "BraxStatsPolicy" not in src
+    from carl_amd.build import SOURCES
+
+    assert SOURCES["carl_brax_policy_stats.hip"] == SOURCES["carl_brax_episodes.hip"] == SOURCES["carl_brax_policy.hip"]
 
 
 # (model, n_lanes, pinned width or 0, n_steps) -> (grid, wavefronts per workgroup, lanes per env); 256 compute units

@@ -1,55 +1,28 @@
 """Host side of the input statistics of the Brax closed-loop rollout (include/carl_amd.h: carl_brax_evaluate_policy_stats,
 carl_brax_policy_stats_slabs, carl_brax_policy_stats_merge): everything that runs before a HIP call.  The refusals of both
 new entry points by their messages (fake device pointers: nothing is enqueued), the slab count against
-carl_brax_policy_launch_shape, the kernel table against the episodes table entry for entry, InputStats' offsets with an Ant
-template, and the keyword rules of EvolutionStrategy on fake engines."""
+carl_brax_policy_launch_shape, InputStats' offsets with an Ant template, and the keyword rules of EvolutionStrategy on fake
+engines.  (The kernel table: test_brax_policy_abi.py, with the other two.)"""
 import ctypes as C
-import os
-import re
+import functools
 
 import numpy as np
 import pytest
 import torch
 
+import brax_policy_abi_util as U
 import brax_policy_cases as BP
 import stats_ref as SR
+from brax_policy_abi_util import (ant_policy as _ant_policy, batch as _batch, episodes_out as _out,
+                                  fake_brax_engine as _fake_brax_engine, policy as _policy)
 from carl_amd import _lib
 from carl_amd import es as ES
-from carl_amd.brax_engine import _BRAX_FAMILY, BraxVecEngine, _BraxInfo
 from carl_amd.brax_policy import BraxMLPPolicy
 from carl_amd.policy import InputStats, MLPPolicy
-from policy_cases import c_batch, fake_engine, rand_layers
+from policy_cases import fake_engine, rand_layers
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-WHO = b"carl_brax_evaluate_policy_stats: "
+_refused = functools.partial(U.refused, b"carl_brax_evaluate_policy_stats: ")
 PTR = 0x6000
-
-
-def _batch(n=1000, **kw):
-    kw.setdefault("n_ctx_obs", 2)
-    kw.setdefault("ctx_obs_feat", (0, 1))
-    kw.setdefault("flags", _lib.FLAG_AUTORESET)
-    return c_batch(family=_BRAX_FAMILY, n=n, **kw)
-
-
-def _policy(s, **kw):
-    """a valid carl_policy_t for _batch() and model `s` (2 context inputs, 2 x 64 tanh), kw: the fields to spoil"""
-    p = _lib.Policy()
-    p.n_ctx, p.n_hidden, p.n_out = 2, 2, s.n_act
-    p.n_in = 2 + s.obs_dim
-    p.ctx_rows[0], p.ctx_rows[1] = 0, 1
-    p.width[0], p.width[1] = 64, 64
-    p.activation, p.head, p.n_sets, p.lanes_per_set, p.params = _lib.POLICY_TANH, _lib.POLICY_HEAD_BOX, 1, 1024, 0x2000
-    for k, v in kw.items():
-        setattr(p, k, v)
-    return p
-
-
-def _out(**kw):
-    out = _lib.PolicyEpisodes(0x3000, 0x3000, 0x3000, 0x3000, 0x3000, 0x3000)
-    for k, v in kw.items():
-        setattr(out, k, v)
-    return out
 
 
 def _slabs(b, s, p, max_steps=10):
@@ -63,11 +36,6 @@ def _call(b, s, p, out="all", n_episodes=2, max_steps=10, obs=0x5000, stats="eno
     return _lib.load().carl_brax_evaluate_policy_stats(
         C.byref(b), 0x4000, C.byref(s), obs, C.byref(p), n_episodes, max_steps, None if out is None else C.byref(out),
         None if stats is None else C.byref(stats), None)
-
-
-def _refused(code, msg, want=_lib.ERR_INVALID_ARGUMENT):
-    err = _lib.load().carl_last_error()
-    assert code == want and err == WHO + msg, (code, err)
 
 
 def test_evaluate_stats_refusals_by_their_messages():
@@ -197,39 +165,11 @@ def test_the_classic_merge_keeps_refusing_a_brax_shape():
     assert _lib.load().carl_last_error() == b"carl_brax_policy_stats_merge: params is NULL"
 
 
-def _entries(path, table, macro):
-    with open(os.path.join(ROOT, "carl_amd", "csrc", path)) as f:
-        src = f.read()
-    body = re.search(r"const \w+ " + table + r"\[\] = \{(.*?)\n\};", src, re.S).group(1)
-    return re.findall(macro + r"\((\w+), (\d+), (\w+), (\w+)\)", re.sub(r"//[^\n]*", "", body))
-
-
-def test_kernel_table_is_the_episodes_table_entry_for_entry():
-    want = _entries("carl_brax_episodes.hip", "kBraxEpisodesKernels", "CARL_BRAX_EPISODES")
-    got = _entries("carl_brax_policy_stats.hip", "kBraxStatsKernels", "CARL_BRAX_STATS")
-    assert got == want and len(got) == 16 and len(set(got)) == 16
-    for unit in ("carl_brax_episodes.hip", "carl_brax_policy.hip", "carl_brax.hip"):
-        with open(os.path.join(ROOT, "carl_amd", "csrc", unit)) as f:
-            src = f.read()  # the other Brax units instantiate nothing of the statistics variant
-            assert "brax_episodes_stats_kernel" not in src and "BraxStatsPolicy" not in src
-    from carl_amd.build import SOURCES
-
-    assert SOURCES["carl_brax_policy_stats.hip"] == SOURCES["carl_brax_episodes.hip"]
-
-
-def _info(obs_dim, n_act, n_features=8):
-    return _BraxInfo(0, obs_dim, n_features, n_act, 0, 0, 1000, -1.0, 1.0)
-
-
-def _ant_policy(rng, widths=(8,), rows=(0, 3)):
-    return BraxMLPPolicy(_info(27, 8), list(rows), BP.make_layers(rng, 27 + len(rows), widths, 8), "relu")
-
-
 @pytest.mark.parametrize("widths", [(64, 64), (32,), ()])
 def test_input_stats_with_an_ant_template(widths):
     """29 inputs, 8 outputs: the offsets the merge writes at are the packing's, and the Brax entry point is the one called"""
     rng = np.random.default_rng(7)
-    tmpl = _ant_policy(rng, widths)
+    tmpl = _ant_policy(rng, widths, rows=(0, 3))
     assert (tmpl.n_in, tmpl.n_out) == (29, 8)
     p_shift, p_scale, p_clip, S = SR.transform_offsets(29, widths, 8)
     assert (tmpl.weight_floats, tmpl.set_floats) == (p_shift, S)
@@ -255,13 +195,6 @@ def test_input_stats_with_an_ant_template(widths):
     assert flat[keep].tobytes() == tmpl.params[0][keep].tobytes()
     for k, v in stats.state_dict().items():
         assert torch.equal(v.double().reshape(-1), state[k].double().reshape(-1)), k
-
-
-def _fake_brax_engine(auto_reset=True, n=1024):
-    eng = object.__new__(BraxVecEngine)
-    eng.b = _lib.Batch()
-    eng.D, eng.sys, eng.n, eng.auto_reset, eng.device = 27, BP.build_model("ant")[0], n, auto_reset, torch.device("cpu")
-    return eng
 
 
 def _fake_classic_engine():
