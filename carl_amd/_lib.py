@@ -297,6 +297,9 @@ class BraxLaunchShape(C.Structure):
 EXPORTS.update({
     "carl_brax_rollout_policy": (C.c_int, [C.POINTER(Batch), _vp, C.POINTER(BraxSys), _vp, C.POINTER(Policy),
                                            C.POINTER(StepIO), C.c_int32, C.POINTER(PolicySummary), _vp]),
+    "carl_brax_rollout_policy_sampled": (C.c_int, [C.POINTER(Batch), _vp, C.POINTER(BraxSys), _vp, C.POINTER(Policy),
+                                                   C.POINTER(PolicySampling), C.POINTER(StepIO), C.c_int32,
+                                                   C.POINTER(PolicySummary), _vp]),
     "carl_brax_evaluate_policy": (C.c_int, [C.POINTER(Batch), _vp, C.POINTER(BraxSys), _vp, C.POINTER(Policy), C.c_int32,
                                             C.c_int32, C.POINTER(PolicyEpisodes), _vp]),
     "carl_brax_policy_set_floats": (C.c_int32, [C.POINTER(Policy)]),

@@ -336,7 +336,8 @@ class BraxVecEngine(LaneEngine):
             raise ValueError(f"the policy was built for {policy.obs_dim} observations and {policy.n_out} actuators, this "
                              f"engine's model has {self.D} and {self.sys.n_act}")
 
-    def rollout_policy(self, policy, n_steps: int, out: dict | None = None, mode: str = "transitions") -> dict:
+    def rollout_policy(self, policy, n_steps: int, out: dict | None = None, mode: str = "transitions", *,
+                       deterministic: bool = True, sample_seed: int = 0, log_prob: bool = False) -> dict:
         """``n_steps`` steps in ONE launch, each env's action computed inside the rollout kernel by ``policy`` (a
         ``carl_amd.brax_policy.BraxMLPPolicy``) from the env's current context and observation (include/carl_amd.h:
         carl_brax_rollout_policy).  ``mode="transitions"``: ``rollout``'s dict (``alloc_rollout(T, action=True)`` layout)
@@ -345,10 +346,21 @@ class BraxVecEngine(LaneEngine):
         "length_sum"}`` per lane, needs ``auto_reset``.  The launch starts from ``obs`` -- the observation ``reset`` and
         ``step`` leave there; after an open-loop ``rollout`` its last row is copied in first, read from that rollout's
         output as it is NOW (``rollout``'s docstring: a caller who changed it calls ``set_current_obs``) -- and leaves
-        every env's last observation in ``obs``.  No host synchronisation."""
+        every env's last observation in ``obs``.  No host synchronisation.
+        ``deterministic=False``: each action is sampled from a diagonal Gaussian around the head's outputs, of
+        ``policy.log_std`` ``[n_sets, n_act]`` (include/carl_amd.h: carl_brax_rollout_policy_sampled), the draws keyed by
+        ``sample_seed`` and by (env, episode, step in episode, actuator) -- the same in either mode, however the horizon is
+        split into launches; ``"action"`` holds the raw samples, which the step clips as it clips any action, and
+        ``rollout`` of them still gives the same bits.  ``log_prob=True`` (sampled, transitions mode) adds ``"log_prob"``
+        ``[T, N]`` float32: the joint log-probability of each env-step's action (a buffer in ``out`` is checked like
+        ``"action"``).  With the caller's critic on ``"obs"`` and ``gae`` that is a PPO collection step."""
         self._check_policy(policy, "rollout_policy")
         if mode not in ("transitions", "summary"):
             raise ValueError(f"mode {mode!r}: 'transitions' or 'summary'")
+        if log_prob and deterministic:
+            raise ValueError("log_prob=True: sampled launches only (deterministic=False)")
+        if log_prob and mode == "summary":
+            raise ValueError("log_prob=True: transitions mode only (a summary launch stores nothing per step)")
         T = int(n_steps)
         if mode == "summary":
             if not self.auto_reset:
@@ -369,6 +381,14 @@ class BraxVecEngine(LaneEngine):
                     or tuple(a.shape[1:]) != (self.n, self.sys.n_act) or not a.is_contiguous()):
                 raise ValueError(f"rollout_policy output needs a contiguous float32 'action' [>= {T}, {self.n}, "
                                  f"{self.sys.n_act}] buffer on {self.device}")
+            if log_prob:
+                lp = res.get("log_prob")
+                if lp is None:
+                    lp = res["log_prob"] = torch.empty((T, self.n), dtype=torch.float32, device=self.device)
+                if (lp.dtype != torch.float32 or lp.device != self.device or lp.dim() != 2 or lp.shape[0] < T
+                        or lp.shape[1] != self.n or not lp.is_contiguous()):
+                    raise ValueError(f"rollout_policy output needs a contiguous float32 'log_prob' [>= {T}, {self.n}] "
+                                     f"buffer on {self.device}")
             io, summ = C.byref(self._rollout_io(a, _lib.ACTION_F32, res, T)), None
         # (after ``autotune``: the width that was fastest for the OPEN-loop rollout of this length class.  The closed loop
         # has 164 more LDS rows per env and another instruction mix; whether its best width differs is not measured)
@@ -376,13 +396,19 @@ class BraxVecEngine(LaneEngine):
         self._flush_obs()
         params = policy.device_params(self.device)
         pol = policy.struct(self.n, params.data_ptr())
+        head = (C.byref(self.b), _ptr(self.sys_dev), C.byref(self.sys), _ptr(self.obs), C.byref(pol))
+        if deterministic:
+            fn = self.lib.carl_brax_rollout_policy
+        else:  # the sampled twin, with its carl_policy_sampling_t behind the policy
+            smp = _lib.PolicySampling(int(sample_seed) & (2**64 - 1), policy.device_log_std(self.device).data_ptr(),
+                                      _ptr(res["log_prob"]) if log_prob else None)
+            fn, head = self.lib.carl_brax_rollout_policy_sampled, (*head, C.byref(smp))
         goal = self.sys.goal_mode and mode == "transitions"
         if goal:
             self.b.success = res["success"].data_ptr()  # [T][N] for the duration of this launch
         try:
             with torch.cuda.device(self.device):
-                _lib.check(self.lib.carl_brax_rollout_policy(C.byref(self.b), _ptr(self.sys_dev), C.byref(self.sys),
-                                                             _ptr(self.obs), C.byref(pol), io, T, summ, self._stream()))
+                _lib.check(fn(*head, io, T, summ, self._stream()))
         finally:
             if goal:
                 self.b.success = self.success.data_ptr()

@@ -12,9 +12,14 @@ stopping at its K-th episode end -- and ``carl_amd.es.EvolutionStrategy`` takes 
 ``input_stats=True`` that launch also gathers the sums of every input every env visited; ``carl_amd.policy.InputStats``
 with a ``BraxMLPPolicy`` template merges them into running statistics on the device (ARS V2's normalisation).
 
-At most ``CARL_POLICY_MAX_IN`` = 32 inputs: Humanoid's and HumanoidStandup's 244 observations do not fit.  Out of scope
-here: sampled actions and log-probabilities, value networks and GAE (``evaluate_policy`` stays the classic-control
-families') and ``MixedVecEngine``.
+``rollout_policy(..., deterministic=False)`` samples each action from a diagonal Gaussian around the head's outputs
+(include/carl_amd.h: carl_brax_rollout_policy_sampled): ``log_std`` holds one state-independent value per weight set and
+actuator, as SB3's ``log_std`` parameter does, and ``log_prob=True`` returns each env-step's joint log-probability.  With
+the caller's torch critic on the returned ``obs`` rows and ``BraxVecEngine.gae`` that is a PPO collection step.
+
+At most ``CARL_POLICY_MAX_IN`` = 32 inputs: Humanoid's and HumanoidStandup's 244 observations do not fit.  Still out of
+scope: a sampled episodes mode (``evaluate_episodes`` and ``EvolutionStrategy`` stay deterministic; ``evaluate_policy``
+stays the classic-control families'), a critic inside the Brax launch, Humanoid-size inputs and ``MixedVecEngine``.
 """
 from __future__ import annotations
 
@@ -40,17 +45,26 @@ def _brax_engine_of(env):
 
 class BraxMLPPolicy(MLPPolicy):
     """One or more weight sets of one MLP shape for one Brax model (see the module docstring).  ``info``: the engine's
-    info record (``BraxVecEngine.info``); the other parameters are ``MLPPolicy``'s."""
+    info record (``BraxVecEngine.info``); the other parameters are ``MLPPolicy``'s, but ``log_std``: a float or ``[n_act]``
+    values (default 0), held as float32 ``[n_sets, n_act]`` -- ``stack`` concatenates the sets' rows, ``on_device(...,
+    log_std=)`` takes a ``[n_sets, n_act]`` device tensor and ``device_log_std`` uploads it."""
 
     _STATS_MERGE = "carl_brax_policy_stats_merge"  # (n_out up to the model's actuators: the Brax packing rule)
 
     def __init__(self, info, ctx_rows: Sequence[int], layers: Sequence, activation: str = "tanh", input_shift=None,
-                 input_scale=None, input_clip: float | None = None, context_names: Sequence | None = None):
+                 input_scale=None, input_clip: float | None = None, context_names: Sequence | None = None, log_std=None):
         from carl_amd.brax_engine import _BRAX_FAMILY
 
         super().__init__(_BRAX_FAMILY, info.obs_dim, ctx_rows, layers, activation, input_shift, input_scale, input_clip,
                          context_names, None, "policy", info=info)
         self._info = info  # (unpack builds its result through this constructor)
+        if hasattr(log_std, "detach"):
+            log_std = log_std.detach().cpu()
+        ls = np.asarray(0.0 if log_std is None else log_std, np.float32).reshape(-1)
+        if ls.size not in (1, self.n_out):
+            raise ValueError(f"log_std: one value or one per actuator ({self.n_out}), got {ls.size}")
+        # [n_sets, n_act] float32: the Gaussian's log standard deviation per weight set and actuator
+        self.log_std = np.broadcast_to(ls, (self.n_out,)).copy()[None]
 
     @staticmethod
     def _box_outputs(info) -> int:
@@ -58,23 +72,27 @@ class BraxMLPPolicy(MLPPolicy):
 
     @classmethod
     def for_env(cls, env, layers: Sequence, activation: str = "tanh", input_shift=None, input_scale=None,
-                input_clip: float | None = None, context_features: Sequence | None = None) -> "BraxMLPPolicy":
+                input_clip: float | None = None, context_features: Sequence | None = None, log_std=None) -> "BraxMLPPolicy":
         """A policy for ``env`` (a ``CARLBraxEnv`` or ``BraxVecEngine``) from explicit ``(W [out, in], b [out])`` arrays,
-        hidden layers first, the head (``n_act`` outputs) last; ``context_features`` as ``MLPPolicy.for_env``'s."""
+        hidden layers first, the head (``n_act`` outputs) last; ``context_features`` as ``MLPPolicy.for_env``'s;
+        ``log_std``: a float or ``[n_act]`` values (default 0), for sampled launches.  (``from_sequential`` passes its
+        keywords, ``log_std=`` among them, through to here.)"""
         eng, _ = _brax_engine_of(env)
         rows, names = flattened_context_rows(env, context_features, _brax_engine_of)
-        return cls(eng.info, rows, layers, activation, input_shift, input_scale, input_clip, names)
+        return cls(eng.info, rows, layers, activation, input_shift, input_scale, input_clip, names, log_std)
 
     @staticmethod
     def unpack(template, packed, log_std=None) -> "BraxMLPPolicy":
         """A one-set host policy of ``template``'s model, inputs, shape and activation from one packed weight set
         ``[set_floats]`` (host floats): the inverse of the packing, bit for bit, its shift | scale | clip section included
         (``MLPPolicy.unpack`` for a Brax template; ``EvolutionStrategy.policy()`` reads the centre through it).  A
-        ``log_std`` is refused: the Brax closed loop samples nothing."""
+        ``log_std`` is refused: evolution strategies on the Brax families stay deterministic, and the result carries the
+        default ``log_std`` (zeros)."""
         if not isinstance(template, BraxMLPPolicy):
             raise TypeError(f"BraxMLPPolicy.unpack: the template is a {type(template).__name__}, not a BraxMLPPolicy")
         if log_std is not None:
-            raise NotImplementedError("BraxMLPPolicy: log_std (sampled actions) is out of scope for the Brax families")
+            raise NotImplementedError("BraxMLPPolicy.unpack: log_std is not unpacked (ES on the Brax families is "
+                                      "deterministic); pass log_std= to the constructor, for_env or on_device")
         if template._on_device or template.n_sets != 1:
             raise ValueError("unpack(): the template must be a one-set host-built BraxMLPPolicy")
         flat = np.ascontiguousarray(np.asarray(packed, dtype=np.float32).reshape(-1))

@@ -407,10 +407,12 @@ __host__ __device__ inline Layout policy_layout_of(const carl_brax_sys_t& s) {
 }
 // run()'s policy argument in modes 0 and 1: none.  kEpisodes: the policy type selects the episodes variant of MODE 2
 // (brax_episodes_kernels.hip.h: BraxEpisodesPolicy); kStats: its variant that also gathers input statistics
-// (brax_stats_kernels.hip.h: BraxStatsPolicy).
+// (brax_stats_kernels.hip.h: BraxStatsPolicy); kSampled: the transitions / summary variant whose actions are drawn around
+// the head's outputs (brax_sample_kernels.hip.h: BraxSampledPolicy).
 struct NoPolicy {
   static constexpr bool kEpisodes = false;
   static constexpr bool kStats = false;
+  static constexpr bool kSampled = false;
 };
 
 // tree topology derived from the model table once per workgroup
@@ -2214,6 +2216,10 @@ static __device__ __forceinline__ void write_ctx_obs(const carl_batch_t& b, cons
 // the episodes mode with Pol::kStats (include/carl_amd.h: carl_brax_evaluate_policy_stats; compiled from
 // carl_brax_policy_stats.hip alone): the policy is called with the env's liveness and the wavefront's two float64 sums,
 // which it adds the live envs' raw inputs to (brax_stats_kernels.hip.h), and the sums are stored once behind the fragment loop.
+// mode 2 with Pol::kSampled (include/carl_amd.h: carl_brax_rollout_policy_sampled; compiled from carl_brax_policy_sample.hip
+// alone): the policy is called with what keys the env-step's draws -- the env's global index, its episode counter and its
+// step count in the episode, all three in registers here -- and with where the step's log-probability goes
+// (brax_sample_kernels.hip.h); everything else, the summary mode and the fragment hand-over included, is mode 2's.
 // F32 (MODE 1, CARL_FLAG_BRAX_FP32): the n_frames substeps of an env step run their pose algebra in float32.
 template <int MODE, bool MULTI, bool TASK, bool PLANAR = false, bool F32 = false, class Pol = NoPolicy>
 static __device__ __forceinline__ void run(const carl_batch_t& b, const carl_brax_sys_t* __restrict__ sys_dev,
@@ -2296,6 +2302,8 @@ static __device__ __forceinline__ void run(const carl_batch_t& b, const carl_bra
   static_assert(!EP || MODE == 2, "the episodes mode is a variant of the closed-loop rollout");
   constexpr bool ST = Pol::kStats;
   static_assert(!ST || EP, "input statistics are gathered in the episodes mode");
+  constexpr bool SM = Pol::kSampled;
+  static_assert(!SM || (MODE == 2 && !EP), "sampled actions are a variant of the transitions / summary closed-loop rollout");
 
   if constexpr (MODE == 0) {
     const int gwave = (int)blockIdx.x * n_waves + wave;  // global wavefront = group of kEnvs envs
@@ -2454,6 +2462,13 @@ static __device__ __forceinline__ void run(const carl_batch_t& b, const carl_bra
       // The env's episode scalars (identical in all its lanes) wait in LDS until the reward needs them: a dozen registers
       // per lane that the substeps and observe need more.
       if (lead) stash_put(m, r);
+      if constexpr (SM) {
+        // the policy as below, its action drawn around the head's outputs; the step's log-probability behind the same
+        // wavefront-uniform branch as the other per-step stores
+        pol.template act_sampled<kSub>(m, pol_rows, b, r.cidx, env, active, genv, r.episode, r.elapsed, s.obs_dim, n_act,
+                per_step ? const_cast<float*>(static_cast<const float*>(io.action)) + (step_off + (size_t)env) * n_act : nullptr,
+                per_step, step_off + (size_t)env);
+      } else
       if constexpr (ST) {
         // the policy as below, gathering the raw inputs of the envs that are live at this step (no per-step record)
         pol.template act_stats<kSub>(m, pol_rows, b, r.cidx, env, active, ep_left > 0, tid, s.obs_dim, n_act, st_s1, st_s2);

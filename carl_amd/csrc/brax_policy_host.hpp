@@ -1,6 +1,7 @@
-// brax_policy_host.hpp -- the host side of the closed-loop entry points of the Brax families, shared by their three
+// brax_policy_host.hpp -- the host side of the closed-loop entry points of the Brax families, shared by their four
 // translation units (carl_brax_policy.hip: carl_brax_rollout_policy; carl_brax_episodes.hip: carl_brax_evaluate_policy;
-// carl_brax_policy_stats.hip: carl_brax_evaluate_policy_stats): the packed size of a policy's shape, the kernel class of a
+// carl_brax_policy_stats.hip: carl_brax_evaluate_policy_stats; carl_brax_policy_sample.hip:
+// carl_brax_rollout_policy_sampled): the packed size of a policy's shape, the kernel class of a
 // closed-loop launch, the policy's validation against the batch and the model, the list of kernel instances and the entry
 // type of a unit's table of them, the kernels' policy argument, the launch shape and the launch.  Host code only; the
 // kernels are each unit's own: every table is one expansion of the list with the unit's kernel template.
@@ -84,6 +85,26 @@ inline int validate_closed_loop(const char* who, const carl_batch_t* batch, cons
   return validate_policy(who, batch, sys_host, policy_host);
 }
 
+// What the rollout entry points (carl_brax_rollout_policy, carl_brax_rollout_policy_sampled) check after that, in this
+// order: the step count, io (NULL: summary mode) and the summary.
+inline bool summary_complete(const carl_policy_summary_t* s) { return s->episodes && s->return_sum && s->length_sum; }
+inline int validate_rollout(const char* who, const carl_batch_t* batch, const carl_step_io_t* io, int32_t n_steps,
+                            const carl_policy_summary_t* summary_out) {
+  if (n_steps < 0) return fail(CARL_ERR_INVALID_ARGUMENT, "%s: n_steps %d < 0", who, n_steps);
+  if (io == nullptr) {
+    if (summary_out == nullptr || !summary_complete(summary_out))
+      return fail(CARL_ERR_INVALID_ARGUMENT, "%s: summary mode (io NULL) needs all three summary arrays", who);
+  } else {
+    if (int e = validate_brax_io(io, who)) return e;
+    if (summary_out != nullptr && !summary_complete(summary_out))
+      return fail(CARL_ERR_INVALID_ARGUMENT, "%s: a summary needs all three arrays", who);
+  }
+  if (summary_out != nullptr && !(batch->flags & CARL_FLAG_AUTORESET))
+    return fail(CARL_ERR_UNSUPPORTED, "%s: a summary needs CARL_FLAG_AUTORESET (without auto-reset a finished lane "
+                "reports done on every later step, and its episode would be counted on each of them)", who);
+  return 0;
+}
+
 // What the episodes entry points (carl_brax_evaluate_policy, carl_brax_evaluate_policy_stats) check after that, in this order.
 inline int validate_episodes(const char* who, const carl_batch_t* batch, int32_t n_episodes, int32_t max_steps,
                              const carl_policy_episodes_t* out) {
@@ -100,7 +121,7 @@ inline int validate_episodes(const char* who, const carl_batch_t* batch, int32_t
   return 0;
 }
 
-// Every instantiated closed-loop kernel<MULTI, K, TASK, PLANAR>, of each of the three variants: the non-F32 step classes
+// Every instantiated closed-loop kernel<MULTI, K, TASK, PLANAR>, of each of the four variants: the non-F32 step classes
 // of carl_brax.hip's kBraxKernels, at the widths it has for them (tests/test_brax_policy_abi.py holds the list against
 // that table).  A unit's table is `#define X(M, K, T, P) {{M, T, P, false}, K, its_kernel<M, K, T, P>},` around one
 // expansion.

@@ -32,9 +32,16 @@ struct NoInputTap {
   static constexpr bool kOn = false;
 };
 
+// act()'s hook on the head's outputs: none, the action is the head's outputs as they come.  brax_sample_kernels.hip.h has
+// the one that draws a Gaussian action around them.
+struct PlainHead {
+  static constexpr bool kOn = false;
+};
+
 struct BraxPolicy {
   static constexpr bool kEpisodes = false;  // (run(): not the episodes variant -- brax_episodes_kernels.hip.h)
   static constexpr bool kStats = false;     // (nor its statistics variant -- brax_stats_kernels.hip.h)
+  static constexpr bool kSampled = false;   // (nor the sampled variant -- brax_sample_kernels.hip.h)
   carl_policy_t p;            // validated by the host (carl_brax_policy.hip)
   int set_floats;             // floats per packed weight set
   carl_policy_summary_t sum;  // per-env totals; all NULL: none
@@ -42,12 +49,16 @@ struct BraxPolicy {
 
   // out rows [out_row, out_row + n_out) = act(b + W in), W [n_out][n_in] row-major at w + p_w, b at w + p_b; lane `sub`
   // of the env computes units sub, sub + kSub, ...  ACT: the hidden activation is applied; else (the head) the unit is
-  // also stored to gout[u] when gout != NULL.
-  template <int kSub, bool ACT, class LdsT>
+  // also stored to gout[u] when gout != NULL -- with a `head` (Head::kOn) what is put and stored is head.action(u, unit),
+  // for which the lane calls head.draw(u) before the row's products.
+  template <int kSub, bool ACT, class LdsT, class Head = PlainHead>
   __device__ __forceinline__ void layer(const LdsT& m, const float* __restrict__ w, int p_w, int p_b, int n_in, int n_out,
-                                        int in_row, int out_row, bool active, float* __restrict__ gout) const {
+                                        int in_row, int out_row, bool active, float* __restrict__ gout,
+                                        const Head& head = Head()) const {
     if (active) {
       for (int u = m.sub; u < n_out; u += kSub) {
+        [[maybe_unused]] float drawn = 0.0f;
+        if constexpr (Head::kOn) drawn = head.draw(u);
         float acc = w[p_b + u];
         const int a = p_w + u * n_in, end = a + n_in;  // the row's floats [a, end); its aligned pieces start at a & ~3
         // a piece that reaches into a neighbouring row (the first and the last one may): a select per element
@@ -81,6 +92,7 @@ struct BraxPolicy {
           activate(h, p.activation, 1);
           m.at(out_row + u) = h[0];
         } else {
+          if constexpr (Head::kOn) acc = head.action(m, u, acc, drawn);
           m.at(out_row + u) = acc;
           if (gout != nullptr) gout[u] = acc;
         }
@@ -93,9 +105,11 @@ struct BraxPolicy {
   // that is not NULL.  `rows`: the first of the env's policy rows; cidx: the env's current context.  Wavefront-uniform call.
   // `tap` (Tap::kOn): sees every raw input beside its shift where the first phase normalises it, marks the env before that
   // phase's hand-over and gathers behind it, while h2 and the summary-total rows are still dead.
-  template <int kSub, class LdsT, class Tap = NoInputTap>
+  // `head` (Head::kOn): the head layer's hook, see layer().
+  template <int kSub, class LdsT, class Tap = NoInputTap, class Head = PlainHead>
   __device__ __forceinline__ void act(const LdsT& m, int rows, const carl_batch_t& b, int cidx, int env, bool active,
-                                      int obs_dim, int n_act, float* __restrict__ action_out, const Tap& tap = Tap()) const {
+                                      int obs_dim, int n_act, float* __restrict__ action_out, const Tap& tap = Tap(),
+                                      const Head& head = Head()) const {
     const int X = rows, H1 = rows + kPolicyXRows, H2 = H1 + kPolicyHRows;
     const int n_in = p.n_in, n_ctx = p.n_ctx, nh = p.n_hidden;
     const int w0 = nh > 0 ? p.width[0] : 0, w1 = nh > 1 ? p.width[1] : 0;
@@ -125,14 +139,14 @@ struct BraxPolicy {
     Group<kSub>::phase_sync();
     if constexpr (Tap::kOn) tap.template gather<kSub>(m, H2, H2 + kPolicyHRows, n_in);
     if (nh == 0) {
-      layer<kSub, false>(m, w, p_w0, p_b0, n_in, n_act, X, m.lay.io, active, action_out);
+      layer<kSub, false>(m, w, p_w0, p_b0, n_in, n_act, X, m.lay.io, active, action_out, head);
     } else {
       layer<kSub, true>(m, w, p_w0, p_b0, n_in, w0, X, H1, active, nullptr);
       if (nh > 1) {
         layer<kSub, true>(m, w, p_w1, p_b1, w0, w1, H1, H2, active, nullptr);
-        layer<kSub, false>(m, w, p_w2, p_b2, w1, n_act, H2, m.lay.io, active, action_out);
+        layer<kSub, false>(m, w, p_w2, p_b2, w1, n_act, H2, m.lay.io, active, action_out, head);
       } else {
-        layer<kSub, false>(m, w, p_w1, p_b1, w0, n_act, H1, m.lay.io, active, action_out);
+        layer<kSub, false>(m, w, p_w1, p_b1, w0, n_act, H1, m.lay.io, active, action_out, head);
       }
     }
   }

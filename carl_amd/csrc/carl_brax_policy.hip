@@ -3,8 +3,9 @@
 // brax_kernels.hip.h's run(), instantiated here and nowhere else, so that the reset / step / rollout kernels of
 // carl_brax.hip compile exactly as they did without them (profiles/brax_policy_isa_identity.txt).  The batch, model and io
 // checks and the launch-shape rule are carl_brax.hip's (brax_launch.hpp); the network's shape rules are the classic
-// closed-loop rollout's (policy_host.hpp); the policy's checks, the list of instances and the launch are the three
-// closed-loop units' (brax_policy_host.hpp).  Same flags as carl_brax.hip (carl_amd/build.py).
+// closed-loop rollout's (policy_host.hpp); the policy's and the rollout's checks, the list of instances and the launch are
+// the closed-loop units' (brax_policy_host.hpp).  The tables of all of them hold the same instances under one launch
+// rule, so carl_brax_policy_launch_shape answers for carl_brax_rollout_policy_sampled too.  Same flags as carl_brax.hip (carl_amd/build.py).
 #include <hip/hip_runtime.h>
 
 #include <cstdint>
@@ -28,8 +29,6 @@ using carl_host::brax::policy_class;
 #define X(M, K, T, P) {{M, T, P, false}, K, carl::brax::brax_policy_kernel<M, K, T, P>},
 const carl_host::brax::ClosedLoopKernel<carl::brax::BraxPolicy> kBraxPolicyKernels[] = {CARL_BRAX_CLOSED_LOOP_INSTANCES(X)};
 #undef X
-
-bool summary_complete(const carl_policy_summary_t* s) { return s->episodes && s->return_sum && s->length_sum; }
 
 }  // namespace
 
@@ -62,18 +61,7 @@ int carl_brax_rollout_policy(const carl_batch_t* batch, const carl_brax_sys_t* s
   const char* who = "carl_brax_rollout_policy";
   BraxClass c;
   if (int e = carl_host::brax::validate_closed_loop(who, batch, sys_dev, sys_host, obs, policy_host, &c)) return e;
-  if (n_steps < 0) return fail(CARL_ERR_INVALID_ARGUMENT, "%s: n_steps %d < 0", who, n_steps);
-  if (io == nullptr) {
-    if (summary_out == nullptr || !summary_complete(summary_out))
-      return fail(CARL_ERR_INVALID_ARGUMENT, "%s: summary mode (io NULL) needs all three summary arrays", who);
-  } else {
-    if (int e = carl_host::brax::validate_brax_io(io, who)) return e;
-    if (summary_out != nullptr && !summary_complete(summary_out))
-      return fail(CARL_ERR_INVALID_ARGUMENT, "%s: a summary needs all three arrays", who);
-  }
-  if (summary_out != nullptr && !(batch->flags & CARL_FLAG_AUTORESET))
-    return fail(CARL_ERR_UNSUPPORTED, "%s: a summary needs CARL_FLAG_AUTORESET (without auto-reset a finished lane "
-                "reports done on every later step, and its episode would be counted on each of them)", who);
+  if (int e = carl_host::brax::validate_rollout(who, batch, io, n_steps, summary_out)) return e;
   if (batch->n_lanes == 0 || n_steps == 0) return carl_host::policy_rollout_without_steps(who, batch, summary_out, stream);
 
   carl_step_io_t io_v{};

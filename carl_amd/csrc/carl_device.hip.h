@@ -48,6 +48,14 @@ __device__ __forceinline__ u32x4 lane_words(uint64_t seed, uint64_t glane, uint3
 __device__ __forceinline__ float u01(uint32_t w) {
   return (float)(w >> 8) * (1.0f / 16777216.0f);
 }
+// carl_policy_sampling_t's Gaussian rule (include/carl_amd.h): z = sqrt(-2 ln u1) cos(2 pi u2), u1 = ((a >> 8) + 1) 2^-24 in
+// (0, 1], u2 = u01(b); the accurate logf / sqrtf / cospif, every product rounded on its own
+__device__ __forceinline__ float normal_from_words(uint32_t a, uint32_t b) {
+#pragma clang fp contract(off)
+  const float u1 = (float)((a >> 8) + 1u) * (1.0f / 16777216.0f);  // (0, 1]
+  const float u2 = u01(b);
+  return sqrtf(-2.0f * logf(u1)) * cospif(2.0f * u2);
+}
 // numpy's uniform(low, high) = low + (high - low) * u, as ONE fma so the CPU
 // oracle can reproduce the reset state bit for bit
 __device__ __forceinline__ float uniform_between(float lo, float hi, uint32_t w) {

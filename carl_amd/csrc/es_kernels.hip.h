@@ -20,14 +20,8 @@ __device__ __forceinline__ u32x4 es_words(const carl_es_t& es, uint32_t block, u
   return philox4x32_10(u32x4{block, pair, es.generation, kSubEsNoise}, (uint32_t)es.seed, (uint32_t)(es.seed >> 32));
 }
 
-// carl_policy_sampling_t's Gaussian rule, restated (policy_kernels.hip.h: SampledPick::choose): the accurate logf /
-// sqrtf / cospif, every product rounded on its own
-__device__ __forceinline__ float es_normal(uint32_t a, uint32_t b) {
-#pragma clang fp contract(off)
-  const float u1 = (float)((a >> 8) + 1u) * (1.0f / 16777216.0f);  // (0, 1]
-  const float u2 = u01(b);
-  return sqrtf(-2.0f * logf(u1)) * cospif(2.0f * u2);
-}
+// carl_policy_sampling_t's Gaussian rule (carl_device.hip.h: normal_from_words)
+__device__ __forceinline__ float es_normal(uint32_t a, uint32_t b) { return normal_from_words(a, b); }
 
 // One thread per (pair, Philox block): floats 2k and 2k + 1 of sets 2i and 2i + 1, as one 8-byte store each (set_floats
 // is a multiple of 4 and params 16-byte aligned), so a wavefront writes two contiguous 512-byte runs.  Threads of the

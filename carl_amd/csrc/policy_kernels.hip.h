@@ -307,9 +307,7 @@ struct SampledPick {
     const u32x4 wd = lane_words(seed, glane, r.episode - 1u, kSubSample | (uint32_t)r.elapsed);
     float y[4];
     if constexpr (std::is_same_v<typename Fam::Action, float>) {
-      const float u1 = (float)((wd.x >> 8) + 1u) * (1.0f / 16777216.0f);  // (0, 1]
-      const float u2 = u01(wd.y);
-      const float z = sqrtf(-2.0f * logf(u1)) * cospif(2.0f * u2);
+      const float z = normal_from_words(wd.x, wd.y);
       policy_head<Fam, H>(w, x, n_hidden, act, w0, w1, y);
       if constexpr (LOGP) lp = __fmaf_rn(-0.5f * z, z, lp0);
       return __fmaf_rn(sigma, z, y[0]);

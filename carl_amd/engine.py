@@ -530,6 +530,48 @@ class LaneEngine:
                 raise ValueError(f"{who} output '{k}': shape {tuple(t.shape)} / strides {tuple(t.stride())} do not form "
                                  f"[{rows}, {n}{', ' + str(D) if tail else ''}] rows of one common pitch ({P} lanes)")
 
+    def gae(self, reward, value, terminated, truncated, last_value, gamma: float, lam: float, boot_value=None,
+            out: dict | None = None) -> dict:
+        """Generalised advantage estimation in one launch (include/carl_amd.h: carl_gae) over ``[T, N]`` float32
+        ``reward`` / ``value`` (/ ``boot_value``), uint8 or bool ``terminated`` / ``truncated`` and ``last_value`` ``[N]``:
+        rows of one common pitch (``alloc_rollout``-style views or dense), on this engine's device.  Returns
+        ``{"advantage", "return"}`` ``[T, N]`` float32 (``out``: buffers of the same layout to write into).  The rule is
+        SB3's ``RolloutBuffer.compute_returns_and_advantage`` with ``boot_value`` as the timeout bootstrap; a finished
+        step (either flag) cuts the recurrence.  No host synchronisation."""
+        T, N = (int(v) for v in reward.shape)
+        P = int(reward.stride(0)) if T > 1 else N
+
+        def rows(name, t, dtypes):
+            if t.dtype not in dtypes or t.device != self.device or tuple(t.shape) != (T, N) or (
+                    N > 1 and t.stride(1) != 1) or (T > 1 and t.stride(0) != P):
+                raise ValueError(f"gae '{name}': needs {dtypes[0]} [{T}, {N}] rows of pitch {P} on {self.device}, got "
+                                 f"{t.dtype} {tuple(t.shape)} strides {tuple(t.stride())}")
+            return t
+
+        if P < N:
+            raise ValueError(f"gae 'reward': rows of pitch {P} < {N} lanes")
+        f32, u8 = (torch.float32,), (torch.uint8, torch.bool)
+        rows("reward", reward, f32), rows("value", value, f32), rows("terminated", terminated, u8)
+        rows("truncated", truncated, u8)
+        if boot_value is not None:
+            rows("boot_value", boot_value, f32)
+        if last_value.dtype != torch.float32 or last_value.device != self.device or tuple(last_value.shape) != (N,) or (
+                N > 1 and last_value.stride(0) != 1):
+            raise ValueError(f"gae 'last_value': needs a contiguous float32 [{N}] tensor on {self.device}")
+        res = {} if out is None else out
+        for k in ("advantage", "return"):
+            if k not in res:
+                res[k] = torch.empty((T, P), dtype=torch.float32, device=self.device)[:, :N]
+            rows(k, res[k], f32)
+        g = _lib.Gae()
+        g.n_lanes, g.n_steps, g.row_pitch, g.gamma, g.lam = N, T, (P if P != N else 0), float(gamma), float(lam)
+        g.reward, g.value, g.boot_value, g.last_value = _ptr(reward), _ptr(value), _ptr(boot_value), _ptr(last_value)
+        g.terminated, g.truncated = _ptr(terminated), _ptr(truncated)
+        g.advantage, g.ret = _ptr(res["advantage"]), _ptr(res["return"])
+        with torch.cuda.device(self.device):
+            _lib.check(self.lib.carl_gae(C.byref(g), self._stream()))
+        return res
+
     def drain_finished(self):
         """Finished-episode log since the last drain -> (global lane ids, returns, lengths,
         n_dropped); resets the counter.  Synchronises."""
@@ -839,48 +881,6 @@ class VecEngine(LaneEngine):
         if not np.array_equal(np.ascontiguousarray(a).view(np.int32), np.ascontiguousarray(c).view(np.int32)):
             raise ValueError("value_net's input_shift / input_scale / input_clip must equal the policy's bit for bit: the "
                              "critic reads the actor's transformed inputs")
-
-    def gae(self, reward, value, terminated, truncated, last_value, gamma: float, lam: float, boot_value=None,
-            out: dict | None = None) -> dict:
-        """Generalised advantage estimation in one launch (include/carl_amd.h: carl_gae) over ``[T, N]`` float32
-        ``reward`` / ``value`` (/ ``boot_value``), uint8 or bool ``terminated`` / ``truncated`` and ``last_value`` ``[N]``:
-        rows of one common pitch (``alloc_rollout``-style views or dense), on this engine's device.  Returns
-        ``{"advantage", "return"}`` ``[T, N]`` float32 (``out``: buffers of the same layout to write into).  The rule is
-        SB3's ``RolloutBuffer.compute_returns_and_advantage`` with ``boot_value`` as the timeout bootstrap; a finished
-        step (either flag) cuts the recurrence.  No host synchronisation."""
-        T, N = (int(v) for v in reward.shape)
-        P = int(reward.stride(0)) if T > 1 else N
-
-        def rows(name, t, dtypes):
-            if t.dtype not in dtypes or t.device != self.device or tuple(t.shape) != (T, N) or (
-                    N > 1 and t.stride(1) != 1) or (T > 1 and t.stride(0) != P):
-                raise ValueError(f"gae '{name}': needs {dtypes[0]} [{T}, {N}] rows of pitch {P} on {self.device}, got "
-                                 f"{t.dtype} {tuple(t.shape)} strides {tuple(t.stride())}")
-            return t
-
-        if P < N:
-            raise ValueError(f"gae 'reward': rows of pitch {P} < {N} lanes")
-        f32, u8 = (torch.float32,), (torch.uint8, torch.bool)
-        rows("reward", reward, f32), rows("value", value, f32), rows("terminated", terminated, u8)
-        rows("truncated", truncated, u8)
-        if boot_value is not None:
-            rows("boot_value", boot_value, f32)
-        if last_value.dtype != torch.float32 or last_value.device != self.device or tuple(last_value.shape) != (N,) or (
-                N > 1 and last_value.stride(0) != 1):
-            raise ValueError(f"gae 'last_value': needs a contiguous float32 [{N}] tensor on {self.device}")
-        res = {} if out is None else out
-        for k in ("advantage", "return"):
-            if k not in res:
-                res[k] = torch.empty((T, P), dtype=torch.float32, device=self.device)[:, :N]
-            rows(k, res[k], f32)
-        g = _lib.Gae()
-        g.n_lanes, g.n_steps, g.row_pitch, g.gamma, g.lam = N, T, (P if P != N else 0), float(gamma), float(lam)
-        g.reward, g.value, g.boot_value, g.last_value = _ptr(reward), _ptr(value), _ptr(boot_value), _ptr(last_value)
-        g.terminated, g.truncated = _ptr(terminated), _ptr(truncated)
-        g.advantage, g.ret = _ptr(res["advantage"]), _ptr(res["return"])
-        with torch.cuda.device(self.device):
-            _lib.check(self.lib.carl_gae(C.byref(g), self._stream()))
-        return res
 
     # (key, dtype, per-episode rows) of an evaluate_policy result
     _EPISODE_KEYS = (("episodes", torch.int32, False), ("steps", torch.int32, False), ("return", torch.float32, True),

@@ -263,16 +263,7 @@ class MLPPolicy:
         q = _lib.load().carl_policy_lane_quantum()
         if lanes_per_set <= 0 or lanes_per_set % q:
             raise ValueError(f"lanes_per_set {lanes_per_set} is not a positive multiple of {q}")
-        n_sets = int(params.shape[0])
-        if log_std is None:
-            ls = torch.full((n_sets,), float(template.log_std[0]), dtype=torch.float32, device=params.device)
-        else:
-            if template.discrete or template.head == "value":
-                raise ValueError("log_std: Box policies only")
-            ls = log_std
-            if (not isinstance(ls, torch.Tensor) or ls.device != params.device or ls.dtype != torch.float32
-                    or tuple(ls.shape) != (n_sets,) or not ls.is_contiguous()):
-                raise ValueError(f"on_device(): log_std must be a contiguous float32 [{n_sets}] tensor on {params.device}")
+        ls = template._device_log_std_of(log_std, params)
         out = object.__new__(type(template))
         out.__dict__.update(template.__dict__)
         out.params, out.log_std = params, ls
@@ -280,6 +271,22 @@ class MLPPolicy:
         out._on_device = True
         out._dev = {}
         return out
+
+    def _device_log_std_of(self, log_std, params: torch.Tensor) -> torch.Tensor:
+        """``on_device``'s ``log_std`` for the sets of ``params`` with this policy as the template: the caller's tensor,
+        checked, or the template's values for every set.  One value per set, of shape ``log_std.shape[1:]``."""
+        n_sets = int(params.shape[0])
+        shape = (n_sets, *self.log_std.shape[1:])
+        if log_std is None:
+            row = torch.as_tensor(self.log_std[0], dtype=torch.float32, device=params.device)
+            return row.expand(shape).contiguous()
+        if self.discrete or self.head == "value":
+            raise ValueError("log_std: Box policies only")
+        ls = log_std
+        if (not isinstance(ls, torch.Tensor) or ls.device != params.device or ls.dtype != torch.float32
+                or tuple(ls.shape) != shape or not ls.is_contiguous()):
+            raise ValueError(f"on_device(): log_std must be a contiguous float32 {list(shape)} tensor on {params.device}")
+        return ls
 
     @staticmethod
     def unpack(template: "MLPPolicy", packed, log_std=None) -> "MLPPolicy":

@@ -1,8 +1,8 @@
 /* carl_amd.h -- C ABI of the MI355X batched step/reset engine for CARL's
  * contextual classic-control (and Brax-locomotion) families: reset / step / fused open-loop rollout for both, and the
  * closed-loop rollout with a policy network on the device (carl_rollout_policy and its sampled / valued / episodes / ES
- * forms for the classic-control families; carl_brax_rollout_policy, deterministic transitions and summary, and
- * carl_brax_evaluate_policy, whole episodes, for Brax).
+ * forms for the classic-control families; carl_brax_rollout_policy, transitions and summary, its sampled form
+ * carl_brax_rollout_policy_sampled and carl_brax_evaluate_policy, whole episodes, for Brax).
  *
  * The reference (automl/CARL v1.1.1) has NO FFI on this path: its boundary is a
  * Python protocol, "the object CARLEnv wraps" (SURVEY.md section 8b).  This header
@@ -916,12 +916,48 @@ int carl_brax_fragment_plan(int32_t n_groups, int32_t n_workgroups, int32_t wave
  *  - summary mode (io == NULL): no per-step stores; summary_out (required) receives each env's totals as
  *    carl_rollout_policy defines them.  A summary (in either mode) needs CARL_FLAG_AUTORESET, else CARL_ERR_UNSUPPORTED.
  * The batch, the model and io are checked as carl_brax_rollout checks them.  CARL_FLAG_BRAX_FP32 is refused with
- * CARL_ERR_UNSUPPORTED; both auto-reset modes and the goal wrapper work as in carl_brax_rollout.  Out of scope: sampled
- * actions and log-probabilities, critics and GAE (the episodes mode is carl_brax_evaluate_policy, its input statistics
- * carl_brax_evaluate_policy_stats). */
+ * CARL_ERR_UNSUPPORTED; both auto-reset modes and the goal wrapper work as in carl_brax_rollout.  Sampled actions and
+ * their log-probabilities: carl_brax_rollout_policy_sampled below; the episodes mode: carl_brax_evaluate_policy, its input
+ * statistics carl_brax_evaluate_policy_stats.  Out of scope: a sampled episodes mode, a critic inside the launch (the
+ * caller's critic on the returned obs rows, then carl_gae, which takes dense [T][n_lanes] rows) and Humanoid-size inputs. */
 int carl_brax_rollout_policy(const carl_batch_t* batch, const carl_brax_sys_t* sys_dev, const carl_brax_sys_t* sys_host,
                              float* obs, const carl_policy_t* policy_host, const carl_step_io_t* io, int32_t n_steps,
                              const carl_policy_summary_t* summary_out, void* stream);
+/* carl_brax_rollout_policy with sampled actions (additive; ABI version unchanged): a diagonal Gaussian over all the model's
+ * actuators, the data an on-policy learner collects (the reference's example agent is SB3 PPO over a CARL env,
+ * examples/carl_with_sb3.py, which samples and scores the action in Python between two env steps).
+ * The network, its inputs and its arithmetic are carl_brax_rollout_policy's, unchanged; the head's n_act outputs are the
+ * means mu_j.  `sampling` is a carl_policy_sampling_t with these meanings:
+ *   seed      sample_seed, the Philox key of the draws;
+ *   log_std   DEVICE [n_sets][n_act]: one state-independent value per weight set and actuator (SB3's log_std parameter);
+ *   log_prob  optional DEVICE [T][n_lanes] fp32, dense rows as every Brax output: the joint log-probability of each
+ *             env-step's action; transitions mode only.
+ * Random words: actuator j of an env-step uses Philox4x32-10 block b = j >> 1, key sample_seed, counter
+ *   (genv lo, genv hi, e, 0x40000000 | (b << 28) | elapsed)
+ * with genv = lane_offset + env, e the env's episode counter - 1 and elapsed the env's step count in that episode before
+ * the step, both as carl_policy_sampling_t defines them.  Even j takes (w.x, w.y) of its block, odd j (w.z, w.w), as the
+ * (u1, u2) of the Gaussian rule above:
+ *   u1 = ((wa >> 8) + 1) * 2^-24, u2 = (wb >> 8) * 2^-24;  z_j = sqrt(-2 ln u1) * cos(2 pi u2);
+ *   a_j = fma(exp(log_std[set][j]), z_j, mu_j);  lp_j = fma(-z_j / 2, z_j, -log_std[set][j] - ln(2 pi) / 2);
+ *   log_prob = lp_0 + lp_1 + ... summed in fp32 in actuator order;
+ * exp / log / sqrt / cos the device's accurate fp32 functions, every product rounded on its own.  The tag is 0x4..., not
+ * the classic rule's 0x8...: the Brax reset draws use 0x80000000 | block with the batch seed, which a caller may pass as
+ * sample_seed.  b has two bits -- eight actuators, what every model whose observation fits CARL_POLICY_MAX_IN has at most
+ * (a model table with more, up to CARL_BRAX_MAX_ACT, is refused) -- which leaves elapsed < 2^28.
+ * A draw is therefore a pure function of (sample_seed, global env, episode, step in episode, actuator): it does not depend
+ * on the mode, on how a horizon is split into launches, on the lane width or on which wavefront of a split group runs the
+ * step.  The recorded action is the raw a_j; the step clips it exactly as it clips a deterministic action, and
+ * carl_brax_rollout of the recorded actions from the same engine state reproduces the launch bit for bit.  A summary
+ * launch stores nothing per step and leaves the state the transitions launch leaves.  An env past the end of the batch
+ * draws nothing.
+ * Validation: everything carl_brax_rollout_policy checks, in its order and with its codes; then `sampling` non-NULL,
+ * log_std non-NULL, no log_prob in summary mode (io == NULL), sys.n_act <= 8 and 0 < batch->max_episode_steps <= 2^28, each refused with
+ * CARL_ERR_INVALID_ARGUMENT before anything is enqueued.  n_lanes == 0 enqueues nothing.  The launch has the shape
+ * carl_brax_policy_launch_shape reports.  Out of scope: a sampled episodes mode and a critic inside the launch. */
+int carl_brax_rollout_policy_sampled(const carl_batch_t* batch, const carl_brax_sys_t* sys_dev, const carl_brax_sys_t* sys_host,
+                                     float* obs, const carl_policy_t* policy_host, const carl_policy_sampling_t* sampling,
+                                     const carl_step_io_t* io, int32_t n_steps, const carl_policy_summary_t* summary_out,
+                                     void* stream);
 /* Episodes mode of carl_brax_rollout_policy (additive; ABI version unchanged): carl_evaluate_policy's semantics for the
  * Brax families, a variant of the same rollout kernel.  No reference counterpart: the reference evaluates a policy by
  * stepping the env per Python call until `done` (carl/envs/carl_env.py:321-342; examples/carl_with_sb3.py runs SB3's
@@ -999,7 +1035,7 @@ int carl_brax_policy_stats_merge(const carl_policy_t* policy_host, const carl_po
                                  void* stream);
 /* floats per packed weight set of a Brax policy's shape (n_out up to CARL_BRAX_MAX_ACT); -1 for an invalid shape */
 int32_t carl_brax_policy_set_floats(const carl_policy_t* policy_host);
-/* The shape carl_brax_rollout_policy launches for this batch, model and step count (host only, no device access beyond the
+/* The shape carl_brax_rollout_policy and carl_brax_rollout_policy_sampled launch for this batch, model and step count (host only, no device access beyond the
  * compute-unit count of the current device; 256 where there is none): with n_groups = ceil(n_lanes / (64 / lanes_per_env))
  * it is what carl_brax_fragment_plan takes. */
 typedef struct carl_brax_launch_shape {

@@ -51,10 +51,19 @@
                    --reps after a warm-up (the launches: of two interleaved runs of --reps per side).  Written to key
                    "brax_stats" of --out.
 
+  --legs brax_sample  sampled actions and log-probabilities inside the Brax closed-loop launch (runs on its own engines;
+                   --lanes is not used): Ant x 32 768 and Halfcheetah x 32 768, 100-step transitions launches, 2x64 tanh,
+                   TimeLimit 1 000, log_std 0.  rollout_policy(deterministic=False) with and without log_prob against the
+                   deterministic launch (the kernel of the parent commit: profiles/brax_policy_sample_isa_identity.txt) in
+                   the same process, state restored before each launch, device events, the three sides interleaved over
+                   two rounds; a warm-up, then the median of --reps per round (reported: of both rounds together, and the
+                   spread of the deterministic side's repetitions, which a difference has to exceed to count).  Written
+                   to key "brax_sample" of --out.
+
 Host timing with torch.cuda events around `--reps` launches after one warm-up launch; the median per launch is
 reported.  Kernel times belong to a separate `rocprofv3 --kernel-trace --stats` run of this script.
 
-  python tools/policy_rollout_bench.py [--lanes 65536] [--steps 1000] [--reps 5] [--legs rollout,evaluate,value,es,stats,brax_es,brax_stats] [--out FILE]
+  python tools/policy_rollout_bench.py [--lanes 65536] [--steps 1000] [--reps 5] [--legs rollout,evaluate,value,es,stats,brax_es,brax_stats,brax_sample] [--out FILE]
 
 --out FILE: a JSON file whose keys of the legs run ("results": rollout, "evaluate") are replaced, others kept.
 """
@@ -518,6 +527,42 @@ def brax_stats_leg(reps, n=32768, L=256, max_steps=1000, time_limit=100):
     return [r]
 
 
+def brax_sample_leg(reps, n=32768, steps=100, time_limit=1000):
+    """the sampled transitions launch, with and without log_prob, against the deterministic one: Ant and Halfcheetah"""
+    from carl_amd import envs as E
+
+    rows = []
+    for model, cls in (("ant", E.CARLBraxAnt), ("halfcheetah", E.CARLBraxHalfcheetah)):
+        eng = brax_bench_engine(cls, n, time_limit)
+        pol = brax_bench_policy(eng)
+        snap = eng.snapshot()
+        out = eng.alloc_rollout(steps, action=True)
+        out_lp = dict(out, log_prob=torch.empty((steps, n), dtype=torch.float32, device=eng.device))
+        kw = dict(deterministic=False, sample_seed=1)
+        sides = {"deterministic": lambda: eng.rollout_policy(pol, steps, out=out),
+                 "sampled": lambda: eng.rollout_policy(pol, steps, out=out, **kw),
+                 "sampled_log_prob": lambda: eng.rollout_policy(pol, steps, out=out_lp, log_prob=True, **kw)}
+        ts = {k: [] for k in sides}
+        for _ in range(2):  # interleaved A, B, C, A, B, C: a drift of the clock over the run lands on every side
+            for k, fn in sides.items():
+                ts[k] += timed_from_snapshot(eng, snap, fn, reps)[1]
+        sec = {k: float(np.median(v)) for k, v in ts.items()}
+        det = ts["deterministic"]
+        r = {"config": f"brax_sample_{model}_2x64_tanh", "envs": n, "steps": steps, "time_limit": time_limit,
+             "deterministic_sec": sec["deterministic"], "sampled_sec": sec["sampled"],
+             "sampled_log_prob_sec": sec["sampled_log_prob"],
+             "sampled_over_deterministic": sec["sampled"] / sec["deterministic"],
+             "sampled_log_prob_over_deterministic": sec["sampled_log_prob"] / sec["deterministic"],
+             "deterministic_spread": (max(det) - min(det)) / sec["deterministic"],
+             "env_steps_per_s": {k: n * steps / v for k, v in sec.items()}, "reps_sec": ts}
+        rows.append(r)
+        print(json.dumps(r), flush=True)
+    return rows
+
+
+BRAX_LEGS = (("brax_es", brax_es_leg), ("brax_stats", brax_stats_leg), ("brax_sample", brax_sample_leg))
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--lanes", type=int, default=65536)
@@ -528,9 +573,8 @@ def main():
     ap.add_argument("--sampled", action="store_true")
     args = ap.parse_args()
     legs = set(args.legs.split(","))
-    if legs <= {"brax_es", "brax_stats"}:  # (their own engines: the CartPole engine below is not built)
-        return write(args.out, {k: leg(args.reps) for k, leg in (("brax_es", brax_es_leg), ("brax_stats", brax_stats_leg))
-                                if k in legs})
+    if legs <= {k for k, _ in BRAX_LEGS}:  # (their own engines: the CartPole engine below is not built)
+        return write(args.out, {k: leg(args.reps) for k, leg in BRAX_LEGS if k in legs})
     n, T = args.lanes, args.steps
     eng = make_engine(n)
     n_in = len(eng.ctx_obs_rows) + eng.D
@@ -548,6 +592,8 @@ def main():
         doc["brax_es"] = brax_es_leg(args.reps)
     if "brax_stats" in legs:
         doc["brax_stats"] = brax_stats_leg(args.reps)
+    if "brax_sample" in legs:
+        doc["brax_sample"] = brax_sample_leg(args.reps)
     if "rollout" not in legs:
         return write(args.out, doc)
 
