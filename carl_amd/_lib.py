@@ -326,6 +326,9 @@ EXPORTS.update({
                                              C.POINTER(PolicySampling), C.POINTER(StepIO), C.c_int32,
                                              C.POINTER(PolicySummary), C.POINTER(PolicyValue), _vp]),
     "carl_gae": (C.c_int, [C.POINTER(Gae), _vp]),
+    "carl_brax_rollout_policy_valued": (C.c_int, [C.POINTER(Batch), _vp, C.POINTER(BraxSys), _vp, C.POINTER(Policy),
+                                                  C.POINTER(Policy), C.POINTER(PolicySampling), C.POINTER(StepIO),
+                                                  C.c_int32, C.POINTER(PolicySummary), C.POINTER(PolicyValue), _vp]),
 })
 
 

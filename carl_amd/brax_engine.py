@@ -336,8 +336,32 @@ class BraxVecEngine(LaneEngine):
             raise ValueError(f"the policy was built for {policy.obs_dim} observations and {policy.n_out} actuators, this "
                              f"engine's model has {self.D} and {self.sys.n_act}")
 
+    def _policy_column(self, res: dict, key: str, T: int) -> torch.Tensor:
+        """``res[key]``, a float32 ``[>= T, N]`` column of a closed-loop launch (dense rows): allocated when missing,
+        checked when the caller passed it"""
+        t = res.get(key)
+        if t is None:
+            t = res[key] = torch.empty((T, self.n), dtype=torch.float32, device=self.device)
+        if (t.dtype != torch.float32 or t.device != self.device or t.dim() != 2 or t.shape[0] < T or t.shape[1] != self.n
+                or not t.is_contiguous()):
+            raise ValueError(f"rollout_policy output needs a contiguous float32 '{key}' [>= {T}, {self.n}] buffer on "
+                             f"{self.device}")
+        return t
+
+    def _check_value_net(self, policy, value_net) -> None:
+        """ValueError unless ``value_net`` is a critic the valued launch can run next to ``policy``: a one-output
+        ``BraxMLPPolicy`` of this model with the actor's context rows, set layout and -- bit for bit -- transform"""
+        from carl_amd.brax_policy import BraxMLPPolicy
+
+        if (not isinstance(value_net, BraxMLPPolicy) or value_net.head != "value" or value_net.n_out != 1
+                or value_net.obs_dim != self.D):
+            raise ValueError(f"value_net must be a carl_amd.brax_policy.BraxMLPPolicy built with head='value' for this "
+                             f"engine's model ({self.D} observations)")
+        VecEngine._check_value_net(self, policy, value_net)  # (the rules the two engines share)
+
     def rollout_policy(self, policy, n_steps: int, out: dict | None = None, mode: str = "transitions", *,
-                       deterministic: bool = True, sample_seed: int = 0, log_prob: bool = False) -> dict:
+                       deterministic: bool = True, sample_seed: int = 0, log_prob: bool = False, value_net=None,
+                       bootstrap_truncated: bool = True, gae: tuple | None = None) -> dict:
         """``n_steps`` steps in ONE launch, each env's action computed inside the rollout kernel by ``policy`` (a
         ``carl_amd.brax_policy.BraxMLPPolicy``) from the env's current context and observation (include/carl_amd.h:
         carl_brax_rollout_policy).  ``mode="transitions"``: ``rollout``'s dict (``alloc_rollout(T, action=True)`` layout)
@@ -353,10 +377,34 @@ class BraxVecEngine(LaneEngine):
         split into launches; ``"action"`` holds the raw samples, which the step clips as it clips any action, and
         ``rollout`` of them still gives the same bits.  ``log_prob=True`` (sampled, transitions mode) adds ``"log_prob"``
         ``[T, N]`` float32: the joint log-probability of each env-step's action (a buffer in ``out`` is checked like
-        ``"action"``).  With the caller's critic on ``"obs"`` and ``gae`` that is a PPO collection step."""
+        ``"action"``).
+        ``value_net=critic`` (a ``BraxMLPPolicy`` with ``head="value"``; sampled, transitions mode): the critic runs inside
+        the same launch on the inputs the actor sees (include/carl_amd.h: carl_brax_rollout_policy_valued) and the result
+        gains ``"value"`` ``[T, N]`` (V of the input each action was chosen from), ``"last_value"`` ``[N]`` (V of each env's
+        input after the last step: its current context and observation), ``"log_prob"`` (always) and, with
+        ``bootstrap_truncated`` (needs ``auto_reset``), ``"boot_value"`` ``[T, N]``: V of the terminal observation under the
+        context the episode ran in where a step ended an episode by truncation alone, +0 elsewhere (SB3's timeout
+        bootstrap).  Right under every context selector.  Everything else the launch writes keeps its bits.  Buffers in
+        ``out`` are checked like ``"log_prob"``.  ``gae=(gamma, lam)`` adds ``"advantage"`` and ``"return"`` ``[T, N]``
+        from one ``gae`` launch of the launch's own columns on the same stream: a PPO collection step."""
         self._check_policy(policy, "rollout_policy")
         if mode not in ("transitions", "summary"):
             raise ValueError(f"mode {mode!r}: 'transitions' or 'summary'")
+        if gae is not None and value_net is None:
+            raise ValueError("gae=(gamma, lam) needs value_net: advantages are computed from the critic's values")
+        if value_net is not None:
+            if deterministic:
+                raise ValueError("value_net: sampled launches only (deterministic=False); a deterministic valued launch "
+                                 "is not built for the Brax families")
+            if mode == "summary":
+                raise ValueError("value_net: transitions mode only (mode='summary' stores nothing per step)")
+            self._check_value_net(policy, value_net)
+            if bootstrap_truncated and not self.auto_reset:
+                raise ValueError("bootstrap_truncated=True needs auto_reset=True: without it no terminal observation is "
+                                 "kept apart from the next one (pass bootstrap_truncated=False)")
+            if gae is not None:
+                gamma, lam = (float(v) for v in gae)
+            log_prob = True  # (a valued launch always stores the log-probabilities)
         if log_prob and deterministic:
             raise ValueError("log_prob=True: sampled launches only (deterministic=False)")
         if log_prob and mode == "summary":
@@ -382,13 +430,18 @@ class BraxVecEngine(LaneEngine):
                 raise ValueError(f"rollout_policy output needs a contiguous float32 'action' [>= {T}, {self.n}, "
                                  f"{self.sys.n_act}] buffer on {self.device}")
             if log_prob:
-                lp = res.get("log_prob")
-                if lp is None:
-                    lp = res["log_prob"] = torch.empty((T, self.n), dtype=torch.float32, device=self.device)
-                if (lp.dtype != torch.float32 or lp.device != self.device or lp.dim() != 2 or lp.shape[0] < T
-                        or lp.shape[1] != self.n or not lp.is_contiguous()):
-                    raise ValueError(f"rollout_policy output needs a contiguous float32 'log_prob' [>= {T}, {self.n}] "
-                                     f"buffer on {self.device}")
+                self._policy_column(res, "log_prob", T)
+            if value_net is not None:
+                self._policy_column(res, "value", T)
+                if bootstrap_truncated:
+                    self._policy_column(res, "boot_value", T)
+                lv = res.get("last_value")
+                if lv is None:
+                    lv = res["last_value"] = torch.empty(self.n, dtype=torch.float32, device=self.device)
+                if (lv.dtype != torch.float32 or lv.device != self.device or tuple(lv.shape) != (self.n,)
+                        or not lv.is_contiguous()):
+                    raise ValueError(f"rollout_policy 'last_value' must be a contiguous float32 [{self.n}] tensor on "
+                                     f"{self.device}")
             io, summ = C.byref(self._rollout_io(a, _lib.ACTION_F32, res, T)), None
         # (after ``autotune``: the width that was fastest for the OPEN-loop rollout of this length class.  The closed loop
         # has 164 more LDS rows per env and another instruction mix; whether its best width differs is not measured)
@@ -403,15 +456,27 @@ class BraxVecEngine(LaneEngine):
             smp = _lib.PolicySampling(int(sample_seed) & (2**64 - 1), policy.device_log_std(self.device).data_ptr(),
                                       _ptr(res["log_prob"]) if log_prob else None)
             fn, head = self.lib.carl_brax_rollout_policy_sampled, (*head, C.byref(smp))
+        tail = ()
+        if value_net is not None:  # its valued twin: the critic behind the actor, the three columns behind the summary
+            cparams = value_net.device_params(self.device)
+            crit = value_net.struct(self.n, cparams.data_ptr())
+            vout = _lib.PolicyValue(_ptr(res["value"]), _ptr(res["last_value"]),
+                                    _ptr(res["boot_value"]) if bootstrap_truncated else None)
+            fn, head, tail = self.lib.carl_brax_rollout_policy_valued, (*head[:5], C.byref(crit), head[5]), (C.byref(vout),)
         goal = self.sys.goal_mode and mode == "transitions"
         if goal:
             self.b.success = res["success"].data_ptr()  # [T][N] for the duration of this launch
         try:
             with torch.cuda.device(self.device):
-                _lib.check(fn(*head, io, T, summ, self._stream()))
+                _lib.check(fn(*head, io, T, summ, *tail, self._stream()))
         finally:
             if goal:
                 self.b.success = self.success.data_ptr()
+        if gae is not None:
+            adv = self.gae(res["reward"][:T], res["value"][:T], res["terminated"][:T], res["truncated"][:T],
+                           res["last_value"], gamma, lam, boot_value=res["boot_value"][:T] if bootstrap_truncated else None,
+                           out={k: res[k] for k in ("advantage", "return") if k in res} or None)
+            res["advantage"], res["return"] = adv["advantage"], adv["return"]
         return res
 
     def evaluate_policy(self, *args, **kwargs):

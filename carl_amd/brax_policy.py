@@ -14,12 +14,20 @@ with a ``BraxMLPPolicy`` template merges them into running statistics on the dev
 
 ``rollout_policy(..., deterministic=False)`` samples each action from a diagonal Gaussian around the head's outputs
 (include/carl_amd.h: carl_brax_rollout_policy_sampled): ``log_std`` holds one state-independent value per weight set and
-actuator, as SB3's ``log_std`` parameter does, and ``log_prob=True`` returns each env-step's joint log-probability.  With
-the caller's torch critic on the returned ``obs`` rows and ``BraxVecEngine.gae`` that is a PPO collection step.
+actuator, as SB3's ``log_std`` parameter does, and ``log_prob=True`` returns each env-step's joint log-probability.
+
+Value networks: ``head="value"`` (the constructor, ``for_env``, ``from_sequential``) builds a critic for the model -- one
+output, no ``log_std`` -- packed, stacked and uploaded by the same code.  ``rollout_policy(..., deterministic=False,
+value_net=critic)`` evaluates it inside the same launch on the inputs the actor sees (include/carl_amd.h:
+carl_brax_rollout_policy_valued): ``"value"``, ``"last_value"`` and the timeout bootstrap ``"boot_value"`` are right
+under every context selector, because the launch knows the context each env ran in at every step; ``gae=(gamma, lam)``
+adds advantages and returns from one more launch.  That is a PPO collection step with no host synchronisation.  The
+critic reads the actor's transformed inputs, so its ``input_shift`` / ``input_scale`` / ``input_clip`` must equal the
+actor's bit for bit.
 
 At most ``CARL_POLICY_MAX_IN`` = 32 inputs: Humanoid's and HumanoidStandup's 244 observations do not fit.  Still out of
 scope: a sampled episodes mode (``evaluate_episodes`` and ``EvolutionStrategy`` stay deterministic; ``evaluate_policy``
-stays the classic-control families'), a critic inside the Brax launch, Humanoid-size inputs and ``MixedVecEngine``.
+stays the classic-control families'), a critic next to a deterministic actor, Humanoid-size inputs and ``MixedVecEngine``.
 """
 from __future__ import annotations
 
@@ -47,17 +55,24 @@ class BraxMLPPolicy(MLPPolicy):
     """One or more weight sets of one MLP shape for one Brax model (see the module docstring).  ``info``: the engine's
     info record (``BraxVecEngine.info``); the other parameters are ``MLPPolicy``'s, but ``log_std``: a float or ``[n_act]``
     values (default 0), held as float32 ``[n_sets, n_act]`` -- ``stack`` concatenates the sets' rows, ``on_device(...,
-    log_std=)`` takes a ``[n_sets, n_act]`` device tensor and ``device_log_std`` uploads it."""
+    log_std=)`` takes a ``[n_sets, n_act]`` device tensor and ``device_log_std`` uploads it.  ``head="value"``: a critic --
+    the last layer has one output and ``log_std`` is an empty ``[n_sets, 0]`` array (passing one is refused)."""
 
     _STATS_MERGE = "carl_brax_policy_stats_merge"  # (n_out up to the model's actuators: the Brax packing rule)
 
     def __init__(self, info, ctx_rows: Sequence[int], layers: Sequence, activation: str = "tanh", input_shift=None,
-                 input_scale=None, input_clip: float | None = None, context_names: Sequence | None = None, log_std=None):
+                 input_scale=None, input_clip: float | None = None, context_names: Sequence | None = None, log_std=None,
+                 head: str = "policy"):
         from carl_amd.brax_engine import _BRAX_FAMILY
 
         super().__init__(_BRAX_FAMILY, info.obs_dim, ctx_rows, layers, activation, input_shift, input_scale, input_clip,
-                         context_names, None, "policy", info=info)
+                         context_names, None, head, info=info)
         self._info = info  # (unpack builds its result through this constructor)
+        if head == "value":  # a critic samples nothing: no column per actuator (stack / on_device keep the empty shape)
+            if log_std is not None:
+                raise ValueError("log_std: a value network samples nothing")
+            self.log_std = np.zeros((1, 0), np.float32)
+            return
         if hasattr(log_std, "detach"):
             log_std = log_std.detach().cpu()
         ls = np.asarray(0.0 if log_std is None else log_std, np.float32).reshape(-1)
@@ -72,14 +87,16 @@ class BraxMLPPolicy(MLPPolicy):
 
     @classmethod
     def for_env(cls, env, layers: Sequence, activation: str = "tanh", input_shift=None, input_scale=None,
-                input_clip: float | None = None, context_features: Sequence | None = None, log_std=None) -> "BraxMLPPolicy":
+                input_clip: float | None = None, context_features: Sequence | None = None, log_std=None,
+                head: str = "policy") -> "BraxMLPPolicy":
         """A policy for ``env`` (a ``CARLBraxEnv`` or ``BraxVecEngine``) from explicit ``(W [out, in], b [out])`` arrays,
         hidden layers first, the head (``n_act`` outputs) last; ``context_features`` as ``MLPPolicy.for_env``'s;
-        ``log_std``: a float or ``[n_act]`` values (default 0), for sampled launches.  (``from_sequential`` passes its
-        keywords, ``log_std=`` among them, through to here.)"""
+        ``log_std``: a float or ``[n_act]`` values (default 0), for sampled launches; ``head="value"``: a critic, whose
+        last layer has one output.  (``from_sequential`` passes its keywords, ``log_std=`` and ``head=`` among them,
+        through to here.)"""
         eng, _ = _brax_engine_of(env)
         rows, names = flattened_context_rows(env, context_features, _brax_engine_of)
-        return cls(eng.info, rows, layers, activation, input_shift, input_scale, input_clip, names, log_std)
+        return cls(eng.info, rows, layers, activation, input_shift, input_scale, input_clip, names, log_std, head)
 
     @staticmethod
     def unpack(template, packed, log_std=None) -> "BraxMLPPolicy":
@@ -104,4 +121,4 @@ class BraxMLPPolicy(MLPPolicy):
             off += W.size + b.size
         n = template.n_in
         return BraxMLPPolicy(template._info, template.ctx_rows, layers, template.activation, flat[off: off + n],
-                             flat[off + n: off + 2 * n], flat[off + 2 * n], template.context_names)
+                             flat[off + n: off + 2 * n], flat[off + 2 * n], template.context_names, head=template.head)

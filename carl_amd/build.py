@@ -29,13 +29,14 @@ ARCH = "gfx950"
 # carl_brax_episodes.hip (the episodes mode of that rollout) instantiates the same mode's episodes variant: the same flags.
 # carl_brax_policy_stats.hip (that mode gathering input statistics) instantiates the episodes variant once more: its flags.
 # carl_brax_policy_sample.hip (the sampled twin of carl_brax_policy.hip's rollout) instantiates that mode's sampled variant: its flags.
-# (The four closed-loop units expand one list of instances and share one host launch path: csrc/brax_policy_host.hpp.)
+# carl_brax_policy_value.hip (the sampled rollout with a critic) instantiates the sampled variant's valued variant: its flags.
+# (The five closed-loop units expand one list of instances and share one host launch path: csrc/brax_policy_host.hpp.)
 SOURCES = {"carl_amd.hip": ["-fno-slp-vectorize"], "carl_brax.hip": ["-fno-slp-vectorize"],
            "carl_policy.hip": ["-fno-slp-vectorize"], "carl_policy_sample.hip": ["-fno-slp-vectorize"],
            "carl_policy_value.hip": ["-fno-slp-vectorize"], "carl_es.hip": ["-fno-slp-vectorize"],
            "carl_policy_stats.hip": ["-fno-slp-vectorize"], "carl_brax_policy.hip": ["-fno-slp-vectorize"],
            "carl_brax_episodes.hip": ["-fno-slp-vectorize"], "carl_brax_policy_stats.hip": ["-fno-slp-vectorize"],
-           "carl_brax_policy_sample.hip": ["-fno-slp-vectorize"]}
+           "carl_brax_policy_sample.hip": ["-fno-slp-vectorize"], "carl_brax_policy_value.hip": ["-fno-slp-vectorize"]}
 
 
 def _hipcc() -> str:

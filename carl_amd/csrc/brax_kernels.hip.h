@@ -408,11 +408,13 @@ __host__ __device__ inline Layout policy_layout_of(const carl_brax_sys_t& s) {
 // run()'s policy argument in modes 0 and 1: none.  kEpisodes: the policy type selects the episodes variant of MODE 2
 // (brax_episodes_kernels.hip.h: BraxEpisodesPolicy); kStats: its variant that also gathers input statistics
 // (brax_stats_kernels.hip.h: BraxStatsPolicy); kSampled: the transitions / summary variant whose actions are drawn around
-// the head's outputs (brax_sample_kernels.hip.h: BraxSampledPolicy).
+// the head's outputs (brax_sample_kernels.hip.h: BraxSampledPolicy); kValued: the sampled transitions variant that also
+// evaluates a critic (brax_value_kernels.hip.h: BraxValuedPolicy).
 struct NoPolicy {
   static constexpr bool kEpisodes = false;
   static constexpr bool kStats = false;
   static constexpr bool kSampled = false;
+  static constexpr bool kValued = false;
 };
 
 // tree topology derived from the model table once per workgroup
@@ -2220,6 +2222,12 @@ static __device__ __forceinline__ void write_ctx_obs(const carl_batch_t& b, cons
 // alone): the policy is called with what keys the env-step's draws -- the env's global index, its episode counter and its
 // step count in the episode, all three in registers here -- and with where the step's log-probability goes
 // (brax_sample_kernels.hip.h); everything else, the summary mode and the fragment hand-over included, is mode 2's.
+// the sampled variant with Pol::kValued (include/carl_amd.h: carl_brax_rollout_policy_valued; compiled from
+// carl_brax_policy_value.hip alone; transitions mode only): the policy's act_sampled also evaluates the critic on the
+// step's inputs and stores value[t][env] (brax_value_kernels.hip.h); here, a step that ends an episode by truncation
+// alone evaluates it once more on the terminal observation, which the io rows hold until the auto-reset, with the context
+// part of the x rows still the episode's (boot_value, +0.0f on every other env-step), and the fragment that runs the
+// launch's last step evaluates it on each env's inputs after that step (last_value).
 // F32 (MODE 1, CARL_FLAG_BRAX_FP32): the n_frames substeps of an env step run their pose algebra in float32.
 template <int MODE, bool MULTI, bool TASK, bool PLANAR = false, bool F32 = false, class Pol = NoPolicy>
 static __device__ __forceinline__ void run(const carl_batch_t& b, const carl_brax_sys_t* __restrict__ sys_dev,
@@ -2304,6 +2312,8 @@ static __device__ __forceinline__ void run(const carl_batch_t& b, const carl_bra
   static_assert(!ST || EP, "input statistics are gathered in the episodes mode");
   constexpr bool SM = Pol::kSampled;
   static_assert(!SM || (MODE == 2 && !EP), "sampled actions are a variant of the transitions / summary closed-loop rollout");
+  constexpr bool VL = Pol::kValued;
+  static_assert(!VL || SM, "the critic is evaluated in the sampled closed-loop rollout");
 
   if constexpr (MODE == 0) {
     const int gwave = (int)blockIdx.x * n_waves + wave;  // global wavefront = group of kEnvs envs
@@ -2640,6 +2650,9 @@ static __device__ __forceinline__ void run(const carl_batch_t& b, const carl_bra
         io.terminated[step_off + env] = (uint8_t)terminated;
         io.truncated[step_off + env] = (uint8_t)truncated;
         if (io.done != nullptr && n_steps == 1) io.done[env] = (uint8_t)(terminated | truncated);  // per-call step
+        if constexpr (VL) {  // (a step truncated alone: its slot is stored in the done block below, and only there)
+          if (pol.boot_value != nullptr && !(truncated && !terminated)) pol.boot_value[step_off + env] = 0.0f;
+        }
       }
       prof.mark(kProfReward);
       if (__builtin_expect(ballot(done) != 0ull, 0)) {  // (cold: the register allocator may spill around it, not through the step)
@@ -2674,6 +2687,13 @@ static __device__ __forceinline__ void run(const carl_batch_t& b, const carl_bra
         }
         log_finished(b, done && m.sub == 0 && (!EP || live), genv, fin_ret, fin_len);
         if (b.flags & CARL_FLAG_AUTORESET) {
+          if constexpr (VL) {
+            // the timeout bootstrap: V([the episode's context values, terminal observation]) while the io rows still hold
+            // that observation and the x rows that context (boot_value needs auto-reset: checked by the host)
+            const bool boot = done && truncated && !terminated;
+            if (pol.boot_value != nullptr && ballot(boot) != 0ull)
+              pol.template value_of_io<kSub>(m, pol_rows, env, boot, s.obs_dim, pol.boot_value + (step_off + (size_t)env));
+          }
           if (io.final_obs != nullptr)  // terminal observation, done envs only
             record_out(io.final_obs + step_off * s.obs_dim, (size_t)env, s.obs_dim, m, done);
           phase_sync();  // the io rows are rewritten below
@@ -2763,6 +2783,17 @@ static __device__ __forceinline__ void run(const carl_batch_t& b, const carl_bra
         }
       }
     } else {
+    if constexpr (VL) {
+      if (t_hi == T) {  // the launch's last step ran here: V of each env's inputs after it (wavefront-uniform)
+        // (opaque copies of the lane's coordinates, as the episodes mode's stores take them: no address of this block is
+        // hoisted through the step loop)
+        Lds m_last = m_launch;
+        int env_last = env_frag;
+        asm volatile("" : "+v"(m_last.sub), "+v"(m_last.env), "+v"(env_last));
+        pol.template put_context<kSub>(m_last, pol_rows, b, r.cidx, env_last, active);
+        pol.template value_of_io<kSub>(m_last, pol_rows, env_last, active, s.obs_dim, pol.last_value + env_last);
+      }
+    }
     if constexpr (MODE == 2) {
       record_out(pol.cur_obs, (size_t)env, s.obs_dim, m, active);  // the env's current observation (the io rows hold it)
       if (lead && pol.sum.episodes != nullptr) {

@@ -1,8 +1,8 @@
-// brax_policy_host.hpp -- the host side of the closed-loop entry points of the Brax families, shared by their four
+// brax_policy_host.hpp -- the host side of the closed-loop entry points of the Brax families, shared by their five
 // translation units (carl_brax_policy.hip: carl_brax_rollout_policy; carl_brax_episodes.hip: carl_brax_evaluate_policy;
 // carl_brax_policy_stats.hip: carl_brax_evaluate_policy_stats; carl_brax_policy_sample.hip:
-// carl_brax_rollout_policy_sampled): the packed size of a policy's shape, the kernel class of a
-// closed-loop launch, the policy's validation against the batch and the model, the list of kernel instances and the entry
+// carl_brax_rollout_policy_sampled; carl_brax_policy_value.hip: carl_brax_rollout_policy_valued): the packed size of a
+// policy's shape, the kernel class of a closed-loop launch, the policy's validation against the batch and the model, the list of kernel instances and the entry
 // type of a unit's table of them, the kernels' policy argument, the launch shape and the launch.  Host code only; the
 // kernels are each unit's own: every table is one expansion of the list with the unit's kernel template.
 #pragma once
@@ -85,8 +85,8 @@ inline int validate_closed_loop(const char* who, const carl_batch_t* batch, cons
   return validate_policy(who, batch, sys_host, policy_host);
 }
 
-// What the rollout entry points (carl_brax_rollout_policy, carl_brax_rollout_policy_sampled) check after that, in this
-// order: the step count, io (NULL: summary mode) and the summary.
+// What the rollout entry points (carl_brax_rollout_policy, carl_brax_rollout_policy_sampled,
+// carl_brax_rollout_policy_valued) check after that, in this order: the step count, io (NULL: summary mode) and the summary.
 inline bool summary_complete(const carl_policy_summary_t* s) { return s->episodes && s->return_sum && s->length_sum; }
 inline int validate_rollout(const char* who, const carl_batch_t* batch, const carl_step_io_t* io, int32_t n_steps,
                             const carl_policy_summary_t* summary_out) {
@@ -102,6 +102,26 @@ inline int validate_rollout(const char* who, const carl_batch_t* batch, const ca
   if (summary_out != nullptr && !(batch->flags & CARL_FLAG_AUTORESET))
     return fail(CARL_ERR_UNSUPPORTED, "%s: a summary needs CARL_FLAG_AUTORESET (without auto-reset a finished lane "
                 "reports done on every later step, and its episode would be counted on each of them)", who);
+  return 0;
+}
+
+// What the sampled entry points (carl_brax_rollout_policy_sampled, carl_brax_rollout_policy_valued) check after that, in
+// this order.  block << 28 | elapsed under the draws' 0x40000000 tag: two bits of block (eight actuators), 28 of elapsed.
+constexpr int kMaxSampledAct = 8;
+constexpr int64_t kMaxSampledEpisodeSteps = (int64_t)1 << 28;
+inline int validate_sampling(const char* who, const carl_batch_t* batch, const carl_brax_sys_t* sys_host,
+                             const carl_step_io_t* io, const carl_policy_sampling_t* sampling) {
+  if (sampling == nullptr) return fail(CARL_ERR_INVALID_ARGUMENT, "%s: sampling is NULL", who);
+  if (sampling->log_std == nullptr)
+    return fail(CARL_ERR_INVALID_ARGUMENT, "%s: sampling->log_std is NULL (one value per weight set and actuator)", who);
+  if (io == nullptr && sampling->log_prob != nullptr)
+    return fail(CARL_ERR_INVALID_ARGUMENT, "%s: log_prob in summary mode (io NULL): a summary stores nothing per step", who);
+  if (sys_host->n_act > kMaxSampledAct)
+    return fail(CARL_ERR_INVALID_ARGUMENT, "%s: %d actuators: the draws' counter holds the Philox block in two bits (at most "
+                "%d actuators)", who, sys_host->n_act, kMaxSampledAct);
+  if (batch->max_episode_steps <= 0 || (int64_t)batch->max_episode_steps > kMaxSampledEpisodeSteps)
+    return fail(CARL_ERR_INVALID_ARGUMENT, "%s: max_episode_steps %lld outside [1, 2^28]: the draws' counter holds the step "
+                "count of an episode in 28 bits", who, (long long)batch->max_episode_steps);
   return 0;
 }
 
@@ -121,7 +141,7 @@ inline int validate_episodes(const char* who, const carl_batch_t* batch, int32_t
   return 0;
 }
 
-// Every instantiated closed-loop kernel<MULTI, K, TASK, PLANAR>, of each of the four variants: the non-F32 step classes
+// Every instantiated closed-loop kernel<MULTI, K, TASK, PLANAR>, of each of the five variants: the non-F32 step classes
 // of carl_brax.hip's kBraxKernels, at the widths it has for them (tests/test_brax_policy_abi.py holds the list against
 // that table).  A unit's table is `#define X(M, K, T, P) {{M, T, P, false}, K, its_kernel<M, K, T, P>},` around one
 // expansion.

@@ -38,10 +38,17 @@ struct PlainHead {
   static constexpr bool kOn = false;
 };
 
+// act()'s hook between the input phase and the layers: none.  brax_value_kernels.hip.h has the one that evaluates a
+// critic on the x rows there, while the h1 / h2 rows are still dead.
+struct NoInputUse {
+  static constexpr bool kOn = false;
+};
+
 struct BraxPolicy {
   static constexpr bool kEpisodes = false;  // (run(): not the episodes variant -- brax_episodes_kernels.hip.h)
   static constexpr bool kStats = false;     // (nor its statistics variant -- brax_stats_kernels.hip.h)
   static constexpr bool kSampled = false;   // (nor the sampled variant -- brax_sample_kernels.hip.h)
+  static constexpr bool kValued = false;    // (nor its valued variant -- brax_value_kernels.hip.h)
   carl_policy_t p;            // validated by the host (carl_brax_policy.hip)
   int set_floats;             // floats per packed weight set
   carl_policy_summary_t sum;  // per-env totals; all NULL: none
@@ -106,10 +113,12 @@ struct BraxPolicy {
   // `tap` (Tap::kOn): sees every raw input beside its shift where the first phase normalises it, marks the env before that
   // phase's hand-over and gathers behind it, while h2 and the summary-total rows are still dead.
   // `head` (Head::kOn): the head layer's hook, see layer().
-  template <int kSub, class LdsT, class Tap = NoInputTap, class Head = PlainHead>
+  // `use` (Use::kOn): runs behind the first phase's hand-over, when the x rows hold the transformed inputs and before the
+  // layers write h1 / h2; it may use h1, h2 and the fourth summary-total row and must end on a phase_sync.
+  template <int kSub, class LdsT, class Tap = NoInputTap, class Head = PlainHead, class Use = NoInputUse>
   __device__ __forceinline__ void act(const LdsT& m, int rows, const carl_batch_t& b, int cidx, int env, bool active,
                                       int obs_dim, int n_act, float* __restrict__ action_out, const Tap& tap = Tap(),
-                                      const Head& head = Head()) const {
+                                      const Head& head = Head(), const Use& use = Use()) const {
     const int X = rows, H1 = rows + kPolicyXRows, H2 = H1 + kPolicyHRows;
     const int n_in = p.n_in, n_ctx = p.n_ctx, nh = p.n_hidden;
     const int w0 = nh > 0 ? p.width[0] : 0, w1 = nh > 1 ? p.width[1] : 0;
@@ -138,6 +147,7 @@ struct BraxPolicy {
     if constexpr (Tap::kOn) tap.mark(m, H2 + kPolicyHRows);
     Group<kSub>::phase_sync();
     if constexpr (Tap::kOn) tap.template gather<kSub>(m, H2, H2 + kPolicyHRows, n_in);
+    if constexpr (Use::kOn) use.template run<kSub>(m, X, active);
     if (nh == 0) {
       layer<kSub, false>(m, w, p_w0, p_b0, n_in, n_act, X, m.lay.io, active, action_out, head);
     } else {

@@ -63,15 +63,16 @@ struct BraxSampledPolicy : BraxPolicy {
 
   // BraxPolicy::act with the Gaussian head.  genv / episode / elapsed: the env's global index, episode counter and step
   // count in its episode, as run() holds them at the top of the step; log_prob[lp_at] takes the step's log-probability
-  // when `per_step` (wavefront-uniform) and there is a log_prob array.
-  template <int kSub, class LdsT>
+  // when `per_step` (wavefront-uniform) and there is a log_prob array.  `use`: act()'s hook behind the input phase.
+  template <int kSub, class LdsT, class Use = NoInputUse>
   __device__ __forceinline__ void act_sampled(const LdsT& m, int rows, const carl_batch_t& b, int cidx, int env, bool active,
                                               uint64_t genv, uint32_t episode, int elapsed, int obs_dim, int n_act,
-                                              float* __restrict__ action_out, bool per_step, size_t lp_at) const {
+                                              float* __restrict__ action_out, bool per_step, size_t lp_at,
+                                              const Use& use = Use()) const {
     const int lp_row = rows + kPolicyXRows + (p.n_hidden == 1 ? kPolicyHRows : 0);
     const GaussianHead head{seed, genv, episode - 1u, kSubBraxSample | (uint32_t)elapsed,
                             log_std + (size_t)(active ? env / p.lanes_per_set : 0) * n_act, lp_row};
-    this->template act<kSub>(m, rows, b, cidx, env, active, obs_dim, n_act, action_out, NoInputTap(), head);
+    this->template act<kSub>(m, rows, b, cidx, env, active, obs_dim, n_act, action_out, NoInputTap(), head, use);
     if (per_step && log_prob != nullptr) {
       if (active && m.sub == 0) {
 #pragma clang fp contract(off)

@@ -26,10 +26,6 @@ using carl_host::brax::BraxClass;
 const carl_host::brax::ClosedLoopKernel<carl::brax::BraxSampledPolicy> kBraxSampledKernels[] = {CARL_BRAX_CLOSED_LOOP_INSTANCES(X)};
 #undef X
 
-// block << 28 | elapsed under the 0x40000000 tag: two bits of block (eight actuators), 28 of elapsed
-constexpr int kMaxSampledAct = 8;
-constexpr int64_t kMaxEpisodeSteps = (int64_t)1 << 28;
-
 }  // namespace
 
 extern "C" {
@@ -42,17 +38,7 @@ int carl_brax_rollout_policy_sampled(const carl_batch_t* batch, const carl_brax_
   BraxClass c;
   if (int e = carl_host::brax::validate_closed_loop(who, batch, sys_dev, sys_host, obs, policy_host, &c)) return e;
   if (int e = carl_host::brax::validate_rollout(who, batch, io, n_steps, summary_out)) return e;
-  if (sampling == nullptr) return fail(CARL_ERR_INVALID_ARGUMENT, "%s: sampling is NULL", who);
-  if (sampling->log_std == nullptr)
-    return fail(CARL_ERR_INVALID_ARGUMENT, "%s: sampling->log_std is NULL (one value per weight set and actuator)", who);
-  if (io == nullptr && sampling->log_prob != nullptr)
-    return fail(CARL_ERR_INVALID_ARGUMENT, "%s: log_prob in summary mode (io NULL): a summary stores nothing per step", who);
-  if (sys_host->n_act > kMaxSampledAct)
-    return fail(CARL_ERR_INVALID_ARGUMENT, "%s: %d actuators: the draws' counter holds the Philox block in two bits (at most "
-                "%d actuators)", who, sys_host->n_act, kMaxSampledAct);
-  if (batch->max_episode_steps <= 0 || (int64_t)batch->max_episode_steps > kMaxEpisodeSteps)
-    return fail(CARL_ERR_INVALID_ARGUMENT, "%s: max_episode_steps %lld outside [1, 2^28]: the draws' counter holds the step "
-                "count of an episode in 28 bits", who, (long long)batch->max_episode_steps);
+  if (int e = carl_host::brax::validate_sampling(who, batch, sys_host, io, sampling)) return e;
   if (batch->n_lanes == 0 || n_steps == 0) return carl_host::policy_rollout_without_steps(who, batch, summary_out, stream);
 
   carl_step_io_t io_v{};

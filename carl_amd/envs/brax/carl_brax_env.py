@@ -331,13 +331,16 @@ class CARLBraxEnv(CARLEnv):
         return self._with_goal_text(obs, info.get("context_id")), info
 
     def rollout_policy(self, policy, n_steps: int, out: dict | None = None, mode: str = "transitions", *,
-                       deterministic: bool = True, sample_seed: int = 0, log_prob: bool = False) -> dict:
+                       deterministic: bool = True, sample_seed: int = 0, log_prob: bool = False, value_net=None,
+                       bootstrap_truncated: bool = True, gae: tuple | None = None) -> dict:
         """``n_steps`` closed-loop steps of every env in one launch, actions computed inside the rollout kernel by
         ``policy`` (``carl_amd.brax_policy.BraxMLPPolicy.for_env(self, ...)``): ``BraxVecEngine.rollout_policy`` of this
         env's engine (``deterministic=False``: actions sampled from the policy's Gaussian, ``log_prob=True``: with their
-        log-probabilities).  The host selector object is not consulted."""
+        log-probabilities; ``value_net`` / ``bootstrap_truncated`` / ``gae``: critic values and GAE advantages from the
+        same launch, see there).  The host selector object is not consulted."""
         return self.env.rollout_policy(policy, n_steps, out=out, mode=mode, deterministic=deterministic,
-                                       sample_seed=sample_seed, log_prob=log_prob)
+                                       sample_seed=sample_seed, log_prob=log_prob, value_net=value_net,
+                                       bootstrap_truncated=bootstrap_truncated, gae=gae)
 
     def evaluate_episodes(self, policy, n_episodes: int, max_steps: int, seed: int | None = None,
                           input_stats: bool = False) -> dict:

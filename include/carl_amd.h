@@ -918,8 +918,8 @@ int carl_brax_fragment_plan(int32_t n_groups, int32_t n_workgroups, int32_t wave
  * The batch, the model and io are checked as carl_brax_rollout checks them.  CARL_FLAG_BRAX_FP32 is refused with
  * CARL_ERR_UNSUPPORTED; both auto-reset modes and the goal wrapper work as in carl_brax_rollout.  Sampled actions and
  * their log-probabilities: carl_brax_rollout_policy_sampled below; the episodes mode: carl_brax_evaluate_policy, its input
- * statistics carl_brax_evaluate_policy_stats.  Out of scope: a sampled episodes mode, a critic inside the launch (the
- * caller's critic on the returned obs rows, then carl_gae, which takes dense [T][n_lanes] rows) and Humanoid-size inputs. */
+ * statistics carl_brax_evaluate_policy_stats; a critic inside the sampled launch: carl_brax_rollout_policy_valued (then
+ * carl_gae, which takes dense [T][n_lanes] rows).  Out of scope: a sampled episodes mode and Humanoid-size inputs. */
 int carl_brax_rollout_policy(const carl_batch_t* batch, const carl_brax_sys_t* sys_dev, const carl_brax_sys_t* sys_host,
                              float* obs, const carl_policy_t* policy_host, const carl_step_io_t* io, int32_t n_steps,
                              const carl_policy_summary_t* summary_out, void* stream);
@@ -953,11 +953,43 @@ int carl_brax_rollout_policy(const carl_batch_t* batch, const carl_brax_sys_t* s
  * Validation: everything carl_brax_rollout_policy checks, in its order and with its codes; then `sampling` non-NULL,
  * log_std non-NULL, no log_prob in summary mode (io == NULL), sys.n_act <= 8 and 0 < batch->max_episode_steps <= 2^28, each refused with
  * CARL_ERR_INVALID_ARGUMENT before anything is enqueued.  n_lanes == 0 enqueues nothing.  The launch has the shape
- * carl_brax_policy_launch_shape reports.  Out of scope: a sampled episodes mode and a critic inside the launch. */
+ * carl_brax_policy_launch_shape reports.  With a critic: carl_brax_rollout_policy_valued.  Out of scope: a sampled episodes
+ * mode. */
 int carl_brax_rollout_policy_sampled(const carl_batch_t* batch, const carl_brax_sys_t* sys_dev, const carl_brax_sys_t* sys_host,
                                      float* obs, const carl_policy_t* policy_host, const carl_policy_sampling_t* sampling,
                                      const carl_step_io_t* io, int32_t n_steps, const carl_policy_summary_t* summary_out,
                                      void* stream);
+/* ---- a critic in the sampled Brax launch (additive; ABI version unchanged) ----
+ * carl_brax_rollout_policy_valued is the transitions-mode carl_brax_rollout_policy_sampled with a second network, the
+ * critic, evaluated inside the rollout kernel on the inputs the actor sees: everything the sampled call writes (records,
+ * actions, log-probabilities, engine state, `obs`, summary totals) keeps its bits, and the three columns of
+ * carl_policy_value_t are written beside them, dense rows as every Brax output.  carl_rollout_policy_valued's contract,
+ * for these families: with carl_gae one launch and one GAE launch fill an on-policy rollout buffer, under every context
+ * selector and without host synchronisation -- the launch knows the context an env ran in at every step, and at a
+ * truncation it still holds both the terminal observation and the context of the episode that just ended.
+ * The critic is a carl_policy_t with n_out == 1, hidden widths in [1, CARL_POLICY_MAX_WIDTH] and an activation of its own,
+ * and the actor's n_in, n_ctx, ctx_rows, n_sets and lanes_per_set; `head` is not read.  It reads the actor's transformed
+ * inputs x (after the actor's shift / scale / clip): the shift | scale | clip section of its own packed block is NOT READ.
+ * V = y[0]: bias first, explicit fma in input order, the actor's activations and tanh.  Its block is packed by the Brax
+ * rule (carl_brax_policy_set_floats() floats per set) and params starts on a 16-byte boundary.
+ *   value      [n_steps][n_lanes] fp32: V(x_t), x_t the input step t's action was chosen from
+ *   last_value [n_lanes] fp32: V of each env's input after the launch's last step -- its current context (the new one if
+ *              that step reset it) and its current observation
+ *   boot_value [n_steps][n_lanes] fp32, NULL: not wanted.  Needs CARL_FLAG_AUTORESET (CARL_ERR_UNSUPPORTED without).  On an
+ *              env-step with truncated && !terminated: V([context values of the context the episode ran in, terminal
+ *              observation]); +0.0f on every other env-step; every slot of rows [0, n_steps) is written.  Both auto-reset
+ *              modes give the same rule.
+ * Validation, in this order: everything carl_brax_rollout_policy checks (batch, model, policy / obs, the refusal of
+ * CARL_FLAG_BRAX_FP32, the policy; then n_steps, io, the summary); io != NULL (transitions mode only:
+ * CARL_ERR_INVALID_ARGUMENT); the sampling checks of carl_brax_rollout_policy_sampled, with `sampling` and
+ * sampling->log_prob required; the critic, each refusal with a message of its own; out, out->value and out->last_value
+ * non-NULL.  n_lanes == 0 or n_steps == 0 enqueues nothing and writes nothing.  The launch has the shape
+ * carl_brax_policy_launch_shape reports, and no LDS beyond the sampled launch's.  Out of scope: a deterministic valued
+ * launch. */
+int carl_brax_rollout_policy_valued(const carl_batch_t* batch, const carl_brax_sys_t* sys_dev, const carl_brax_sys_t* sys_host,
+                                    float* obs, const carl_policy_t* policy_host, const carl_policy_t* critic_host,
+                                    const carl_policy_sampling_t* sampling, const carl_step_io_t* io, int32_t n_steps,
+                                    const carl_policy_summary_t* summary_out, const carl_policy_value_t* out, void* stream);
 /* Episodes mode of carl_brax_rollout_policy (additive; ABI version unchanged): carl_evaluate_policy's semantics for the
  * Brax families, a variant of the same rollout kernel.  No reference counterpart: the reference evaluates a policy by
  * stepping the env per Python call until `done` (carl/envs/carl_env.py:321-342; examples/carl_with_sb3.py runs SB3's
@@ -1035,7 +1067,8 @@ int carl_brax_policy_stats_merge(const carl_policy_t* policy_host, const carl_po
                                  void* stream);
 /* floats per packed weight set of a Brax policy's shape (n_out up to CARL_BRAX_MAX_ACT); -1 for an invalid shape */
 int32_t carl_brax_policy_set_floats(const carl_policy_t* policy_host);
-/* The shape carl_brax_rollout_policy and carl_brax_rollout_policy_sampled launch for this batch, model and step count (host only, no device access beyond the
+/* The shape carl_brax_rollout_policy, carl_brax_rollout_policy_sampled and carl_brax_rollout_policy_valued launch for this
+ * batch, model and step count (host only, no device access beyond the
  * compute-unit count of the current device; 256 where there is none): with n_groups = ceil(n_lanes / (64 / lanes_per_env))
  * it is what carl_brax_fragment_plan takes. */
 typedef struct carl_brax_launch_shape {

@@ -60,10 +60,20 @@
                    spread of the deterministic side's repetitions, which a difference has to exceed to count).  Written
                    to key "brax_sample" of --out.
 
+  --legs brax_value  a critic inside the sampled Brax launch (runs on its own engines; --lanes is not used): Ant x 32 768 and
+                   Halfcheetah x 32 768, 100-step transitions launches, 2x64 tanh actor and critic, static selector,
+                   TimeLimit 1 000.  Sides: (a) the sampled launch with log_prob (the kernel of the parent commit:
+                   profiles/brax_policy_value_isa_identity.txt); (b) rollout_policy(value_net=); (c) the route to the same
+                   arrays without it: (a) with final_obs, then a torch critic of the same shape on the observation rows
+                   and the terminal rows (right only because the selector is static: no context inputs); (d) (b) and (c)
+                   each followed by gae.  State restored before each launch, device events, the sides interleaved over
+                   two rounds, a warm-up per side and round, the median and range of the 2 x --reps repetitions.
+                   Written to key "brax_value" of --out.
+
 Host timing with torch.cuda events around `--reps` launches after one warm-up launch; the median per launch is
 reported.  Kernel times belong to a separate `rocprofv3 --kernel-trace --stats` run of this script.
 
-  python tools/policy_rollout_bench.py [--lanes 65536] [--steps 1000] [--reps 5] [--legs rollout,evaluate,value,es,stats,brax_es,brax_stats,brax_sample] [--out FILE]
+  python tools/policy_rollout_bench.py [--lanes 65536] [--steps 1000] [--reps 5] [--legs rollout,evaluate,value,es,stats,brax_es,brax_stats,brax_sample,brax_value] [--out FILE]
 
 --out FILE: a JSON file whose keys of the legs run ("results": rollout, "evaluate") are replaced, others kept.
 """
@@ -560,7 +570,73 @@ def brax_sample_leg(reps, n=32768, steps=100, time_limit=1000):
     return rows
 
 
-BRAX_LEGS = (("brax_es", brax_es_leg), ("brax_stats", brax_stats_leg), ("brax_sample", brax_sample_leg))
+def brax_value_leg(reps, n=32768, steps=100, time_limit=1000):
+    """the valued launch against the sampled one, and against the sampled one followed by a torch critic: Ant and
+    Halfcheetah"""
+    from carl_amd import envs as E
+    from carl_amd.brax_policy import BraxMLPPolicy
+
+    rows = []
+    for model, cls in (("ant", E.CARLBraxAnt), ("halfcheetah", E.CARLBraxHalfcheetah)):
+        eng = brax_bench_engine(cls, n, time_limit)
+        pol = brax_bench_policy(eng)
+        rng = np.random.default_rng(1)
+        dims = [eng.D, 64, 64, 1]
+        layers = [((rng.normal(size=(o, i)) / np.sqrt(i)).astype(np.float32), np.zeros(o, np.float32))
+                  for i, o in zip(dims[:-1], dims[1:])]
+        crit = BraxMLPPolicy.for_env(eng, layers, "tanh", head="value")
+        net = torch.nn.Sequential(torch.nn.Linear(eng.D, 64), torch.nn.Tanh(), torch.nn.Linear(64, 64), torch.nn.Tanh(),
+                                  torch.nn.Linear(64, 1)).to(eng.device)
+        with torch.no_grad():
+            for lin, (W, b) in zip([m for m in net if isinstance(m, torch.nn.Linear)], layers):
+                lin.weight.copy_(torch.as_tensor(W))
+                lin.bias.copy_(torch.as_tensor(b))
+        snap = eng.snapshot()
+        f32 = lambda *shape: torch.empty(shape, dtype=torch.float32, device=eng.device)  # noqa: E731
+        out_a = dict(eng.alloc_rollout(steps, action=True), log_prob=f32(steps, n))
+        out_b = dict(eng.alloc_rollout(steps, action=True), log_prob=f32(steps, n), value=f32(steps, n),
+                     boot_value=f32(steps, n), last_value=f32(n), advantage=f32(steps, n))
+        out_b["return"] = f32(steps, n)
+        out_c = dict(eng.alloc_rollout(steps, final_obs=True, action=True), log_prob=f32(steps, n))
+        gae_c = {"advantage": f32(steps, n), "return": f32(steps, n)}
+        kw = dict(deterministic=False, sample_seed=1)
+
+        def torch_route(gae):
+            obs0 = eng.obs.clone()
+            o = eng.rollout_policy(pol, steps, out=out_c, log_prob=True, **kw)
+            with torch.no_grad():
+                before = torch.cat([obs0[None], o["obs"][:-1]])
+                value = net(before.reshape(steps * n, -1)).reshape(steps, n)
+                last = net(o["obs"][-1]).reshape(n)
+                cut = o["truncated"].bool() & ~o["terminated"].bool()
+                boot = torch.where(cut, net(torch.nan_to_num(o["final_obs"]).reshape(steps * n, -1)).reshape(steps, n),
+                                   torch.zeros((), device=eng.device))
+            if gae:
+                eng.gae(o["reward"], value, o["terminated"], o["truncated"], last, 0.99, 0.95, boot_value=boot, out=gae_c)
+
+        sides = {"sampled_log_prob": lambda: eng.rollout_policy(pol, steps, out=out_a, log_prob=True, **kw),
+                 "valued": lambda: eng.rollout_policy(pol, steps, out=out_b, value_net=crit, **kw),
+                 "sampled_then_torch_critic": lambda: torch_route(False),
+                 "valued_gae": lambda: eng.rollout_policy(pol, steps, out=out_b, value_net=crit, gae=(0.99, 0.95), **kw),
+                 "sampled_then_torch_critic_gae": lambda: torch_route(True)}
+        ts = {k: [] for k in sides}
+        for _ in range(2):  # interleaved: a drift of the clock over the run lands on every side
+            for k, fn in sides.items():
+                ts[k] += timed_from_snapshot(eng, snap, fn, reps)[1]
+        sec = {k: float(np.median(v)) for k, v in ts.items()}
+        r = {"config": f"brax_value_{model}_2x64_tanh", "envs": n, "steps": steps, "time_limit": time_limit,
+             "median_sec": sec, "range_sec": {k: [min(v), max(v)] for k, v in ts.items()},
+             "valued_over_sampled": sec["valued"] / sec["sampled_log_prob"],
+             "valued_over_torch_route": sec["valued"] / sec["sampled_then_torch_critic"],
+             "valued_gae_over_torch_route_gae": sec["valued_gae"] / sec["sampled_then_torch_critic_gae"],
+             "env_steps_per_s": {k: n * steps / v for k, v in sec.items()}, "reps_sec": ts}
+        rows.append(r)
+        print(json.dumps(r), flush=True)
+    return rows
+
+
+BRAX_LEGS = (("brax_es", brax_es_leg), ("brax_stats", brax_stats_leg), ("brax_sample", brax_sample_leg),
+             ("brax_value", brax_value_leg))
 
 
 def main():
@@ -594,6 +670,8 @@ def main():
         doc["brax_stats"] = brax_stats_leg(args.reps)
     if "brax_sample" in legs:
         doc["brax_sample"] = brax_sample_leg(args.reps)
+    if "brax_value" in legs:
+        doc["brax_value"] = brax_value_leg(args.reps)
     if "rollout" not in legs:
         return write(args.out, doc)
 
