@@ -28,6 +28,7 @@ _LAZY = {
     "CARLBraxHumanoidStiffness": "carl_amd.envs.brax",
     "VecEngine": "carl_amd.engine",
     "EvolutionStrategy": "carl_amd.es",
+    "PPO": "carl_amd.ppo",
 }
 
 

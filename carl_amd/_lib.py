@@ -367,3 +367,26 @@ EXPORTS.update({
     "carl_brax_policy_stats_merge": (C.c_int, [C.POINTER(Policy), C.POINTER(PolicyStats), C.c_int32, _vp, C.c_int32,
                                                C.POINTER(PolicyRunningStats), C.c_double, C.c_double, _vp, C.c_int32, _vp]),
 })
+
+
+# ---- the PPO update on the device (include/carl_amd.h: carl_policy_context_trace, carl_ppo_batch_t) ---------------
+class PpoBatch(C.Structure):
+    _fields_ = [("family", _i), ("n_lanes", _i), ("n_steps", _i), ("row_pitch", _i), ("obs_dim", _i), ("n_contexts", _i),
+                ("ctx_stride", _i), ("action_dtype", _i), ("n_samples", _i), ("reserved", _i),
+                ("clip_range", C.c_float), ("vf_coef", C.c_float), ("ent_coef", C.c_float), ("reserved2", _i),
+                ("obs0", _vp), ("obs", _vp), ("context_id", _vp), ("ctx_table", _vp), ("action", _vp), ("log_prob", _vp),
+                ("advantage", _vp), ("ret", _vp), ("idx", _vp), ("adv_norm", _vp)]
+
+
+class PpoOut(C.Structure):
+    _fields_ = [("grad_actor", _vp), ("grad_critic", _vp), ("grad_log_std", _vp), ("stats", _vp), ("new_log_prob", _vp),
+                ("new_value", _vp), ("workspace", _vp), ("workspace_floats", C.c_int64)]
+
+
+EXPORTS.update({
+    "carl_policy_context_trace": (C.c_int, [C.POINTER(Batch), _vp, _vp, _vp, _vp, C.c_int32, C.c_int32, _vp, _vp]),
+    "carl_ppo_tile": (C.c_int32, []),
+    "carl_ppo_grad_workgroups": (C.c_int32, [C.c_int32]),
+    "carl_ppo_workspace_floats": (C.c_int64, [C.POINTER(Policy), C.POINTER(Policy), C.c_int32]),
+    "carl_ppo_grad": (C.c_int, [C.POINTER(PpoBatch), C.POINTER(Policy), C.POINTER(Policy), _vp, C.POINTER(PpoOut), _vp]),
+})

@@ -1,0 +1,178 @@
+"""PPO on the device: collect, trace, update (include/carl_amd.h: carl_policy_context_trace, carl_ppo_grad).
+
+``PPO`` runs SB3's PPO (clipped surrogate, value loss, entropy bonus, GAE, advantage normalisation per minibatch, a
+global-norm gradient clip, Adam) on a classic-control ``CARLEnv`` or ``VecEngine`` as a fixed sequence of launches on the
+engine's stream:
+
+1. ``collect()``: clones ``ctx_idx`` / ``episode``, keeps the observation the first action is chosen from, runs
+   ``rollout_policy(deterministic=False, value_net=, gae=)`` -- one launch for the T steps of every lane with sampled
+   actions, log-probabilities, values, timeout bootstrap values, one for GAE -- and one ``context_trace`` launch that
+   rebuilds the context each step ran in (a moving selector changes it at every reset).
+2. ``update()``: per epoch a ``torch.randperm`` on the device, sliced into minibatches; per minibatch the advantage mean
+   and standard deviation by torch ops on the gathered slice, ``carl_ppo_grad`` (loss and gradients of the actor, the
+   critic and ``log_std`` in three launches, no floating-point atomics), the global-norm clip and ``torch.optim.Adam``
+   on the packed parameter tensors.  The gradient of a packed tensor's shift | scale | clip entries and padding is +0.0,
+   so Adam leaves them untouched.
+
+The actor, the critic and ``log_std`` live on the device as packed tensors, handed to the launches through
+``MLPPolicy.on_device``; nothing here reads a result back (``rollout_policy``'s check of the critic's transform section
+against the actor's compares the host templates' sections, which no update changes).  ``info`` holds device tensors.
+
+Out of scope, and refused as ``carl_amd.policy`` refuses them: the Brax families, ``MixedVecEngine`` pairs, the gymnasium
+drop-in.
+"""
+from __future__ import annotations
+
+import torch
+
+from carl_amd import _lib
+from carl_amd.policy import MLPPolicy, _engine_of
+
+
+class _ResidentPolicy(MLPPolicy):
+    """An ``on_device`` policy whose shift | scale | clip section is known on the host: the template's, which ``PPO`` never
+    changes (its gradient is +0.0).  ``rollout_policy`` compares the critic's section with the actor's at every launch; for
+    a plain ``on_device`` policy that is a device-to-host copy."""
+
+    def transform_section(self):
+        return self._host_section
+
+    @staticmethod
+    def of(template: MLPPolicy, params: torch.Tensor, lanes_per_set: int, log_std=None) -> "_ResidentPolicy":
+        out = MLPPolicy.on_device(template, params, lanes_per_set, log_std)
+        out.__class__ = _ResidentPolicy
+        out._host_section = template.transform_section().copy()
+        return out
+
+
+class PPO:
+    """``policy`` / ``value_net``: one-set host-built ``MLPPolicy`` objects for ``env`` (``head="policy"`` /
+    ``head="value"``, the critic's shift | scale | clip the actor's) -- the shapes and the starting parameters.
+    ``n_steps``: steps per lane and collection; ``batch_size``: samples per minibatch (default: a quarter of the buffer);
+    the other arguments are SB3's.  ``seed``: the sample seed of the first collection (one more per collection) and the
+    seed of the minibatch permutations."""
+
+    def __init__(self, env, policy: MLPPolicy, value_net: MLPPolicy, n_steps: int = 128, n_epochs: int = 4,
+                 batch_size: int | None = None, lr: float = 3e-4, gamma: float = 0.99, lam: float = 0.95,
+                 clip_range: float = 0.2, vf_coef: float = 0.5, ent_coef: float = 0.0, max_grad_norm: float = 0.5,
+                 normalize_advantage: bool = True, seed: int = 0):
+        eng, cenv = _engine_of(env)
+        for p, head in ((policy, "policy"), (value_net, "value")):
+            if not isinstance(p, MLPPolicy) or p._on_device or p.n_sets != 1 or p.lanes_per_set is not None:
+                raise ValueError("PPO: policy and value_net must be one-set host-built MLPPolicy objects")
+            if p.head != head:
+                raise ValueError(f"PPO: the {'actor' if head == 'policy' else 'critic'} must have head={head!r}")
+            if p.family != eng.family or p.obs_dim != eng.D:
+                raise ValueError(f"the policy was built for family {p.family}, this engine runs family {eng.family}")
+        if not eng.auto_reset:
+            raise ValueError("PPO needs auto_reset=True (a collection runs through episode ends)")
+        eng._check_value_net(policy, value_net)
+        self.env, self.engine, self._carl_env = env, eng, cenv
+        self.n_steps, self.n_epochs = int(n_steps), int(n_epochs)
+        total = self.n_steps * eng.n
+        self.batch_size = max(1, total // 4) if batch_size is None else int(batch_size)
+        if not 1 <= self.batch_size <= total:
+            raise ValueError(f"batch_size {self.batch_size} outside [1, n_steps x n_lanes = {total}]")
+        self.gamma, self.lam = float(gamma), float(lam)
+        self.clip_range, self.vf_coef, self.ent_coef = float(clip_range), float(vf_coef), float(ent_coef)
+        self.max_grad_norm, self.normalize_advantage = max_grad_norm, bool(normalize_advantage)
+        self.seed, self.collections = int(seed), 0
+        dev = eng.device
+        q = int(_lib.load().carl_policy_lane_quantum())
+        lanes = max(q, (eng.n + q - 1) // q * q)
+        self._templates = (policy, value_net)
+        self.actor_params = torch.as_tensor(policy.params).to(dev).contiguous().clone()   # [1, set_floats]
+        self.critic_params = torch.as_tensor(value_net.params).to(dev).contiguous().clone()
+        self.box = not policy.discrete
+        self.log_std = torch.as_tensor(policy.log_std).to(dev).contiguous().clone()        # [1]
+        self._actor = _ResidentPolicy.of(policy, self.actor_params, lanes, self.log_std if self.box else None)
+        self._critic = _ResidentPolicy.of(value_net, self.critic_params, lanes)
+        self._opt_params = [self.actor_params, self.critic_params] + ([self.log_std] if self.box else [])
+        self.optimizer = torch.optim.Adam(self._opt_params, lr=float(lr), eps=1e-5)
+        self._gen = torch.Generator(device=dev)
+        self._gen.manual_seed(self.seed)
+        self._obs0 = None  # the observation the next collection's first action is chosen from
+        self._buf = None
+        self._ws = eng.ppo_workspace(policy, value_net, self.batch_size)
+
+    # ------------------------------------------------------------------ state
+    def actor(self) -> MLPPolicy:
+        """The actor as a one-set host ``MLPPolicy`` (device-to-host copies)."""
+        ls = float(self.log_std.cpu()[0]) if self.box else None
+        return MLPPolicy.unpack(self._templates[0], self.actor_params.cpu().numpy()[0], ls)
+
+    def critic(self) -> MLPPolicy:
+        """The critic as a one-set host ``MLPPolicy`` (one device-to-host copy)."""
+        return MLPPolicy.unpack(self._templates[1], self.critic_params.cpu().numpy()[0])
+
+    # ------------------------------------------------------------------ one iteration
+    def collect(self) -> dict:
+        """One rollout buffer: ``rollout_policy``'s dict plus ``"obs0"`` ``[N, D]`` and ``"context_id"`` ``[T, N]``."""
+        eng = self.engine
+        if self._obs0 is None:
+            if self._carl_env is not None:
+                self._carl_env.reset()  # (the env's own bookkeeping; the engine's observation buffer is read below)
+            else:
+                eng.reset()
+            self._obs0 = eng.obs.clone()
+        ctx0, ep0 = eng.ctx_idx.clone(), eng.episode.clone()
+        buf = eng.rollout_policy(self._actor, self.n_steps, deterministic=False, sample_seed=self.seed + self.collections,
+                                 value_net=self._critic, gae=(self.gamma, self.lam))
+        self.collections += 1
+        T = self.n_steps
+        buf["context_id"] = eng.context_trace(ctx0, ep0, buf["terminated"][:T], buf["truncated"][:T])
+        buf["obs0"] = self._obs0
+        self._obs0 = buf["obs"][T - 1].clone()  # (contiguous [N, D]: the next collection starts from it)
+        self._buf = buf
+        return buf
+
+    def minibatches(self):
+        """The int32 flat sample indices ``t * pitch + lane`` of one epoch's minibatches, in order (device tensors)."""
+        eng, T = self.engine, self.n_steps
+        P = int(self._buf["action"].stride(0)) if T > 1 else eng.n
+        perm = torch.randperm(T * eng.n, device=eng.device, generator=self._gen)
+        flat = ((perm // eng.n) * P + perm % eng.n).to(torch.int32)
+        return [flat[s: s + self.batch_size].contiguous() for s in range(0, T * eng.n, self.batch_size)]
+
+    def update(self) -> dict:
+        """``n_epochs`` passes over the last collection.  Returns ``{"stats" [n_minibatches, 6]}``: per minibatch the
+        policy loss, value loss, mean entropy, approx_kl, clip fraction and sample count, on the device."""
+        if self._buf is None:
+            raise RuntimeError("PPO.update: collect() first")
+        eng, buf = self.engine, self._buf
+        adv_flat = buf["advantage"]
+        P = int(adv_flat.stride(0)) if self.n_steps > 1 else eng.n
+        adv_storage = torch.as_strided(adv_flat, (self.n_steps * P,), (1,)) if P != eng.n else adv_flat.reshape(-1)
+        stats = []
+        for _ in range(self.n_epochs):
+            for idx in self.minibatches():
+                norm = None
+                if self.normalize_advantage and idx.numel() > 1:
+                    a = adv_storage[idx.long()]
+                    norm = torch.stack([a.mean(), 1.0 / (a.std() + 1e-8)]).contiguous()
+                g = eng.ppo_grad(self._actor, self._critic, buf, buf["obs0"], buf["context_id"], idx=idx, adv_norm=norm,
+                                 clip_range=self.clip_range, vf_coef=self.vf_coef, ent_coef=self.ent_coef,
+                                 workspace=self._ws)  # (sized for batch_size: a last, shorter minibatch needs no more)
+                grads = [g["grad_actor"].view_as(self.actor_params), g["grad_critic"].view_as(self.critic_params)]
+                if self.box:
+                    grads.append(g["grad_log_std"].view_as(self.log_std))
+                if self.max_grad_norm is not None:
+                    total = torch.sqrt(sum((x.double() ** 2).sum() for x in grads)).float()
+                    coef = torch.clamp(float(self.max_grad_norm) / (total + 1e-6), max=1.0)
+                    grads = [x * coef for x in grads]
+                for p, x in zip(self._opt_params, grads):
+                    p.grad = x
+                self.optimizer.step()
+                stats.append(g["stats"])
+        return {"stats": torch.stack(stats)}
+
+    def learn(self, iterations: int) -> list:
+        """``iterations`` times ``collect()`` + ``update()``; returns each iteration's ``{"stats", "mean_reward"}`` (device
+        tensors; ``mean_reward``: the mean per-step reward of the collection)."""
+        info = []
+        for _ in range(int(iterations)):
+            buf = self.collect()
+            res = self.update()
+            res["mean_reward"] = buf["reward"][: self.n_steps].mean()
+            info.append(res)
+        return info

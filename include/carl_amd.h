@@ -681,6 +681,116 @@ int carl_policy_stats_merge(const carl_policy_t* policy_host, const carl_policy_
                             float* params_out /* DEVICE [n_write][set_floats], nullable */, int32_t n_write,
                             void* stream);
 
+/* ---- the PPO update on the device: per-step context ids and minibatch gradients (additive; ABI version unchanged) ----
+ * carl_rollout_policy_valued + carl_gae leave a complete PPO rollout buffer on the device (actions, log-probabilities,
+ * values, advantages, returns).  The two calls below turn it into the clipped-surrogate loss and its gradients (SB3's
+ * PPO; the reference's one training example, examples/carl_with_sb3.py, trains PPO on FlattenObservation(env)) without
+ * carrying the buffer into an autograd framework.  Classic-control families only.  No existing kernel is touched.
+ *
+ * carl_policy_context_trace: the context each step of a launch ran in.  A launch stores each step's observation but not
+ * the context half of the policy's input, and a moving selector changes a lane's context at every reset.  From each
+ * lane's ctx_idx / episode BEFORE the traced launch (copies the caller took: ctx_idx0 [n_lanes] int32, episode0
+ * [n_lanes] uint32) and that launch's terminated / truncated rows the walk is replayed, one thread per lane:
+ *   c = ctx_idx0[lane], e = episode0[lane];  for t = 0 .. n_steps - 1:
+ *     context_id[t][lane] = c                                      (the context step t's action was chosen in)
+ *     with CARL_FLAG_AUTORESET, if terminated[t][lane] | truncated[t][lane]:
+ *       c = the selector's next context (the engine's own rule, called with (c, lane_offset + lane, e));  e += 1
+ * -- the order of a lane's reset.  Without auto-reset the context never moves.  `batch` is read for family, n_lanes,
+ * n_contexts, selector, selector_stride, flags, seed and lane_offset only (no pointer of it is read).  Rows are
+ * row_pitch lanes long (0 = n_lanes); only columns [0, n_lanes) of context_id are written.  Validation, each
+ * CARL_ERR_INVALID_ARGUMENT before anything is enqueued: a NULL batch or pointer, a Brax family, n_lanes or n_steps < 0,
+ * n_contexts < 1, an unknown selector, a pitch that is neither 0 nor >= n_lanes.  n_lanes == 0 or n_steps == 0 enqueues
+ * nothing. */
+int carl_policy_context_trace(const carl_batch_t* batch, const int32_t* ctx_idx0 /* DEVICE [n_lanes] */,
+                              const uint32_t* episode0 /* DEVICE [n_lanes] */,
+                              const uint8_t* terminated /* DEVICE [n_steps][pitch] */,
+                              const uint8_t* truncated /* DEVICE [n_steps][pitch] */, int32_t n_steps, int32_t row_pitch,
+                              int32_t* context_id /* DEVICE [n_steps][pitch] */, void* stream);
+
+/* carl_ppo_grad: loss and gradients of one minibatch of a rollout buffer.  All pointers of carl_ppo_batch_t are DEVICE
+ * pointers; the [n_steps][pitch] columns use the layout carl_rollout_policy writes (pitch = row_pitch, 0 = n_lanes).
+ * Sample (t, lane) has the flat index t * pitch + lane.  Its input is exactly what the rollout's actor saw:
+ *   x_k = ctx_table[ctx_rows[k]][context_id[t][lane]] for k < n_ctx, then obs0[lane] (t == 0) or obs[t - 1][lane],
+ * transformed by the actor's shift / scale / clip; the critic reads the same transformed x (its own section is not
+ * read), as in carl_rollout_policy_valued.  Forward arithmetic is the rollout's (explicit fma in input order, bias
+ * first, the same tanh, expf / logf for the heads).  With lp, V and the entropy H under the given parameters,
+ * A' = adv_norm ? (A - adv_norm[0]) * adv_norm[1] : A,  r = exp(lp - log_prob) and c = clip_range:
+ *   pl = -mean(min(r A', clamp(r, 1 - c, 1 + c) A'))    vl = mean((ret - V)^2)    el = -mean(H)
+ *   L  = pl + ent_coef el + vf_coef vl
+ * Categorical head: lp = (y_a - m) - log S, H = -sum_k p_k log p_k.  Gaussian head (log_std [1] on the device):
+ * z = (a - mu) exp(-log_std), lp = -z^2 / 2 - log_std - ln(2 pi) / 2, H = 1/2 + ln(2 pi) / 2 + log_std.  The surrogate's
+ * gradient flows through r A' unless the clip is active (A' > 0 && r > 1 + c, or A' < 0 && r < 1 - c).
+ * Outputs (carl_ppo_out_t):
+ *   grad_actor  [carl_policy_set_floats(actor)]: dL/dparams in the packed layout; the shift / scale / clip entries and
+ *               the padding receive +0.0 (an optimiser stepping the whole packed block leaves them untouched)
+ *   grad_critic [carl_policy_set_floats(critic)]: likewise
+ *   grad_log_std [1]: Box families only (ignored, may be NULL, for discrete ones)
+ *   stats [6]: pl, vl, mean entropy, approx_kl = mean((r - 1) - log r), clip fraction = mean(|r - 1| > c), n_samples
+ *   new_log_prob / new_value [n_samples], nullable: lp and V of each sample, in idx order
+ * How it runs: a launch per network (the actor, then the critic: both at width 64 with a tile's activations do not fit
+ * the LDS of a compute unit) of carl_ppo_grad_workgroups(n_samples) persistent workgroups that loop over tiles of
+ * carl_ppo_tile() samples with a grid stride.  The weights are staged in LDS once per workgroup; one thread runs one
+ * sample's forward and backward pass in registers; the tile's activations and deltas go to LDS, and every thread adds
+ * dW[i][j] = sum_s delta[s][i] h[s][j] for its own fixed (i, j) entries, walking the tile's samples in index order
+ * (blocks of 16 samples, block sums added in order).  Each workgroup writes one partial slab to `workspace`; a last
+ * small kernel adds the slabs in workgroup order in float64, multiplies by 1 / n_samples and rounds once.  No
+ * floating-point atomics: the same call twice gives the same bits.
+ * Preconditions the host cannot check: idx entries are distinct, each t * pitch + lane with lane < n_lanes (an entry
+ * outside the buffer is skipped: it contributes zero); actions of a discrete family lie in [0, n_actions).
+ * Validation, each CARL_ERR_INVALID_ARGUMENT with a message before anything is enqueued: a NULL struct or required
+ * pointer; a Brax family; n_lanes < 1, n_steps < 1; a pitch that is neither 0 nor >= n_lanes; the networks as
+ * carl_rollout_policy_valued validates them (shape limits, the head against the family, n_in == n_ctx + obs_dim, context
+ * rows, activation, params; the critic's inputs against the actor's) and n_sets == 1 (several weight sets are
+ * evolution-strategies territory); obs_dim against the family; the action dtype against the head (CARL_ACTION_I32 /
+ * CARL_ACTION_F32); n_contexts < 1 or ctx_stride < n_contexts; n_samples < 1, n_samples > n_steps * n_lanes, or idx NULL
+ * with n_samples != n_steps * n_lanes; clip_range / vf_coef / ent_coef negative or not finite; a Box family without
+ * log_std or grad_log_std; workspace NULL, off a 16-byte boundary or smaller than carl_ppo_workspace_floats().
+ * Stream-ordered and capturable; never synchronises with the host; allocates nothing. */
+typedef struct carl_ppo_batch {
+  int32_t family;          /* carl_family_t of the batch that produced the buffer */
+  int32_t n_lanes;
+  int32_t n_steps;
+  int32_t row_pitch;       /* lanes per row of every [n_steps][pitch] column; 0 = n_lanes */
+  int32_t obs_dim;         /* D */
+  int32_t n_contexts;      /* valid columns of ctx_table */
+  int32_t ctx_stride;      /* elements between its feature rows */
+  int32_t action_dtype;    /* CARL_ACTION_I32 (discrete families) / CARL_ACTION_F32 (Box) */
+  int32_t n_samples;       /* M */
+  int32_t reserved;
+  float clip_range;        /* c >= 0 */
+  float vf_coef;           /* >= 0 */
+  float ent_coef;          /* >= 0 */
+  int32_t reserved2;
+  const float* obs0;       /* [n_lanes][D]: the observation step 0's action was chosen from */
+  const float* obs;        /* [n_steps][pitch][D]: the launch's observation rows */
+  const int32_t* context_id; /* [n_steps][pitch]: carl_policy_context_trace's output */
+  const float* ctx_table;  /* [F][ctx_stride] */
+  const void* action;      /* [n_steps][pitch] int32 or float32 */
+  const float* log_prob;   /* [n_steps][pitch] */
+  const float* advantage;  /* [n_steps][pitch] */
+  const float* ret;        /* [n_steps][pitch] */
+  const int32_t* idx;      /* [n_samples] flat sample indices, or NULL: every (t, lane), t-major */
+  const float* adv_norm;   /* [2] (mean, 1 / (std + eps)), or NULL: advantages as they are */
+} carl_ppo_batch_t;
+
+typedef struct carl_ppo_out {
+  float* grad_actor;       /* [carl_policy_set_floats(actor)] */
+  float* grad_critic;      /* [carl_policy_set_floats(critic)] */
+  float* grad_log_std;     /* [1], Box families */
+  float* stats;            /* [6] */
+  float* new_log_prob;     /* [n_samples], nullable */
+  float* new_value;        /* [n_samples], nullable */
+  float* workspace;        /* [workspace_floats], 16-byte aligned */
+  int64_t workspace_floats; /* >= carl_ppo_workspace_floats() */
+} carl_ppo_out_t;
+
+int32_t carl_ppo_tile(void);                           /* samples of one tile (256) */
+int32_t carl_ppo_grad_workgroups(int32_t n_samples);   /* workgroups of a launch: min(tiles, 256); 0 for n_samples < 1 */
+/* floats of the workspace for these shapes and n_samples; -1 for an invalid shape or n_samples < 1 */
+int64_t carl_ppo_workspace_floats(const carl_policy_t* policy_host, const carl_policy_t* critic_host, int32_t n_samples);
+int carl_ppo_grad(const carl_ppo_batch_t* ppo_host, const carl_policy_t* policy_host, const carl_policy_t* critic_host,
+                  const float* log_std /* DEVICE [1], Box families */, const carl_ppo_out_t* out, void* stream);
+
 /* ======================= Brax-locomotion families (spring backend) =======================
  * Replaces CARLBraxEnv + BraxGymWrapper/VectorGymWrapper + brax.spring.pipeline.step x
  * n_frames + brax.envs.<env>.step/reset (carl/envs/brax/carl_brax_env.py:115-336,
