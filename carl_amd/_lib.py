@@ -389,4 +389,11 @@ EXPORTS.update({
     "carl_ppo_grad_workgroups": (C.c_int32, [C.c_int32]),
     "carl_ppo_workspace_floats": (C.c_int64, [C.POINTER(Policy), C.POINTER(Policy), C.c_int32]),
     "carl_ppo_grad": (C.c_int, [C.POINTER(PpoBatch), C.POINTER(Policy), C.POINTER(Policy), _vp, C.POINTER(PpoOut), _vp]),
+    # the Brax families' (dense rows; a joint Gaussian over the model's actuators: carl_brax_ppo_grad)
+    "carl_brax_policy_context_trace": (C.c_int, [C.POINTER(Batch), _vp, _vp, _vp, _vp, C.c_int32, _vp, _vp]),
+    "carl_brax_ppo_tile": (C.c_int32, []),
+    "carl_brax_ppo_grad_workgroups": (C.c_int32, [C.c_int32]),
+    "carl_brax_ppo_workspace_floats": (C.c_int64, [C.POINTER(Policy), C.POINTER(Policy), C.c_int32]),
+    "carl_brax_ppo_grad": (C.c_int, [C.POINTER(PpoBatch), C.POINTER(BraxSys), C.POINTER(Policy), C.POINTER(Policy), _vp,
+                                     C.POINTER(PpoOut), _vp]),
 })

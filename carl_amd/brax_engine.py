@@ -479,6 +479,28 @@ class BraxVecEngine(LaneEngine):
             res["advantage"], res["return"] = adv["advantage"], adv["return"]
         return res
 
+    # ---- LaneEngine's PPO hooks (context_trace, ppo_workspace, ppo_grad): the Brax entry points, dense rows, an action
+    # column [T, N, n_act], one log_std per actuator
+    def _ppo_check_policy(self, policy) -> None:
+        self._check_policy(policy, "ppo_grad")
+
+    def _ppo_action_tail(self) -> tuple:
+        return (int(self.sys.n_act),)
+
+    def _ppo_log_std_floats(self) -> int:
+        return int(self.sys.n_act)
+
+    def _c_context_trace(self, ctx0, ep0, te, tr, T, pitch, out) -> int:
+        if pitch != 0:
+            raise ValueError(f"{type(self).__name__}.context_trace: dense rows only ({self.n} lanes per row)")
+        return self.lib.carl_brax_policy_context_trace(self._b_ref, ctx0, ep0, te, tr, T, out, self._stream())
+
+    def _c_ppo_workspace_floats(self, pol, crit, n_samples) -> int:
+        return self.lib.carl_brax_ppo_workspace_floats(pol, crit, n_samples)
+
+    def _c_ppo_grad(self, pb, pol, crit, log_std, po) -> int:
+        return self.lib.carl_brax_ppo_grad(pb, self._sys_ref, pol, crit, log_std, po, self._stream())
+
     def evaluate_policy(self, *args, **kwargs):
         raise NotImplementedError(f"{type(self).__name__}: evaluate_policy (sampling, input statistics) covers the "
                                   "classic-control families only; the episodes mode of the Brax closed-loop rollout is "

@@ -25,9 +25,15 @@ adds advantages and returns from one more launch.  That is a PPO collection step
 critic reads the actor's transformed inputs, so its ``input_shift`` / ``input_scale`` / ``input_clip`` must equal the
 actor's bit for bit.
 
+The update runs on the device too: ``carl_amd.PPO`` takes a ``CARLBraxEnv`` / ``BraxVecEngine`` with a ``BraxMLPPolicy``
+actor and critic, and ``BraxVecEngine.context_trace`` / ``ppo_grad`` are its two launches (include/carl_amd.h:
+carl_brax_policy_context_trace, carl_brax_ppo_grad): the context each step ran in, then the clipped-surrogate loss and the
+gradients of the actor, the critic and the per-actuator ``log_std`` for one minibatch.
+
 At most ``CARL_POLICY_MAX_IN`` = 32 inputs: Humanoid's and HumanoidStandup's 244 observations do not fit.  Still out of
 scope: a sampled episodes mode (``evaluate_episodes`` and ``EvolutionStrategy`` stay deterministic; ``evaluate_policy``
-stays the classic-control families'), a critic next to a deterministic actor, Humanoid-size inputs and ``MixedVecEngine``.
+stays the classic-control families'), a critic next to a deterministic actor, Humanoid-size inputs and ``MixedVecEngine``;
+for PPO also more than 8 actuators, collection under the first-state auto-reset and the gymnasium drop-in.
 """
 from __future__ import annotations
 

@@ -32,13 +32,14 @@ ARCH = "gfx950"
 # carl_brax_policy_value.hip (the sampled rollout with a critic) instantiates the sampled variant's valued variant: its flags.
 # (The five closed-loop units expand one list of instances and share one host launch path: csrc/brax_policy_host.hpp.)
 # carl_ppo.hip (the PPO update: context trace, minibatch gradients) calls the closed-loop rollout's device functions: same flags.
+# carl_brax_ppo.hip (that update for the Brax families) calls carl_ppo.hip's device functions and instantiates its kernels: same flags.
 SOURCES = {"carl_amd.hip": ["-fno-slp-vectorize"], "carl_brax.hip": ["-fno-slp-vectorize"],
            "carl_policy.hip": ["-fno-slp-vectorize"], "carl_policy_sample.hip": ["-fno-slp-vectorize"],
            "carl_policy_value.hip": ["-fno-slp-vectorize"], "carl_es.hip": ["-fno-slp-vectorize"],
            "carl_policy_stats.hip": ["-fno-slp-vectorize"], "carl_brax_policy.hip": ["-fno-slp-vectorize"],
            "carl_brax_episodes.hip": ["-fno-slp-vectorize"], "carl_brax_policy_stats.hip": ["-fno-slp-vectorize"],
            "carl_brax_policy_sample.hip": ["-fno-slp-vectorize"], "carl_brax_policy_value.hip": ["-fno-slp-vectorize"],
-           "carl_ppo.hip": ["-fno-slp-vectorize"]}
+           "carl_ppo.hip": ["-fno-slp-vectorize"], "carl_brax_ppo.hip": ["-fno-slp-vectorize"]}
 
 
 def _hipcc() -> str:

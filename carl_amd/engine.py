@@ -572,6 +572,133 @@ class LaneEngine:
             _lib.check(self.lib.carl_gae(C.byref(g), self._stream()))
         return res
 
+    # ------------------------------------------------------------------ the PPO update (carl_amd/ppo.py)
+    # One set of argument checks for both engines.  What an engine brings: its C entry points (``_c_context_trace``,
+    # ``_c_ppo_workspace_floats``, ``_c_ppo_grad``), its policy check (``_ppo_check_policy``), the trailing shape of its
+    # action column (``_ppo_action_tail``: () -- one value per step -- or (n_act,)) and the length of ``log_std``
+    # (``_ppo_log_std_floats``: 0 for a discrete family).
+    def context_trace(self, ctx_idx0: torch.Tensor, episode0: torch.Tensor, terminated: torch.Tensor,
+                      truncated: torch.Tensor, out: torch.Tensor | None = None) -> torch.Tensor:
+        """The context-table index each step of a launch ran in (include/carl_amd.h: carl_policy_context_trace):
+        ``[T, N]`` int32 (the Brax families: carl_brax_policy_context_trace, dense rows), from clones of ``ctx_idx`` /
+        ``episode`` taken BEFORE that launch and its ``terminated`` /
+        ``truncated`` rows (``alloc_rollout``-style views or dense; uint8 or bool).  The selector's walk is replayed with
+        this engine's selector, stride, seed, lane offset and auto-reset setting, so those must be what the launch ran
+        under.  ``out``: an int32 buffer of the flags' row layout to write into.  One launch, no host synchronisation."""
+        T, N = (int(v) for v in terminated.shape)
+        P = int(terminated.stride(0)) if T > 1 else N
+        if N != self.n or P < N:
+            raise ValueError(f"context_trace: flag rows of {N} lanes (pitch {P}) for an engine of {self.n}")
+        for name, t in (("terminated", terminated), ("truncated", truncated)):
+            if t.dtype not in (torch.uint8, torch.bool) or t.device != self.device or tuple(t.shape) != (T, N) or (
+                    N > 1 and t.stride(1) != 1) or (T > 1 and t.stride(0) != P):
+                raise ValueError(f"context_trace '{name}': needs uint8 [{T}, {N}] rows of pitch {P} on {self.device}")
+        for name, t in (("ctx_idx0", ctx_idx0), ("episode0", episode0)):
+            if t.dtype != torch.int32 or t.device != self.device or tuple(t.shape) != (N,) or not t.is_contiguous():
+                raise ValueError(f"context_trace '{name}': needs a contiguous int32 [{N}] tensor on {self.device}")
+        if out is None:
+            out = torch.empty((T, P), dtype=torch.int32, device=self.device)[:, :N]
+        elif out.dtype != torch.int32 or out.device != self.device or tuple(out.shape) != (T, N) or (
+                N > 1 and out.stride(1) != 1) or (T > 1 and out.stride(0) != P):
+            raise ValueError(f"context_trace 'out': needs int32 [{T}, {N}] rows of pitch {P} on {self.device}")
+        with torch.cuda.device(self.device):
+            _lib.check(self._c_context_trace(_ptr(ctx_idx0), _ptr(episode0), _ptr(terminated), _ptr(truncated), T,
+                                             P if P != N else 0, _ptr(out)))
+        return out
+
+    def ppo_workspace(self, policy, value_net, n_samples: int) -> torch.Tensor:
+        """A float32 workspace for ``ppo_grad`` of ``n_samples`` samples (carl_ppo_workspace_floats)."""
+        need = int(self._c_ppo_workspace_floats(C.byref(policy.struct(self.n, 0x10)), C.byref(value_net.struct(self.n, 0x10)),
+                                                int(n_samples)))
+        if need < 0:
+            raise ValueError(f"ppo_workspace: invalid shapes or n_samples {n_samples}")
+        return torch.empty(need, dtype=torch.float32, device=self.device)
+
+    def ppo_grad(self, policy, value_net, buf: dict, obs0: torch.Tensor, context_id: torch.Tensor, *, idx=None,
+                 adv_norm=None, clip_range: float = 0.2, vf_coef: float = 0.5, ent_coef: float = 0.0,
+                 forward: bool = False, out: dict | None = None, workspace: torch.Tensor | None = None) -> dict:
+        """Loss and gradients of one PPO minibatch in three launches (include/carl_amd.h: carl_ppo_grad).  ``buf``: the dict
+        of ``rollout_policy(..., deterministic=False, value_net=, gae=)`` (``obs``, ``action``, ``log_prob``, ``advantage``,
+        ``return``: rows of one pitch); ``obs0`` ``[N, D]``: the observation its step 0 was chosen from; ``context_id``:
+        ``context_trace``'s result for that launch (the same pitch).  ``idx``: int32 ``[M]`` flat sample indices
+        ``t * pitch + lane`` (distinct, ``lane < N``; the pitch is ``buf["action"].stride(0)``), None: every sample.
+        ``adv_norm``: a float32 ``[2]`` device tensor (mean, 1 / (std + eps)) or None.  Returns ``{"grad_actor"
+        [set_floats], "grad_critic" [set_floats], "grad_log_std" [1] (Box families; ``[n_act]`` for a Brax model, whose ``action`` is ``[T, N, n_act]`` in dense rows:
+        carl_brax_ppo_grad), "stats" [6]: policy loss, value
+        loss, mean entropy, approx_kl, clip fraction, M}`` and, with ``forward=True``, ``"new_log_prob"`` / ``"new_value"``
+        ``[M]`` -- float32 device tensors (``out``: such a dict to write into).  ``policy`` / ``value_net``: one-set policies
+        (host-built or ``on_device``).  No host synchronisation."""
+        self._ppo_check_policy(policy)
+        act = buf["action"]
+        tail = self._ppo_action_tail()
+        if tail:  # [T, N, n_act]: dense rows
+            if act.dim() != 3 or tuple(act.shape[2:]) != tail or not act.is_contiguous():
+                raise ValueError(f"ppo_grad 'action': needs a contiguous float32 [T, {self.n}, {tail[0]}] tensor on {self.device}")
+            T, N = int(act.shape[0]), int(act.shape[1])
+            P = N
+        else:
+            T, N = (int(v) for v in act.shape)
+            P = int(act.stride(0)) if T > 1 else N
+        if N != self.n:
+            raise ValueError(f"ppo_grad: a buffer of {N} lanes for an engine of {self.n}")
+        f32, i32 = torch.float32, torch.int32
+        adt = i32 if self.info.action_is_discrete else f32
+        cols = {"action": (act, adt), "log_prob": (buf["log_prob"], f32), "advantage": (buf["advantage"], f32),
+                "return": (buf["return"], f32), "context_id": (context_id, i32)}
+        if tail:  # (its shape is checked above)
+            if act.dtype != adt or act.device != self.device:
+                raise ValueError(f"ppo_grad 'action': needs a contiguous float32 [T, {self.n}, {tail[0]}] tensor on {self.device}")
+            del cols["action"]
+        for k, (t, dt) in cols.items():
+            if t.dtype != dt or t.device != self.device or t.shape[0] < T or tuple(t.shape[1:]) != (N,) or (
+                    N > 1 and t.stride(1) != 1) or (T > 1 and t.stride(0) != P):
+                raise ValueError(f"ppo_grad '{k}': needs {dt} [{T}, {N}] rows of pitch {P} on {self.device}")
+        obs = buf["obs"]
+        if obs.dtype != f32 or obs.device != self.device or obs.shape[0] < T or tuple(obs.shape[1:]) != (N, self.D) or any(
+                sz > 1 and st != w for sz, st, w in zip(obs.shape, obs.stride(), (P * self.D, self.D, 1))):
+            raise ValueError(f"ppo_grad 'obs': needs float32 [{T}, {N}, {self.D}] rows of pitch {P} on {self.device}")
+        if obs0.dtype != f32 or obs0.device != self.device or tuple(obs0.shape) != (N, self.D) or not obs0.is_contiguous():
+            raise ValueError(f"ppo_grad 'obs0': needs a contiguous float32 [{N}, {self.D}] tensor on {self.device}")
+        if idx is not None and (idx.dtype != i32 or idx.device != self.device or idx.dim() != 1 or not idx.is_contiguous()):
+            raise ValueError(f"ppo_grad 'idx': needs a contiguous int32 [M] tensor on {self.device}")
+        if adv_norm is not None and (adv_norm.dtype != f32 or adv_norm.device != self.device or adv_norm.numel() != 2
+                                     or not adv_norm.is_contiguous()):
+            raise ValueError(f"ppo_grad 'adv_norm': needs a contiguous float32 [2] tensor on {self.device}")
+        M = T * N if idx is None else int(idx.numel())
+        res = {} if out is None else out
+        n_ls = self._ppo_log_std_floats()
+        box = n_ls > 0
+        want = {"grad_actor": policy.set_floats, "grad_critic": value_net.set_floats, "stats": 6}
+        if box:
+            want["grad_log_std"] = n_ls
+        if forward:
+            want["new_log_prob"] = want["new_value"] = M
+        for k, size in want.items():
+            if k not in res:
+                res[k] = torch.empty(size, dtype=f32, device=self.device)
+            t = res[k]
+            if t.dtype != f32 or t.device != self.device or t.numel() != size or not t.is_contiguous():
+                raise ValueError(f"ppo_grad output '{k}': needs a contiguous float32 [{size}] tensor on {self.device}")
+        pol = policy.struct(self.n, policy.device_params(self.device).data_ptr())
+        crit = value_net.struct(self.n, value_net.device_params(self.device).data_ptr())
+        ws = self.ppo_workspace(policy, value_net, M) if workspace is None else workspace
+        pb = _lib.PpoBatch()
+        pb.family, pb.n_lanes, pb.n_steps, pb.row_pitch, pb.obs_dim = self.family, N, T, (P if P != N else 0), self.D
+        pb.n_contexts, pb.ctx_stride = int(self.b.n_contexts), int(self.b.ctx_stride)
+        pb.action_dtype = _lib.ACTION_I32 if self.info.action_is_discrete else _lib.ACTION_F32
+        pb.n_samples = M
+        pb.clip_range, pb.vf_coef, pb.ent_coef = float(clip_range), float(vf_coef), float(ent_coef)
+        pb.obs0, pb.obs, pb.context_id, pb.ctx_table = _ptr(obs0), _ptr(obs), _ptr(context_id), _ptr(self.ctx_table)
+        pb.action, pb.log_prob, pb.advantage, pb.ret = _ptr(act), _ptr(buf["log_prob"]), _ptr(buf["advantage"]), _ptr(buf["return"])
+        pb.idx, pb.adv_norm = _ptr(idx), _ptr(adv_norm)
+        po = _lib.PpoOut(_ptr(res["grad_actor"]), _ptr(res["grad_critic"]), _ptr(res.get("grad_log_std")), _ptr(res["stats"]),
+                         _ptr(res.get("new_log_prob")) if forward else None, _ptr(res.get("new_value")) if forward else None,
+                         _ptr(ws), int(ws.numel()))
+        ls = policy.device_log_std(self.device).data_ptr() if box else None
+        with torch.cuda.device(self.device):
+            _lib.check(self._c_ppo_grad(C.byref(pb), C.byref(pol), C.byref(crit), ls, C.byref(po)))
+        return res
+
     def drain_finished(self):
         """Finished-episode log since the last drain -> (global lane ids, returns, lengths,
         n_dropped); resets the counter.  Synchronises."""
@@ -747,6 +874,25 @@ class VecEngine(LaneEngine):
         s.log_prob = _ptr(log_prob)
         return s
 
+    # ---- LaneEngine's PPO hooks: the classic-control entry points
+    def _ppo_check_policy(self, policy) -> None:
+        _check_policy_family(self, policy)
+
+    def _ppo_action_tail(self) -> tuple:
+        return ()
+
+    def _ppo_log_std_floats(self) -> int:
+        return 0 if self.info.action_is_discrete else 1
+
+    def _c_context_trace(self, ctx0, ep0, te, tr, T, pitch, out) -> int:
+        return self.lib.carl_policy_context_trace(self._b_ref, ctx0, ep0, te, tr, T, pitch, out, self._stream())
+
+    def _c_ppo_workspace_floats(self, pol, crit, n_samples) -> int:
+        return self.lib.carl_ppo_workspace_floats(pol, crit, n_samples)
+
+    def _c_ppo_grad(self, pb, pol, crit, log_std, po) -> int:
+        return self.lib.carl_ppo_grad(pb, pol, crit, log_std, po, self._stream())
+
     def _policy_call(self, fn, *args) -> None:
         """One closed-loop C call ``fn(batch, *args, stream)`` on the current stream, its error code raised."""
         with torch.cuda.device(self.device):
@@ -881,114 +1027,6 @@ class VecEngine(LaneEngine):
         if not np.array_equal(np.ascontiguousarray(a).view(np.int32), np.ascontiguousarray(c).view(np.int32)):
             raise ValueError("value_net's input_shift / input_scale / input_clip must equal the policy's bit for bit: the "
                              "critic reads the actor's transformed inputs")
-
-    # ------------------------------------------------------------------ the PPO update (carl_amd/ppo.py)
-    def context_trace(self, ctx_idx0: torch.Tensor, episode0: torch.Tensor, terminated: torch.Tensor,
-                      truncated: torch.Tensor, out: torch.Tensor | None = None) -> torch.Tensor:
-        """The context-table index each step of a launch ran in (include/carl_amd.h: carl_policy_context_trace):
-        ``[T, N]`` int32, from clones of ``ctx_idx`` / ``episode`` taken BEFORE that launch and its ``terminated`` /
-        ``truncated`` rows (``alloc_rollout``-style views or dense; uint8 or bool).  The selector's walk is replayed with
-        this engine's selector, stride, seed, lane offset and auto-reset setting, so those must be what the launch ran
-        under.  ``out``: an int32 buffer of the flags' row layout to write into.  One launch, no host synchronisation."""
-        T, N = (int(v) for v in terminated.shape)
-        P = int(terminated.stride(0)) if T > 1 else N
-        if N != self.n or P < N:
-            raise ValueError(f"context_trace: flag rows of {N} lanes (pitch {P}) for an engine of {self.n}")
-        for name, t in (("terminated", terminated), ("truncated", truncated)):
-            if t.dtype not in (torch.uint8, torch.bool) or t.device != self.device or tuple(t.shape) != (T, N) or (
-                    N > 1 and t.stride(1) != 1) or (T > 1 and t.stride(0) != P):
-                raise ValueError(f"context_trace '{name}': needs uint8 [{T}, {N}] rows of pitch {P} on {self.device}")
-        for name, t in (("ctx_idx0", ctx_idx0), ("episode0", episode0)):
-            if t.dtype != torch.int32 or t.device != self.device or tuple(t.shape) != (N,) or not t.is_contiguous():
-                raise ValueError(f"context_trace '{name}': needs a contiguous int32 [{N}] tensor on {self.device}")
-        if out is None:
-            out = torch.empty((T, P), dtype=torch.int32, device=self.device)[:, :N]
-        elif out.dtype != torch.int32 or out.device != self.device or tuple(out.shape) != (T, N) or (
-                N > 1 and out.stride(1) != 1) or (T > 1 and out.stride(0) != P):
-            raise ValueError(f"context_trace 'out': needs int32 [{T}, {N}] rows of pitch {P} on {self.device}")
-        self._policy_call(self.lib.carl_policy_context_trace, _ptr(ctx_idx0), _ptr(episode0), _ptr(terminated),
-                          _ptr(truncated), T, P if P != N else 0, _ptr(out))
-        return out
-
-    def ppo_workspace(self, policy, value_net, n_samples: int) -> torch.Tensor:
-        """A float32 workspace for ``ppo_grad`` of ``n_samples`` samples (carl_ppo_workspace_floats)."""
-        need = int(self.lib.carl_ppo_workspace_floats(C.byref(policy.struct(self.n, 0x10)), C.byref(value_net.struct(self.n, 0x10)),
-                                                      int(n_samples)))
-        if need < 0:
-            raise ValueError(f"ppo_workspace: invalid shapes or n_samples {n_samples}")
-        return torch.empty(need, dtype=torch.float32, device=self.device)
-
-    def ppo_grad(self, policy, value_net, buf: dict, obs0: torch.Tensor, context_id: torch.Tensor, *, idx=None,
-                 adv_norm=None, clip_range: float = 0.2, vf_coef: float = 0.5, ent_coef: float = 0.0,
-                 forward: bool = False, out: dict | None = None, workspace: torch.Tensor | None = None) -> dict:
-        """Loss and gradients of one PPO minibatch in three launches (include/carl_amd.h: carl_ppo_grad).  ``buf``: the dict
-        of ``rollout_policy(..., deterministic=False, value_net=, gae=)`` (``obs``, ``action``, ``log_prob``, ``advantage``,
-        ``return``: rows of one pitch); ``obs0`` ``[N, D]``: the observation its step 0 was chosen from; ``context_id``:
-        ``context_trace``'s result for that launch (the same pitch).  ``idx``: int32 ``[M]`` flat sample indices
-        ``t * pitch + lane`` (distinct, ``lane < N``; the pitch is ``buf["action"].stride(0)``), None: every sample.
-        ``adv_norm``: a float32 ``[2]`` device tensor (mean, 1 / (std + eps)) or None.  Returns ``{"grad_actor"
-        [set_floats], "grad_critic" [set_floats], "grad_log_std" [1] (Box families), "stats" [6]: policy loss, value
-        loss, mean entropy, approx_kl, clip fraction, M}`` and, with ``forward=True``, ``"new_log_prob"`` / ``"new_value"``
-        ``[M]`` -- float32 device tensors (``out``: such a dict to write into).  ``policy`` / ``value_net``: one-set policies
-        (host-built or ``on_device``).  No host synchronisation."""
-        _check_policy_family(self, policy)
-        act = buf["action"]
-        T, N = (int(v) for v in act.shape)
-        P = int(act.stride(0)) if T > 1 else N
-        if N != self.n:
-            raise ValueError(f"ppo_grad: a buffer of {N} lanes for an engine of {self.n}")
-        f32, i32 = torch.float32, torch.int32
-        adt = i32 if self.info.action_is_discrete else f32
-        cols = {"action": (act, adt), "log_prob": (buf["log_prob"], f32), "advantage": (buf["advantage"], f32),
-                "return": (buf["return"], f32), "context_id": (context_id, i32)}
-        for k, (t, dt) in cols.items():
-            if t.dtype != dt or t.device != self.device or t.shape[0] < T or tuple(t.shape[1:]) != (N,) or (
-                    N > 1 and t.stride(1) != 1) or (T > 1 and t.stride(0) != P):
-                raise ValueError(f"ppo_grad '{k}': needs {dt} [{T}, {N}] rows of pitch {P} on {self.device}")
-        obs = buf["obs"]
-        if obs.dtype != f32 or obs.device != self.device or obs.shape[0] < T or tuple(obs.shape[1:]) != (N, self.D) or any(
-                sz > 1 and st != w for sz, st, w in zip(obs.shape, obs.stride(), (P * self.D, self.D, 1))):
-            raise ValueError(f"ppo_grad 'obs': needs float32 [{T}, {N}, {self.D}] rows of pitch {P} on {self.device}")
-        if obs0.dtype != f32 or obs0.device != self.device or tuple(obs0.shape) != (N, self.D) or not obs0.is_contiguous():
-            raise ValueError(f"ppo_grad 'obs0': needs a contiguous float32 [{N}, {self.D}] tensor on {self.device}")
-        if idx is not None and (idx.dtype != i32 or idx.device != self.device or idx.dim() != 1 or not idx.is_contiguous()):
-            raise ValueError(f"ppo_grad 'idx': needs a contiguous int32 [M] tensor on {self.device}")
-        if adv_norm is not None and (adv_norm.dtype != f32 or adv_norm.device != self.device or adv_norm.numel() != 2
-                                     or not adv_norm.is_contiguous()):
-            raise ValueError(f"ppo_grad 'adv_norm': needs a contiguous float32 [2] tensor on {self.device}")
-        M = T * N if idx is None else int(idx.numel())
-        res = {} if out is None else out
-        box = not self.info.action_is_discrete
-        want = {"grad_actor": policy.set_floats, "grad_critic": value_net.set_floats, "stats": 6}
-        if box:
-            want["grad_log_std"] = 1
-        if forward:
-            want["new_log_prob"] = want["new_value"] = M
-        for k, size in want.items():
-            if k not in res:
-                res[k] = torch.empty(size, dtype=f32, device=self.device)
-            t = res[k]
-            if t.dtype != f32 or t.device != self.device or t.numel() != size or not t.is_contiguous():
-                raise ValueError(f"ppo_grad output '{k}': needs a contiguous float32 [{size}] tensor on {self.device}")
-        pol = policy.struct(self.n, policy.device_params(self.device).data_ptr())
-        crit = value_net.struct(self.n, value_net.device_params(self.device).data_ptr())
-        ws = self.ppo_workspace(policy, value_net, M) if workspace is None else workspace
-        pb = _lib.PpoBatch()
-        pb.family, pb.n_lanes, pb.n_steps, pb.row_pitch, pb.obs_dim = self.family, N, T, (P if P != N else 0), self.D
-        pb.n_contexts, pb.ctx_stride = int(self.b.n_contexts), int(self.b.ctx_stride)
-        pb.action_dtype = _lib.ACTION_I32 if self.info.action_is_discrete else _lib.ACTION_F32
-        pb.n_samples = M
-        pb.clip_range, pb.vf_coef, pb.ent_coef = float(clip_range), float(vf_coef), float(ent_coef)
-        pb.obs0, pb.obs, pb.context_id, pb.ctx_table = _ptr(obs0), _ptr(obs), _ptr(context_id), _ptr(self.ctx_table)
-        pb.action, pb.log_prob, pb.advantage, pb.ret = _ptr(act), _ptr(buf["log_prob"]), _ptr(buf["advantage"]), _ptr(buf["return"])
-        pb.idx, pb.adv_norm = _ptr(idx), _ptr(adv_norm)
-        po = _lib.PpoOut(_ptr(res["grad_actor"]), _ptr(res["grad_critic"]), _ptr(res.get("grad_log_std")), _ptr(res["stats"]),
-                         _ptr(res.get("new_log_prob")) if forward else None, _ptr(res.get("new_value")) if forward else None,
-                         _ptr(ws), int(ws.numel()))
-        ls = policy.device_log_std(self.device).data_ptr() if box else None
-        with torch.cuda.device(self.device):
-            _lib.check(self.lib.carl_ppo_grad(C.byref(pb), C.byref(pol), C.byref(crit), ls, C.byref(po), self._stream()))
-        return res
 
     # (key, dtype, per-episode rows) of an evaluate_policy result
     _EPISODE_KEYS =(("episodes", torch.int32, False), ("steps", torch.int32, False), ("return", torch.float32, True),

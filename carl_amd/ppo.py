@@ -1,8 +1,10 @@
-"""PPO on the device: collect, trace, update (include/carl_amd.h: carl_policy_context_trace, carl_ppo_grad).
+"""PPO on the device: collect, trace, update (include/carl_amd.h: carl_policy_context_trace, carl_ppo_grad; for the Brax
+families carl_brax_policy_context_trace, carl_brax_ppo_grad).
 
 ``PPO`` runs SB3's PPO (clipped surrogate, value loss, entropy bonus, GAE, advantage normalisation per minibatch, a
-global-norm gradient clip, Adam) on a classic-control ``CARLEnv`` or ``VecEngine`` as a fixed sequence of launches on the
-engine's stream:
+global-norm gradient clip, Adam) on a classic-control ``CARLEnv`` or ``VecEngine`` with ``MLPPolicy`` networks, or on a
+``CARLBraxEnv`` or ``BraxVecEngine`` with ``BraxMLPPolicy`` networks, as a fixed sequence of launches on the engine's
+stream:
 
 1. ``collect()``: clones ``ctx_idx`` / ``episode``, keeps the observation the first action is chosen from, runs
    ``rollout_policy(deterministic=False, value_net=, gae=)`` -- one launch for the T steps of every lane with sampled
@@ -18,14 +20,19 @@ The actor, the critic and ``log_std`` live on the device as packed tensors, hand
 ``MLPPolicy.on_device``; nothing here reads a result back (``rollout_policy``'s check of the critic's transform section
 against the actor's compares the host templates' sections, which no update changes).  ``info`` holds device tensors.
 
-Out of scope, and refused as ``carl_amd.policy`` refuses them: the Brax families, ``MixedVecEngine`` pairs, the gymnasium
-drop-in.
+A Brax model is a Box family whose Gaussian is the joint one over the model's actuators: ``log_std`` is ``[1, n_act]``
+(one value per actuator), the action column ``[T, N, n_act]`` in dense rows; everything else is the same sequence.
+
+Out of scope, and refused: ``MixedVecEngine`` pairs, the gymnasium drop-in; of the Brax families the models the closed
+loop refuses (more than 8 actuators, Humanoid-size inputs beyond ``CARL_POLICY_MAX_IN``) and collection under the
+first-state auto-reset (``autoreset_mode="first_state"``: an env's next episode would repeat the previous one's noise).
 """
 from __future__ import annotations
 
 import torch
 
 from carl_amd import _lib
+from carl_amd.brax_policy import BraxMLPPolicy, _brax_engine_of
 from carl_amd.policy import MLPPolicy, _engine_of
 
 
@@ -45,9 +52,44 @@ class _ResidentPolicy(MLPPolicy):
         return out
 
 
+class _ResidentBraxPolicy(BraxMLPPolicy):
+    """``_ResidentPolicy`` for a Brax model"""
+
+    transform_section = _ResidentPolicy.transform_section
+
+    @staticmethod
+    def of(template: BraxMLPPolicy, params: torch.Tensor, lanes_per_set: int, log_std=None) -> "_ResidentBraxPolicy":
+        out = BraxMLPPolicy.on_device(template, params, lanes_per_set, log_std)
+        out.__class__ = _ResidentBraxPolicy
+        out._host_section = template.transform_section().copy()
+        return out
+
+
+_MAX_BRAX_ACT = 8  # actuators of a sampled closed-loop launch (include/carl_amd.h: carl_brax_rollout_policy_sampled)
+
+
+def _brax_engine_for_ppo(env):
+    """(BraxVecEngine, CARLBraxEnv or None), with PPO's refusals of what the Brax closed loop does not cover"""
+    try:
+        eng, cenv = _brax_engine_of(env)
+    except TypeError:
+        raise ValueError(f"PPO: {type(env).__name__} is not a CARLBraxEnv or BraxVecEngine (MixedVecEngine pairs and the "
+                         "gymnasium drop-in are out of scope of the PPO update)") from None
+    if eng.autoreset_mode == "first_state":
+        raise ValueError("PPO: autoreset_mode='first_state' (CARL_FLAG_AUTORESET_FIRST_STATE) repeats an env's sampling "
+                         "noise in its next episode; PPO collects under the default auto-reset mode")
+    if eng.sys.n_act > _MAX_BRAX_ACT:
+        raise ValueError(f"PPO: the model has {eng.sys.n_act} actuators, the sampled closed loop holds at most {_MAX_BRAX_ACT}")
+    if eng.D > _lib.POLICY_MAX_IN:
+        raise ValueError(f"PPO: {eng.D} observations are more than CARL_POLICY_MAX_IN = {_lib.POLICY_MAX_IN} policy inputs "
+                         "(Humanoid-size observations are out of scope)")
+    return eng, cenv
+
+
 class PPO:
     """``policy`` / ``value_net``: one-set host-built ``MLPPolicy`` objects for ``env`` (``head="policy"`` /
-    ``head="value"``, the critic's shift | scale | clip the actor's) -- the shapes and the starting parameters.
+    ``head="value"``, the critic's shift | scale | clip the actor's) -- the shapes and the starting parameters; for a
+    ``CARLBraxEnv`` / ``BraxVecEngine`` they are ``BraxMLPPolicy`` objects, the actor's ``log_std`` one value per actuator.
     ``n_steps``: steps per lane and collection; ``batch_size``: samples per minibatch (default: a quarter of the buffer);
     the other arguments are SB3's.  ``seed``: the sample seed of the first collection (one more per collection) and the
     seed of the minibatch permutations."""
@@ -56,7 +98,8 @@ class PPO:
                  batch_size: int | None = None, lr: float = 3e-4, gamma: float = 0.99, lam: float = 0.95,
                  clip_range: float = 0.2, vf_coef: float = 0.5, ent_coef: float = 0.0, max_grad_norm: float = 0.5,
                  normalize_advantage: bool = True, seed: int = 0):
-        eng, cenv = _engine_of(env)
+        self.brax = isinstance(policy, BraxMLPPolicy) or isinstance(value_net, BraxMLPPolicy)
+        eng, cenv = _brax_engine_for_ppo(env) if self.brax else _engine_of(env)
         for p, head in ((policy, "policy"), (value_net, "value")):
             if not isinstance(p, MLPPolicy) or p._on_device or p.n_sets != 1 or p.lanes_per_set is not None:
                 raise ValueError("PPO: policy and value_net must be one-set host-built MLPPolicy objects")
@@ -66,6 +109,8 @@ class PPO:
                 raise ValueError(f"the policy was built for family {p.family}, this engine runs family {eng.family}")
         if not eng.auto_reset:
             raise ValueError("PPO needs auto_reset=True (a collection runs through episode ends)")
+        if self.brax:
+            eng._check_policy(policy, "PPO")
         eng._check_value_net(policy, value_net)
         self.env, self.engine, self._carl_env = env, eng, cenv
         self.n_steps, self.n_epochs = int(n_steps), int(n_epochs)
@@ -84,9 +129,10 @@ class PPO:
         self.actor_params = torch.as_tensor(policy.params).to(dev).contiguous().clone()   # [1, set_floats]
         self.critic_params = torch.as_tensor(value_net.params).to(dev).contiguous().clone()
         self.box = not policy.discrete
-        self.log_std = torch.as_tensor(policy.log_std).to(dev).contiguous().clone()        # [1]
-        self._actor = _ResidentPolicy.of(policy, self.actor_params, lanes, self.log_std if self.box else None)
-        self._critic = _ResidentPolicy.of(value_net, self.critic_params, lanes)
+        self.log_std = torch.as_tensor(policy.log_std).to(dev).contiguous().clone()        # [1]; a Brax model: [1, n_act]
+        resident = _ResidentBraxPolicy if self.brax else _ResidentPolicy
+        self._actor = resident.of(policy, self.actor_params, lanes, self.log_std if self.box else None)
+        self._critic = resident.of(value_net, self.critic_params, lanes)
         self._opt_params = [self.actor_params, self.critic_params] + ([self.log_std] if self.box else [])
         self.optimizer = torch.optim.Adam(self._opt_params, lr=float(lr), eps=1e-5)
         self._gen = torch.Generator(device=dev)
@@ -98,12 +144,18 @@ class PPO:
     # ------------------------------------------------------------------ state
     def actor(self) -> MLPPolicy:
         """The actor as a one-set host ``MLPPolicy`` (device-to-host copies)."""
+        if self.brax:  # (BraxMLPPolicy.unpack takes no log_std: through the constructor)
+            t = self._templates[0]
+            q = BraxMLPPolicy.unpack(t, self.actor_params.cpu().numpy()[0])
+            return BraxMLPPolicy(t._info, t.ctx_rows, q.layers, t.activation, q.shift, q.scale, q.clip, t.context_names,
+                                 self.log_std.cpu().numpy()[0], t.head)
         ls = float(self.log_std.cpu()[0]) if self.box else None
         return MLPPolicy.unpack(self._templates[0], self.actor_params.cpu().numpy()[0], ls)
 
     def critic(self) -> MLPPolicy:
         """The critic as a one-set host ``MLPPolicy`` (one device-to-host copy)."""
-        return MLPPolicy.unpack(self._templates[1], self.critic_params.cpu().numpy()[0])
+        unpack = BraxMLPPolicy.unpack if self.brax else MLPPolicy.unpack
+        return unpack(self._templates[1], self.critic_params.cpu().numpy()[0])
 
     # ------------------------------------------------------------------ one iteration
     def collect(self) -> dict:
@@ -129,7 +181,7 @@ class PPO:
     def minibatches(self):
         """The int32 flat sample indices ``t * pitch + lane`` of one epoch's minibatches, in order (device tensors)."""
         eng, T = self.engine, self.n_steps
-        P = int(self._buf["action"].stride(0)) if T > 1 else eng.n
+        P = int(self._buf["action"].stride(0)) if T > 1 and not self.brax else eng.n  # (a Brax buffer: dense rows)
         perm = torch.randperm(T * eng.n, device=eng.device, generator=self._gen)
         flat = ((perm // eng.n) * P + perm % eng.n).to(torch.int32)
         return [flat[s: s + self.batch_size].contiguous() for s in range(0, T * eng.n, self.batch_size)]

@@ -1177,6 +1177,69 @@ int carl_brax_policy_stats_merge(const carl_policy_t* policy_host, const carl_po
                                  void* stream);
 /* floats per packed weight set of a Brax policy's shape (n_out up to CARL_BRAX_MAX_ACT); -1 for an invalid shape */
 int32_t carl_brax_policy_set_floats(const carl_policy_t* policy_host);
+
+/* ---- the PPO update on the device for the Brax families (additive; ABI version unchanged) ----
+ * carl_brax_rollout_policy_valued + carl_gae leave a complete PPO rollout buffer on the device; the two calls below are
+ * carl_policy_context_trace and carl_ppo_grad for it: dense rows, a joint Gaussian over the model's n_act <= 8 actuators
+ * with one log_std each, networks packed by the Brax rule (carl_brax_policy_set_floats() floats per set).  The classic
+ * entry points keep refusing a Brax family; these refuse a classic one.  No existing kernel is touched.
+ *
+ * carl_brax_policy_context_trace: the walk documented at carl_policy_context_trace over dense rows ([n_steps][n_lanes]),
+ * one thread per env, the selector called with (c, lane_offset + env, e).  One rule is added: with
+ * CARL_FLAG_AUTORESET_FIRST_STATE set and batch->first_state != NULL a done env is put back to its first state, keeps its
+ * context and does not advance its episode counter, so c never moves and e does not advance (as without auto-reset).
+ * `batch` is read for family, n_lanes, n_contexts, selector, selector_stride, flags, seed, lane_offset and for whether
+ * first_state is NULL.  Validation, each CARL_ERR_INVALID_ARGUMENT before anything is enqueued, in this order: a NULL
+ * batch, a classic-control family, n_lanes or n_steps < 0, n_contexts < 1, an unknown selector, a NULL pointer.
+ * n_lanes == 0 or n_steps == 0 enqueues nothing. */
+int carl_brax_policy_context_trace(const carl_batch_t* batch, const int32_t* ctx_idx0 /* DEVICE [n_lanes] */,
+                                   const uint32_t* episode0 /* DEVICE [n_lanes] */,
+                                   const uint8_t* terminated /* DEVICE [n_steps][n_lanes] */,
+                                   const uint8_t* truncated /* DEVICE [n_steps][n_lanes] */, int32_t n_steps,
+                                   int32_t* context_id /* DEVICE [n_steps][n_lanes] */, void* stream);
+
+/* carl_brax_ppo_grad: carl_ppo_grad for a Brax model.  `ppo` is a carl_ppo_batch_t read with Brax meanings: family is
+ * not a classic one; rows are dense (row_pitch 0 or n_lanes); obs_dim == sys_host->obs_dim; action is
+ * [n_steps][n_lanes][n_act] float32 (CARL_ACTION_F32), the raw samples the launch recorded (the env's clip does not
+ * enter, as in SB3); context_id comes from carl_brax_policy_context_trace.  sys_host is read for obs_dim and n_act only.
+ * A sample's input is [ctx_table[ctx_rows[k]][context_id[t][env]] for k < n_ctx, then obs0[env] (t == 0) or
+ * obs[t - 1][env]] under the actor's shift / scale / clip; the critic reads the same transformed x.  Forward arithmetic
+ * is the closed loop's (bias first, explicit fma in input order, the same tanh).  The loss, the statistics and the
+ * clipping rule are exactly carl_ppo_grad's; the head is the joint Gaussian with log_std [n_act] on the device:
+ *   z_j = (a_j - mu_j) exp(-log_std_j)
+ *   lp  = sum_j fma(-z_j / 2, z_j, -log_std_j - ln(2 pi) / 2)   summed in fp32 in actuator order, as the sampled launch sums
+ *   H   = sum_j (1/2 + ln(2 pi) / 2 + log_std_j)
+ *   dlp/dmu_j = z_j exp(-log_std_j),  dlp/dlog_std_j = z_j^2 - 1,  dH/dlog_std_j = 1
+ * Outputs (carl_ppo_out_t): grad_actor / grad_critic [carl_brax_policy_set_floats()] in the packed layout, their shift |
+ * scale | clip entries and round-up padding +0.0; grad_log_std [n_act]; stats [6], new_log_prob / new_value [n_samples] as
+ * carl_ppo_grad's.
+ * How it runs: carl_ppo_grad's scheme -- a persistent launch per network of carl_brax_ppo_grad_workgroups(n_samples)
+ * workgroups over tiles of carl_brax_ppo_tile() samples, the weights staged in LDS once per workgroup, one sample per
+ * thread, a fixed block of every dW per thread summed in sample order in blocks of 16, one slab per workgroup in
+ * `workspace`, a last kernel adding the slabs in workgroup order in float64.  The actor's kernel holds a head of 8
+ * outputs (two transposed halves of four) and computes the n_act gradients of log_std as column sums like the head's
+ * bias gradients; the critic's launch is carl_ppo_grad's own kernel.  No floating-point atomics: the same call twice
+ * gives the same bits.
+ * Validation, each CARL_ERR_INVALID_ARGUMENT with a message of its own before anything is enqueued, in this order: a NULL
+ * struct; a classic-control family; n_lanes < 1 or n_steps < 1; a row_pitch that is neither 0 nor n_lanes; a model table
+ * out of range; obs_dim against the model; more than 8 actuators; the actor as carl_brax_rollout_policy_valued checks it
+ * (hidden layers, n_ctx, n_ctx + obs_dim <= CARL_POLICY_MAX_IN, context rows -- a carl_ppo_batch_t does not say which rows
+ * its producer made visible, so only their sign is checked --, n_in == n_ctx + obs_dim, n_out == n_act, a Box head, the
+ * activation, n_sets == 1, params); the critic likewise with one output, then its n_ctx and context rows against the
+ * actor's; the action dtype; n_contexts < 1 or ctx_stride < n_contexts; n_steps * n_lanes >= 2^31; n_samples < 1,
+ * n_samples > n_steps * n_lanes, or idx NULL with n_samples != n_steps * n_lanes; clip_range / vf_coef / ent_coef negative
+ * or not finite; a NULL required pointer of ppo; of out; log_std or out->grad_log_std NULL; workspace NULL, off a 16-byte
+ * boundary or smaller than carl_brax_ppo_workspace_floats().
+ * Stream-ordered and capturable; never synchronises with the host; allocates nothing.
+ * Out of scope: Humanoid-size inputs, more than 8 actuators, several weight sets. */
+int32_t carl_brax_ppo_tile(void);                          /* samples of one tile (256) */
+int32_t carl_brax_ppo_grad_workgroups(int32_t n_samples);  /* workgroups of a launch: min(tiles, 256); 0 for n_samples < 1 */
+/* floats of the workspace for these shapes and n_samples; -1 for an invalid shape (an actor with more than 8 outputs, a
+ * critic with more than one) or n_samples < 1 */
+int64_t carl_brax_ppo_workspace_floats(const carl_policy_t* policy_host, const carl_policy_t* critic_host, int32_t n_samples);
+int carl_brax_ppo_grad(const carl_ppo_batch_t* ppo_host, const carl_brax_sys_t* sys_host, const carl_policy_t* policy_host,
+                       const carl_policy_t* critic_host, const float* log_std /* DEVICE [n_act] */,
+                       const carl_ppo_out_t* out, void* stream);
 /* The shape carl_brax_rollout_policy, carl_brax_rollout_policy_sampled and carl_brax_rollout_policy_valued launch for this
  * batch, model and step count (host only, no device access beyond the
  * compute-unit count of the current device; 256 where there is none): with n_groups = ceil(n_lanes / (64 / lanes_per_env))
