@@ -32,7 +32,10 @@ ARCH = "gfx950"
 # carl_brax_policy_value.hip (the sampled rollout with a critic) instantiates the sampled variant's valued variant: its flags.
 # (The five closed-loop units expand one list of instances and share one host launch path: csrc/brax_policy_host.hpp.)
 # carl_ppo.hip (the PPO update: context trace, minibatch gradients) calls the closed-loop rollout's device functions: same flags.
-# carl_brax_ppo.hip (that update for the Brax families) calls carl_ppo.hip's device functions and instantiates its kernels: same flags.
+# It holds the library's one trace walk and classic reduction, and the function that launches the trace.
+# carl_brax_ppo.hip (that update for the Brax families) calls the same device helpers (csrc/ppo_device.hip.h) in its actor
+# kernel and its reduction, instantiates the network kernel (csrc/ppo_net_kernel.hip.h) for its critic and runs the trace
+# through carl_ppo.hip's launch function: same flags.  (The two PPO units share one host path: csrc/ppo_host.hpp.)
 SOURCES = {"carl_amd.hip": ["-fno-slp-vectorize"], "carl_brax.hip": ["-fno-slp-vectorize"],
            "carl_policy.hip": ["-fno-slp-vectorize"], "carl_policy_sample.hip": ["-fno-slp-vectorize"],
            "carl_policy_value.hip": ["-fno-slp-vectorize"], "carl_es.hip": ["-fno-slp-vectorize"],

@@ -1,10 +1,11 @@
 // brax_ppo_kernels.hip.h -- the PPO update of the Brax families on the device (include/carl_amd.h:
 // carl_brax_policy_context_trace, carl_brax_ppo_grad).  Included by carl_brax_ppo.hip only.  Everything the classic unit
-// has is called, not restated: ppo_kernels.hip.h's tile helpers (ppo_put, ppo_accumulate, ppo_accumulate_row,
-// ppo_block_sum, ppo_act_grad, ppo_slab_index / ppo_slab_sum), its whole ppo_net_kernel<H> for the CRITIC (one output, the
-// same dense rows, the same input gather: the classic instance's layout as it is) and its context_trace_kernel for the
-// trace (carl_brax_ppo.hip), policy_kernels.hip.h's dense_layer / head_layer / activate / normalize_input.  No kernel of
-// another unit changes (profiles/brax_ppo_isa_identity.txt).
+// has is called, not restated: ppo_device.hip.h's tile helpers (ppo_put, ppo_accumulate, ppo_accumulate_row,
+// ppo_block_sum, ppo_act_grad, ppo_slab_index / ppo_slab_sum), policy_kernels.hip.h's dense_layer / head_layer / activate /
+// normalize_input.  The CRITIC (one output, the same dense rows, the same input gather) is ppo_net_kernel<H> as it is
+// (ppo_net_kernel.hip.h, instantiated by ppo_host.hpp's launch_ppo_net); the trace runs carl_ppo.hip's
+// context_trace_kernel through launch_context_trace.  No kernel of another unit changes
+// (profiles/brax_ppo_isa_identity.txt).
 //
 // What is new is the ACTOR's kernel, brax_ppo_actor_kernel<H>: ppo_net_kernel's scheme -- one persistent launch, the
 // network staged in LDS once per workgroup, one sample per thread with its forward and backward pass in registers, a
@@ -28,14 +29,7 @@
 // dlog_std [8] (head row tid).
 #pragma once
 
-// ppo_kernels.hip.h defines two kernels that are not templates (the slab reduction, the trace walk); a second unit that
-// includes it would define their symbols a second time.  This unit's instances of them get names of their own -- the
-// trace walk is launched under its name by carl_brax_ppo.hip, the classic reduction is not launched from here.
-#define ppo_reduce_kernel brax_unit_ppo_reduce_kernel
-#define context_trace_kernel brax_unit_context_trace_kernel
-#include "ppo_kernels.hip.h"
-#undef ppo_reduce_kernel
-#undef context_trace_kernel
+#include "ppo_device.hip.h"
 
 namespace carl {
 

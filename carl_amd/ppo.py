@@ -44,25 +44,19 @@ class _ResidentPolicy(MLPPolicy):
     def transform_section(self):
         return self._host_section
 
-    @staticmethod
-    def of(template: MLPPolicy, params: torch.Tensor, lanes_per_set: int, log_std=None) -> "_ResidentPolicy":
-        out = MLPPolicy.on_device(template, params, lanes_per_set, log_std)
-        out.__class__ = _ResidentPolicy
-        out._host_section = template.transform_section().copy()
-        return out
-
 
 class _ResidentBraxPolicy(BraxMLPPolicy):
     """``_ResidentPolicy`` for a Brax model"""
 
     transform_section = _ResidentPolicy.transform_section
 
-    @staticmethod
-    def of(template: BraxMLPPolicy, params: torch.Tensor, lanes_per_set: int, log_std=None) -> "_ResidentBraxPolicy":
-        out = BraxMLPPolicy.on_device(template, params, lanes_per_set, log_std)
-        out.__class__ = _ResidentBraxPolicy
-        out._host_section = template.transform_section().copy()
-        return out
+
+def _resident(cls, template: MLPPolicy, params: torch.Tensor, lanes_per_set: int, log_std=None):
+    """``template`` on the device as a ``cls`` (``_ResidentPolicy`` / ``_ResidentBraxPolicy``)"""
+    out = cls.on_device(template, params, lanes_per_set, log_std)
+    out.__class__ = cls
+    out._host_section = template.transform_section().copy()
+    return out
 
 
 _MAX_BRAX_ACT = 8  # actuators of a sampled closed-loop launch (include/carl_amd.h: carl_brax_rollout_policy_sampled)
@@ -131,8 +125,8 @@ class PPO:
         self.box = not policy.discrete
         self.log_std = torch.as_tensor(policy.log_std).to(dev).contiguous().clone()        # [1]; a Brax model: [1, n_act]
         resident = _ResidentBraxPolicy if self.brax else _ResidentPolicy
-        self._actor = resident.of(policy, self.actor_params, lanes, self.log_std if self.box else None)
-        self._critic = resident.of(value_net, self.critic_params, lanes)
+        self._actor = _resident(resident, policy, self.actor_params, lanes, self.log_std if self.box else None)
+        self._critic = _resident(resident, value_net, self.critic_params, lanes)
         self._opt_params = [self.actor_params, self.critic_params] + ([self.log_std] if self.box else [])
         self.optimizer = torch.optim.Adam(self._opt_params, lr=float(lr), eps=1e-5)
         self._gen = torch.Generator(device=dev)

@@ -1,7 +1,7 @@
 """carl_amd.PPO on a Brax model on the GPU (inverted pendulum: 1 actuator; Reacher: 2): after every update the device
 parameters against a host replica -- brax_ppo_ref.py's float64 gradients of the same minibatches in the same order, the
 same global-norm clip, torch's CPU Adam -- within the gradient tolerance of test_gpu_brax_ppo_grad.py propagated through
-Adam's step (the bound test_gpu_ppo.py derives, restated in Replica below for a log_std vector); the rollout buffer's
+Adam's step (ppo_checks.AdamReplica, which test_gpu_ppo.py shares, here with a log_std vector); the rollout buffer's
 context ids and first observation; the transform entries and padding of the packed tensors unchanged bit for bit; the
 refusals of the first-state auto-reset, of auto_reset=False and of the engines out of scope."""
 import numpy as np
@@ -11,38 +11,21 @@ import torch
 import brax_policy_cases as BPC
 import brax_ppo_ref as BR
 import brax_sampling_cases as BSC
+import ppo_checks as PK
 import ppo_ref as R
 from carl_amd import PPO, _lib
 from carl_amd.brax_policy import BraxMLPPolicy
+from ppo_checks import CLIP, ENT, LR, MAX_NORM, VF
 
 pytestmark = pytest.mark.gpu
 
-LR, B1, B2, EPS = 3e-4, 0.9, 0.999, 1e-5
-CLIP, VF, ENT, MAX_NORM = 0.2, 0.5, 0.01, 0.5
 
-
-class Replica:
-    """The host side of one PPO run: packed float32 parameters (actor, critic, log_std [n_act]) under torch's CPU Adam,
-    and next to them a bound on how far the device's parameters may be from them.
-
-    The bound is test_gpu_ppo.py's.  The device's gradient entry differs from the reference's by at most dg = K 2^-24 S
-    (brax_ppo_ref.py).  The clip multiplies by coef = min(1, max_norm / (|g| + 1e-6)), whose relative error is at most
-    |dg|_2 / |g|_2.  Adam keeps m = b1 m + (1 - b1) g and v = b2 v + (1 - b2) g^2, so their errors obey
-    em = b1 em + (1 - b1) dg and ev = b2 ev + (1 - b2) (2 |g| dg + dg^2); with the bias corrections the step is
-    lr * mh / (sqrt(vh) + eps), whose error is at most lr * (emh / D + |mh| ds / (D_ref D)), ds = min(sqrt(evh),
-    evh / sqrt(vh)) the error of sqrt(vh) and D = max(D_ref - ds, eps) the smallest denominator the device can have; never
-    more than lr * 2 / sqrt(1 - b2).  The per-step errors add up over the steps; the total is doubled for the second-order
-    effect of the parameters' own difference on later gradients, and 4 roundings of the parameter are added."""
+class Replica(PK.AdamReplica):
+    """ppo_checks.AdamReplica on brax_ppo_ref.py's gradients: the actor, the critic and log_std [n_act]"""
 
     def __init__(self, actor, critic):
         self.templates = (actor, critic)
-        self.params = [torch.tensor(actor.params[0].copy()), torch.tensor(critic.params[0].copy()),
-                       torch.tensor(actor.log_std[0].copy())]
-        self.opt = torch.optim.Adam(self.params, lr=LR, eps=EPS)
-        self.em = [np.zeros(p.numel()) for p in self.params]
-        self.ev = [np.zeros(p.numel()) for p in self.params]
-        self.err = [np.zeros(p.numel()) for p in self.params]
-        self.steps = 0
+        super().__init__([actor.params[0], critic.params[0], actor.log_std[0]])
 
     def policies(self):
         a, c = self.templates
@@ -61,31 +44,7 @@ class Replica:
                                    pick(buf["advantage"]), pick(buf["return"]), norm, CLIP, VF, ENT)
         g = [ref["grad_actor"], ref["grad_critic"], ref["grad_log_std"]]
         dg = [BR.K * BR.U * ref["S_actor"], BR.K * BR.U * ref["S_critic"], BR.K * BR.U * ref["S_log_std"]]
-        total = np.sqrt(sum((v ** 2).sum() for v in g))
-        coef = min(1.0, MAX_NORM / (total + 1e-6))
-        rel = np.sqrt(sum((v ** 2).sum() for v in dg)) / total
-        self.steps += 1
-        k = self.steps
-        for i, p in enumerate(self.params):
-            p.grad = torch.tensor((g[i] * coef).astype(np.float32))
-            gi, dgi = np.abs(g[i]) * coef, coef * dg[i] + np.abs(g[i]) * coef * rel
-            self.em[i] = B1 * self.em[i] + (1 - B1) * dgi
-            self.ev[i] = B2 * self.ev[i] + (1 - B2) * (2 * gi * dgi + dgi ** 2)
-        self.opt.step()
-        for i, p in enumerate(self.params):
-            st = self.opt.state[p]
-            mh = np.abs(st["exp_avg"].numpy().astype(np.float64)) / (1 - B1 ** k)
-            vh = st["exp_avg_sq"].numpy().astype(np.float64) / (1 - B2 ** k)
-            emh, evh = self.em[i] / (1 - B1 ** k), self.ev[i] / (1 - B2 ** k)
-            with np.errstate(divide="ignore", invalid="ignore"):
-                ds = np.minimum(np.sqrt(evh), np.where(vh > 0, evh / np.sqrt(vh), np.inf))
-            d_ref = np.sqrt(vh) + EPS
-            d_min = np.maximum(d_ref - ds, EPS)
-            du = emh / d_min + mh * ds / (d_ref * d_min)
-            self.err[i] += LR * np.minimum(du, 2 / np.sqrt(1 - B2))
-
-    def bound(self, i):
-        return 2 * self.err[i] + 4 * BR.U * np.abs(self.params[i].numpy().astype(np.float64))
+        self.apply(g, dg)
 
 
 def networks(eng, seed):
@@ -105,21 +64,7 @@ def test_ppo_updates_match_the_host_replica(model):
     ppo = PPO(eng, actor, critic, n_steps=T, n_epochs=2, batch_size=128, lr=LR, clip_range=CLIP, vf_coef=VF, ent_coef=ENT,
               max_grad_norm=MAX_NORM, seed=9)
     assert ppo.brax and tuple(ppo.log_std.shape) == (1, eng.sys.n_act)
-    order, draw = [], ppo.minibatches
-
-    def recording():
-        mbs = draw()
-        order.append([m.cpu().numpy().astype(np.int64) for m in mbs])
-        return mbs
-
-    ppo.minibatches = recording
-    start, roll = {}, eng.rollout_policy
-
-    def recording_rollout(*a, **kw):  # ctx_idx / episode right before the launch (the first collect() resets the engine)
-        start["ctx"], start["ep"] = eng.ctx_idx.cpu().numpy(), eng.episode.cpu().numpy().view(np.uint32)
-        return roll(*a, **kw)
-
-    eng.rollout_policy = recording_rollout
+    order, start = PK.record(ppo, eng)
     rep = Replica(actor, critic)
     table = eng.ctx_table.cpu().numpy()
     for it in range(2):
@@ -127,8 +72,8 @@ def test_ppo_updates_match_the_host_replica(model):
         hb = {k: buf[k][:T].cpu().numpy() for k in ("obs", "action", "log_prob", "advantage", "return", "context_id",
                                                      "terminated", "truncated")}
         hb["obs0"] = buf["obs0"].cpu().numpy()
-        walk = BR.context_walk(start["ctx"], start["ep"], hb["terminated"], hb["truncated"], _lib.SEL_ROUND_ROBIN, 1,
-                               BSC.N_CTX, 5, 0, True)
+        walk = BR.context_walk(start["ctx"], start["ep"].view(np.uint32), hb["terminated"], hb["truncated"],
+                               _lib.SEL_ROUND_ROBIN, 1, BSC.N_CTX, 5, 0, True)
         np.testing.assert_array_equal(hb["context_id"], walk)
         assert (walk != walk[0]).any()
         if it:
@@ -142,15 +87,7 @@ def test_ppo_updates_match_the_host_replica(model):
             for flat in epoch:
                 rep.step(table, hb, flat, N)
         dev = [ppo.actor_params[0], ppo.critic_params[0], ppo.log_std[0]]
-        for i, d in enumerate(dev):
-            diff = np.abs(d.cpu().numpy().astype(np.float64) - rep.params[i].numpy().astype(np.float64))
-            bound = rep.bound(i)
-            print(f"{model}, iteration {it}, tensor {i}: largest difference {diff.max():.3e}, bound there "
-                  f"{bound[np.argmax(diff)]:.3e}, largest difference / bound {np.max(diff / np.maximum(bound, 1e-300)):.3e}")
-            assert np.all(diff <= bound)
-        for d, pol in ((ppo.actor_params[0], actor), (ppo.critic_params[0], critic)):
-            np.testing.assert_array_equal(d.cpu().numpy()[pol.weight_floats:].view(np.uint32),
-                                          pol.params[0][pol.weight_floats:].view(np.uint32))
+        PK.check_against_replica(f"{model}, iteration {it}", dev, rep, ppo, actor, critic)
     got = ppo.actor()
     assert isinstance(got, BraxMLPPolicy) and not np.array_equal(got.params, actor.params)
     np.testing.assert_array_equal(got.log_std, ppo.log_std.cpu().numpy())

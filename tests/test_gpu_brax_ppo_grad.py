@@ -4,7 +4,7 @@ the three activations, with and without context inputs and advantage normalisati
 as permuted index subsets and every sample (idx NULL), one M just past workgroups_cap x TS (some workgroup runs a second
 tile), a distinct log_std per actuator.  The synthetic shapes go through the C entry point directly (it reads obs_dim and
 n_act of the model table, nothing else); the engine's method is held by the end-to-end test below.  Per case: new_value
-within value_cases.check_values; new_log_prob within test_gpu_ppo_grad.py's bound, summed over the actuators; every
+within value_cases.check_values; new_log_prob within ppo_checks.py's Gaussian bound, summed over the actuators; every
 gradient entry within K * 2^-24 * S (brax_ppo_ref.py: K = 8 K0, K0 measured on the CPU); the shift | scale | clip entries
 and the padding exactly +0.0; two calls bit-identical; a canary behind every output and the workspace; the statistics as
 in the classic test.
@@ -21,36 +21,23 @@ import torch
 import brax_policy_cases as BPC
 import brax_ppo_ref as BR
 import brax_sampling_cases as BSC
-import sampling_ref as SR
+import ppo_checks as PK
 import value_cases as VC
 from carl_amd import _lib
 from carl_amd.brax_policy import BraxMLPPolicy
 
 pytestmark = pytest.mark.gpu
 
-CANARY = 7.25
-
 
 def log_prob_reference(actor, x, action):
-    """(lp64 [M], bound [M]) of the joint Gaussian log-probability of actions [M, n_act] on raw inputs x: per actuator
-    test_gpu_ppo_grad.py's bound -- z = (a - mu) * exp(-log_std) in fp32: the forward bound on mu and the roundings of the
-    subtraction, of expf and of the product, then fma(-z / 2, z, lp0) -- summed over the actuators"""
+    """(lp64 [M], bound [M]) of the joint Gaussian log-probability of actions [M, n_act] on raw inputs x
+    (ppo_checks.gaussian_log_prob_reference on the host reference's means)"""
     _, y64, ybound = BPC.reference_actions(actor, x)
-    ls = np.asarray(actor.log_std, np.float32).reshape(-1).astype(np.float64)
-    a = np.asarray(action, np.float32).reshape(-1, actor.n_out)
-    lp64, bound = np.zeros(len(a)), np.zeros(len(a))
-    for j in range(actor.n_out):
-        mu = y64[:, j]
-        z = (a[:, j].astype(np.float64) - mu) * np.exp(-ls[j])
-        dz = (ybound[:, j] + 4 * SR.ULP * (np.abs(a[:, j]) + np.abs(mu))) * np.exp(-ls[j]) + 4 * SR.ULP * np.abs(z)
-        lpj = SR.gaussian_log_prob64(z, ls[j])
-        lp64 += lpj
-        bound += np.abs(z) * dz + dz * dz + 4 * SR.ULP * (abs(ls[j]) + 2 + np.abs(lpj))
-    return lp64, bound
+    return PK.gaussian_log_prob_reference(y64, ybound, actor.log_std, action)
 
 
 def run(case):
-    """the case on the GPU, twice -> [(outputs as NumPy arrays, what lies behind each output and the workspace)] * 2"""
+    """the case on the GPU, twice (ppo_checks.run_twice)"""
     dev = "cuda"
     lib = _lib.load()
     actor, critic = case["actor"], case["critic"]
@@ -68,18 +55,14 @@ def run(case):
     assert need > 0
     sys_t = BR.fake_sys(case["shape"])
     pb = BR.ppo_batch(case, {k: (None if v is None else v.data_ptr()) for k, v in t.items()})
-    results = []
-    for _ in range(2):
-        big = {k: torch.full((n + 16,), CANARY, dtype=torch.float32, device=dev) for k, n in sizes.items()}
-        ws = torch.full((need + 16,), CANARY, dtype=torch.float32, device=dev)
-        po = _lib.PpoOut(*(big[k].data_ptr() for k in ("grad_actor", "grad_critic", "grad_log_std", "stats", "new_log_prob",
+
+    def launch(out, ws):
+        po = _lib.PpoOut(*(out[k].data_ptr() for k in ("grad_actor", "grad_critic", "grad_log_std", "stats", "new_log_prob",
                                                         "new_value")), ws.data_ptr(), need)
         _lib.check(lib.carl_brax_ppo_grad(C.byref(pb), C.byref(sys_t), C.byref(pol), C.byref(crit), ls.data_ptr(),
                                           C.byref(po), torch.cuda.current_stream().cuda_stream))
-        torch.cuda.synchronize()
-        results.append(({k: big[k][:n].cpu().numpy() for k, n in sizes.items()},
-                        {**{k: big[k][n:].cpu().numpy() for k, n in sizes.items()}, "workspace": ws[need:].cpu().numpy()}))
-    return results
+
+    return PK.run_twice(sizes, need, launch, dev)
 
 
 @pytest.mark.parametrize("spec", BR.grad_cases(), ids=[c[0] for c in BR.grad_cases()])
@@ -91,34 +74,22 @@ def test_brax_ppo_grad_against_the_reference(spec):
     BR.assert_conditioned(case, ref)
     actor, critic, x = case["actor"], case["critic"], case["x"]
     M = case["flat"].size
-    (got, tail), (again, tail2) = run(case)
-    for t in (tail, tail2):
-        for k, v in t.items():
-            assert (v == CANARY).all(), k
-    for k in got:
-        np.testing.assert_array_equal(got[k].view(np.uint32), again[k].view(np.uint32), err_msg=k)
+    got = PK.check_canaries_and_bits(run(case))
 
     # ---- the forward pass, at the tolerances of the closed-loop tests
     VC.check_values(critic, x, got["new_value"])
     a = case["action"].reshape(-1, actor.n_out)[case["flat"]]
     lp64, bound = log_prob_reference(actor, x, a)
-    err = np.abs(got["new_log_prob"].astype(np.float64) - lp64)
+    err = PK.check_log_prob(got["new_log_prob"], lp64, bound, ref["new_log_prob"])
     print(f"{case['id']}: largest log-prob error / bound {np.max(err / bound):.3f}")
-    assert np.all(err <= bound * (1 + 1e-9)), (err.max(), bound[np.argmax(err - bound)])
-    np.testing.assert_allclose(lp64, ref["new_log_prob"], rtol=0, atol=1e-9 * (1 + np.abs(lp64).max()))
 
     # ---- the gradients
-    for name, pol in (("actor", actor), ("critic", critic)):
-        assert not got["grad_" + name][pol.weight_floats:].view(np.uint32).any(), name  # transform | padding: +0.0 bits
+    PK.check_transform_entries(got, actor, critic)
     worst = BR.case_k(got, ref)
     print(f"{case['id']}: M = {M}, largest gradient error {worst:.2f} x 2^-24 S (K = {BR.K:.0f})")
     assert worst <= BR.K
 
-    # ---- the statistics, as in test_gpu_ppo_grad.py
-    s = got["stats"].astype(np.float64)
-    assert s[5] == M
-    np.testing.assert_allclose(s[:4], ref["stats"][:4], rtol=2e-5, atol=2e-5)
-    assert s[4] == pytest.approx(ref["stats"][4], abs=0.5 / M + 1e-6)
+    PK.check_statistics(got["stats"], ref["stats"], M)
 
 
 # ---------------------------------------------------------------- end to end: the launch's own columns

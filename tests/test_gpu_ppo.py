@@ -7,42 +7,23 @@ import pytest
 import torch
 
 import policy_cases as PC
+import ppo_checks as PK
 import ppo_ref as R
 import value_cases as VC
 from carl_amd import PPO, _lib
 from carl_amd.policy import MLPPolicy
+from ppo_checks import CLIP, ENT, LR, MAX_NORM, VF
 
 pytestmark = pytest.mark.gpu
 
-LR, B1, B2, EPS = 3e-4, 0.9, 0.999, 1e-5
-CLIP, VF, ENT, MAX_NORM = 0.2, 0.5, 0.01, 0.5
 
-
-class Replica:
-    """The host side of one PPO run: packed float32 parameters under torch's CPU Adam, and next to them a bound on how far
-    the device's parameters may be from them.
-
-    The bound.  The device's gradient entry differs from the reference's by at most dg = K 2^-24 S (ppo_ref.py).  The clip
-    multiplies by coef = min(1, max_norm / (|g| + 1e-6)), whose relative error is at most |dg|_2 / |g|_2.  Adam keeps
-    m = b1 m + (1 - b1) g and v = b2 v + (1 - b2) g^2, so their errors obey em = b1 em + (1 - b1) dg and
-    ev = b2 ev + (1 - b2) (2 |g| dg + dg^2); with the bias corrections the step is lr * mh / (sqrt(vh) + eps), whose error
-    is at most lr * (emh / D + |mh| ds / (D_ref D)), ds = min(sqrt(evh), evh / sqrt(vh)) the error of sqrt(vh) and
-    D = max(D_ref - ds, eps) the smallest denominator the device can have; never more than lr * 2 / sqrt(1 - b2) (|step|
-    <= lr / sqrt(1 - b2) on both sides).  The per-step errors add up over the steps.  The parameters' own difference
-    changes later gradients too, a second-order effect: the total is doubled for it, and 4 roundings of the parameter
-    are added."""
+class Replica(PK.AdamReplica):
+    """ppo_checks.AdamReplica on ppo_ref.py's gradients: the actor, the critic and, for a Box family, log_std [1]"""
 
     def __init__(self, actor, critic):
         self.templates = (actor, critic)
         self.box = not actor.discrete
-        self.params = [torch.tensor(actor.params[0].copy()), torch.tensor(critic.params[0].copy())]
-        if self.box:
-            self.params.append(torch.tensor(actor.log_std.copy()))
-        self.opt = torch.optim.Adam(self.params, lr=LR, eps=EPS)
-        self.em = [np.zeros(p.numel()) for p in self.params]
-        self.ev = [np.zeros(p.numel()) for p in self.params]
-        self.err = [np.zeros(p.numel()) for p in self.params]
-        self.steps = 0
+        super().__init__([actor.params[0], critic.params[0]] + ([actor.log_std] if self.box else []))
 
     def policies(self):
         ls = float(self.params[2][0]) if self.box else None
@@ -59,31 +40,7 @@ class Replica:
                              pick(buf["return"]), norm, CLIP, VF, ENT)
         g = [ref["grad_actor"], ref["grad_critic"]] + ([np.array([ref["grad_log_std"]])] if self.box else [])
         dg = [R.K * R.U * ref["S_actor"], R.K * R.U * ref["S_critic"]] + ([np.array([R.K * R.U * ref["S_log_std"]])] if self.box else [])
-        total = np.sqrt(sum((v ** 2).sum() for v in g))
-        coef = min(1.0, MAX_NORM / (total + 1e-6))
-        rel = np.sqrt(sum((v ** 2).sum() for v in dg)) / total
-        self.steps += 1
-        k = self.steps
-        for i, p in enumerate(self.params):
-            p.grad = torch.tensor((g[i] * coef).astype(np.float32))
-            gi, dgi = np.abs(g[i]) * coef, coef * dg[i] + np.abs(g[i]) * coef * rel
-            self.em[i] = B1 * self.em[i] + (1 - B1) * dgi
-            self.ev[i] = B2 * self.ev[i] + (1 - B2) * (2 * gi * dgi + dgi ** 2)
-        self.opt.step()
-        for i, p in enumerate(self.params):
-            st = self.opt.state[p]
-            mh = np.abs(st["exp_avg"].numpy().astype(np.float64)) / (1 - B1 ** k)
-            vh = st["exp_avg_sq"].numpy().astype(np.float64) / (1 - B2 ** k)
-            emh, evh = self.em[i] / (1 - B1 ** k), self.ev[i] / (1 - B2 ** k)
-            with np.errstate(divide="ignore", invalid="ignore"):
-                ds = np.minimum(np.sqrt(evh), np.where(vh > 0, evh / np.sqrt(vh), np.inf))
-            d_ref = np.sqrt(vh) + EPS
-            d_min = np.maximum(d_ref - ds, EPS)
-            du = emh / d_min + mh * ds / (d_ref * d_min)
-            self.err[i] += LR * np.minimum(du, 2 / np.sqrt(1 - B2))
-
-    def bound(self, i):
-        return 2 * self.err[i] + 4 * R.U * np.abs(self.params[i].numpy().astype(np.float64))
+        self.apply(g, dg)
 
 
 def host(buf, T):
@@ -108,21 +65,7 @@ def test_ppo_updates_match_the_host_replica(family):
     critic = VC.make_critic(eng, actor, (8,), "tanh", rng)
     ppo = PPO(eng, actor, critic, n_steps=T, n_epochs=2, batch_size=2048, lr=LR, clip_range=CLIP, vf_coef=VF, ent_coef=ENT,
               max_grad_norm=MAX_NORM, seed=9)
-    order, draw = [], ppo.minibatches
-
-    def recording():
-        mbs = draw()
-        order.append([m.cpu().numpy().astype(np.int64) for m in mbs])
-        return mbs
-
-    ppo.minibatches = recording
-    start, roll = {}, eng.rollout_policy
-
-    def recording_rollout(*a, **kw):  # ctx_idx / episode right before the launch (the first collect() resets the engine)
-        start["ctx"], start["ep"] = eng.ctx_idx.cpu().numpy(), eng.episode.cpu().numpy()
-        return roll(*a, **kw)
-
-    eng.rollout_policy = recording_rollout
+    order, start = PK.record(ppo, eng)
     rep = Replica(actor, critic)
     table = eng.ctx_table.cpu().numpy()
     for it in range(2):
@@ -144,16 +87,7 @@ def test_ppo_updates_match_the_host_replica(family):
             for flat in epoch:
                 rep.step(table, hb, flat, P)
         dev = [ppo.actor_params[0], ppo.critic_params[0]] + ([ppo.log_std] if box else [])
-        for i, d in enumerate(dev):
-            diff = np.abs(d.cpu().numpy().astype(np.float64) - rep.params[i].numpy().astype(np.float64))
-            bound = rep.bound(i)
-            print(f"iteration {it}, tensor {i}: largest difference {diff.max():.3e}, bound there "
-                  f"{bound[np.argmax(diff)]:.3e}, largest difference / bound {np.max(diff / np.maximum(bound, 1e-300)):.3e}")
-            assert np.all(diff <= bound)
-        # the transform section and the padding keep their bits
-        for d, pol in ((ppo.actor_params[0], actor), (ppo.critic_params[0], critic)):
-            np.testing.assert_array_equal(d.cpu().numpy()[pol.weight_floats:].view(np.uint32),
-                                          pol.params[0][pol.weight_floats:].view(np.uint32))
+        PK.check_against_replica(f"iteration {it}", dev, rep, ppo, actor, critic)
     # the parameters moved, and come back as host policies
     assert not np.array_equal(ppo.actor().params, actor.params) and ppo.critic().head == "value"
     info = ppo.learn(1)
