@@ -397,3 +397,20 @@ EXPORTS.update({
     "carl_brax_ppo_grad": (C.c_int, [C.POINTER(PpoBatch), C.POINTER(BraxSys), C.POINTER(Policy), C.POINTER(Policy), _vp,
                                      C.POINTER(PpoOut), _vp]),
 })
+
+
+# ---- PPO's running normalisation (include/carl_amd.h: carl_ppo_input_stats, carl_ppo_return_stats_t) ----------------
+class PpoReturnStats(C.Structure):
+    _fields_ = [("n_lanes", _i), ("n_steps", _i), ("row_pitch", _i), ("gamma", C.c_float), ("reward", _vp),
+                ("terminated", _vp), ("truncated", _vp), ("ret", _vp), ("ret_rows", _vp), ("partial", _vp),
+                ("partial_capacity", _i), ("reserved", _i)]
+
+
+EXPORTS.update({
+    "carl_ppo_input_stats_slabs": (C.c_int32, [C.c_int32, C.c_int32]),
+    "carl_ppo_input_stats": (C.c_int, [C.POINTER(PpoBatch), C.POINTER(Policy), C.POINTER(PolicyStats), _vp]),
+    "carl_brax_ppo_input_stats": (C.c_int, [C.POINTER(PpoBatch), C.POINTER(Policy), C.POINTER(PolicyStats), _vp]),
+    "carl_ppo_return_stats_slabs": (C.c_int32, [C.c_int32]),
+    "carl_ppo_return_stats": (C.c_int, [C.POINTER(PpoReturnStats), _vp]),
+    "carl_ppo_return_merge": (C.c_int, [_vp, C.c_int32, C.c_int64, C.POINTER(PolicyRunningStats), C.c_double, _vp, _vp]),
+})

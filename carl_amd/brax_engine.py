@@ -501,6 +501,9 @@ class BraxVecEngine(LaneEngine):
     def _c_ppo_grad(self, pb, pol, crit, log_std, po) -> int:
         return self.lib.carl_brax_ppo_grad(pb, self._sys_ref, pol, crit, log_std, po, self._stream())
 
+    def _c_ppo_input_stats(self, pb, pol, st) -> int:
+        return self.lib.carl_brax_ppo_input_stats(pb, pol, st, self._stream())
+
     def evaluate_policy(self, *args, **kwargs):
         raise NotImplementedError(f"{type(self).__name__}: evaluate_policy (sampling, input statistics) covers the "
                                   "classic-control families only; the episodes mode of the Brax closed-loop rollout is "

@@ -36,13 +36,16 @@ ARCH = "gfx950"
 # carl_brax_ppo.hip (that update for the Brax families) calls the same device helpers (csrc/ppo_device.hip.h) in its actor
 # kernel and its reduction, instantiates the network kernel (csrc/ppo_net_kernel.hip.h) for its critic and runs the trace
 # through carl_ppo.hip's launch function: same flags.  (The two PPO units share one host path: csrc/ppo_host.hpp.)
+# carl_ppo_norm.hip (PPO's running normalisation: input sums over a rollout buffer, return statistics) has kernels of its
+# own (csrc/ppo_norm_kernels.hip.h) and instantiates none of another unit's: same flags.
 SOURCES = {"carl_amd.hip": ["-fno-slp-vectorize"], "carl_brax.hip": ["-fno-slp-vectorize"],
            "carl_policy.hip": ["-fno-slp-vectorize"], "carl_policy_sample.hip": ["-fno-slp-vectorize"],
            "carl_policy_value.hip": ["-fno-slp-vectorize"], "carl_es.hip": ["-fno-slp-vectorize"],
            "carl_policy_stats.hip": ["-fno-slp-vectorize"], "carl_brax_policy.hip": ["-fno-slp-vectorize"],
            "carl_brax_episodes.hip": ["-fno-slp-vectorize"], "carl_brax_policy_stats.hip": ["-fno-slp-vectorize"],
            "carl_brax_policy_sample.hip": ["-fno-slp-vectorize"], "carl_brax_policy_value.hip": ["-fno-slp-vectorize"],
-           "carl_ppo.hip": ["-fno-slp-vectorize"], "carl_brax_ppo.hip": ["-fno-slp-vectorize"]}
+           "carl_ppo.hip": ["-fno-slp-vectorize"], "carl_brax_ppo.hip": ["-fno-slp-vectorize"],
+           "carl_ppo_norm.hip": ["-fno-slp-vectorize"]}
 
 
 def _hipcc() -> str:

@@ -699,6 +699,124 @@ class LaneEngine:
             _lib.check(self._c_ppo_grad(C.byref(pb), C.byref(pol), C.byref(crit), ls, C.byref(po)))
         return res
 
+    # ------------------------------------------------------------------ PPO's running normalisation (carl_amd/ppo.py)
+    # What an engine brings: ``_c_ppo_input_stats`` (the return statistics serve both engines as they are).
+    def ppo_input_stats(self, policy, buf: dict, obs0: torch.Tensor, context_id: torch.Tensor, out: dict | None = None) -> dict:
+        """The shifted float64 sums of every policy input over a rollout buffer in one launch (include/carl_amd.h:
+        carl_ppo_input_stats; a Brax model: carl_brax_ppo_input_stats).  ``buf["obs"]``, ``obs0`` and ``context_id`` as
+        ``ppo_grad`` takes them; every sample ``(t, lane)`` counts, its input gathered as ``ppo_grad`` gathers it (row
+        ``T - 1`` of ``obs`` is the next collection's ``obs0`` and is not counted).  Returns ``{"input_partial"
+        [slabs, 2, 32] float64, "steps" [N] int32 filled with T}`` -- what ``InputStats.update(result, block,
+        policy=policy)`` merges (``out``: such a dict to write into).  ``policy``: the one-set policy the collection ran
+        (its shift centres the sums).  No host synchronisation."""
+        self._ppo_check_policy(policy)
+        f32, i32 = torch.float32, torch.int32
+        if context_id.dim() != 2:
+            raise ValueError(f"ppo_input_stats 'context_id': needs int32 [T, {self.n}] rows on {self.device}")
+        T, N = (int(v) for v in context_id.shape)
+        P = N if self._ppo_action_tail() or T == 1 else int(context_id.stride(0))
+        if N != self.n or T < 1:
+            raise ValueError(f"ppo_input_stats: a buffer of {T} steps x {N} lanes for an engine of {self.n}")
+        if context_id.dtype != i32 or context_id.device != self.device or (N > 1 and context_id.stride(1) != 1) or (
+                T > 1 and context_id.stride(0) != P) or P < N:
+            raise ValueError(f"ppo_input_stats 'context_id': needs int32 [{T}, {N}] rows of pitch {P} on {self.device}")
+        obs = buf["obs"]
+        if obs.dtype != f32 or obs.device != self.device or obs.shape[0] < T or tuple(obs.shape[1:]) != (N, self.D) or any(
+                sz > 1 and st != w for sz, st, w in zip(obs.shape, obs.stride(), (P * self.D, self.D, 1))):
+            raise ValueError(f"ppo_input_stats 'obs': needs float32 [{T}, {N}, {self.D}] rows of pitch {P} on {self.device}")
+        if obs0.dtype != f32 or obs0.device != self.device or tuple(obs0.shape) != (N, self.D) or not obs0.is_contiguous():
+            raise ValueError(f"ppo_input_stats 'obs0': needs a contiguous float32 [{N}, {self.D}] tensor on {self.device}")
+        slabs = int(self.lib.carl_ppo_input_stats_slabs(N, T))
+        res = {} if out is None else out
+        if "input_partial" not in res:
+            res["input_partial"] = torch.empty((slabs, 2, _lib.POLICY_MAX_IN), dtype=torch.float64, device=self.device)
+        if "steps" not in res:
+            res["steps"] = torch.full((N,), T, dtype=i32, device=self.device)
+        part, steps = res["input_partial"], res["steps"]
+        if (part.dtype != torch.float64 or part.device != self.device or part.dim() != 3 or part.shape[0] < slabs
+                or tuple(part.shape[1:]) != (2, _lib.POLICY_MAX_IN) or not part.is_contiguous()):
+            raise ValueError(f"ppo_input_stats 'input_partial': needs a contiguous float64 [>= {slabs}, 2, "
+                             f"{_lib.POLICY_MAX_IN}] tensor on {self.device}")
+        if steps.dtype != i32 or steps.device != self.device or tuple(steps.shape) != (N,) or not steps.is_contiguous():
+            raise ValueError(f"ppo_input_stats 'steps': needs a contiguous int32 [{N}] tensor on {self.device} (filled with T)")
+        if part.shape[0] != slabs:
+            res["input_partial"] = part = part[:slabs]  # (the merge adds every slab of the tensor it is given)
+        pol = policy.struct(self.n, policy.device_params(self.device).data_ptr())
+        pb = _lib.PpoBatch()
+        pb.family, pb.n_lanes, pb.n_steps, pb.row_pitch, pb.obs_dim = self.family, N, T, (P if P != N else 0), self.D
+        pb.n_contexts, pb.ctx_stride = int(self.b.n_contexts), int(self.b.ctx_stride)
+        pb.n_samples = T * N
+        pb.obs0, pb.obs, pb.context_id, pb.ctx_table = _ptr(obs0), _ptr(obs), _ptr(context_id), _ptr(self.ctx_table)
+        st = _lib.PolicyStats(part.data_ptr(), slabs)
+        with torch.cuda.device(self.device):
+            _lib.check(self._c_ppo_input_stats(C.byref(pb), C.byref(pol), C.byref(st)))
+        return res
+
+    def ppo_return_stats(self, reward, terminated, truncated, ret, gamma: float, out: dict | None = None,
+                         ret_rows: bool = False) -> dict:
+        """One forward walk of the discounted return per lane (include/carl_amd.h: carl_ppo_return_stats): ``ret`` ``[N]``
+        float32 is read, advanced by ``ret = gamma * ret + reward[t]`` over the ``[T, N]`` rows (float32, zeroed after a
+        finished step: VecNormalize's order) and written back.  Returns ``{"return_partial" [slabs, 2] float64}`` -- each
+        workgroup's sums of the returns and of their squares -- and, with ``ret_rows=True``, ``"ret_rows"`` ``[T, N]``:
+        the return after each step's reward (rows of the reward's pitch).  No host synchronisation."""
+        T, N = (int(v) for v in reward.shape)
+        P = int(reward.stride(0)) if T > 1 else N
+        if N != self.n or P < N or T < 1:
+            raise ValueError(f"ppo_return_stats: reward rows of {T} steps x {N} lanes (pitch {P}) for an engine of {self.n}")
+        for name, t, dts in (("reward", reward, (torch.float32,)), ("terminated", terminated, (torch.uint8, torch.bool)),
+                             ("truncated", truncated, (torch.uint8, torch.bool))):
+            if t.dtype not in dts or t.device != self.device or tuple(t.shape) != (T, N) or (
+                    N > 1 and t.stride(1) != 1) or (T > 1 and t.stride(0) != P):
+                raise ValueError(f"ppo_return_stats '{name}': needs {dts[0]} [{T}, {N}] rows of pitch {P} on {self.device}")
+        if ret.dtype != torch.float32 or ret.device != self.device or tuple(ret.shape) != (N,) or not ret.is_contiguous():
+            raise ValueError(f"ppo_return_stats 'ret': needs a contiguous float32 [{N}] tensor on {self.device}")
+        slabs = int(self.lib.carl_ppo_return_stats_slabs(N))
+        res = {} if out is None else out
+        if "return_partial" not in res:
+            res["return_partial"] = torch.empty((slabs, 2), dtype=torch.float64, device=self.device)
+        part = res["return_partial"]
+        if (part.dtype != torch.float64 or part.device != self.device or tuple(part.shape) != (slabs, 2)
+                or not part.is_contiguous()):
+            raise ValueError(f"ppo_return_stats 'return_partial': needs a contiguous float64 [{slabs}, 2] tensor on {self.device}")
+        rows = None
+        if ret_rows:
+            if "ret_rows" not in res:
+                res["ret_rows"] = torch.empty((T, P), dtype=torch.float32, device=self.device)[:, :N]
+            rows = res["ret_rows"]
+            if rows.dtype != torch.float32 or rows.device != self.device or tuple(rows.shape) != (T, N) or (
+                    N > 1 and rows.stride(1) != 1) or (T > 1 and rows.stride(0) != P):
+                raise ValueError(f"ppo_return_stats 'ret_rows': needs float32 [{T}, {N}] rows of pitch {P} on {self.device}")
+        rs = _lib.PpoReturnStats()
+        rs.n_lanes, rs.n_steps, rs.row_pitch, rs.gamma = N, T, (P if P != N else 0), float(gamma)
+        rs.reward, rs.terminated, rs.truncated = _ptr(reward), _ptr(terminated), _ptr(truncated)
+        rs.ret, rs.ret_rows, rs.partial, rs.partial_capacity = _ptr(ret), _ptr(rows), _ptr(part), slabs
+        with torch.cuda.device(self.device):
+            _lib.check(self.lib.carl_ppo_return_stats(C.byref(rs), self._stream()))
+        return res
+
+    def ppo_return_merge(self, partial: torch.Tensor, n_b: int, running: dict, eps: float = 1e-8,
+                         scale: torch.Tensor | None = None) -> torch.Tensor:
+        """Merge ``ppo_return_stats``'s slabs over ``n_b`` = T x N returns into ``running`` = ``{"count" int64 [1], "mean"
+        float64 [1], "m2" float64 [1]}`` (device tensors, all zero before the first merge) by Chan's rule and write
+        ``1 / sqrt(m2 / count + eps)`` to ``scale`` (a float32 ``[1]`` device tensor, allocated when None), which is
+        returned (include/carl_amd.h: carl_ppo_return_merge).  No host synchronisation."""
+        if (partial.dtype != torch.float64 or partial.device != self.device or partial.dim() != 2 or partial.shape[1] != 2
+                or not partial.is_contiguous()):
+            raise ValueError(f"ppo_return_merge 'partial': needs a contiguous float64 [slabs, 2] tensor on {self.device}")
+        for k, dt in (("count", torch.int64), ("mean", torch.float64), ("m2", torch.float64)):
+            t = running[k]
+            if t.dtype != dt or t.device != self.device or t.numel() != 1:
+                raise ValueError(f"ppo_return_merge running['{k}']: needs a {dt} [1] tensor on {self.device}")
+        if scale is None:
+            scale = torch.empty(1, dtype=torch.float32, device=self.device)
+        if scale.dtype != torch.float32 or scale.device != self.device or scale.numel() != 1:
+            raise ValueError(f"ppo_return_merge 'scale': needs a float32 [1] tensor on {self.device}")
+        run = _lib.PolicyRunningStats(_ptr(running["count"]), _ptr(running["mean"]), _ptr(running["m2"]))
+        with torch.cuda.device(self.device):
+            _lib.check(self.lib.carl_ppo_return_merge(_ptr(partial), int(partial.shape[0]), int(n_b), C.byref(run),
+                                                      float(eps), _ptr(scale), self._stream()))
+        return scale
+
     def drain_finished(self):
         """Finished-episode log since the last drain -> (global lane ids, returns, lengths,
         n_dropped); resets the counter.  Synchronises."""
@@ -892,6 +1010,9 @@ class VecEngine(LaneEngine):
 
     def _c_ppo_grad(self, pb, pol, crit, log_std, po) -> int:
         return self.lib.carl_ppo_grad(pb, pol, crit, log_std, po, self._stream())
+
+    def _c_ppo_input_stats(self, pb, pol, st) -> int:
+        return self.lib.carl_ppo_input_stats(pb, pol, st, self._stream())
 
     def _policy_call(self, fn, *args) -> None:
         """One closed-loop C call ``fn(batch, *args, stream)`` on the current stream, its error code raised."""

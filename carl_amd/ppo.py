@@ -23,6 +23,18 @@ against the actor's compares the host templates' sections, which no update chang
 A Brax model is a Box family whose Gaussian is the joint one over the model's actuators: ``log_std`` is ``[1, n_act]``
 (one value per actuator), the action column ``[T, N, n_act]`` in dense rows; everything else is the same sequence.
 
+Running normalisation (both off by default; with both off the sequence of launches and every result are as described
+above).  ``normalize_inputs=True``: ``collect()`` launches the input sums of the buffer right after the trace
+(``ppo_input_stats``: every input the policy acted on, float64); the running merge (``InputStats``) writes the new shift |
+scale into ``actor_params`` AFTER the last minibatch of ``update()`` -- the buffer's ``log_prob`` and ``value`` were
+computed under the transform the collection ran, and ``ppo_grad`` must see that same transform -- or at the start of the
+next ``collect()`` when no update came between, once per collection; the same section is then copied device-to-device
+into ``critic_params``, so the two stay bit-equal.  ``normalize_reward=True``: ``collect()`` runs the launch without
+``gae=``, walks the discounted return of every lane (``ppo_return_stats``, a persistent per-lane return as in SB3's
+VecNormalize), merges its sums into ``return_stats`` and computes the advantages from ``reward_normalized = clamp(reward
+* scale, -clip_reward, clip_reward)``: a collection is scaled by the statistics that include it.  ``buf["reward"]``
+stays raw.
+
 Out of scope, and refused: ``MixedVecEngine`` pairs, the gymnasium drop-in; of the Brax families the models the closed
 loop refuses (more than 8 actuators, Humanoid-size inputs beyond ``CARL_POLICY_MAX_IN``) and collection under the
 first-state auto-reset (``autoreset_mode="first_state"``: an env's next episode would repeat the previous one's noise).
@@ -33,7 +45,7 @@ import torch
 
 from carl_amd import _lib
 from carl_amd.brax_policy import BraxMLPPolicy, _brax_engine_of
-from carl_amd.policy import MLPPolicy, _engine_of
+from carl_amd.policy import InputStats, MLPPolicy, _engine_of
 
 
 class _ResidentPolicy(MLPPolicy):
@@ -86,12 +98,17 @@ class PPO:
     ``CARLBraxEnv`` / ``BraxVecEngine`` they are ``BraxMLPPolicy`` objects, the actor's ``log_std`` one value per actuator.
     ``n_steps``: steps per lane and collection; ``batch_size``: samples per minibatch (default: a quarter of the buffer);
     the other arguments are SB3's.  ``seed``: the sample seed of the first collection (one more per collection) and the
-    seed of the minibatch permutations."""
+    seed of the minibatch permutations.  ``normalize_inputs`` / ``normalize_reward``: running normalisation of the
+    policy's inputs / of the rewards (module docstring); ``clip_reward``: the bound of a scaled reward; ``norm_eps`` (> 0 with
+    ``normalize_reward``; with ``normalize_inputs`` a second ``update()`` of one collection is refused): the
+    epsilon under both square roots.  ``input_stats`` (an ``InputStats``) and ``return_stats`` (``{"count", "mean",
+    "m2", "scale", "ret"}`` device tensors) hold the running state, None where the flag is off."""
 
     def __init__(self, env, policy: MLPPolicy, value_net: MLPPolicy, n_steps: int = 128, n_epochs: int = 4,
                  batch_size: int | None = None, lr: float = 3e-4, gamma: float = 0.99, lam: float = 0.95,
                  clip_range: float = 0.2, vf_coef: float = 0.5, ent_coef: float = 0.0, max_grad_norm: float = 0.5,
-                 normalize_advantage: bool = True, seed: int = 0):
+                 normalize_advantage: bool = True, seed: int = 0, normalize_inputs: bool = False,
+                 normalize_reward: bool = False, clip_reward: float = 10.0, norm_eps: float = 1e-8):
         self.brax = isinstance(policy, BraxMLPPolicy) or isinstance(value_net, BraxMLPPolicy)
         eng, cenv = _brax_engine_for_ppo(env) if self.brax else _engine_of(env)
         for p, head in ((policy, "policy"), (value_net, "value")):
@@ -116,6 +133,15 @@ class PPO:
         self.clip_range, self.vf_coef, self.ent_coef = float(clip_range), float(vf_coef), float(ent_coef)
         self.max_grad_norm, self.normalize_advantage = max_grad_norm, bool(normalize_advantage)
         self.seed, self.collections = int(seed), 0
+        self.normalize_inputs, self.normalize_reward = bool(normalize_inputs), bool(normalize_reward)
+        self.clip_reward, self.norm_eps = float(clip_reward), float(norm_eps)
+        if not 0.0 < self.clip_reward or self.clip_reward != self.clip_reward:
+            raise ValueError(f"clip_reward {clip_reward}: > 0")
+        if not 0.0 <= self.norm_eps < float("inf"):
+            raise ValueError(f"norm_eps {norm_eps}: finite and >= 0")
+        if self.normalize_reward and self.norm_eps == 0.0:
+            raise ValueError("norm_eps 0 with normalize_reward: constant returns (all-zero rewards) would give scale = inf, "
+                             "and 0 * inf is a NaN the clip does not remove; norm_eps > 0")
         dev = eng.device
         q = int(_lib.load().carl_policy_lane_quantum())
         lanes = max(q, (eng.n + q - 1) // q * q)
@@ -134,6 +160,14 @@ class PPO:
         self._obs0 = None  # the observation the next collection's first action is chosen from
         self._buf = None
         self._ws = eng.ppo_workspace(policy, value_net, self.batch_size)
+        self.input_stats = InputStats(policy, dev, eps=self.norm_eps) if self.normalize_inputs else None
+        self._pending_inputs = None  # the last collection's input sums, until they are merged
+        self._input_out, self._return_out = {}, {}  # the slabs and the step counts: allocated by the first collection, kept
+        self.return_stats = None
+        if self.normalize_reward:
+            z = lambda dt, n=1: torch.zeros(n, dtype=dt, device=dev)  # noqa: E731
+            self.return_stats = {"count": z(torch.int64), "mean": z(torch.float64), "m2": z(torch.float64),
+                                 "scale": torch.ones(1, dtype=torch.float32, device=dev), "ret": z(torch.float32, eng.n)}
 
     # ------------------------------------------------------------------ state
     def actor(self) -> MLPPolicy:
@@ -151,10 +185,22 @@ class PPO:
         unpack = BraxMLPPolicy.unpack if self.brax else MLPPolicy.unpack
         return unpack(self._templates[1], self.critic_params.cpu().numpy()[0])
 
+    def _merge_inputs(self) -> None:
+        """The pending collection's input sums into the running statistics, the new shift | scale into the actor's packed
+        block and from there into the critic's (two launches, no host synchronisation); once per collection."""
+        if self._pending_inputs is None:
+            return
+        self.input_stats.update(self._pending_inputs, self.actor_params, policy=self._actor)
+        self._pending_inputs = None
+        n, a0, c0 = self._actor.n_in, self._actor.weight_floats, self._critic.weight_floats
+        self.critic_params[0, c0: c0 + 2 * n].copy_(self.actor_params[0, a0: a0 + 2 * n])
+
     # ------------------------------------------------------------------ one iteration
     def collect(self) -> dict:
-        """One rollout buffer: ``rollout_policy``'s dict plus ``"obs0"`` ``[N, D]`` and ``"context_id"`` ``[T, N]``."""
+        """One rollout buffer: ``rollout_policy``'s dict plus ``"obs0"`` ``[N, D]`` and ``"context_id"`` ``[T, N]``; with
+        ``normalize_reward`` also ``"reward_normalized"`` ``[T, N]``, what the advantages were computed from."""
         eng = self.engine
+        self._merge_inputs()  # (a collection without an update behind it)
         if self._obs0 is None:
             if self._carl_env is not None:
                 self._carl_env.reset()  # (the env's own bookkeeping; the engine's observation buffer is read below)
@@ -162,12 +208,26 @@ class PPO:
                 eng.reset()
             self._obs0 = eng.obs.clone()
         ctx0, ep0 = eng.ctx_idx.clone(), eng.episode.clone()
-        buf = eng.rollout_policy(self._actor, self.n_steps, deterministic=False, sample_seed=self.seed + self.collections,
-                                 value_net=self._critic, gae=(self.gamma, self.lam))
-        self.collections += 1
         T = self.n_steps
+        buf = eng.rollout_policy(self._actor, self.n_steps, deterministic=False, sample_seed=self.seed + self.collections,
+                                 value_net=self._critic, gae=None if self.normalize_reward else (self.gamma, self.lam))
+        if self.normalize_reward:
+            rs = self.return_stats
+            rew, te, tr = buf["reward"][:T], buf["terminated"][:T], buf["truncated"][:T]
+            part = eng.ppo_return_stats(rew, te, tr, rs["ret"], self.gamma, out=self._return_out)["return_partial"]
+            eng.ppo_return_merge(part, T * eng.n, rs, self.norm_eps, rs["scale"])
+            P = int(rew.stride(0)) if T > 1 else eng.n
+            rn = torch.empty((T, P), dtype=torch.float32, device=eng.device)[:, : eng.n]  # (the reward rows' pitch)
+            torch.mul(rew, rs["scale"], out=rn)
+            rn.clamp_(-self.clip_reward, self.clip_reward)
+            adv = eng.gae(rn, buf["value"][:T], te, tr, buf["last_value"], self.gamma, self.lam,
+                          boot_value=buf["boot_value"][:T])
+            buf["reward_normalized"], buf["advantage"], buf["return"] = rn, adv["advantage"], adv["return"]
+        self.collections += 1
         buf["context_id"] = eng.context_trace(ctx0, ep0, buf["terminated"][:T], buf["truncated"][:T])
         buf["obs0"] = self._obs0
+        if self.normalize_inputs:
+            self._pending_inputs = eng.ppo_input_stats(self._actor, buf, buf["obs0"], buf["context_id"], out=self._input_out)
         self._obs0 = buf["obs"][T - 1].clone()  # (contiguous [N, D]: the next collection starts from it)
         self._buf = buf
         return buf
@@ -185,6 +245,10 @@ class PPO:
         policy loss, value loss, mean entropy, approx_kl, clip fraction and sample count, on the device."""
         if self._buf is None:
             raise RuntimeError("PPO.update: collect() first")
+        if self.normalize_inputs and self._pending_inputs is None:
+            raise RuntimeError("PPO.update: with normalize_inputs a collection is updated on once -- the first update() "
+                               "merged its input statistics, and the buffer's log_prob and value were computed under the "
+                               "transform before that merge; collect() first")
         eng, buf = self.engine, self._buf
         adv_flat = buf["advantage"]
         P = int(adv_flat.stride(0)) if self.n_steps > 1 else eng.n
@@ -210,6 +274,7 @@ class PPO:
                     p.grad = x
                 self.optimizer.step()
                 stats.append(g["stats"])
+        self._merge_inputs()  # (after the last minibatch: every ppo_grad above saw the transform the collection ran)
         return {"stats": torch.stack(stats)}
 
     def learn(self, iterations: int) -> list:

@@ -791,6 +791,88 @@ int64_t carl_ppo_workspace_floats(const carl_policy_t* policy_host, const carl_p
 int carl_ppo_grad(const carl_ppo_batch_t* ppo_host, const carl_policy_t* policy_host, const carl_policy_t* critic_host,
                   const float* log_std /* DEVICE [1], Box families */, const carl_ppo_out_t* out, void* stream);
 
+/* ---- PPO's running normalisation: input sums over a rollout buffer, return statistics (additive; ABI version unchanged) ----
+ * What SB3's VecNormalize and Brax's PPO do around the update: the policy's inputs are shifted and scaled by running
+ * statistics, the rewards divided by the running deviation of the discounted return.  The input transform and its
+ * running merge exist (the shift | scale | clip section; carl_policy_stats_merge); the calls below are the source of sums
+ * for a PPO collection, and everything for rewards.  No existing kernel is touched; no reference counterpart.
+ *
+ * carl_ppo_input_stats: for EVERY sample (t, lane), t < n_steps, lane < n_lanes, of a carl_ppo_batch_t and every policy
+ * input i < n_in, the input is formed exactly as carl_ppo_grad's gather forms it --
+ *   x_i = ctx_table[ctx_rows[i]][clamp(context_id[t][lane], 0, n_contexts - 1)]   for i < n_ctx,
+ *   else entry i - n_ctx of obs0[lane] (t == 0) or of obs[t - 1][lane]
+ * -- and accumulated by carl_evaluate_policy_stats's definition,
+ *   d_i = fp32(x_i - shift_i)   shift_i that of weight set 0;      S1_i += d_i,  S2_i += d_i * d_i
+ * with EVERY addition and the product in float64 from the first sample on (the product of two widened floats is exact).
+ * So |S_i - exact| <= n * 2^-53 * sum |terms| for n samples, for every input alike, and a constant observation entry is
+ * recognised by the merge's constant rule, which the fp32 chunk sums of the episodes launch do not give.
+ * Row n_steps - 1 of obs is deliberately not counted: it is the next collection's obs0, so over a run every input the
+ * policy acts on is counted once.  Of the batch idx must be NULL; adv_norm, action, log_prob, advantage, ret, n_samples,
+ * action_dtype and the three coefficients are not read.  Rows are row_pitch lanes long (0 = n_lanes).
+ * Output: partial[slab][2][CARL_POLICY_MAX_IN] float64, slab < carl_ppo_input_stats_slabs(n_lanes, n_steps), every slab
+ * written in full, entries i >= n_in +0.0 -- what carl_policy_stats_merge reads, with `steps` an int32 [n_lanes] array
+ * filled with n_steps.
+ * How it runs: min(ceil(n_steps * n_lanes / 256), 256) persistent workgroups of 256 threads.  A thread owns one input
+ * slot of one sample of each pass of floor(256 / n_in) consecutive samples (t-major), so it holds one (S1, S2) pair
+ * and consecutive threads read consecutive floats of consecutive observation rows; the passes go round the grid; a
+ * thread chains its samples in order, the workgroup's pairs of a slot are added from LDS in thread order, one slab
+ * per workgroup.  No floating-point atomics: two calls give the same bits, and the slabs are a fixed function of the
+ * buffer and the launch shape.  One read of the observation rows and the id rows.
+ * Validation, each CARL_ERR_INVALID_ARGUMENT before anything is enqueued: a NULL ppo or policy; a Brax family; obs_dim
+ * against the family; a policy shape outside the limits or NULL params; n_ctx, the context rows, n_in != n_ctx + obs_dim;
+ * idx != NULL; n_steps < 1 or n_lanes < 0; a pitch that is neither 0 nor >= n_lanes; n_steps * pitch >= 2^31;
+ * n_contexts < 1 or ctx_stride < n_contexts; obs0, obs, context_id or ctx_table NULL; stats / stats->partial NULL,
+ * partial off a 16-byte boundary, partial_capacity below the slab count.  n_lanes == 0 enqueues nothing.
+ * Stream-ordered and capturable; never synchronises with the host; allocates nothing. */
+int32_t carl_ppo_input_stats_slabs(int32_t n_lanes, int32_t n_steps); /* host only; 0 for n_lanes < 1 or n_steps < 1 */
+int carl_ppo_input_stats(const carl_ppo_batch_t* ppo_host, const carl_policy_t* policy_host,
+                         const carl_policy_stats_t* stats, void* stream);
+
+/* carl_ppo_return_stats: the discounted return of every lane and its sums, for reward scaling.  One thread per lane walks
+ * its column forward from the persistent ret[lane] (the caller zeroes it once, before the first collection):
+ *   for t = 0 .. n_steps - 1:
+ *     ret = fp32(fp32(gamma * ret) + reward[t][lane])          (no fma: a NumPy float32 restatement gives the same bits)
+ *     ret_rows[t][lane] = ret  (when ret_rows != NULL);    S1 += ret,  S2 += ret * ret  (float64, the product exact)
+ *     ret = 0  where terminated[t][lane] | truncated[t][lane]                                (VecNormalize's order)
+ * and writes ret[lane] back.  Workgroup w -- lanes [256 w, 256 w + 256) -- adds its lanes' sums in a fixed order and
+ * writes partial[w][0] = S1, partial[w][1] = S2 (float64); no atomics.  Rows are row_pitch lanes long (0 = n_lanes).
+ * Validation, each CARL_ERR_INVALID_ARGUMENT before anything is enqueued: a NULL struct; n_steps < 1 or n_lanes < 0; a pitch
+ * that is neither 0 nor >= n_lanes; gamma negative or not finite; reward, terminated, truncated or ret NULL; partial NULL
+ * or off a 16-byte boundary; partial_capacity < carl_ppo_return_stats_slabs(n_lanes).  n_lanes == 0 enqueues nothing. */
+typedef struct carl_ppo_return_stats {
+  int32_t n_lanes;
+  int32_t n_steps;
+  int32_t row_pitch;         /* lanes per row of the [n_steps][pitch] columns; 0 = n_lanes */
+  float gamma;
+  const float* reward;       /* DEVICE [n_steps][pitch] */
+  const uint8_t* terminated; /* DEVICE [n_steps][pitch] */
+  const uint8_t* truncated;  /* DEVICE [n_steps][pitch] */
+  float* ret;                /* DEVICE [n_lanes]: read, advanced, written back */
+  float* ret_rows;           /* DEVICE [n_steps][pitch], nullable: the return after each step's reward */
+  double* partial;           /* DEVICE [partial_capacity][2] float64 */
+  int32_t partial_capacity;
+  int32_t reserved;
+} carl_ppo_return_stats_t;
+
+int32_t carl_ppo_return_stats_slabs(int32_t n_lanes); /* ceil(n_lanes / 256); 0 for n_lanes < 1 */
+int carl_ppo_return_stats(const carl_ppo_return_stats_t* rs_host, void* stream);
+
+/* carl_ppo_return_merge: the slabs of one carl_ppo_return_stats launch into the running (count, mean[0], m2[0]) and the
+ * reward scale.  One thread, every operation in float64, each rounded on its own (no fma) -- carl_policy_stats_merge's
+ * rule for one entry, without a shift and without the constant rule:
+ *   S1 = 0.0; S1 += partial[w][0] for w = 0 .. n_slabs - 1 in order;  S2 likewise from partial[w][1]
+ *   mean_b = S1 / n_b;   M2_b = max(S2 - S1 * S1 / n_b, 0)                  n_b = n_steps * n_lanes, given by the host
+ *   count == 0:  mean = mean_b, M2 = M2_b
+ *   else:        n = count + n_b;  delta = mean_b - mean;
+ *                mean = mean + delta * (n_b / n);   M2 = (M2 + M2_b) + delta * delta * (count * n_b / n)
+ *   count = count + n_b;    scale[0] = fp32(1 / sqrt(M2 / count + eps))
+ * Validation, each CARL_ERR_INVALID_ARGUMENT before anything is enqueued: partial NULL or off a 16-byte boundary; n_slabs
+ * < 0; n_b < 0; `running` or one of its pointers NULL; eps negative or not finite; scale NULL.  n_b == 0 enqueues nothing.
+ * Both calls are stream-ordered and capturable, never synchronise with the host and allocate nothing. */
+int carl_ppo_return_merge(const double* partial /* DEVICE [n_slabs][2] */, int32_t n_slabs, int64_t n_b,
+                          const carl_policy_running_stats_t* running, double eps, float* scale /* DEVICE [1] */,
+                          void* stream);
+
 /* ======================= Brax-locomotion families (spring backend) =======================
  * Replaces CARLBraxEnv + BraxGymWrapper/VectorGymWrapper + brax.spring.pipeline.step x
  * n_frames + brax.envs.<env>.step/reset (carl/envs/brax/carl_brax_env.py:115-336,
@@ -1240,6 +1322,13 @@ int64_t carl_brax_ppo_workspace_floats(const carl_policy_t* policy_host, const c
 int carl_brax_ppo_grad(const carl_ppo_batch_t* ppo_host, const carl_brax_sys_t* sys_host, const carl_policy_t* policy_host,
                        const carl_policy_t* critic_host, const float* log_std /* DEVICE [n_act] */,
                        const carl_ppo_out_t* out, void* stream);
+/* carl_ppo_input_stats for a Brax buffer: the same kernel, sums, slabs (carl_ppo_input_stats_slabs) and validation list,
+ * with `ppo` read with Brax meanings -- family is not a classic one (a classic one is refused; carl_ppo_input_stats
+ * refuses a Brax one), rows are dense (row_pitch 0 or n_lanes), obs_dim up to CARL_POLICY_MAX_IN - n_ctx, a context row is
+ * checked for its sign alone -- and the packing rule of the Brax families (carl_brax_policy_set_floats()).  Its slabs
+ * are merged by carl_brax_policy_stats_merge.  carl_ppo_return_stats and carl_ppo_return_merge serve both. */
+int carl_brax_ppo_input_stats(const carl_ppo_batch_t* ppo_host, const carl_policy_t* policy_host,
+                              const carl_policy_stats_t* stats, void* stream);
 /* The shape carl_brax_rollout_policy, carl_brax_rollout_policy_sampled and carl_brax_rollout_policy_valued launch for this
  * batch, model and step count (host only, no device access beyond the
  * compute-unit count of the current device; 256 where there is none): with n_groups = ceil(n_lanes / (64 / lanes_per_env))
