@@ -414,3 +414,27 @@ EXPORTS.update({
     "carl_ppo_return_stats": (C.c_int, [C.POINTER(PpoReturnStats), _vp]),
     "carl_ppo_return_merge": (C.c_int, [_vp, C.c_int32, C.c_int64, C.POINTER(PolicyRunningStats), C.c_double, _vp, _vp]),
 })
+
+
+# ---- PPO's minibatch step (include/carl_amd.h: carl_ppo_adv_stats_t, carl_adam_t) -----------------------------------
+ADAM_MAX_TENSORS = 4
+
+
+class PpoAdvStats(C.Structure):
+    _fields_ = [("advantage", _vp), ("idx", _vp), ("adv_norm", _vp), ("storage_floats", C.c_int64), ("n_total", _i),
+                ("batch_size", _i), ("eps", C.c_double)]
+
+
+class Adam(C.Structure):
+    _fields_ = [("n_tensors", _i), ("reserved", _i), ("n", C.c_int64 * ADAM_MAX_TENSORS),
+                ("param", _vp * ADAM_MAX_TENSORS), ("grad", _vp * ADAM_MAX_TENSORS), ("m", _vp * ADAM_MAX_TENSORS),
+                ("v", _vp * ADAM_MAX_TENSORS), ("lr", C.c_double), ("beta1", C.c_double), ("beta2", C.c_double),
+                ("eps", C.c_double), ("max_grad_norm", C.c_double), ("step", _vp), ("beta_pow", _vp), ("norm_out", _vp)]
+
+
+EXPORTS.update({
+    "carl_ppo_adv_stats_rows": (C.c_int32, [C.c_int32, C.c_int32]),
+    "carl_ppo_adv_stats": (C.c_int, [C.POINTER(PpoAdvStats), _vp]),
+    "carl_adam_step_max_floats": (C.c_int64, []),
+    "carl_adam_step": (C.c_int, [C.POINTER(Adam), _vp]),
+})

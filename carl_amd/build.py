@@ -38,6 +38,8 @@ ARCH = "gfx950"
 # through carl_ppo.hip's launch function: same flags.  (The two PPO units share one host path: csrc/ppo_host.hpp.)
 # carl_ppo_norm.hip (PPO's running normalisation: input sums over a rollout buffer, return statistics) has kernels of its
 # own (csrc/ppo_norm_kernels.hip.h) and instantiates none of another unit's: same flags.
+# carl_ppo_step.hip (PPO's minibatch step: advantage statistics, global-norm clip and Adam) likewise has kernels of its own
+# (csrc/ppo_step_kernels.hip.h): same flags.
 SOURCES = {"carl_amd.hip": ["-fno-slp-vectorize"], "carl_brax.hip": ["-fno-slp-vectorize"],
            "carl_policy.hip": ["-fno-slp-vectorize"], "carl_policy_sample.hip": ["-fno-slp-vectorize"],
            "carl_policy_value.hip": ["-fno-slp-vectorize"], "carl_es.hip": ["-fno-slp-vectorize"],
@@ -45,7 +47,7 @@ SOURCES = {"carl_amd.hip": ["-fno-slp-vectorize"], "carl_brax.hip": ["-fno-slp-v
            "carl_brax_episodes.hip": ["-fno-slp-vectorize"], "carl_brax_policy_stats.hip": ["-fno-slp-vectorize"],
            "carl_brax_policy_sample.hip": ["-fno-slp-vectorize"], "carl_brax_policy_value.hip": ["-fno-slp-vectorize"],
            "carl_ppo.hip": ["-fno-slp-vectorize"], "carl_brax_ppo.hip": ["-fno-slp-vectorize"],
-           "carl_ppo_norm.hip": ["-fno-slp-vectorize"]}
+           "carl_ppo_norm.hip": ["-fno-slp-vectorize"], "carl_ppo_step.hip": ["-fno-slp-vectorize"]}
 
 
 def _hipcc() -> str:

@@ -817,6 +817,86 @@ class LaneEngine:
                                                       float(eps), _ptr(scale), self._stream()))
         return scale
 
+    # ------------------------------------------------------------------ PPO's minibatch step (carl_amd/ppo.py: fused_step)
+    def ppo_adv_stats(self, advantage: torch.Tensor, idx: torch.Tensor, batch_size: int, eps: float = 1e-8,
+                      out: torch.Tensor | None = None) -> torch.Tensor:
+        """The advantage mean and ``1 / (std + eps)`` of every minibatch of an epoch in one launch (include/carl_amd.h:
+        carl_ppo_adv_stats).  ``advantage``: the float32 ``[T, N]`` rows ``ppo_grad`` reads (of any pitch), or a contiguous
+        1-D float32 storage; ``idx``: int32 ``[n_total]`` flat indices into it, the epoch's minibatches of ``batch_size``
+        samples in order (the last may be shorter).  Returns float32 ``[ceil(n_total / batch_size), 2]``: row ``k`` is
+        ``ppo_grad``'s ``adv_norm`` for minibatch ``k`` (``out``: such a tensor to write into).  No host synchronisation."""
+        f32, i32 = torch.float32, torch.int32
+        if advantage.dtype != f32 or advantage.device != self.device or advantage.dim() not in (1, 2) or advantage.numel() < 1:
+            raise ValueError(f"ppo_adv_stats 'advantage': needs float32 [T, N] rows or a contiguous float32 [n] tensor on {self.device}")
+        if advantage.dim() == 1:
+            if not advantage.is_contiguous():
+                raise ValueError(f"ppo_adv_stats 'advantage': needs float32 [T, N] rows or a contiguous float32 [n] tensor on {self.device}")
+            storage = int(advantage.numel())
+        else:
+            T, N = (int(v) for v in advantage.shape)
+            P = int(advantage.stride(0)) if T > 1 else N
+            if (N > 1 and advantage.stride(1) != 1) or P < N:
+                raise ValueError(f"ppo_adv_stats 'advantage': needs float32 [{T}, {N}] rows of one pitch on {self.device}")
+            storage = (T - 1) * P + N
+        if idx.dtype != i32 or idx.device != self.device or idx.dim() != 1 or not idx.is_contiguous() or idx.numel() < 1:
+            raise ValueError(f"ppo_adv_stats 'idx': needs a contiguous int32 [n_total >= 1] tensor on {self.device}")
+        n_total, batch_size = int(idx.numel()), int(batch_size)
+        rows = int(self.lib.carl_ppo_adv_stats_rows(n_total, batch_size))
+        if rows < 1:
+            raise ValueError(f"ppo_adv_stats: batch_size {batch_size} < 1")
+        if out is None:
+            out = torch.empty((rows, 2), dtype=f32, device=self.device)
+        if out.dtype != f32 or out.device != self.device or tuple(out.shape) != (rows, 2) or not out.is_contiguous():
+            raise ValueError(f"ppo_adv_stats 'out': needs a contiguous float32 [{rows}, 2] tensor on {self.device}")
+        a = _lib.PpoAdvStats(_ptr(advantage), _ptr(idx), _ptr(out), storage, n_total, batch_size, float(eps))
+        with torch.cuda.device(self.device):
+            _lib.check(self.lib.carl_ppo_adv_stats(C.byref(a), self._stream()))
+        return out
+
+    def adam_state(self, params: Sequence[torch.Tensor]) -> dict:
+        """Fresh state for ``adam_step`` over ``params``: ``{"m", "v"}`` zero tensors like each parameter, ``"step"`` int64
+        ``[1]`` = 0, ``"beta_pow"`` float64 ``[2]`` = (1, 1), on the device."""
+        return {"m": [torch.zeros_like(p) for p in params], "v": [torch.zeros_like(p) for p in params],
+                "step": torch.zeros(1, dtype=torch.int64, device=self.device),
+                "beta_pow": torch.ones(2, dtype=torch.float64, device=self.device)}
+
+    def adam_step(self, params: Sequence[torch.Tensor], grads: Sequence[torch.Tensor], state: dict, lr: float,
+                  betas=(0.9, 0.999), eps: float = 1e-5, max_grad_norm: float | None = None,
+                  norm_out: torch.Tensor | None = None) -> None:
+        """The global-norm clip of ``grads`` and one Adam step on ``params`` in one launch (include/carl_amd.h:
+        carl_adam_step): up to 4 contiguous float32 device tensors, ``grads[i]`` with as many elements as ``params[i]``.
+        ``state``: ``adam_state(params)``'s dict, advanced in place.  ``max_grad_norm=None``: no clip.  ``norm_out``: a
+        float64 ``[2]`` device tensor that receives the norm before the clip and the coefficient.  No host synchronisation."""
+        f32 = torch.float32
+        k = len(params)
+        if not 1 <= k <= _lib.ADAM_MAX_TENSORS:
+            raise ValueError(f"adam_step: {k} tensors, the launch takes 1 to {_lib.ADAM_MAX_TENSORS}")
+        if len(grads) != k or len(state["m"]) != k or len(state["v"]) != k:
+            raise ValueError(f"adam_step: {k} parameters need {k} gradients and {k} entries of state['m'] / state['v']")
+        a = _lib.Adam()
+        a.n_tensors = k
+        for i in range(k):
+            n = int(params[i].numel())
+            for name, t in (("params", params[i]), ("grads", grads[i]), ("state['m']", state["m"][i]),
+                            ("state['v']", state["v"][i])):
+                if t.dtype != f32 or t.device != self.device or t.numel() != n or not t.is_contiguous():
+                    raise ValueError(f"adam_step {name}[{i}]: needs a contiguous float32 tensor of {n} elements on {self.device}")
+            a.n[i], a.param[i], a.grad[i] = n, _ptr(params[i]), _ptr(grads[i])
+            a.m[i], a.v[i] = _ptr(state["m"][i]), _ptr(state["v"][i])
+        step, bp = state["step"], state["beta_pow"]
+        if step.dtype != torch.int64 or step.device != self.device or step.numel() != 1:
+            raise ValueError(f"adam_step state['step']: needs an int64 [1] tensor on {self.device}")
+        if bp.dtype != torch.float64 or bp.device != self.device or bp.numel() != 2 or not bp.is_contiguous():
+            raise ValueError(f"adam_step state['beta_pow']: needs a contiguous float64 [2] tensor on {self.device}")
+        if norm_out is not None and (norm_out.dtype != torch.float64 or norm_out.device != self.device
+                                     or norm_out.numel() != 2 or not norm_out.is_contiguous()):
+            raise ValueError(f"adam_step 'norm_out': needs a contiguous float64 [2] tensor on {self.device}")
+        a.lr, a.beta1, a.beta2, a.eps = float(lr), float(betas[0]), float(betas[1]), float(eps)
+        a.max_grad_norm = float("inf") if max_grad_norm is None else float(max_grad_norm)
+        a.step, a.beta_pow, a.norm_out = _ptr(step), _ptr(bp), _ptr(norm_out)
+        with torch.cuda.device(self.device):
+            _lib.check(self.lib.carl_adam_step(C.byref(a), self._stream()))
+
     def drain_finished(self):
         """Finished-episode log since the last drain -> (global lane ids, returns, lengths,
         n_dropped); resets the counter.  Synchronises."""

@@ -35,6 +35,15 @@ VecNormalize), merges its sums into ``return_stats`` and computes the advantages
 * scale, -clip_reward, clip_reward)``: a collection is scaled by the statistics that include it.  ``buf["reward"]``
 stays raw.
 
+The fused minibatch step (``fused_step=True``; off by default, and with it off every launch and every result are as
+described above).  Per epoch ONE launch gives every minibatch's advantage mean and scale (``ppo_adv_stats``:
+carl_ppo_adv_stats, float64 sums in a fixed order; skipped with ``normalize_advantage=False``); per minibatch
+``carl_ppo_grad``'s three launches write into one persistent set of gradient tensors and ONE launch clips them by their
+global norm and applies Adam to the packed tensors (``adam_step``: carl_adam_step, float64 arithmetic, state in
+``adam_state``).  No ``torch.optim.Adam`` exists then (``optimizer`` is None); ``lr`` is read at every step, so a caller may
+change it between updates.  ``update()`` also returns each minibatch's ``adv_norm`` row and ``grad_norm`` (the norm
+before the clip, the coefficient).
+
 Out of scope, and refused: ``MixedVecEngine`` pairs, the gymnasium drop-in; of the Brax families the models the closed
 loop refuses (more than 8 actuators, Humanoid-size inputs beyond ``CARL_POLICY_MAX_IN``) and collection under the
 first-state auto-reset (``autoreset_mode="first_state"``: an env's next episode would repeat the previous one's noise).
@@ -102,13 +111,17 @@ class PPO:
     policy's inputs / of the rewards (module docstring); ``clip_reward``: the bound of a scaled reward; ``norm_eps`` (> 0 with
     ``normalize_reward``; with ``normalize_inputs`` a second ``update()`` of one collection is refused): the
     epsilon under both square roots.  ``input_stats`` (an ``InputStats``) and ``return_stats`` (``{"count", "mean",
-    "m2", "scale", "ret"}`` device tensors) hold the running state, None where the flag is off."""
+    "m2", "scale", "ret"}`` device tensors) hold the running state, None where the flag is off.  ``fused_step``: the
+    advantage statistics of an epoch in one launch and clip + Adam in one launch per minibatch (module docstring);
+    ``adam_state`` (``{"m", "v", "step", "beta_pow"}`` device tensors) then holds the optimiser's state and ``optimizer`` is
+    None.  ``lr``: the attribute the fused step reads at every minibatch."""
 
     def __init__(self, env, policy: MLPPolicy, value_net: MLPPolicy, n_steps: int = 128, n_epochs: int = 4,
                  batch_size: int | None = None, lr: float = 3e-4, gamma: float = 0.99, lam: float = 0.95,
                  clip_range: float = 0.2, vf_coef: float = 0.5, ent_coef: float = 0.0, max_grad_norm: float = 0.5,
                  normalize_advantage: bool = True, seed: int = 0, normalize_inputs: bool = False,
-                 normalize_reward: bool = False, clip_reward: float = 10.0, norm_eps: float = 1e-8):
+                 normalize_reward: bool = False, clip_reward: float = 10.0, norm_eps: float = 1e-8,
+                 fused_step: bool = False):
         self.brax = isinstance(policy, BraxMLPPolicy) or isinstance(value_net, BraxMLPPolicy)
         eng, cenv = _brax_engine_for_ppo(env) if self.brax else _engine_of(env)
         for p, head in ((policy, "policy"), (value_net, "value")):
@@ -142,6 +155,12 @@ class PPO:
         if self.normalize_reward and self.norm_eps == 0.0:
             raise ValueError("norm_eps 0 with normalize_reward: constant returns (all-zero rewards) would give scale = inf, "
                              "and 0 * inf is a NaN the clip does not remove; norm_eps > 0")
+        self.lr, self.fused_step = float(lr), bool(fused_step)
+        if self.fused_step:  # (what carl_adam_step would refuse at the first minibatch)
+            if not 0.0 <= self.lr < float("inf"):
+                raise ValueError(f"fused_step: lr {lr}: finite and >= 0")
+            if max_grad_norm is not None and not float(max_grad_norm) >= 0.0:
+                raise ValueError(f"fused_step: max_grad_norm {max_grad_norm}: >= 0, or None for no clip")
         dev = eng.device
         q = int(_lib.load().carl_policy_lane_quantum())
         lanes = max(q, (eng.n + q - 1) // q * q)
@@ -154,7 +173,17 @@ class PPO:
         self._actor = _resident(resident, policy, self.actor_params, lanes, self.log_std if self.box else None)
         self._critic = _resident(resident, value_net, self.critic_params, lanes)
         self._opt_params = [self.actor_params, self.critic_params] + ([self.log_std] if self.box else [])
-        self.optimizer = torch.optim.Adam(self._opt_params, lr=float(lr), eps=1e-5)
+        if self.fused_step:
+            if len(self._opt_params) > _lib.ADAM_MAX_TENSORS:
+                raise ValueError(f"fused_step: {len(self._opt_params)} tensors, carl_adam_step takes {_lib.ADAM_MAX_TENSORS}")
+            floats, most = sum(p.numel() for p in self._opt_params), int(_lib.load().carl_adam_step_max_floats())
+            if floats > most:
+                raise ValueError(f"fused_step: {floats} parameters are more than carl_adam_step_max_floats() = {most}")
+            self.optimizer, self.adam_state = None, eng.adam_state(self._opt_params)
+            self._grad_out = {}  # ppo_grad's outputs: allocated by the first minibatch, kept
+        else:
+            self.optimizer, self.adam_state = torch.optim.Adam(self._opt_params, lr=self.lr, eps=1e-5), None
+        self._epoch_idx = None  # the last epoch's permutation as one contiguous tensor (minibatches())
         self._gen = torch.Generator(device=dev)
         self._gen.manual_seed(self.seed)
         self._obs0 = None  # the observation the next collection's first action is chosen from
@@ -238,6 +267,7 @@ class PPO:
         P = int(self._buf["action"].stride(0)) if T > 1 and not self.brax else eng.n  # (a Brax buffer: dense rows)
         perm = torch.randperm(T * eng.n, device=eng.device, generator=self._gen)
         flat = ((perm // eng.n) * P + perm % eng.n).to(torch.int32)
+        self._epoch_idx = flat  # (the minibatches are views of it, in order: what ppo_adv_stats reads)
         return [flat[s: s + self.batch_size].contiguous() for s in range(0, T * eng.n, self.batch_size)]
 
     def update(self) -> dict:
@@ -250,6 +280,8 @@ class PPO:
                                "merged its input statistics, and the buffer's log_prob and value were computed under the "
                                "transform before that merge; collect() first")
         eng, buf = self.engine, self._buf
+        if self.fused_step:
+            return self._update_fused()
         adv_flat = buf["advantage"]
         P = int(adv_flat.stride(0)) if self.n_steps > 1 else eng.n
         adv_storage = torch.as_strided(adv_flat, (self.n_steps * P,), (1,)) if P != eng.n else adv_flat.reshape(-1)
@@ -276,6 +308,38 @@ class PPO:
                 stats.append(g["stats"])
         self._merge_inputs()  # (after the last minibatch: every ppo_grad above saw the transform the collection ran)
         return {"stats": torch.stack(stats)}
+
+    def _update_fused(self) -> dict:
+        """``update()`` with ``fused_step``: per epoch one ``ppo_adv_stats`` launch, per minibatch ``ppo_grad`` + one
+        ``adam_step`` launch.  Returns ``{"stats" [n_minibatches, 6], "adv_norm" [n_minibatches, 2] float32, "grad_norm"
+        [n_minibatches, 2] float64: the norm before the clip and the coefficient}`` on the device."""
+        eng, buf, dev = self.engine, self._buf, self.engine.device
+        total = self.n_steps * eng.n
+        per_epoch = (total + self.batch_size - 1) // self.batch_size
+        n_mb = self.n_epochs * per_epoch
+        stats = torch.empty((n_mb, 6), dtype=torch.float32, device=dev)
+        grad_norm = torch.empty((n_mb, 2), dtype=torch.float64, device=dev)
+        adv_norm = torch.empty((n_mb, 2), dtype=torch.float32, device=dev)
+        if not self.normalize_advantage:
+            adv_norm[:, 0], adv_norm[:, 1] = 0.0, 1.0  # (the identity; ppo_grad gets no adv_norm)
+        adv = buf["advantage"][: self.n_steps]
+        out, k = self._grad_out, 0
+        for e in range(self.n_epochs):
+            mbs = self.minibatches()
+            rows = adv_norm[e * per_epoch: (e + 1) * per_epoch]
+            if self.normalize_advantage:
+                eng.ppo_adv_stats(adv, self._epoch_idx, self.batch_size, 1e-8, out=rows)
+            for j, idx in enumerate(mbs):
+                out["stats"] = stats[k]
+                g = eng.ppo_grad(self._actor, self._critic, buf, buf["obs0"], buf["context_id"], idx=idx,
+                                 adv_norm=rows[j] if self.normalize_advantage else None, clip_range=self.clip_range,
+                                 vf_coef=self.vf_coef, ent_coef=self.ent_coef, out=out, workspace=self._ws)
+                grads = [g["grad_actor"], g["grad_critic"]] + ([g["grad_log_std"]] if self.box else [])
+                eng.adam_step(self._opt_params, grads, self.adam_state, self.lr, eps=1e-5,
+                              max_grad_norm=self.max_grad_norm, norm_out=grad_norm[k])
+                k += 1
+        self._merge_inputs()  # (after the last minibatch, as in update())
+        return {"stats": stats, "adv_norm": adv_norm, "grad_norm": grad_norm}
 
     def learn(self, iterations: int) -> list:
         """``iterations`` times ``collect()`` + ``update()``; returns each iteration's ``{"stats", "mean_reward"}`` (device

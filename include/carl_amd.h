@@ -873,6 +873,84 @@ int carl_ppo_return_merge(const double* partial /* DEVICE [n_slabs][2] */, int32
                           const carl_policy_running_stats_t* running, double eps, float* scale /* DEVICE [1] */,
                           void* stream);
 
+/* ---- PPO's minibatch step: advantage statistics of an epoch, global-norm clip and Adam (additive; ABI version unchanged) ----
+ * What stands between two carl_ppo_grad calls of a PPO update: each minibatch's advantage mean and scale, the global-norm
+ * clip of the gradients and Adam's step.  With the two calls below a minibatch is carl_ppo_grad's three launches plus one,
+ * and a caller of this header trains without another library.  Neither call knows a family: they serve the classic and
+ * the Brax families alike.  No existing kernel is touched; no reference counterpart.
+ *
+ * carl_ppo_adv_stats: row k of adv_norm is what carl_ppo_batch_t.adv_norm takes for minibatch k of an epoch whose
+ * permutation idx [n_total] is the concatenation of its minibatches of batch_size samples in order (the last one may be
+ * shorter).  With the n samples a_i = advantage[idx[k * batch_size + i]] of minibatch k, everything in float64, every
+ * operation rounded on its own (no fma):
+ *   c = a_0;   d_i = (double)a_i - (double)c;   S1 = sum d_i,  S2 = sum d_i * d_i   in a fixed order
+ *   mean = c + S1 / n;    var = max(0, (S2 - S1 * S1 / n) / (n - 1))                 (unbiased, as torch's std())
+ *   adv_norm[k] = (fp32(mean), fp32(1 / (sqrt(var) + eps)))
+ * n == 1 writes (+0.0, 1.0), the identity (what adv_norm == NULL does).  The shift by the first sample makes a constant
+ * column give var == 0 exactly, so its scale is fp32(1 / eps).  An index outside [0, storage_floats) is not read and counts
+ * as d = 0 (where it is the minibatch's first, c = 0).  |S - exact| <= n * 2^-53 * sum |terms|.
+ * How it runs: one workgroup of 256 threads per minibatch.  Thread t chains samples t, t + 256, ... in that order, 8
+ * gathers issued ahead of the dependent adds; a wavefront adds its 64 values by a shuffle tree, thread 0 the four
+ * wavefronts' sums in order.  No atomics: two calls give the same bits.
+ * Validation, each CARL_ERR_INVALID_ARGUMENT with a message before anything is enqueued: a NULL struct; advantage, idx or
+ * adv_norm NULL; n_total < 1 or batch_size < 1; storage_floats < 1; eps negative or not finite.
+ * Stream-ordered and capturable; never synchronises with the host; allocates nothing. */
+typedef struct carl_ppo_adv_stats {
+  const float* advantage;  /* DEVICE: the [n_steps][pitch] storage carl_ppo_grad reads */
+  const int32_t* idx;      /* DEVICE [n_total]: flat indices into it, an epoch's minibatches in order */
+  float* adv_norm;         /* DEVICE [carl_ppo_adv_stats_rows(n_total, batch_size)][2] */
+  int64_t storage_floats;  /* floats of the storage an index may address */
+  int32_t n_total;
+  int32_t batch_size;
+  double eps;
+} carl_ppo_adv_stats_t;
+
+int32_t carl_ppo_adv_stats_rows(int32_t n_total, int32_t batch_size); /* ceil(n_total / batch_size); 0 where either is < 1 */
+int carl_ppo_adv_stats(const carl_ppo_adv_stats_t* as_host, void* stream);
+
+/* carl_adam_step: the global-norm clip and one Adam step (torch.optim.Adam without weight decay or amsgrad) over
+ * n_tensors float32 tensors in one launch.  Arithmetic is float64, every operation rounded on its own (no fma), each stored
+ * value rounded to float32 once:
+ *   norm = sqrt(sum over all tensors of (double)g * (double)g)   in a fixed order
+ *   coef = min(1, max_grad_norm / (norm + 1e-6))                 (max_grad_norm = +inf: 1, no clip)
+ *   step[0] += 1;   beta_pow[j] = beta_pow[j] * beta_j;   bc_j = 1 - beta_pow[j]
+ *   per element:  gd = (double)g * coef
+ *                 m = fp32(beta1 * m + (1 - beta1) * gd)
+ *                 v = fp32(beta2 * v + ((1 - beta2) * gd) * gd)
+ *                 p = fp32(p - ((lr / bc_1) * m) / (sqrt(v) / sqrt(bc_2) + eps))      m, v: the values just stored
+ * The running products of the betas stand where torch has pow(beta, step), so that a restatement on the host gives the
+ * same bits.  The caller sets step[0] = 0 and beta_pow = (1, 1) once; the call advances them.  An entry with g = +0.0 and
+ * m = v = 0 keeps the bits of p, m and v (p may be -0.0 or infinite): a packed tensor's shift | scale | clip section and
+ * padding, whose gradient carl_ppo_grad writes as +0.0, stay as they are.  norm_out, where given, receives the norm before
+ * the clip and the coefficient.
+ * How it runs: one workgroup of 1 024 threads.  Thread t chains the squares of elements t, t + 1024, ... of tensor 0, then
+ * of tensor 1, ...; a wavefront adds its 64 values by a shuffle tree, thread 0 the sixteen wavefronts' sums in order;
+ * then every thread updates its elements.  No atomics, no hand-over between workgroups: two calls on equal inputs give
+ * the same bits.  carl_adam_step_max_floats() is the largest total of elements this shape takes.
+ * Validation, each CARL_ERR_INVALID_ARGUMENT with a message before anything is enqueued: a NULL struct; n_tensors outside
+ * [1, CARL_ADAM_MAX_TENSORS]; an n < 0; more elements in all than carl_adam_step_max_floats(); a NULL param, grad, m or v;
+ * step or beta_pow NULL; lr, eps or a beta not finite; lr < 0; eps <= 0; a beta outside [0, 1); max_grad_norm negative or
+ * NaN.  A total of 0 elements enqueues nothing (and advances nothing).
+ * Stream-ordered and capturable; never synchronises with the host; allocates nothing. */
+#define CARL_ADAM_MAX_TENSORS 4
+typedef struct carl_adam {
+  int32_t n_tensors;
+  int32_t reserved;
+  int64_t n[CARL_ADAM_MAX_TENSORS];             /* elements of each tensor */
+  float* param[CARL_ADAM_MAX_TENSORS];          /* DEVICE */
+  const float* grad[CARL_ADAM_MAX_TENSORS];     /* DEVICE */
+  float* m[CARL_ADAM_MAX_TENSORS];              /* DEVICE: first moments, zero before the first step */
+  float* v[CARL_ADAM_MAX_TENSORS];              /* DEVICE: second moments, zero before the first step */
+  double lr, beta1, beta2, eps;
+  double max_grad_norm;                         /* >= 0; +inf: no clip */
+  int64_t* step;                                /* DEVICE [1] */
+  double* beta_pow;                             /* DEVICE [2]: beta1^step, beta2^step as running products */
+  double* norm_out;                             /* DEVICE [2], nullable: the norm before the clip, the coefficient */
+} carl_adam_t;
+
+int64_t carl_adam_step_max_floats(void);
+int carl_adam_step(const carl_adam_t* adam_host, void* stream);
+
 /* ======================= Brax-locomotion families (spring backend) =======================
  * Replaces CARLBraxEnv + BraxGymWrapper/VectorGymWrapper + brax.spring.pipeline.step x
  * n_frames + brax.envs.<env>.step/reset (carl/envs/brax/carl_brax_env.py:115-336,
