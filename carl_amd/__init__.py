@@ -29,6 +29,7 @@ _LAZY = {
     "VecEngine": "carl_amd.engine",
     "EvolutionStrategy": "carl_amd.es",
     "PPO": "carl_amd.ppo",
+    "PopulationPPO": "carl_amd.population",
 }
 
 

@@ -438,3 +438,23 @@ EXPORTS.update({
     "carl_adam_step_max_floats": (C.c_int64, []),
     "carl_adam_step": (C.c_int, [C.POINTER(Adam), _vp]),
 })
+
+
+# ---- a population of PPO learners (include/carl_amd.h: carl_ppo_sets_t, carl_ppo_grad_sets) ------------------------------
+PPO_HYPER = 5
+PPO_HYPER_LR, PPO_HYPER_CLIP_RANGE, PPO_HYPER_VF_COEF, PPO_HYPER_ENT_COEF, PPO_HYPER_MAX_GRAD_NORM = range(5)
+PPO_HYPER_NAMES = ("lr", "clip_range", "vf_coef", "ent_coef", "max_grad_norm")  # the columns of a hyper row, in order
+
+
+class PpoSets(C.Structure):
+    _fields_ = [("hyper", _vp), ("idx", _vp), ("adv_norm", _vp), ("idx_set_stride", C.c_int64),
+                ("adv_norm_set_stride", C.c_int64)]
+
+
+EXPORTS.update({
+    "carl_ppo_sets_workspace_floats": (C.c_int64, [C.POINTER(Policy), C.POINTER(Policy), C.c_int32]),
+    "carl_ppo_grad_sets": (C.c_int, [C.POINTER(PpoBatch), C.POINTER(Policy), C.POINTER(Policy), _vp, C.POINTER(PpoSets),
+                                     C.POINTER(PpoOut), _vp]),
+    "carl_ppo_adv_stats_sets": (C.c_int, [C.POINTER(PpoAdvStats), C.c_int32, C.c_int64, _vp]),
+    "carl_adam_step_sets": (C.c_int, [C.POINTER(Adam), C.c_int32, _vp, _vp]),
+})

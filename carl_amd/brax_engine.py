@@ -504,6 +504,14 @@ class BraxVecEngine(LaneEngine):
     def _c_ppo_input_stats(self, pb, pol, st) -> int:
         return self.lib.carl_brax_ppo_input_stats(pb, pol, st, self._stream())
 
+    def ppo_grad_sets(self, *args, **kwargs):
+        raise NotImplementedError(f"{type(self).__name__}: ppo_grad_sets (a population of PPO learners, carl_ppo_grad_sets) "
+                                  "covers the classic-control families only; the Brax actor kernel is a unit of its own")
+
+    def ppo_sets_workspace(self, *args, **kwargs):
+        raise NotImplementedError(f"{type(self).__name__}: ppo_sets_workspace (a population of PPO learners, "
+                                  "carl_ppo_grad_sets) covers the classic-control families only")
+
     def evaluate_policy(self, *args, **kwargs):
         raise NotImplementedError(f"{type(self).__name__}: evaluate_policy (sampling, input statistics) covers the "
                                   "classic-control families only; the episodes mode of the Brax closed-loop rollout is "

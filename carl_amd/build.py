@@ -40,6 +40,9 @@ ARCH = "gfx950"
 # own (csrc/ppo_norm_kernels.hip.h) and instantiates none of another unit's: same flags.
 # carl_ppo_step.hip (PPO's minibatch step: advantage statistics, global-norm clip and Adam) likewise has kernels of its own
 # (csrc/ppo_step_kernels.hip.h): same flags.
+# carl_ppo_sets.hip (a population of PPO learners: gradients, advantage statistics and Adam for several weight sets in one
+# launch sequence) includes the bodies of the two PPO units' kernels textually (csrc/ppo_sets_kernels.hip.h) and
+# instantiates none of their kernels: same flags.
 SOURCES = {"carl_amd.hip": ["-fno-slp-vectorize"], "carl_brax.hip": ["-fno-slp-vectorize"],
            "carl_policy.hip": ["-fno-slp-vectorize"], "carl_policy_sample.hip": ["-fno-slp-vectorize"],
            "carl_policy_value.hip": ["-fno-slp-vectorize"], "carl_es.hip": ["-fno-slp-vectorize"],
@@ -47,7 +50,8 @@ SOURCES = {"carl_amd.hip": ["-fno-slp-vectorize"], "carl_brax.hip": ["-fno-slp-v
            "carl_brax_episodes.hip": ["-fno-slp-vectorize"], "carl_brax_policy_stats.hip": ["-fno-slp-vectorize"],
            "carl_brax_policy_sample.hip": ["-fno-slp-vectorize"], "carl_brax_policy_value.hip": ["-fno-slp-vectorize"],
            "carl_ppo.hip": ["-fno-slp-vectorize"], "carl_brax_ppo.hip": ["-fno-slp-vectorize"],
-           "carl_ppo_norm.hip": ["-fno-slp-vectorize"], "carl_ppo_step.hip": ["-fno-slp-vectorize"]}
+           "carl_ppo_norm.hip": ["-fno-slp-vectorize"], "carl_ppo_step.hip": ["-fno-slp-vectorize"],
+           "carl_ppo_sets.hip": ["-fno-slp-vectorize"]}
 
 
 def _hipcc() -> str:

@@ -20,21 +20,9 @@ namespace {
 
 using carl_host::fail;
 
-// what carl_rollout_policy_valued checks of a network, without a batch: `fi` the family's info, `head_out` the head
-// width the family needs of this network
+// ppo_host.hpp's check of a classic network's shape, then what is this entry point's: one weight set
 int check_network(const char* who, const carl_policy_t* p, const carl_family_info_t& fi, int head_out, const char* kind) {
-  if (int e = carl_host::check_hidden_layers(who, p)) return e;
-  if (p->n_ctx < 0 || p->n_ctx > fi.n_features)
-    return fail(CARL_ERR_INVALID_ARGUMENT, "%s: n_ctx %d outside [0, F = %d]", who, p->n_ctx, fi.n_features);
-  for (int k = 0; k < p->n_ctx; ++k)
-    if (p->ctx_rows[k] < 0 || p->ctx_rows[k] >= fi.n_features)
-      return fail(CARL_ERR_INVALID_ARGUMENT, "%s: ctx_rows[%d] = %d is not a context-table row (F = %d)", who, k,
-                  p->ctx_rows[k], fi.n_features);
-  if (p->n_in != p->n_ctx + fi.obs_dim)
-    return fail(CARL_ERR_INVALID_ARGUMENT, "%s: n_in %d != n_ctx %d + obs_dim %d", who, p->n_in, p->n_ctx, fi.obs_dim);
-  if (p->n_out != head_out)
-    return fail(CARL_ERR_INVALID_ARGUMENT, "%s: head width %d, the family needs %d (%s)", who, p->n_out, head_out, kind);
-  if (int e = carl_host::check_activation(who, p)) return e;
+  if (int e = carl_host::check_ppo_classic_network(who, p, fi, head_out, kind)) return e;
   if (p->n_sets != 1)
     return fail(CARL_ERR_INVALID_ARGUMENT, "%s: n_sets %d, a gradient step has one weight set (several are evolution "
                 "strategies' territory)", who, p->n_sets);
@@ -85,17 +73,8 @@ int carl_ppo_grad(const carl_ppo_batch_t* ppo, const carl_policy_t* policy_host,
   const char* who = "carl_ppo_grad";
   if (ppo == nullptr || policy_host == nullptr || critic_host == nullptr || out == nullptr)
     return fail(CARL_ERR_INVALID_ARGUMENT, "%s: ppo / policy / critic / out is NULL", who);
-  if (ppo->family >= CARL_N_FAMILIES)
-    return fail(CARL_ERR_INVALID_ARGUMENT, "%s: family %d is a Brax family -- the PPO update covers the classic-control "
-                "families only", who, ppo->family);
   carl_family_info_t fi;
-  if (int e = carl_family_info(ppo->family, &fi)) return e;
-  if (ppo->n_lanes < 1 || ppo->n_steps < 1)
-    return fail(CARL_ERR_INVALID_ARGUMENT, "%s: n_lanes %d / n_steps %d < 1", who, ppo->n_lanes, ppo->n_steps);
-  if (ppo->row_pitch != 0 && ppo->row_pitch < ppo->n_lanes)
-    return fail(CARL_ERR_INVALID_ARGUMENT, "%s: row_pitch %d < n_lanes %d", who, ppo->row_pitch, ppo->n_lanes);
-  if (ppo->obs_dim != fi.obs_dim)
-    return fail(CARL_ERR_INVALID_ARGUMENT, "%s: obs_dim %d, the family's is %d", who, ppo->obs_dim, fi.obs_dim);
+  if (int e = carl_host::check_ppo_classic_buffer(who, ppo, &fi)) return e;
   const int want_out = fi.action_is_discrete ? fi.n_actions : 1;
   if (int e = check_network(who, policy_host, fi, want_out, fi.action_is_discrete ? "n_actions" : "one Box value")) return e;
   if (policy_host->head != (fi.action_is_discrete ? CARL_POLICY_HEAD_ARGMAX : CARL_POLICY_HEAD_BOX))
@@ -104,9 +83,7 @@ int carl_ppo_grad(const carl_ppo_batch_t* ppo, const carl_policy_t* policy_host,
   const char* cwho = "carl_ppo_grad: critic";
   if (int e = check_network(cwho, critic_host, fi, 1, "a value network has 1")) return e;
   if (int e = carl_host::check_ppo_critic_inputs(cwho, critic_host, policy_host)) return e;
-  if (ppo->action_dtype != (fi.action_is_discrete ? CARL_ACTION_I32 : CARL_ACTION_F32))
-    return fail(CARL_ERR_INVALID_ARGUMENT, "%s: the action column is %s for this family", who,
-                fi.action_is_discrete ? "int32 (CARL_ACTION_I32)" : "float32 (CARL_ACTION_F32)");
+  if (int e = carl_host::check_ppo_classic_action(who, ppo, fi)) return e;
   const int pitch = ppo->row_pitch > 0 ? ppo->row_pitch : ppo->n_lanes;
   if (int e = carl_host::check_ppo_batch(who, ppo, pitch, out)) return e;
   if (!fi.action_is_discrete && (log_std == nullptr || out->grad_log_std == nullptr))

@@ -1,6 +1,7 @@
 // ppo_host.hpp -- the one host path of the PPO update on the device, shared by its two translation units (carl_ppo.hip,
-// carl_brax_ppo.hip): the shape and grid rules, the batch, workspace and critic checks with their messages, and the
-// launch sequence actor -> critic -> reduction.  Each rule is written once; a unit adds its network, family and row-pitch
+// carl_brax_ppo.hip): the shape and grid rules, the batch, workspace and critic checks with their messages
+// (ppo_host_checks.hpp, which a population's unit includes without the launches), and the launch sequence actor -> critic
+// -> reduction.  Each rule is written once; a unit adds its network, family and row-pitch
 // checks, its workspace size and its own kernels.  Host code; launch_ppo_net instantiates ppo_net_kernel<H> in the unit
 // that includes this file.
 #pragma once
@@ -14,6 +15,7 @@
 #include "host_common.hpp"
 #include "policy_host.hpp"
 #include "policy_launch.hpp"
+#include "ppo_host_checks.hpp"
 #include "ppo_net_kernel.hip.h"
 
 namespace carl_host {
@@ -39,76 +41,6 @@ inline int launch_ppo_net(const char* who, int H, const carl::PpoNetArgs& a, int
     static_assert(carl::ppo_lds_bytes(kH) <= carl::kCuLdsBytes, "a PPO network launch's LDS does not fit a compute unit");
     return launch_ppo_kernel(who, carl::ppo_net_kernel<kH>, carl::ppo_lds_bytes(kH), a, grid, s);
   });
-}
-
-// set_floats: the unit's packed size of a network (policy_set_floats / carl_brax_policy_set_floats)
-inline carl::PpoShape ppo_shape_of(const carl_policy_t* p, int (*set_floats)(const carl_policy_t*)) {
-  carl::PpoShape s{};
-  s.n_in = p->n_in, s.n_out = p->n_out, s.n_hidden = p->n_hidden, s.act = p->activation;
-  s.w0 = p->n_hidden > 0 ? p->width[0] : 0;
-  s.w1 = p->n_hidden > 1 ? p->width[1] : 0;
-  s.weight_floats = policy_transform_offset(p);
-  s.set_floats = set_floats(p);
-  return s;
-}
-
-// carl_ppo_grad_workgroups / carl_brax_ppo_grad_workgroups
-inline int ppo_workgroups(int32_t n_samples) {
-  if (n_samples < 1) return 0;
-  const int tiles = (n_samples + carl::kPpoTile - 1) / carl::kPpoTile;
-  return tiles < carl::kPpoMaxWorkgroups ? tiles : carl::kPpoMaxWorkgroups;
-}
-
-inline bool ppo_bad_coef(float v) { return !std::isfinite(v) || v < 0.0f; }
-
-// `cwho`: "<entry point>: critic"
-inline int check_ppo_critic_inputs(const char* cwho, const carl_policy_t* critic, const carl_policy_t* actor) {
-  if (critic->n_ctx != actor->n_ctx)
-    return fail(CARL_ERR_INVALID_ARGUMENT, "%s: n_ctx %d, the actor has %d (the critic reads the actor's inputs)", cwho,
-                critic->n_ctx, actor->n_ctx);
-  for (int k = 0; k < actor->n_ctx; ++k)
-    if (critic->ctx_rows[k] != actor->ctx_rows[k])
-      return fail(CARL_ERR_INVALID_ARGUMENT, "%s: ctx_rows[%d] = %d, the actor's is %d", cwho, k, critic->ctx_rows[k],
-                  actor->ctx_rows[k]);
-  return 0;
-}
-
-// What both entry points check of the batch and the outputs after their own checks, in this order; pitch: the unit's
-// resolved row pitch (never 0)
-inline int check_ppo_batch(const char* who, const carl_ppo_batch_t* ppo, int pitch, const carl_ppo_out_t* out) {
-  if (ppo->n_contexts < 1 || ppo->ctx_stride < ppo->n_contexts)
-    return fail(CARL_ERR_INVALID_ARGUMENT, "%s: n_contexts %d / ctx_stride %d invalid", who, ppo->n_contexts,
-                ppo->ctx_stride);
-  const int64_t all = (int64_t)ppo->n_steps * ppo->n_lanes;
-  if ((int64_t)ppo->n_steps * pitch >= ((int64_t)1 << 31))
-    return fail(CARL_ERR_INVALID_ARGUMENT, "%s: %d steps x %d lanes per row: flat indices do not fit 2^31 - 1", who,
-                ppo->n_steps, pitch);
-  if (ppo->n_samples < 1) return fail(CARL_ERR_INVALID_ARGUMENT, "%s: n_samples %d < 1", who, ppo->n_samples);
-  if (ppo->n_samples > all)
-    return fail(CARL_ERR_INVALID_ARGUMENT, "%s: n_samples %d > n_steps %d x n_lanes %d", who, ppo->n_samples, ppo->n_steps,
-                ppo->n_lanes);
-  if (ppo->idx == nullptr && ppo->n_samples != all)
-    return fail(CARL_ERR_INVALID_ARGUMENT, "%s: idx is NULL (every sample) but n_samples %d != n_steps %d x n_lanes %d", who,
-                ppo->n_samples, ppo->n_steps, ppo->n_lanes);
-  if (ppo_bad_coef(ppo->clip_range)) return fail(CARL_ERR_INVALID_ARGUMENT, "%s: clip_range %g is not finite and >= 0", who, (double)ppo->clip_range);
-  if (ppo_bad_coef(ppo->vf_coef)) return fail(CARL_ERR_INVALID_ARGUMENT, "%s: vf_coef %g is not finite and >= 0", who, (double)ppo->vf_coef);
-  if (ppo_bad_coef(ppo->ent_coef)) return fail(CARL_ERR_INVALID_ARGUMENT, "%s: ent_coef %g is not finite and >= 0", who, (double)ppo->ent_coef);
-  if (!ppo->obs0 || !ppo->obs || !ppo->context_id || !ppo->ctx_table || !ppo->action || !ppo->log_prob || !ppo->advantage ||
-      !ppo->ret)
-    return fail(CARL_ERR_INVALID_ARGUMENT, "%s: a required pointer of ppo is NULL (all but idx and adv_norm)", who);
-  if (!out->grad_actor || !out->grad_critic || !out->stats)
-    return fail(CARL_ERR_INVALID_ARGUMENT, "%s: out->grad_actor, out->grad_critic and out->stats are required", who);
-  return 0;
-}
-
-// need: the unit's workspace size for this call; size_fn: the name of the function that returns it, for the message
-inline int check_ppo_workspace(const char* who, const carl_ppo_out_t* out, int64_t need, const char* size_fn) {
-  if (out->workspace == nullptr || (reinterpret_cast<uintptr_t>(out->workspace) & 15) != 0)
-    return fail(CARL_ERR_INVALID_ARGUMENT, "%s: out->workspace is NULL or not on a 16-byte boundary", who);
-  if (out->workspace_floats < need)
-    return fail(CARL_ERR_INVALID_ARGUMENT, "%s: workspace of %lld floats, %lld needed (%s)", who,
-                (long long)out->workspace_floats, (long long)need, size_fn);
-  return 0;
 }
 
 // what differs between the units' launch sequences

@@ -606,6 +606,53 @@ class LaneEngine:
                                              P if P != N else 0, _ptr(out)))
         return out
 
+    def _ppo_buffer(self, who: str, buf: dict, obs0: torch.Tensor, context_id: torch.Tensor) -> tuple:
+        """``ppo_grad``'s checks of a rollout buffer, ``obs0`` and ``context_id`` (messages begin with ``who``) -> (T, N, the
+        rows' pitch)."""
+        act = buf["action"]
+        tail = self._ppo_action_tail()
+        if tail:  # [T, N, n_act]: dense rows
+            if act.dim() != 3 or tuple(act.shape[2:]) != tail or not act.is_contiguous():
+                raise ValueError(f"{who} 'action': needs a contiguous float32 [T, {self.n}, {tail[0]}] tensor on {self.device}")
+            T, N = int(act.shape[0]), int(act.shape[1])
+            P = N
+        else:
+            T, N = (int(v) for v in act.shape)
+            P = int(act.stride(0)) if T > 1 else N
+        if N != self.n:
+            raise ValueError(f"{who}: a buffer of {N} lanes for an engine of {self.n}")
+        f32, i32 = torch.float32, torch.int32
+        adt = i32 if self.info.action_is_discrete else f32
+        cols = {"action": (act, adt), "log_prob": (buf["log_prob"], f32), "advantage": (buf["advantage"], f32),
+                "return": (buf["return"], f32), "context_id": (context_id, i32)}
+        if tail:  # (its shape is checked above)
+            if act.dtype != adt or act.device != self.device:
+                raise ValueError(f"{who} 'action': needs a contiguous float32 [T, {self.n}, {tail[0]}] tensor on {self.device}")
+            del cols["action"]
+        for k, (t, dt) in cols.items():
+            if t.dtype != dt or t.device != self.device or t.shape[0] < T or tuple(t.shape[1:]) != (N,) or (
+                    N > 1 and t.stride(1) != 1) or (T > 1 and t.stride(0) != P):
+                raise ValueError(f"{who} '{k}': needs {dt} [{T}, {N}] rows of pitch {P} on {self.device}")
+        obs = buf["obs"]
+        if obs.dtype != f32 or obs.device != self.device or obs.shape[0] < T or tuple(obs.shape[1:]) != (N, self.D) or any(
+                sz > 1 and st != w for sz, st, w in zip(obs.shape, obs.stride(), (P * self.D, self.D, 1))):
+            raise ValueError(f"{who} 'obs': needs float32 [{T}, {N}, {self.D}] rows of pitch {P} on {self.device}")
+        if obs0.dtype != f32 or obs0.device != self.device or tuple(obs0.shape) != (N, self.D) or not obs0.is_contiguous():
+            raise ValueError(f"{who} 'obs0': needs a contiguous float32 [{N}, {self.D}] tensor on {self.device}")
+        return T, N, P
+
+    def _ppo_batch(self, T: int, N: int, P: int, buf: dict, obs0: torch.Tensor, context_id: torch.Tensor) -> "_lib.PpoBatch":
+        """The ``carl_ppo_batch_t`` of a buffer ``_ppo_buffer`` has checked, with everything but ``n_samples``, the
+        coefficients, ``idx`` and ``adv_norm``."""
+        act, obs = buf["action"], buf["obs"]
+        pb = _lib.PpoBatch()
+        pb.family, pb.n_lanes, pb.n_steps, pb.row_pitch, pb.obs_dim = self.family, N, T, (P if P != N else 0), self.D
+        pb.n_contexts, pb.ctx_stride = int(self.b.n_contexts), int(self.b.ctx_stride)
+        pb.action_dtype = _lib.ACTION_I32 if self.info.action_is_discrete else _lib.ACTION_F32
+        pb.obs0, pb.obs, pb.context_id, pb.ctx_table = _ptr(obs0), _ptr(obs), _ptr(context_id), _ptr(self.ctx_table)
+        pb.action, pb.log_prob, pb.advantage, pb.ret = _ptr(act), _ptr(buf["log_prob"]), _ptr(buf["advantage"]), _ptr(buf["return"])
+        return pb
+
     def ppo_workspace(self, policy, value_net, n_samples: int) -> torch.Tensor:
         """A float32 workspace for ``ppo_grad`` of ``n_samples`` samples (carl_ppo_workspace_floats)."""
         need = int(self._c_ppo_workspace_floats(C.byref(policy.struct(self.n, 0x10)), C.byref(value_net.struct(self.n, 0x10)),
@@ -629,36 +676,8 @@ class LaneEngine:
         ``[M]`` -- float32 device tensors (``out``: such a dict to write into).  ``policy`` / ``value_net``: one-set policies
         (host-built or ``on_device``).  No host synchronisation."""
         self._ppo_check_policy(policy)
-        act = buf["action"]
-        tail = self._ppo_action_tail()
-        if tail:  # [T, N, n_act]: dense rows
-            if act.dim() != 3 or tuple(act.shape[2:]) != tail or not act.is_contiguous():
-                raise ValueError(f"ppo_grad 'action': needs a contiguous float32 [T, {self.n}, {tail[0]}] tensor on {self.device}")
-            T, N = int(act.shape[0]), int(act.shape[1])
-            P = N
-        else:
-            T, N = (int(v) for v in act.shape)
-            P = int(act.stride(0)) if T > 1 else N
-        if N != self.n:
-            raise ValueError(f"ppo_grad: a buffer of {N} lanes for an engine of {self.n}")
+        T, N, P = self._ppo_buffer("ppo_grad", buf, obs0, context_id)
         f32, i32 = torch.float32, torch.int32
-        adt = i32 if self.info.action_is_discrete else f32
-        cols = {"action": (act, adt), "log_prob": (buf["log_prob"], f32), "advantage": (buf["advantage"], f32),
-                "return": (buf["return"], f32), "context_id": (context_id, i32)}
-        if tail:  # (its shape is checked above)
-            if act.dtype != adt or act.device != self.device:
-                raise ValueError(f"ppo_grad 'action': needs a contiguous float32 [T, {self.n}, {tail[0]}] tensor on {self.device}")
-            del cols["action"]
-        for k, (t, dt) in cols.items():
-            if t.dtype != dt or t.device != self.device or t.shape[0] < T or tuple(t.shape[1:]) != (N,) or (
-                    N > 1 and t.stride(1) != 1) or (T > 1 and t.stride(0) != P):
-                raise ValueError(f"ppo_grad '{k}': needs {dt} [{T}, {N}] rows of pitch {P} on {self.device}")
-        obs = buf["obs"]
-        if obs.dtype != f32 or obs.device != self.device or obs.shape[0] < T or tuple(obs.shape[1:]) != (N, self.D) or any(
-                sz > 1 and st != w for sz, st, w in zip(obs.shape, obs.stride(), (P * self.D, self.D, 1))):
-            raise ValueError(f"ppo_grad 'obs': needs float32 [{T}, {N}, {self.D}] rows of pitch {P} on {self.device}")
-        if obs0.dtype != f32 or obs0.device != self.device or tuple(obs0.shape) != (N, self.D) or not obs0.is_contiguous():
-            raise ValueError(f"ppo_grad 'obs0': needs a contiguous float32 [{N}, {self.D}] tensor on {self.device}")
         if idx is not None and (idx.dtype != i32 or idx.device != self.device or idx.dim() != 1 or not idx.is_contiguous()):
             raise ValueError(f"ppo_grad 'idx': needs a contiguous int32 [M] tensor on {self.device}")
         if adv_norm is not None and (adv_norm.dtype != f32 or adv_norm.device != self.device or adv_norm.numel() != 2
@@ -682,14 +701,9 @@ class LaneEngine:
         pol = policy.struct(self.n, policy.device_params(self.device).data_ptr())
         crit = value_net.struct(self.n, value_net.device_params(self.device).data_ptr())
         ws = self.ppo_workspace(policy, value_net, M) if workspace is None else workspace
-        pb = _lib.PpoBatch()
-        pb.family, pb.n_lanes, pb.n_steps, pb.row_pitch, pb.obs_dim = self.family, N, T, (P if P != N else 0), self.D
-        pb.n_contexts, pb.ctx_stride = int(self.b.n_contexts), int(self.b.ctx_stride)
-        pb.action_dtype = _lib.ACTION_I32 if self.info.action_is_discrete else _lib.ACTION_F32
+        pb = self._ppo_batch(T, N, P, buf, obs0, context_id)
         pb.n_samples = M
         pb.clip_range, pb.vf_coef, pb.ent_coef = float(clip_range), float(vf_coef), float(ent_coef)
-        pb.obs0, pb.obs, pb.context_id, pb.ctx_table = _ptr(obs0), _ptr(obs), _ptr(context_id), _ptr(self.ctx_table)
-        pb.action, pb.log_prob, pb.advantage, pb.ret = _ptr(act), _ptr(buf["log_prob"]), _ptr(buf["advantage"]), _ptr(buf["return"])
         pb.idx, pb.adv_norm = _ptr(idx), _ptr(adv_norm)
         po = _lib.PpoOut(_ptr(res["grad_actor"]), _ptr(res["grad_critic"]), _ptr(res.get("grad_log_std")), _ptr(res["stats"]),
                          _ptr(res.get("new_log_prob")) if forward else None, _ptr(res.get("new_value")) if forward else None,
@@ -853,12 +867,20 @@ class LaneEngine:
             _lib.check(self.lib.carl_ppo_adv_stats(C.byref(a), self._stream()))
         return out
 
-    def adam_state(self, params: Sequence[torch.Tensor]) -> dict:
+    def adam_state(self, params: Sequence[torch.Tensor], n_sets: int | None = None) -> dict:
         """Fresh state for ``adam_step`` over ``params``: ``{"m", "v"}`` zero tensors like each parameter, ``"step"`` int64
-        ``[1]`` = 0, ``"beta_pow"`` float64 ``[2]`` = (1, 1), on the device."""
+        ``[1]`` = 0, ``"beta_pow"`` float64 ``[2]`` = (1, 1), on the device.  ``n_sets``: the state of a population for
+        ``adam_step_sets`` instead -- every parameter ``[n_sets, n_i]``, ``"step"`` ``[n_sets]``, ``"beta_pow"`` ``[n_sets, 2]``."""
+        if n_sets is None:
+            return {"m": [torch.zeros_like(p) for p in params], "v": [torch.zeros_like(p) for p in params],
+                    "step": torch.zeros(1, dtype=torch.int64, device=self.device),
+                    "beta_pow": torch.ones(2, dtype=torch.float64, device=self.device)}
+        n_sets = int(n_sets)
+        if n_sets < 1 or any(p.dim() < 1 or p.shape[0] != n_sets for p in params):
+            raise ValueError(f"adam_state: n_sets {n_sets} needs every parameter as [{n_sets}, n] rows")
         return {"m": [torch.zeros_like(p) for p in params], "v": [torch.zeros_like(p) for p in params],
-                "step": torch.zeros(1, dtype=torch.int64, device=self.device),
-                "beta_pow": torch.ones(2, dtype=torch.float64, device=self.device)}
+                "step": torch.zeros(n_sets, dtype=torch.int64, device=self.device),
+                "beta_pow": torch.ones((n_sets, 2), dtype=torch.float64, device=self.device)}
 
     def adam_step(self, params: Sequence[torch.Tensor], grads: Sequence[torch.Tensor], state: dict, lr: float,
                   betas=(0.9, 0.999), eps: float = 1e-5, max_grad_norm: float | None = None,
@@ -896,6 +918,95 @@ class LaneEngine:
         a.step, a.beta_pow, a.norm_out = _ptr(step), _ptr(bp), _ptr(norm_out)
         with torch.cuda.device(self.device):
             _lib.check(self.lib.carl_adam_step(C.byref(a), self._stream()))
+
+    # ------------------------------------------------------------------ a population's minibatch step (carl_amd/population.py)
+    def _check_hyper(self, who: str, hyper: torch.Tensor, n_sets: int) -> None:
+        if (not isinstance(hyper, torch.Tensor) or hyper.dtype != torch.float64 or hyper.device != self.device
+                or tuple(hyper.shape) != (n_sets, _lib.PPO_HYPER) or not hyper.is_contiguous()):
+            raise ValueError(f"{who} 'hyper': needs a contiguous float64 [{n_sets}, {_lib.PPO_HYPER}] tensor on {self.device} "
+                             f"(columns {', '.join(_lib.PPO_HYPER_NAMES)})")
+
+    def ppo_adv_stats_sets(self, advantage: torch.Tensor, idx: torch.Tensor, batch_size: int, eps: float = 1e-8,
+                           out: torch.Tensor | None = None) -> torch.Tensor:
+        """``ppo_adv_stats`` for every member of a population in one launch (include/carl_amd.h:
+        carl_ppo_adv_stats_sets).  ``advantage`` as ``ppo_adv_stats`` takes it; ``idx``: int32 ``[P, n_total]`` rows of
+        unit stride (the row pitch may be larger), row ``s`` member ``s``'s epoch, its minibatches of ``batch_size`` in order
+        (the last may be shorter).  Returns float32 ``[P, ceil(n_total / batch_size), 2]``: row ``(s, k)`` is bit-equal to
+        ``ppo_adv_stats`` on row ``s`` (``out``: such a tensor to write into).  No host synchronisation."""
+        f32, i32 = torch.float32, torch.int32
+        if advantage.dtype != f32 or advantage.device != self.device or advantage.dim() not in (1, 2) or advantage.numel() < 1:
+            raise ValueError(f"ppo_adv_stats_sets 'advantage': needs float32 [T, N] rows or a contiguous float32 [n] tensor on {self.device}")
+        if advantage.dim() == 1:
+            if not advantage.is_contiguous():
+                raise ValueError(f"ppo_adv_stats_sets 'advantage': needs float32 [T, N] rows or a contiguous float32 [n] tensor on {self.device}")
+            storage = int(advantage.numel())
+        else:
+            T, N = (int(v) for v in advantage.shape)
+            P = int(advantage.stride(0)) if T > 1 else N
+            if (N > 1 and advantage.stride(1) != 1) or P < N:
+                raise ValueError(f"ppo_adv_stats_sets 'advantage': needs float32 [{T}, {N}] rows of one pitch on {self.device}")
+            storage = (T - 1) * P + N
+        if (idx.dtype != i32 or idx.device != self.device or idx.dim() != 2 or idx.shape[0] < 1 or idx.shape[1] < 1
+                or (idx.shape[1] > 1 and idx.stride(1) != 1) or (idx.shape[0] > 1 and idx.stride(0) < idx.shape[1])):
+            raise ValueError(f"ppo_adv_stats_sets 'idx': needs int32 [P >= 1, n_total >= 1] rows of unit stride on {self.device}")
+        n_sets, n_total, batch_size = int(idx.shape[0]), int(idx.shape[1]), int(batch_size)
+        stride = int(idx.stride(0)) if n_sets > 1 else n_total
+        rows = int(self.lib.carl_ppo_adv_stats_rows(n_total, batch_size))
+        if rows < 1:
+            raise ValueError(f"ppo_adv_stats_sets: batch_size {batch_size} < 1")
+        if out is None:
+            out = torch.empty((n_sets, rows, 2), dtype=f32, device=self.device)
+        if out.dtype != f32 or out.device != self.device or tuple(out.shape) != (n_sets, rows, 2) or not out.is_contiguous():
+            raise ValueError(f"ppo_adv_stats_sets 'out': needs a contiguous float32 [{n_sets}, {rows}, 2] tensor on {self.device}")
+        a = _lib.PpoAdvStats(_ptr(advantage), _ptr(idx), _ptr(out), storage, n_total, batch_size, float(eps))
+        with torch.cuda.device(self.device):
+            _lib.check(self.lib.carl_ppo_adv_stats_sets(C.byref(a), n_sets, stride, self._stream()))
+        return out
+
+    def adam_step_sets(self, params: Sequence[torch.Tensor], grads: Sequence[torch.Tensor], state: dict, hyper: torch.Tensor,
+                       betas=(0.9, 0.999), eps: float = 1e-5, norm_out: torch.Tensor | None = None) -> None:
+        """``adam_step`` for every member of a population in one launch (include/carl_amd.h: carl_adam_step_sets): up to 4
+        contiguous float32 device tensors ``[P, n_i]``, ``grads[i]`` of the same shape, row ``s`` member ``s``'s.  ``state``:
+        ``adam_state(params, n_sets=P)``'s dict, advanced in place.  ``hyper``: the population's float64 ``[P, 5]`` device
+        tensor; member ``s`` steps with its ``lr`` and clips by its ``max_grad_norm`` (``+inf``: no clip) -- values the host
+        cannot see: finite and ``>= 0`` is the caller's to guarantee.  ``norm_out``: a float64 ``[P, 2]`` device tensor.
+        Member ``s`` is bit-equal to ``adam_step`` on its rows.  No host synchronisation."""
+        f32 = torch.float32
+        k = len(params)
+        if not 1 <= k <= _lib.ADAM_MAX_TENSORS:
+            raise ValueError(f"adam_step_sets: {k} tensors, the launch takes 1 to {_lib.ADAM_MAX_TENSORS}")
+        if len(grads) != k or len(state["m"]) != k or len(state["v"]) != k:
+            raise ValueError(f"adam_step_sets: {k} parameters need {k} gradients and {k} entries of state['m'] / state['v']")
+        if params[0].dim() < 1 or params[0].shape[0] < 1:
+            raise ValueError("adam_step_sets params[0]: needs [P, n] rows")
+        n_sets = int(params[0].shape[0])
+        a = _lib.Adam()
+        a.n_tensors = k
+        for i in range(k):
+            shape = tuple(params[i].shape)
+            if len(shape) < 1 or shape[0] != n_sets:
+                raise ValueError(f"adam_step_sets params[{i}]: needs [{n_sets}, n] rows, one per member")
+            n = int(params[i].numel()) // n_sets
+            for name, t in (("params", params[i]), ("grads", grads[i]), ("state['m']", state["m"][i]),
+                            ("state['v']", state["v"][i])):
+                if t.dtype != f32 or t.device != self.device or t.numel() != n * n_sets or not t.is_contiguous() or (
+                        t.dim() < 1 or t.shape[0] != n_sets):
+                    raise ValueError(f"adam_step_sets {name}[{i}]: needs a contiguous float32 [{n_sets}, {n}] tensor on {self.device}")
+            a.n[i], a.param[i], a.grad[i] = n, _ptr(params[i]), _ptr(grads[i])
+            a.m[i], a.v[i] = _ptr(state["m"][i]), _ptr(state["v"][i])
+        step, bp = state["step"], state["beta_pow"]
+        if step.dtype != torch.int64 or step.device != self.device or tuple(step.shape) != (n_sets,) or not step.is_contiguous():
+            raise ValueError(f"adam_step_sets state['step']: needs a contiguous int64 [{n_sets}] tensor on {self.device}")
+        if bp.dtype != torch.float64 or bp.device != self.device or tuple(bp.shape) != (n_sets, 2) or not bp.is_contiguous():
+            raise ValueError(f"adam_step_sets state['beta_pow']: needs a contiguous float64 [{n_sets}, 2] tensor on {self.device}")
+        if norm_out is not None and (norm_out.dtype != torch.float64 or norm_out.device != self.device
+                                     or tuple(norm_out.shape) != (n_sets, 2) or not norm_out.is_contiguous()):
+            raise ValueError(f"adam_step_sets 'norm_out': needs a contiguous float64 [{n_sets}, 2] tensor on {self.device}")
+        self._check_hyper("adam_step_sets", hyper, n_sets)
+        a.lr, a.beta1, a.beta2, a.eps, a.max_grad_norm = 0.0, float(betas[0]), float(betas[1]), float(eps), float("inf")
+        a.step, a.beta_pow, a.norm_out = _ptr(step), _ptr(bp), _ptr(norm_out)
+        with torch.cuda.device(self.device):
+            _lib.check(self.lib.carl_adam_step_sets(C.byref(a), n_sets, _ptr(hyper), self._stream()))
 
     def drain_finished(self):
         """Finished-episode log since the last drain -> (global lane ids, returns, lengths,
@@ -1093,6 +1204,83 @@ class VecEngine(LaneEngine):
 
     def _c_ppo_input_stats(self, pb, pol, st) -> int:
         return self.lib.carl_ppo_input_stats(pb, pol, st, self._stream())
+
+    # ---- a population of PPO learners (carl_amd/population.py): the classic-control families only
+    def _check_population(self, who: str, policy, value_net) -> tuple[int, int]:
+        """(P, L) of a stacked actor and critic whose sets tile this engine's lanes"""
+        _check_policy_family(self, policy)
+        _check_policy_family(self, value_net)
+        P, L = policy.n_sets, policy.lanes_per_set
+        if L is None or value_net.lanes_per_set != L or value_net.n_sets != P:
+            raise ValueError(f"{who}: the actor and the critic need the same weight sets and lanes_per_set (MLPPolicy.stack / "
+                             f"on_device), got {P} x {L} and {value_net.n_sets} x {value_net.lanes_per_set}")
+        if P * L != self.n:
+            raise ValueError(f"{who}: {P} sets x {L} lanes are not this engine's {self.n} lanes (member s owns lanes "
+                             "[s * lanes_per_set, (s + 1) * lanes_per_set))")
+        return P, L
+
+    def ppo_sets_workspace(self, policy, value_net, n_samples: int) -> torch.Tensor:
+        """A float32 workspace for ``ppo_grad_sets`` with ``n_samples`` samples per member
+        (carl_ppo_sets_workspace_floats): as many one-set workspaces as the policy has sets -- up to about 13 MB per member
+        at 256 workgroups of 64-wide networks."""
+        need = int(self.lib.carl_ppo_sets_workspace_floats(C.byref(policy.struct(self.n, 0x10)),
+                                                           C.byref(value_net.struct(self.n, 0x10)), int(n_samples)))
+        if need < 0:
+            raise ValueError(f"ppo_sets_workspace: invalid shapes or n_samples {n_samples}")
+        return torch.empty(need, dtype=torch.float32, device=self.device)
+
+    def ppo_grad_sets(self, policy, value_net, buf: dict, obs0: torch.Tensor, context_id: torch.Tensor, *, idx: torch.Tensor,
+                      hyper: torch.Tensor, adv_norm: torch.Tensor | None = None, out: dict | None = None,
+                      workspace: torch.Tensor | None = None) -> dict:
+        """``ppo_grad`` for ``P`` independent learners in its three launches (include/carl_amd.h: carl_ppo_grad_sets).
+        ``policy`` / ``value_net``: ``P`` weight sets of ``L`` lanes each (``MLPPolicy.stack`` / ``on_device``) with ``P * L``
+        this engine's lanes; member ``s`` owns lanes ``[s * L, (s + 1) * L)`` of ``buf`` (``buf``, ``obs0``, ``context_id`` as
+        ``ppo_grad`` takes them).  ``idx``: int32 ``[P, M]`` rows of unit stride, row ``s`` the flat indices ``t * pitch +
+        lane`` of member ``s``'s minibatch (a lane outside the member's contributes zero).  ``hyper``: float64 ``[P, 5]`` on
+        the device (lr, clip_range, vf_coef, ent_coef, max_grad_norm; finite and ``>= 0``, which the host cannot check there).
+        ``adv_norm``: float32 ``[P, 2]`` rows of unit stride or None.  Returns ``{"grad_actor" [P, set_floats], "grad_critic"
+        [P, set_floats], "grad_log_std" [P] (Box families), "stats" [P, 6]}``, row ``s`` bit-equal to ``ppo_grad`` with
+        member ``s``'s one-set networks, index row, ``adv_norm`` row and float32 coefficients (``out``: such a dict to write
+        into).  No host synchronisation."""
+        P, L = self._check_population("ppo_grad_sets", policy, value_net)
+        T, N, pitch = self._ppo_buffer("ppo_grad_sets", buf, obs0, context_id)
+        f32, i32 = torch.float32, torch.int32
+        if (not isinstance(idx, torch.Tensor) or idx.dtype != i32 or idx.device != self.device or idx.dim() != 2
+                or idx.shape[0] != P or idx.shape[1] < 1 or (idx.shape[1] > 1 and idx.stride(1) != 1)
+                or (P > 1 and idx.stride(0) < idx.shape[1])):
+            raise ValueError(f"ppo_grad_sets 'idx': needs int32 [{P}, M >= 1] rows of unit stride on {self.device}")
+        M = int(idx.shape[1])
+        if M > T * L:
+            raise ValueError(f"ppo_grad_sets 'idx': {M} samples per member, a member has {T} steps x {L} lanes")
+        if adv_norm is not None and (adv_norm.dtype != f32 or adv_norm.device != self.device or tuple(adv_norm.shape) != (P, 2)
+                                     or adv_norm.stride(1) != 1 or (P > 1 and adv_norm.stride(0) < 2)):
+            raise ValueError(f"ppo_grad_sets 'adv_norm': needs float32 [{P}, 2] rows of unit stride on {self.device}")
+        self._check_hyper("ppo_grad_sets", hyper, P)
+        res = {} if out is None else out
+        box = not self.info.action_is_discrete
+        want = {"grad_actor": (P, policy.set_floats), "grad_critic": (P, value_net.set_floats), "stats": (P, 6)}
+        if box:
+            want["grad_log_std"] = (P,)
+        for k, shape in want.items():
+            if k not in res:
+                res[k] = torch.empty(shape, dtype=f32, device=self.device)
+            t = res[k]
+            if t.dtype != f32 or t.device != self.device or tuple(t.shape) != shape or not t.is_contiguous():
+                raise ValueError(f"ppo_grad_sets output '{k}': needs a contiguous float32 {list(shape)} tensor on {self.device}")
+        pol = policy.struct(self.n, policy.device_params(self.device).data_ptr())
+        crit = value_net.struct(self.n, value_net.device_params(self.device).data_ptr())
+        ws = self.ppo_sets_workspace(policy, value_net, M) if workspace is None else workspace
+        pb = self._ppo_batch(T, N, pitch, buf, obs0, context_id)
+        pb.n_samples = M
+        st = _lib.PpoSets(_ptr(hyper), _ptr(idx), _ptr(adv_norm), int(idx.stride(0)) if P > 1 else M,
+                          0 if adv_norm is None else (int(adv_norm.stride(0)) if P > 1 else 2))
+        po = _lib.PpoOut(_ptr(res["grad_actor"]), _ptr(res["grad_critic"]), _ptr(res.get("grad_log_std")), _ptr(res["stats"]),
+                         None, None, _ptr(ws), int(ws.numel()))
+        ls = policy.device_log_std(self.device).data_ptr() if box else None
+        with torch.cuda.device(self.device):
+            _lib.check(self.lib.carl_ppo_grad_sets(C.byref(pb), C.byref(pol), C.byref(crit), ls, C.byref(st), C.byref(po),
+                                                   self._stream()))
+        return res
 
     def _policy_call(self, fn, *args) -> None:
         """One closed-loop C call ``fn(batch, *args, stream)`` on the current stream, its error code raised."""

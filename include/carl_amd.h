@@ -951,6 +951,84 @@ typedef struct carl_adam {
 int64_t carl_adam_step_max_floats(void);
 int carl_adam_step(const carl_adam_t* adam_host, void* stream);
 
+/* ---- a population of PPO learners: the update of n_sets independent learners in one sequence of launches (additive; ABI
+ * version unchanged) ----
+ * carl_rollout_policy_valued runs several weight sets in one launch (lane l uses set l / lanes_per_set, with a log_std, a
+ * critic and GAE per set).  The three calls below are carl_ppo_grad, carl_ppo_adv_stats and carl_adam_step for such a
+ * population: member s owns lanes [s * lanes_per_set, (s + 1) * lanes_per_set) of one buffer and has its own actor, critic,
+ * log_std, minibatch, advantage statistics, gradients, Adam state and hyperparameters.  The whole population takes the
+ * launches of one learner: four per minibatch step and one per epoch.  Classic-control families only.  Each kernel runs
+ * the existing kernel's own body once per member (its source is included, not restated), so MEMBER s's OUTPUTS ARE
+ * BIT-EQUAL to the one-set call's on member s's rows, and no existing kernel's code changes
+ * (profiles/ppo_sets_refactor_identity.txt).  No reference counterpart.
+ *
+ * Hyperparameters live on the device: hyper is a DEVICE double [n_sets][CARL_PPO_HYPER], row s member s's, the columns
+ * named below.  The kernels read member s's row; clip_range, vf_coef and ent_coef are rounded to float32 once, where
+ * carl_ppo_grad takes floats.  Precondition the host cannot check (the values are in device memory): every entry is finite
+ * and >= 0, except max_grad_norm, which may be +inf (no clip).  A caller validates before it uploads.
+ *
+ * carl_ppo_grad_sets: carl_ppo_grad for n_sets members in its three launches.  `ppo`: the whole buffer (n_lanes = n_sets *
+ * lanes_per_set); n_samples is the size of EVERY member's minibatch; its clip_range, vf_coef, ent_coef, idx and adv_norm
+ * are not read.  policy / critic: n_sets = P weight sets of lanes_per_set = L lanes, params DEVICE [P][set_floats];
+ * log_std DEVICE [P] (Box families).  `sets`: hyper; idx [P][idx_set_stride], required, row s the n_samples flat indices
+ * t * pitch + lane of member s's minibatch; adv_norm, nullable: row s at adv_norm + s * adv_norm_set_stride is member s's
+ * (mean, 1 / (std + eps)).  Outputs (carl_ppo_out_t): grad_actor [P][set_floats], grad_critic [P][set_floats],
+ * grad_log_std [P] (Box families), stats [P][6], each row what carl_ppo_grad writes; new_log_prob and new_value are not
+ * offered and must be NULL.  workspace: carl_ppo_sets_workspace_floats() floats, P times the one-set call's need for
+ * n_samples -- up to about 13 MB per member at 256 workgroups of 64-wide networks.
+ * How it runs: the grid of each launch is (carl_ppo_grad_workgroups(n_samples), P).  Member s gets the workgroup count, the
+ * tile-to-workgroup mapping, the slab order and the reduction carl_ppo_grad uses for n_samples samples; the second grid
+ * index picks the member's parameters, log_std, hyper row, idx row, adv_norm row, slabs and outputs, all wavefront-uniform
+ * reads.  One guard is new: a sample in row s whose lane is outside member s's lanes contributes zero, exactly like an
+ * index outside the buffer (n_samples still counts it), so a bad index can never mix two learners.
+ * Preconditions the host cannot check: carl_ppo_grad's, per row of idx; the hyper values (above).
+ * Validation, each CARL_ERR_INVALID_ARGUMENT with a message before anything is enqueued: a NULL struct; a Brax family;
+ * everything carl_ppo_grad checks of the buffer, the networks' shapes and the outputs, with the same messages; n_sets < 1 or
+ * n_sets > 65535 (the members are the second grid dimension; the same limit holds in the two calls below);
+ * lanes_per_set not a positive multiple of carl_policy_lane_quantum(); n_sets * lanes_per_set != n_lanes; actor and critic
+ * set layouts that differ; hyper or idx NULL; idx_set_stride < n_samples; adv_norm given with adv_norm_set_stride < 2;
+ * n_samples > n_steps * lanes_per_set; new_log_prob or new_value not NULL; workspace NULL, off a 16-byte boundary or
+ * smaller than carl_ppo_sets_workspace_floats().
+ *
+ * carl_ppo_adv_stats_sets: carl_ppo_adv_stats over idx [P][idx_set_stride]: row s holds member s's epoch of n_total
+ * indices, the concatenation of its minibatches of batch_size (the last may be short).  Writes adv_norm [P][rows][2], rows
+ * = carl_ppo_adv_stats_rows(n_total, batch_size): one workgroup per (minibatch, member), the existing kernel's arithmetic
+ * and order; row (s, k) is bit-equal to carl_ppo_adv_stats on row s.  Validation: carl_ppo_adv_stats's, then n_sets < 1, n_sets > 65535 and
+ * idx_set_stride < n_total.
+ *
+ * carl_adam_step_sets: carl_adam_step for P members in one launch, one workgroup of 1 024 threads per member.  Tensor i is
+ * [P][n[i]] in dense rows (param, grad, m, v: pointers to row 0), step [P], beta_pow [P][2], norm_out [P][2] or NULL; the
+ * betas and eps are shared; lr and max_grad_norm are member s's hyper columns (the struct's lr and max_grad_norm are not
+ * read).  The element limit carl_adam_step_max_floats() holds per member.  Member s is bit-equal to carl_adam_step on its
+ * rows.  Validation: carl_adam_step's without lr and max_grad_norm, then n_sets < 1, n_sets > 65535 and hyper NULL.  A total of 0 elements
+ * enqueues nothing.
+ *
+ * All three: float64 sums in a fixed order, no floating-point atomics, no cooperative launch and no grid-wide barrier; the
+ * same call twice gives the same bits.  Stream-ordered and capturable; never synchronise with the host; allocate nothing. */
+#define CARL_PPO_HYPER 5               /* columns of a hyper row */
+#define CARL_PPO_HYPER_LR 0            /* Adam's learning rate */
+#define CARL_PPO_HYPER_CLIP_RANGE 1    /* c; float32 in the kernels */
+#define CARL_PPO_HYPER_VF_COEF 2       /* float32 in the kernels */
+#define CARL_PPO_HYPER_ENT_COEF 3      /* float32 in the kernels */
+#define CARL_PPO_HYPER_MAX_GRAD_NORM 4 /* +inf: no clip */
+typedef struct carl_ppo_sets {
+  const double* hyper;         /* DEVICE [n_sets][CARL_PPO_HYPER] */
+  const int32_t* idx;          /* DEVICE [n_sets][idx_set_stride]: row s, member s's n_samples flat indices */
+  const float* adv_norm;       /* DEVICE, member s's [2] at adv_norm + s * adv_norm_set_stride; NULL: advantages as they are */
+  int64_t idx_set_stride;      /* elements between two rows of idx, >= n_samples */
+  int64_t adv_norm_set_stride; /* floats between two members' adv_norm rows, >= 2 (read with adv_norm) */
+} carl_ppo_sets_t;
+
+/* floats of the workspace: n_sets x carl_ppo_workspace_floats() of one-set networks of these shapes; -1 for an invalid shape,
+ * n_sets < 1 (the actor's) or n_samples < 1 */
+int64_t carl_ppo_sets_workspace_floats(const carl_policy_t* policy_host, const carl_policy_t* critic_host, int32_t n_samples);
+int carl_ppo_grad_sets(const carl_ppo_batch_t* ppo_host, const carl_policy_t* policy_host, const carl_policy_t* critic_host,
+                       const float* log_std /* DEVICE [n_sets], Box families */, const carl_ppo_sets_t* sets_host,
+                       const carl_ppo_out_t* out, void* stream);
+int carl_ppo_adv_stats_sets(const carl_ppo_adv_stats_t* as_host, int32_t n_sets, int64_t idx_set_stride, void* stream);
+int carl_adam_step_sets(const carl_adam_t* adam_host, int32_t n_sets, const double* hyper /* DEVICE [n_sets][CARL_PPO_HYPER] */,
+                        void* stream);
+
 /* ======================= Brax-locomotion families (spring backend) =======================
  * Replaces CARLBraxEnv + BraxGymWrapper/VectorGymWrapper + brax.spring.pipeline.step x
  * n_frames + brax.envs.<env>.step/reset (carl/envs/brax/carl_brax_env.py:115-336,
