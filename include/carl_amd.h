@@ -737,6 +737,7 @@ int carl_policy_context_trace(const carl_batch_t* batch, const int32_t* ctx_idx0
  * floating-point atomics: the same call twice gives the same bits.
  * Preconditions the host cannot check: idx entries are distinct, each t * pitch + lane with lane < n_lanes (an entry
  * outside the buffer is skipped: it contributes zero); actions of a discrete family lie in [0, n_actions).
+ * new_log_prob[m] / new_value[m] of a skipped entry are not written.
  * Validation, each CARL_ERR_INVALID_ARGUMENT with a message before anything is enqueued: a NULL struct or required
  * pointer; a Brax family; n_lanes < 1, n_steps < 1; a pitch that is neither 0 nor >= n_lanes; the networks as
  * carl_rollout_policy_valued validates them (shape limits, the head against the family, n_in == n_ctx + obs_dim, context
@@ -1450,7 +1451,8 @@ int carl_brax_policy_context_trace(const carl_batch_t* batch, const int32_t* ctx
  *   dlp/dmu_j = z_j exp(-log_std_j),  dlp/dlog_std_j = z_j^2 - 1,  dH/dlog_std_j = 1
  * Outputs (carl_ppo_out_t): grad_actor / grad_critic [carl_brax_policy_set_floats()] in the packed layout, their shift |
  * scale | clip entries and round-up padding +0.0; grad_log_std [n_act]; stats [6], new_log_prob / new_value [n_samples] as
- * carl_ppo_grad's.
+ * carl_ppo_grad's.  An idx entry outside the buffer is skipped as carl_ppo_grad skips it (it contributes zero, n_samples
+ * still counts it); new_log_prob[m] / new_value[m] of a skipped entry are not written.
  * How it runs: carl_ppo_grad's scheme -- a persistent launch per network of carl_brax_ppo_grad_workgroups(n_samples)
  * workgroups over tiles of carl_brax_ppo_tile() samples, the weights staged in LDS once per workgroup, one sample per
  * thread, a fixed block of every dW per thread summed in sample order in blocks of 16, one slab per workgroup in

@@ -51,16 +51,16 @@ def context_walk(ctx_idx0, episode0, terminated, truncated, selector, stride, n_
 
 # ---------------------------------------------------------------- loss and gradients
 def brax_ppo_grad_ref(actor, critic, x_raw, action, logp_old, adv, ret, adv_norm=None, clip_range=0.2, vf_coef=0.5,
-                      ent_coef=0.0, dtype=np.float64):
+                      ent_coef=0.0, dtype=np.float64, tile_order=False):
     """carl_brax_ppo_grad's outputs for the samples with raw inputs x_raw [M, n_in] (float32), actions [M, n_act] and
     their log_prob / advantage / return entries [M] (float32); every operation in `dtype`.  -> ppo_ref.ppo_grad_ref's
-    dict, with grad_log_std / S_log_std [n_act]"""
+    dict, with grad_log_std / S_log_std [n_act]; tile_order: as ppo_ref.ppo_grad_ref takes it"""
     f = dtype
     M = x_raw.shape[0]
     lim = f(actor.clip)
     x = np.clip((x_raw.astype(f) - actor.shift.astype(f)) * actor.scale.astype(f), -lim, lim)
-    y, hs_a, pre_a = R._network(actor, x, f)
-    v, hs_c, pre_c = R._network(critic, x, f)
+    y, hs_a, pre_a = R._network(actor, x, f, tile_order)
+    v, hs_c, pre_c = R._network(critic, x, f, tile_order)
     V = v[:, 0]
     A = adv.astype(f)
     if adv_norm is not None:
@@ -86,11 +86,11 @@ def brax_ppo_grad_ref(actor, critic, x_raw, action, logp_old, adv, ret, adv_norm
     ec, vc = f(np.float32(ent_coef)), f(np.float32(vf_coef))
     dy = g_lp[:, None] * (z * inv)
     c_ls = g_lp[:, None] * (z * z - 1) - ec
-    g_ls = c_ls.sum(axis=0) / f(M)
+    g_ls = R._tile_order_mean(c_ls, np.ones((M, 1), f))[:, 0] if tile_order else c_ls.sum(axis=0) / f(M)
     S_ls = np.abs(c_ls).astype(np.float64).sum(axis=0) / M
     dv = (vc * 2 * (V - ret.astype(f)))[:, None]
-    g_a, S_a = R._backward(actor, dy, hs_a, pre_a, M, f)
-    g_c, S_c = R._backward(critic, dv, hs_c, pre_c, M, f)
+    g_a, S_a = R._backward(actor, dy, hs_a, pre_a, M, f, tile_order)
+    g_c, S_c = R._backward(critic, dv, hs_c, pre_c, M, f, tile_order)
     pl, vl, ent = -surr.mean(), ((ret.astype(f) - V) ** 2).mean(), H.mean()
     stats = np.array([pl, vl, ent, ((r - 1) - lr).mean(), (np.abs(r - 1) > c).mean(), M], np.float64)
     return dict(new_log_prob=lp, new_value=V, entropy=H, ratio=r, y=y, z=z, pre_actor=pre_a, pre_critic=pre_c,
@@ -204,13 +204,35 @@ def make_case(case):
                 every=every, adv_norm=norm, x=x)
 
 
-def case_reference(case, dtype=np.float64):
-    f = case["flat"]
+def case_reference(case, dtype=np.float64, pos=None, columns=None, adv_norm="case", clip_range=CLIP, ent_coef=ENT,
+                   tile_order=False):
+    """brax_ppo_grad_ref of a case's minibatch; pos, columns, adv_norm: as ppo_ref.case_reference takes them"""
+    f, x = (case["flat"], case["x"]) if pos is None else (case["flat"][pos], case["x"][pos])
+    col = {**case, **(columns or {})}
     pick = lambda a: a.reshape(-1)[f]  # noqa: E731
     n_act = case["actor"].n_out
-    return brax_ppo_grad_ref(case["actor"], case["critic"], case["x"], case["action"].reshape(-1, n_act)[f],
-                             pick(case["log_prob"]), pick(case["advantage"]), pick(case["ret"]), case["adv_norm"], CLIP, VF,
-                             ENT, dtype)
+    return brax_ppo_grad_ref(case["actor"], case["critic"], x, case["action"].reshape(-1, n_act)[f], pick(col["log_prob"]),
+                             pick(col["advantage"]), pick(col["ret"]),
+                             case["adv_norm"] if isinstance(adv_norm, str) else adv_norm, clip_range, VF, ent_coef, dtype,
+                             tile_order)
+
+
+# ---------------------------------------------------------------- the cases of test_gpu_ppo_grad_edges.py
+# (ppo_ref.py holds what the two units share: tile_positions, zero_signal, tile_loop_runs, with_bad_entries, rescaled,
+# clip_edge_columns.)  Part A: H = 0, 32, 64 with 2 or 3 actuators; rows are dense, so the skipped entries of part B are
+# the ones outside the buffer only.
+def tile_loop_cases():
+    return [("reacher-linear-tile-loop", "reacher", 2, "linear", "identity", 272, R.M_TILES, False),
+            ("hopper-1x32-tile-loop", "hopper", 0, "1x32", "relu", 272, R.M_TILES, False),
+            ("reacher-2x(64,64)-tile-loop", "reacher", 0, "2x(64,64)", "tanh", 272, R.M_TILES, False)]
+
+
+def skipped_cases():
+    return [("hopper-1x32-skipped", "hopper", 2, "1x32", "tanh", 260, 2 * TILE + 3, True)]
+
+
+def clip_edge_cases():
+    return [("reacher-1x7-clip-edge", "reacher", 2, "1x7", "tanh", 260, TILE + 1, True)]
 
 
 assert_conditioned = R.assert_conditioned

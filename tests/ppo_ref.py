@@ -1,7 +1,8 @@
 """Host reference of the PPO update on the device (include/carl_amd.h: carl_policy_context_trace, carl_ppo_grad), shared
-by test_ppo_reference.py, test_gpu_context_trace.py, test_gpu_ppo_grad.py and test_gpu_ppo.py: the selector walk, the
-sample inputs, and the forward pass, loss and analytic gradients of a minibatch in NumPy -- float64 from the float32
-inputs (the reference), or float32 throughout (``dtype=np.float32``: the plain restatement k0 is measured with).  A plain
+by test_ppo_reference.py, test_gpu_context_trace.py, test_gpu_ppo_grad.py, test_gpu_ppo_grad_edges.py and test_gpu_ppo.py:
+the selector walk, the sample inputs, and the forward pass, loss and analytic gradients of a minibatch in NumPy -- float64
+from the float32 inputs (the reference), or float32 throughout (``dtype=np.float32``: the plain restatement k0 is measured
+with; with ``tile_order=True`` its sums run in the device's stated order, which the zero-signal identities need).  A plain
 module like policy_cases.py: importing it touches no device.
 
 Gradient tolerance of the device tests.  Each packed gradient entry g = (1 / M) sum_s c_s must satisfy
@@ -75,12 +76,21 @@ def _act_grad(v, h, kind):
     return 1 - h * h if kind == "tanh" else (v > 0).astype(h.dtype) if kind == "relu" else np.ones_like(h)
 
 
-def _network(pol, x, dtype):
-    """forward pass of normalised inputs x -> (head outputs, [layer inputs], [pre-activations])"""
+def _rows_matmul(h, Wt):
+    """h @ Wt with every row's terms added in input order whatever the number of rows: a BLAS product may group a row's
+    terms by the shape of the whole matrix, and then a sample's float32 forward pass depends on the minibatch it is in"""
+    out = np.zeros((h.shape[0], Wt.shape[1]), h.dtype)
+    for k in range(h.shape[1]):
+        out += h[:, k: k + 1] * Wt[k]
+    return out
+
+
+def _network(pol, x, dtype, by_rows=False):
+    """forward pass of normalised inputs x -> (head outputs, [layer inputs], [pre-activations]); by_rows: _rows_matmul"""
     hs, pre = [x], []
     h = x
     for k, (W, b) in enumerate(pol.layers):
-        v = h @ W.astype(dtype).T + b.astype(dtype)
+        v = (_rows_matmul(h, W.astype(dtype).T) if by_rows else h @ W.astype(dtype).T) + b.astype(dtype)
         if k < len(pol.layers) - 1:
             pre.append(v)
             h = _act(v, pol.activation)
@@ -88,18 +98,54 @@ def _network(pol, x, dtype):
     return v, hs, pre
 
 
-def _backward(pol, dy, hs, pre, M, dtype):
-    """packed gradient [set_floats] and its S of per-sample head gradients dy [M, n_out] (not yet divided by M)"""
+def _tile_order_mean(d, h):
+    """(1 / M) sum_s d[s, i] h[s, j] summed as include/carl_amd.h states it, in d's dtype: tiles of TILE samples in index
+    order, blocks of 16 (each product rounded, added in sample order), the block sums added into the tile sum, tile t's sum
+    into accumulator t % workgroups, the accumulators added in order in float64, times 1 / M, rounded once.  Unlike a BLAS
+    product its grouping of the terms does not depend on the shapes, so a sample whose d row is +-0 changes no partial sum:
+    what the zero-signal identities of test_gpu_ppo_grad_edges.py rest on (the device uses fma inside a block; the
+    grouping is the same)."""
+    f = d.dtype.type
+    M = d.shape[0]
+    n_t = -(-M // TILE)
+
+    def tiles(a):
+        return np.concatenate([a, np.zeros((n_t * TILE - M, a.shape[1]), f)]).reshape(n_t, TILE, a.shape[1])
+
+    dp, hp = tiles(d), tiles(h)
+    tile = np.zeros((n_t, d.shape[1], h.shape[1]), f)
+    for b in range(0, TILE, 16):
+        blk = np.zeros_like(tile)
+        for s in range(b, b + 16):
+            blk += dp[:, s, :, None] * hp[:, s, None, :]
+        tile += blk
+    n_wg = min(n_t, WORKGROUPS_CAP)
+    acc = np.zeros((n_wg,) + tile.shape[1:], f)
+    for t0 in range(0, n_t, n_wg):
+        part = tile[t0: t0 + n_wg]
+        acc[: len(part)] += part
+    total = np.zeros(tile.shape[1:], np.float64)
+    for g in range(n_wg):
+        total += acc[g]
+    return (total * (1.0 / M)).astype(f)
+
+
+def _backward(pol, dy, hs, pre, M, dtype, tile_order=False):
+    """packed gradient [set_floats] and its S of per-sample head gradients dy [M, n_out] (not yet divided by M);
+    tile_order: the sums over the samples by _tile_order_mean and the deltas by _rows_matmul instead of matrix products"""
     grads, esses = [], []
     d = dy
     for k in range(len(pol.layers) - 1, -1, -1):
         W = pol.layers[k][0].astype(dtype)
         h = hs[k]
-        grads.append((d.T @ h / dtype(M), d.sum(axis=0) / dtype(M)))
+        if tile_order:
+            grads.append((_tile_order_mean(d, h), _tile_order_mean(d, np.ones((M, 1), dtype))[:, 0]))
+        else:
+            grads.append((d.T @ h / dtype(M), d.sum(axis=0) / dtype(M)))
         esses.append((np.abs(d).T.astype(np.float64) @ np.abs(h).astype(np.float64) / M,
                       np.abs(d).astype(np.float64).sum(axis=0) / M))
         if k > 0:
-            d = (d @ W) * _act_grad(pre[k - 1], hs[k], pol.activation)
+            d = (_rows_matmul(d, W) if tile_order else d @ W) * _act_grad(pre[k - 1], hs[k], pol.activation)
     g = np.zeros(pol.set_floats, dtype)
     S = np.zeros(pol.set_floats, np.float64)
     off = 0
@@ -112,17 +158,19 @@ def _backward(pol, dy, hs, pre, M, dtype):
 
 
 def ppo_grad_ref(actor, critic, x_raw, action, logp_old, adv, ret, adv_norm=None, clip_range=0.2, vf_coef=0.5, ent_coef=0.0,
-                 dtype=np.float64):
+                 dtype=np.float64, tile_order=False):
     """carl_ppo_grad's outputs for the samples with raw inputs x_raw [M, n_in] (float32) and their action / log_prob /
     advantage / return entries [M] (float32), from the policies' own layer arrays; every operation in `dtype`.
     -> dict: new_log_prob, new_value, entropy, ratio [M]; pre_actor / pre_critic: the hidden pre-activations; grad_actor /
-    grad_critic (packed) and grad_log_std with S_actor / S_critic / S_log_std; stats [6]; loss"""
+    grad_critic (packed) and grad_log_std with S_actor / S_critic / S_log_std; stats [6]; loss.  tile_order: the
+    gradients' sums over the samples in the device's stated order (_tile_order_mean) and every sample's own
+    arithmetic independent of the other samples (_rows_matmul)"""
     f = dtype
     M = x_raw.shape[0]
     lim = f(actor.clip)
     x = np.clip((x_raw.astype(f) - actor.shift.astype(f)) * actor.scale.astype(f), -lim, lim)
-    y, hs_a, pre_a = _network(actor, x, f)
-    v, hs_c, pre_c = _network(critic, x, f)
+    y, hs_a, pre_a = _network(actor, x, f, tile_order)
+    v, hs_c, pre_c = _network(critic, x, f, tile_order)
     V = v[:, 0]
     A = adv.astype(f)
     if adv_norm is not None:
@@ -156,10 +204,11 @@ def ppo_grad_ref(actor, critic, x_raw, action, logp_old, adv, ret, adv_norm=None
     else:
         dy = (g_lp * z * np.exp(-ls))[:, None]
         c_ls = g_lp * (z * z - 1) - ec
-        g_ls, S_ls = c_ls.sum() / f(M), float(np.abs(c_ls).astype(np.float64).sum() / M)
+        g_ls = _tile_order_mean(c_ls[:, None], np.ones((M, 1), f))[0, 0] if tile_order else c_ls.sum() / f(M)
+        S_ls = float(np.abs(c_ls).astype(np.float64).sum() / M)
     dv = (vc * 2 * (V - ret.astype(f)))[:, None]
-    g_a, S_a = _backward(actor, dy, hs_a, pre_a, M, f)
-    g_c, S_c = _backward(critic, dv, hs_c, pre_c, M, f)
+    g_a, S_a = _backward(actor, dy, hs_a, pre_a, M, f, tile_order)
+    g_c, S_c = _backward(critic, dv, hs_c, pre_c, M, f, tile_order)
     pl, vl, ent = -surr.mean(), ((ret.astype(f) - V) ** 2).mean(), H.mean()
     stats = np.array([pl, vl, ent, ((r - 1) - lr).mean(), (np.abs(r - 1) > c).mean(), M], np.float64)
     return dict(new_log_prob=lp, new_value=V, entropy=H, ratio=r, y=y, pre_actor=pre_a, pre_critic=pre_c, grad_actor=g_a,
@@ -274,11 +323,132 @@ def make_case(case):
                 every=every, adv_norm=norm, x=x)
 
 
-def case_reference(case, dtype=np.float64):
-    f = case["flat"]
+def case_reference(case, dtype=np.float64, pos=None, columns=None, adv_norm="case", clip_range=CLIP, ent_coef=ENT,
+                   tile_order=False):
+    """ppo_grad_ref of a case's minibatch; pos: positions into case["flat"] to evaluate instead of all of them (a minibatch
+    of its own: M = len(pos)); columns: {"log_prob" / "advantage" / "ret": a [T, P] array of any float dtype} read instead
+    of the case's; adv_norm: "case" for the case's own pair"""
+    f, x = (case["flat"], case["x"]) if pos is None else (case["flat"][pos], case["x"][pos])
+    col = {**case, **(columns or {})}
     pick = lambda a: a.reshape(-1)[f]  # noqa: E731
-    return ppo_grad_ref(case["actor"], case["critic"], case["x"], pick(case["action"]), pick(case["log_prob"]),
-                        pick(case["advantage"]), pick(case["ret"]), case["adv_norm"], CLIP, VF, ENT, dtype)
+    return ppo_grad_ref(case["actor"], case["critic"], x, pick(case["action"]), pick(col["log_prob"]),
+                        pick(col["advantage"]), pick(col["ret"]), case["adv_norm"] if isinstance(adv_norm, str) else adv_norm,
+                        clip_range, VF, ent_coef, dtype, tile_order)
+
+
+# ---------------------------------------------------------------- the cases of test_gpu_ppo_grad_edges.py
+# Part A: M = 256 tiles + 3 full tiles + 7 samples, so workgroups 0 .. 2 run a full second tile and workgroup 3 one of 7
+# samples; 272 lanes x 245 steps hold them.  H = 0, 32 (one and two hidden layers) and 64; a 2-action, two 3-action and the
+# Box family; context inputs on two.
+M_TILES = WORKGROUPS_CAP * TILE + 3 * TILE + 7
+TILE_LOOP_WORKGROUPS = (0, 3)
+
+
+def tile_loop_cases():
+    return [("cartpole-linear-tile-loop", "cartpole", 2, "linear", "identity", 272, M_TILES, False),
+            ("acrobot-1x5-tile-loop", "acrobot", 0, "1x5", "relu", 272, M_TILES, False),
+            ("mountaincar-2x(7,3)-tile-loop", "mountaincar", 0, "2x(7,3)", "tanh", 272, M_TILES, False),
+            ("pendulum-2x(64,64)-tile-loop", "pendulum", 2, "2x(64,64)", "tanh", 272, M_TILES, False)]
+
+
+def tile_positions(M, w):
+    """(A, B): the positions (into idx) of tile w and of tile w + WORKGROUPS_CAP, workgroup w's first and second pass"""
+    A = np.arange(w * TILE, min((w + 1) * TILE, M))
+    B = np.arange((w + WORKGROUPS_CAP) * TILE, min((w + WORKGROUPS_CAP + 1) * TILE, M))
+    assert A.size and B.size
+    return A, B
+
+
+def zero_signal(case, keep, new_value):
+    """{"advantage", "ret"}: copies of the case's columns in which every sample of the minibatch outside the positions
+    `keep` has advantage 0 and return new_value[position] (new_value [M]: the forward pass's own values, so V - ret == 0
+    in its arithmetic; the return column takes new_value's dtype).  With ent_coef = 0 and no advantage normalisation such
+    a sample's dL/dy and grad_log_std term are +-0 whatever its inputs, action and old log-probability are."""
+    off = np.ones(case["flat"].size, bool)
+    off[keep] = False
+    adv, ret = case["advantage"].copy(), case["ret"].astype(new_value.dtype)
+    adv.reshape(-1)[case["flat"][off]] = 0
+    ret.reshape(-1)[case["flat"][off]] = new_value[off]
+    return {"advantage": adv, "ret": ret}
+
+
+def tile_loop_runs(case, w, reference):
+    """Part A's five runs of workgroup w from reference(pos, columns) -> ppo_grad_ref's dict (pos None: every position):
+    small_A / small_B (the tile's samples alone), big_A / big_B / big_AB (all M samples, everything else zero-signal with
+    the returns taken from reference(None, None)'s new_value) -> ({run: dict}, A, B)"""
+    A, B = tile_positions(case["flat"].size, w)
+    v = reference(None, None)["new_value"]
+    runs = {"small_A": reference(A, None), "small_B": reference(B, None)}
+    for name, keep in (("big_A", A), ("big_B", B), ("big_AB", np.concatenate([A, B]))):
+        runs[name] = reference(None, zero_signal(case, keep, v))
+    return runs, A, B
+
+
+# Part B: M = 2 TILE + 3 from a 260-lane buffer of pitch 272, some entries replaced by bad ones
+def skipped_cases():
+    return [("cartpole-2x(7,3)-skipped", "cartpole", 2, "2x(7,3)", "tanh", 260, 2 * TILE + 3, True),
+            ("pendulum-1x5-skipped", "pendulum", 0, "1x5", "relu", 260, 2 * TILE + 3, False)]
+
+
+def bad_positions(M):
+    """the first position of a tile, the last position of the partial tile, one whole wavefront"""
+    assert M % TILE and M > TILE + 128
+    return np.concatenate([[TILE], [M - 1], np.arange(64, 128)])
+
+
+def with_bad_entries(flat, T, pitch, n_lanes):
+    """(idx, valid): flat with the entries at bad_positions() replaced, in turn, by -1, T * pitch, T * pitch + 1 and, where
+    the rows have padding lanes, a padding lane's index t * pitch + n_lanes and t * pitch + pitch - 1 -- each within
+    2 * pitch elements of the buffer"""
+    bad = [-1, T * pitch, T * pitch + 1]
+    if pitch > n_lanes:
+        bad += [(T // 2) * pitch + n_lanes, pitch - 1, (T - 1) * pitch + pitch - 1]
+    pos = bad_positions(flat.size)
+    idx = flat.astype(np.int32).copy()
+    idx[pos] = [bad[k % len(bad)] for k in range(pos.size)]
+    valid = np.ones(flat.size, bool)
+    valid[pos] = False
+    return idx, valid
+
+
+def rescaled(ref, n_valid, M):
+    """a reference over the n_valid valid samples of a minibatch of M as the device reports it: the skipped samples add
+    zero to every sum and the divisor stays M, so the gradients, their S and the five means shrink by n_valid / M"""
+    out = dict(ref)
+    for k in ("grad_actor", "grad_critic", "grad_log_std", "S_actor", "S_critic", "S_log_std"):
+        out[k] = np.asarray(ref[k]) * (n_valid / M)
+    out["stats"] = np.concatenate([ref["stats"][:5] * (n_valid / M), [M]])
+    return out
+
+
+# Part C: M = TILE + 1, the old log-probabilities replaced by the forward pass's own (r == 1) or moved by +- ln 2
+def clip_edge_cases():
+    return [("acrobot-1x5-clip-edge", "acrobot", 2, "1x5", "tanh", 260, TILE + 1, True),
+            ("pendulum-2x(7,3)-clip-edge", "pendulum", 0, "2x(7,3)", "tanh", 260, TILE + 1, False)]
+
+
+LN2_F32 = np.float32(np.log(2.0))
+
+
+def clip_edge_columns(case, lp_forward, lp64, mixed):
+    """(device column, reference column) of old log-probabilities for part C.  The device's: the forward pass's own float32
+    log-probabilities lp_forward [M], so that lr = lp - log_prob == 0 and r == 1 exactly; with `mixed`, position m keeps
+    that for m % 3 == 0 and gets fl32(lp - ln 2) (r about 2) for m % 3 == 1, fl32(lp + ln 2) (r about 1/2) for m % 3 == 2.
+    Those ratios are not exact powers of two: lp -+ ln 2 is rounded wherever lp has bits below the sum's last place, so lr
+    is +-ln 2 within an ulp of lp.  Nothing here needs them exact: the reference's column (float64) is lp64 minus the exact
+    difference lp_forward - column, the log-ratio the device's subtraction rounds -- so the reference has the device's
+    ratios within half an ulp, 1 exactly where the column holds lp_forward, and every moved ratio is far from 1."""
+    M = case["flat"].size
+    shift = np.zeros(M, np.float32)
+    if mixed:
+        shift[np.arange(M) % 3 == 1] = -LN2_F32
+        shift[np.arange(M) % 3 == 2] = LN2_F32
+    q = (lp_forward.astype(np.float32) + shift).astype(np.float32)
+    dev = case["log_prob"].copy()
+    dev.reshape(-1)[case["flat"]] = q
+    ref = case["log_prob"].astype(np.float64)
+    ref.reshape(-1)[case["flat"]] = lp64 - (lp_forward.astype(np.float64) - q.astype(np.float64))
+    return dev, ref
 
 
 def assert_conditioned(case, ref):

@@ -7,6 +7,7 @@ import pytest
 import torch
 
 import brax_ppo_ref as BR
+import ppo_checks as PK
 from carl_amd import _lib
 
 CASES = BR.grad_cases()
@@ -163,3 +164,17 @@ def test_random_walk_by_hand():
     assert len(set(want)) > 1
     assert walk(_lib.SEL_RANDOM, True, True, e0=e0, C=C_, seed=seed, off=off) == [2] * 6
     assert walk(_lib.SEL_RANDOM, False, False, e0=e0, C=C_, seed=seed, off=off) == [2] * 6
+
+
+# ---------------------------------------------------------------- the helpers of test_gpu_ppo_grad_edges.py
+SMALL_TILE_LOOP = [c for c in BR.tile_loop_cases() if "64" not in c[3]]  # (the 64-wide restatement takes half a minute)
+
+
+@pytest.mark.parametrize("spec", SMALL_TILE_LOOP, ids=[c[0] for c in SMALL_TILE_LOOP])
+def test_tile_loop_identities_hold_for_the_float32_restatement(spec):
+    PK.check_tile_loop_helpers(BR, spec)
+
+
+@pytest.mark.parametrize("spec", BR.skipped_cases(), ids=[c[0] for c in BR.skipped_cases()])
+def test_rescaled_subset_reference_is_the_evaluation_with_zero_terms(spec):
+    PK.check_skipped_helpers(BR, spec)

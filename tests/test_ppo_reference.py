@@ -1,10 +1,13 @@
 """ppo_ref.py against independent restatements, on the CPU: its loss and analytic gradients against torch float64
 autograd of SB3's PPO loss (every head, activation and depth, with and without advantage normalisation), and its
-selector walk against the host selectors of carl_amd/context/selection.py.  CPU-only."""
+selector walk against the host selectors of carl_amd/context/selection.py; and the helpers that build the cases of
+test_gpu_ppo_grad_edges.py (zero-signal samples, the rescaled subset reference, the clip-edge columns) on the float32
+restatement.  CPU-only."""
 import numpy as np
 import pytest
 import torch
 
+import ppo_checks as PK
 import ppo_ref as R
 from carl_amd import _lib
 from carl_amd.context.selection import RoundRobinSelector, StaticSelector
@@ -164,3 +167,42 @@ def test_random_walk_draws_once_per_reset_from_the_episode_counter():
                 c = (int(w[0]) * C) >> 32
                 e = (e + 1) & 0xFFFFFFFF
     assert got.min() >= 0 and got.max() < C
+
+
+# ---------------------------------------------------------------- the helpers of test_gpu_ppo_grad_edges.py
+SMALL_TILE_LOOP = [c for c in R.tile_loop_cases() if "64" not in c[3]]  # (the 64-wide restatement takes half a minute)
+
+
+@pytest.mark.parametrize("spec", SMALL_TILE_LOOP, ids=[c[0] for c in SMALL_TILE_LOOP])
+def test_tile_loop_identities_hold_for_the_float32_restatement(spec):
+    PK.check_tile_loop_helpers(R, spec)
+
+
+@pytest.mark.parametrize("spec", R.skipped_cases(), ids=[c[0] for c in R.skipped_cases()])
+def test_rescaled_subset_reference_is_the_evaluation_with_zero_terms(spec):
+    PK.check_skipped_helpers(R, spec)
+
+
+@pytest.mark.parametrize("spec", R.clip_edge_cases(), ids=[c[0] for c in R.clip_edge_cases()])
+def test_clip_edge_columns_give_the_reference_the_float32_ratios(spec):
+    """the float32 restatement's log-probabilities in the device's place: the reference's ratios are 1 exactly where the
+    column holds them and 2 and 1/2 within a few roundings where it was moved, as the float32 ratios are"""
+    case = R.make_case(spec)
+    flat = case["flat"]
+    lp32, lp64 = R.case_reference(case, np.float32)["new_log_prob"], R.case_reference(case)["new_log_prob"]
+    assert lp32.dtype == np.float32
+    m = np.arange(flat.size) % 3
+    for mixed in (False, True):
+        dev, ref = R.clip_edge_columns(case, lp32, lp64, mixed)
+        assert dev.dtype == np.float32 and ref.dtype == np.float64
+        r = R.case_reference(case, columns={"log_prob": ref}, clip_range=0.0)["ratio"]
+        lr32 = lp32 - dev.reshape(-1)[flat]
+        if not mixed:
+            assert (r == 1).all() and (lr32 == 0).all()
+            continue
+        assert (r[m == 0] == 1).all()
+        np.testing.assert_allclose(r[m == 1], 2.0, rtol=2e-6)
+        np.testing.assert_allclose(r[m == 2], 0.5, rtol=2e-6)
+        r32 = np.exp(lr32)
+        assert (r32[m == 0] == 1).all() and (r32[m == 1] > 1.9).all() and (r32[m == 2] < 0.6).all()
+        np.testing.assert_allclose(r32, r, rtol=4 * R.U)  # (half an ulp of lr, a rounding of exp)
