@@ -44,6 +44,43 @@ def sums_bound(n, A):
     return n * U64 * np.asarray(A, np.float64)
 
 
+THREADS, MAX_WORKGROUPS = 256, 256  # ppo_device.hip.h: kPpoThreads, kPpoMaxWorkgroups
+
+
+def input_plan(n, n_in):
+    """ppo_input_stats_kernel's launch shape for n samples of n_in inputs, and which sample each thread chains when ->
+    (G slabs, spt samples per pass, n_pass, passes [G]: the passes workgroup w runs, idx [G, max(passes), spt] int64: the
+    sample that thread (so, any i) of workgroup w takes in its r-th pass, p = w + r * G, or -1 where p >= n_pass or the
+    sample p * spt + so is past the end)"""
+    G = min(-(-n // THREADS), MAX_WORKGROUPS)
+    spt = THREADS // n_in
+    n_pass = -(-n // spt)
+    w = np.arange(G, dtype=np.int64)
+    passes = (n_pass - w + G - 1) // G  # (G <= ceil(n / 256) <= n_pass: every workgroup has at least one)
+    p = w[:, None] + G * np.arange(passes.max(), dtype=np.int64)[None, :]
+    m = p[:, :, None] * spt + np.arange(spt, dtype=np.int64)[None, None, :]
+    return G, spt, n_pass, passes, np.where((p[:, :, None] < n_pass) & (m < n), m, -1)
+
+
+def input_slabs_ref(x, shift):
+    """the slabs [G][2][32] float64 of carl_ppo_input_stats over the samples x [n, n_in] float32 (t-major), every addition
+    in the kernel's order: thread (so, i) of workgroup w chains d = fp32(x - shift) widened, s1 += d, s2 += d * d, over
+    its passes in pass order (samples past the end are skipped); slot i is then the sum over so = 0 .. spt - 1 in that
+    order from +0.0; entries at and beyond n_in are +0.0.  Every term is an exact float64, so the order decides each bit."""
+    n, n_in = x.shape
+    d = (x.astype(np.float32) - np.asarray(shift, np.float32)[None, :]).astype(np.float32).astype(np.float64)
+    terms = np.stack([d, d * d])  # [2, n, n_in]  (the float64 product of two floats is exact)
+    G, spt, _, _, idx = input_plan(n, n_in)
+    acc = np.zeros((2, G, spt, n_in))
+    for r in range(idx.shape[1]):
+        live = idx[:, r, :] >= 0
+        np.add(acc, terms[:, np.where(live, idx[:, r, :], 0)], out=acc, where=live[None, :, :, None])
+    part = np.zeros((G, 2, MAX_IN))
+    for so in range(spt):
+        part[:, :, :n_in] += acc[:, :, so, :].transpose(1, 0, 2)
+    return part
+
+
 def merge_ref(S1, S2, n_b, shift, state=None, eps=1e-8, min_std=1e-6):
     """carl_policy_stats_merge's rule in float64 for sums S1, S2 [n_in] over n_b samples centred on shift ->
     (state' = (count, mean, m2), shift' float32, scale' float32)"""

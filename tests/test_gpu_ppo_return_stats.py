@@ -1,7 +1,9 @@
 """carl_ppo_return_stats and carl_ppo_return_merge on the GPU, through ``ppo_return_stats`` / ``ppo_return_merge``: the
 persistent return and the per-step values bit for bit against the float32 restatement (ppo_norm_ref.return_walk_ref), the
 slab sums at the derived float64 bound (n * 2^-53 * sum |terms|), a walk split into two calls, a done at the last step,
-T = 1, lane counts around the wavefront and the workgroup, pitched and dense rows; the merge against the same operations
+T = 1, lane counts around the wavefront and the workgroup, pitched and dense rows; each slab against the exact sums of its
+own 256 lanes at the same bound over that slab's samples (513 lanes x 17 steps: three slabs, the last of one lane, two full
+rounds of the 8-row load window and one row more); the merge against the same operations
 in NumPy float64 (rtol 1e-12 for mean and M2, as test_gpu_policy_stats_merge.py holds carl_policy_stats_merge) over three
 successive merges."""
 import math
@@ -21,7 +23,7 @@ GAMMA = 0.97
 
 @pytest.fixture(scope="module")
 def engines():
-    return {n: PC.make_engine(_lib.CARTPOLE, n, n_contexts=4) for n in (1, 63, 65, 257)}
+    return {n: PC.make_engine(_lib.CARTPOLE, n, n_contexts=4) for n in (1, 63, 65, 257, 513)}
 
 
 def columns(N, T, seed, pitched):
@@ -42,7 +44,7 @@ def columns(N, T, seed, pitched):
 
 
 @pytest.mark.parametrize("N,T,pitched", [(1, 1, False), (63, 9, True), (65, 9, False), (257, 9, True), (257, 1, True),
-                                         (63, 2, False)])
+                                         (63, 2, False), (513, 17, True)])
 def test_return_walk_bits_and_sums(engines, N, T, pitched):
     eng = engines[N]
     (reward, te, tr), (d_reward, d_te, d_tr) = columns(N, T, 100 + N + T, pitched)
@@ -60,6 +62,17 @@ def test_return_walk_bits_and_sums(engines, N, T, pitched):
         got = math.fsum(part[:, q])
         print(f"n={N} T={T} S{q + 1}: |err| {abs(got - S):.3e}, bound {n * NR.U64 * A:.3e}")
         assert abs(got - S) <= n * NR.U64 * A
+    # slab by slab: workgroup w adds the returns of lanes [256 w, 256 w + 256) in a fixed tree -- any order of n_w terms
+    # stays within n_w * 2^-53 * sum |terms| of their exact sum
+    r64 = rows.astype(np.float64)
+    for w in range(part.shape[0]):
+        mine = r64[:, 256 * w: 256 * w + 256].reshape(-1)
+        n_w = mine.size
+        assert n_w == T * min(256, N - 256 * w)
+        for q, terms in enumerate((mine, mine * mine)):  # (the float64 product of two floats is exact)
+            err, bound = abs(part[w, q] - math.fsum(terms)), n_w * NR.U64 * math.fsum(np.abs(terms))
+            print(f"n={N} T={T} slab {w} S{q + 1}: |err| {err:.3e}, bound {bound:.3e} (n_w = {n_w})")
+            assert err <= bound
     # the same call from the same state: the same bits (and no per-step rows asked for)
     ret_b = torch.as_tensor(ret0).cuda()
     again = eng.ppo_return_stats(d_reward, d_te, d_tr, ret_b, GAMMA)

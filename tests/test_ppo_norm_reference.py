@@ -1,6 +1,10 @@
 """The NumPy references of PPO's running normalisation (ppo_norm_ref.py) against independent statements of the same
 quantities: np.mean / np.var of the gathered inputs, a 2-lane, 3-step case walked by hand, and a step-by-step
-VecNormalize-style loop (SB3's RunningMeanStd.update_from_moments) for the returns.  CPU-only."""
+VecNormalize-style loop (SB3's RunningMeanStd.update_from_moments) for the returns; the ordered restatement of the input
+slabs (input_plan / input_slabs_ref) against the counts of the GPU tests' launch regimes, a thread-by-thread walk of the
+kernel's loops and the exact sums.  CPU-only."""
+import math
+
 import numpy as np
 import pytest
 
@@ -68,6 +72,104 @@ def test_input_sums_of_a_hand_walked_buffer():
     np.testing.assert_array_equal(S2, (d * d).sum(axis=0))
     np.testing.assert_array_equal(A1, np.abs(d).sum(axis=0))
     assert S1.tolist() == [17.0, 19.5, 216.0]
+
+
+# (n samples, n_in) of test_gpu_ppo_input_stats.py's regime cases -> (slabs, spt, passes, workgroups that run one pass
+# more than the others, the passes those run, samples of the last pass)
+PLAN_SHAPES = {(300 * 300, 6): (256, 42, 2143, 95, 9, 36), (700 * 250, 3): (256, 85, 2059, 11, 9, 70),
+               (257 * 257, 6): (256, 42, 1573, 37, 7, 25), (257 * 257, 11): (256, 23, 2872, 56, 12, 16),
+               (300 * 9, 2): (11, 128, 22, 11, 2, 12), (300 * 9, 32): (11, 8, 338, 8, 31, 4)}
+
+
+@pytest.mark.parametrize("n,n_in", list(PLAN_SHAPES), ids=[f"n{n}-in{k}" for n, k in PLAN_SHAPES])
+def test_input_plan_counts_every_sample_once(n, n_in):
+    G, spt, n_pass, extra, longest, last = PLAN_SHAPES[(n, n_in)]
+    got_G, got_spt, got_pass, passes, idx = NR.input_plan(n, n_in)
+    assert (got_G, got_spt, got_pass) == (G, spt, n_pass)
+    assert G == min(-(-n // 256), 256) and spt == 256 // n_in and n_pass == -(-n // spt)
+    # the passes go round the grid: the first `extra` workgroups run `longest`, the others one fewer (extra == G: all)
+    assert passes.shape == (G,) and passes.sum() == n_pass
+    assert passes.tolist() == [longest] * extra + [longest - 1] * (G - extra)
+    assert idx.shape == (G, longest, spt)
+    live = idx[idx >= 0]
+    np.testing.assert_array_equal(np.sort(live), np.arange(n))  # every sample exactly once
+    assert n - (n_pass - 1) * spt == last
+    # a thread's samples ascend (its chain is in pass order) and a pass is spt consecutive samples
+    for w in (0, extra - 1, G - 1):
+        rows = idx[w, : passes[w]]
+        assert (rows[:, 0] == (w + G * np.arange(passes[w])) * spt).all()
+        assert (idx[w, passes[w]:] == -1).all()
+    tail = idx[(n_pass - 1) % G, (n_pass - 1) // G]
+    assert tail[:last].tolist() == list(range(n - last, n)) and (tail[last:] == -1).all()
+
+
+def walked_slabs(x, shift):
+    """ppo_input_stats_kernel read line by line, one Python float per accumulator: the round loop of 8 passes per thread
+    with its stride of 8 * G, the guards of a slot past the end, the LDS array and the 64 reducing threads"""
+    n, n_in = x.shape
+    G, ahead = min(-(-n // 256), 256), 8
+    spt = 256 // n_in
+    n_pass = -(-n // spt)
+    d = (x - np.asarray(shift, np.float32)[None, :]).astype(np.float32).astype(np.float64)
+    part = np.full((G, 2, 32), np.nan)
+    for w in range(G):
+        red = np.zeros((2, 256))
+        for tid in range(256):
+            i, so = tid % n_in, tid // n_in
+            s1 = s2 = 0.0
+            if so < spt:
+                for p0 in range(w, n_pass, ahead * G):
+                    for k in range(ahead):
+                        p = p0 + k * G
+                        m = p * spt + so
+                        if p < n_pass and m < n:
+                            s1 += float(d[m, i])
+                            s2 += float(d[m, i]) * float(d[m, i])
+            red[0, tid], red[1, tid] = s1, s2
+        for q in range(2):
+            for j in range(32):
+                s = 0.0
+                if j < n_in:
+                    for k in range(spt):
+                        s += red[q, k * n_in + j]
+                part[w, q, j] = s
+    return part
+
+
+@pytest.mark.parametrize("n,n_in", [(300 * 9, 32), (300 * 9, 2), (257 * 80, 6), (1, 5), (257, 3)])
+def test_input_slabs_restatement_equals_the_kernel_walked_thread_by_thread(n, n_in):
+    """the vectorised restatement against a literal walk of the kernel's loops, bit for bit; 2 700 x 32 runs four rounds
+    of the ahead loop per thread, 20 560 x 6 two passes, the others one"""
+    rng = np.random.default_rng(n + n_in)
+    x = rng.normal(0.3, 2.0, (n, n_in)).astype(np.float32)
+    x[rng.random((n, n_in)) < 0.01] = -0.0
+    shift = rng.normal(0, 0.5, n_in).astype(np.float32)
+    shift[0] = 0.0  # (x = -0.0 under a zero shift: d = -0.0)
+    got = NR.input_slabs_ref(x, shift)
+    assert got.dtype == np.float64
+    np.testing.assert_array_equal(got.view(np.uint64), walked_slabs(x, shift).view(np.uint64))
+
+
+@pytest.mark.parametrize("n,n_in", list(PLAN_SHAPES), ids=[f"n{n}-in{k}" for n, k in PLAN_SHAPES])
+def test_input_slabs_restatement_meets_the_exact_sums(n, n_in):
+    rng = np.random.default_rng(n_in)
+    x = rng.normal(0.3, 2.0, (n, n_in)).astype(np.float32)
+    shift = rng.normal(0, 0.5, n_in).astype(np.float32)
+    part = NR.input_slabs_ref(x, shift)
+    G = PLAN_SHAPES[(n, n_in)][0]
+    assert part.shape == (G, 2, NR.MAX_IN) and (part[:, :, n_in:].view(np.uint64) == 0).all()
+    S1, S2, A1, A2 = NR.input_sums_ref(x, shift)
+    for q, (S, A) in enumerate(((S1, A1), (S2, A2))):
+        got = np.array([math.fsum(part[:, q, i]) for i in range(n_in)])
+        assert np.all(np.abs(got - S) <= NR.sums_bound(n, A))
+    # a sample moved to another slab, or counted twice: per slab, the plan's samples added exactly
+    _, _, _, _, idx = NR.input_plan(n, n_in)
+    d = (x - shift[None, :]).astype(np.float32).astype(np.float64)
+    for w in (0, G - 1):
+        m = idx[w][idx[w] >= 0]
+        for i in range(n_in):
+            exact, mag = math.fsum(d[m, i]), math.fsum(np.abs(d[m, i]))
+            assert abs(part[w, 0, i] - exact) <= m.size * NR.U64 * mag
 
 
 def vecnormalize_loop(reward, done, gamma, eps, chunks):
