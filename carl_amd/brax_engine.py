@@ -11,7 +11,8 @@ from dataclasses import dataclass
 import torch
 
 from carl_amd import _lib
-from carl_amd.engine import LaneEngine, VecEngine, _ptr
+from carl_amd._tensors import is_exact
+from carl_amd.engine import LaneEngine, _ptr
 
 
 @dataclass
@@ -319,12 +320,6 @@ class BraxVecEngine(LaneEngine):
         raise NotImplementedError("Brax families reset through a lane mask (reset(mask)) or in-kernel auto-reset")
 
     # ------------------------------------------------------------------ closed-loop rollout
-    def alloc_policy_summary(self) -> dict:
-        """Per-lane totals of a summary-mode ``rollout_policy``: ``episodes`` / ``length_sum`` int32, ``return_sum``
-        float32, ``[N]`` each."""
-        z = lambda dt: torch.zeros(self.n, dtype=dt, device=self.device)  # noqa: E731
-        return {"episodes": z(torch.int32), "return_sum": z(torch.float32), "length_sum": z(torch.int32)}
-
     def _check_policy(self, policy, what: str) -> None:
         """the policy / model checks of the closed-loop launches (``rollout_policy``, ``evaluate_episodes``)"""
         from carl_amd.brax_policy import BraxMLPPolicy
@@ -336,18 +331,6 @@ class BraxVecEngine(LaneEngine):
             raise ValueError(f"the policy was built for {policy.obs_dim} observations and {policy.n_out} actuators, this "
                              f"engine's model has {self.D} and {self.sys.n_act}")
 
-    def _policy_column(self, res: dict, key: str, T: int) -> torch.Tensor:
-        """``res[key]``, a float32 ``[>= T, N]`` column of a closed-loop launch (dense rows): allocated when missing,
-        checked when the caller passed it"""
-        t = res.get(key)
-        if t is None:
-            t = res[key] = torch.empty((T, self.n), dtype=torch.float32, device=self.device)
-        if (t.dtype != torch.float32 or t.device != self.device or t.dim() != 2 or t.shape[0] < T or t.shape[1] != self.n
-                or not t.is_contiguous()):
-            raise ValueError(f"rollout_policy output needs a contiguous float32 '{key}' [>= {T}, {self.n}] buffer on "
-                             f"{self.device}")
-        return t
-
     def _check_value_net(self, policy, value_net) -> None:
         """ValueError unless ``value_net`` is a critic the valued launch can run next to ``policy``: a one-output
         ``BraxMLPPolicy`` of this model with the actor's context rows, set layout and -- bit for bit -- transform"""
@@ -357,7 +340,7 @@ class BraxVecEngine(LaneEngine):
                 or value_net.obs_dim != self.D):
             raise ValueError(f"value_net must be a carl_amd.brax_policy.BraxMLPPolicy built with head='value' for this "
                              f"engine's model ({self.D} observations)")
-        VecEngine._check_value_net(self, policy, value_net)  # (the rules the two engines share)
+        super()._check_value_net(policy, value_net)  # (the rules the two engines share)
 
     def rollout_policy(self, policy, n_steps: int, out: dict | None = None, mode: str = "transitions", *,
                        deterministic: bool = True, sample_seed: int = 0, log_prob: bool = False, value_net=None,
@@ -388,60 +371,29 @@ class BraxVecEngine(LaneEngine):
         ``out`` are checked like ``"log_prob"``.  ``gae=(gamma, lam)`` adds ``"advantage"`` and ``"return"`` ``[T, N]``
         from one ``gae`` launch of the launch's own columns on the same stream: a PPO collection step."""
         self._check_policy(policy, "rollout_policy")
-        if mode not in ("transitions", "summary"):
-            raise ValueError(f"mode {mode!r}: 'transitions' or 'summary'")
-        if gae is not None and value_net is None:
-            raise ValueError("gae=(gamma, lam) needs value_net: advantages are computed from the critic's values")
-        if value_net is not None:
-            if deterministic:
-                raise ValueError("value_net: sampled launches only (deterministic=False); a deterministic valued launch "
-                                 "is not built for the Brax families")
-            if mode == "summary":
-                raise ValueError("value_net: transitions mode only (mode='summary' stores nothing per step)")
-            self._check_value_net(policy, value_net)
-            if bootstrap_truncated and not self.auto_reset:
-                raise ValueError("bootstrap_truncated=True needs auto_reset=True: without it no terminal observation is "
-                                 "kept apart from the next one (pass bootstrap_truncated=False)")
-            if gae is not None:
-                gamma, lam = (float(v) for v in gae)
-            log_prob = True  # (a valued launch always stores the log-probabilities)
-        if log_prob and deterministic:
-            raise ValueError("log_prob=True: sampled launches only (deterministic=False)")
-        if log_prob and mode == "summary":
-            raise ValueError("log_prob=True: transitions mode only (a summary launch stores nothing per step)")
+        if value_net is not None and deterministic:
+            raise ValueError("value_net: sampled launches only (deterministic=False); a deterministic valued launch "
+                             "is not built for the Brax families")
+        log_prob, gae = self._policy_keywords(policy, mode, deterministic, log_prob, value_net, bootstrap_truncated, gae)
         T = int(n_steps)
         if mode == "summary":
-            if not self.auto_reset:
-                raise ValueError("mode='summary' needs auto_reset=True: without it a finished lane reports done on every "
-                                 "later step, and the totals would count its episode on each of them")
             res = self.alloc_policy_summary() if out is None else out
-            for k, dt in (("episodes", torch.int32), ("return_sum", torch.float32), ("length_sum", torch.int32)):
-                t = res.get(k)
-                if (t is None or t.device != self.device or t.dtype != dt or tuple(t.shape) != (self.n,)
-                        or not t.is_contiguous()):
+            for k, dt in self._SUMMARY_KEYS:  # (the exact dtypes, where the classic-control engine takes any 4-byte one)
+                if not is_exact(res.get(k), self.device, dt, (self.n,)):
                     raise ValueError(f"rollout_policy summary '{k}' must be a contiguous {dt} [{self.n}] tensor on "
                                      f"{self.device}")
-            io, summ = None, C.byref(_lib.PolicySummary(*(_ptr(res[k]) for k in ("episodes", "return_sum", "length_sum"))))
+            io, summ = None, self._policy_summary(res)
         else:
             res = self.alloc_rollout(T, action=True) if out is None else out
             a = res.get("action")
-            if (a is None or a.dtype != torch.float32 or a.device != self.device or a.dim() != 3 or a.shape[0] < T
-                    or tuple(a.shape[1:]) != (self.n, self.sys.n_act) or not a.is_contiguous()):
+            if not is_exact(a, self.device, torch.float32, (None, self.n, self.sys.n_act)) or a.shape[0] < T:
                 raise ValueError(f"rollout_policy output needs a contiguous float32 'action' [>= {T}, {self.n}, "
                                  f"{self.sys.n_act}] buffer on {self.device}")
             if log_prob:
-                self._policy_column(res, "log_prob", T)
+                self._policy_columns(res, ("log_prob",), T)
             if value_net is not None:
-                self._policy_column(res, "value", T)
-                if bootstrap_truncated:
-                    self._policy_column(res, "boot_value", T)
-                lv = res.get("last_value")
-                if lv is None:
-                    lv = res["last_value"] = torch.empty(self.n, dtype=torch.float32, device=self.device)
-                if (lv.dtype != torch.float32 or lv.device != self.device or tuple(lv.shape) != (self.n,)
-                        or not lv.is_contiguous()):
-                    raise ValueError(f"rollout_policy 'last_value' must be a contiguous float32 [{self.n}] tensor on "
-                                     f"{self.device}")
+                self._policy_columns(res, ("value", "boot_value") if bootstrap_truncated else ("value",), T)
+                self._policy_last_value(res)
             io, summ = C.byref(self._rollout_io(a, _lib.ACTION_F32, res, T)), None
         # (after ``autotune``: the width that was fastest for the OPEN-loop rollout of this length class.  The closed loop
         # has 164 more LDS rows per env and another instruction mix; whether its best width differs is not measured)
@@ -473,10 +425,7 @@ class BraxVecEngine(LaneEngine):
             if goal:
                 self.b.success = self.success.data_ptr()
         if gae is not None:
-            adv = self.gae(res["reward"][:T], res["value"][:T], res["terminated"][:T], res["truncated"][:T],
-                           res["last_value"], gamma, lam, boot_value=res["boot_value"][:T] if bootstrap_truncated else None,
-                           out={k: res[k] for k in ("advantage", "return") if k in res} or None)
-            res["advantage"], res["return"] = adv["advantage"], adv["return"]
+            self._policy_gae(res, T, gae, bootstrap_truncated)
         return res
 
     # ---- LaneEngine's PPO hooks (context_trace, ppo_workspace, ppo_grad): the Brax entry points, dense rows, an action
@@ -517,18 +466,6 @@ class BraxVecEngine(LaneEngine):
                                   "classic-control families only; the episodes mode of the Brax closed-loop rollout is "
                                   "evaluate_episodes")
 
-    _EPISODE_KEYS = VecEngine._EPISODE_KEYS  # (key, dtype, per-episode rows): the result is VecEngine.evaluate_policy's
-
-    def alloc_policy_episodes(self, n_episodes: int) -> dict:
-        """Output buffers of ``evaluate_episodes``, as ``VecEngine.alloc_policy_episodes``: ``episodes`` / ``steps`` int32
-        ``[N]``; ``return`` float32, ``length`` / ``context_id`` int32, ``terminated`` uint8, ``[n_episodes, N]`` each.
-        The launch writes every element."""
-        K = int(n_episodes)
-        if K < 1:
-            raise ValueError(f"n_episodes {K} < 1")
-        return {k: torch.empty((K, self.n) if rows else (self.n,), dtype=dt, device=self.device)
-                for k, dt, rows in self._EPISODE_KEYS}
-
     def evaluate_episodes(self, policy, n_episodes: int, max_steps: int, out: dict | None = None,
                           input_stats: bool = False) -> dict:
         """Run ``policy`` (a ``BraxMLPPolicy``, deterministic) on every env until the env has finished ``n_episodes``
@@ -549,42 +486,17 @@ class BraxVecEngine(LaneEngine):
         as ``VecEngine.evaluate_policy``'s does; with ``input_stats=False`` a reused ``out`` loses that key.  Records and
         engine state are the same bits either way."""
         self._check_policy(policy, "evaluate_episodes")
-        if not self.auto_reset:
-            raise ValueError("evaluate_episodes needs auto_reset=True: without it a finished lane reports done on every "
-                             "later step")
-        K, T = int(n_episodes), int(max_steps)
-        if K < 1:
-            raise ValueError(f"n_episodes {K} < 1")
-        if T < 0:
-            raise ValueError(f"max_steps {T} < 0")
-        if K * self.n >= 1 << 31:
-            raise ValueError(f"{K} episodes x {self.n} lanes: more than 2^31 - 1 records")
-        res = self.alloc_policy_episodes(K) if out is None else out
-        for k, dt, rows in self._EPISODE_KEYS:
-            t = res.get(k)
-            shape = (K, self.n) if rows else (self.n,)
-            if t is None or t.device != self.device or t.dtype != dt or tuple(t.shape) != shape or not t.is_contiguous():
-                raise ValueError(f"evaluate_episodes output '{k}' must be a contiguous {dt} {list(shape)} tensor on "
-                                 f"{self.device}")
+        K, T, res, eps = self._policy_episodes("evaluate_episodes", n_episodes, max_steps, out)
         self._shape_for(T)  # (as rollout_policy: the width autotune found for the open loop of this length class)
         self._flush_obs()
         params = policy.device_params(self.device)
         pol = policy.struct(self.n, params.data_ptr())
-        eps = _lib.PolicyEpisodes(*(_ptr(res[k]) for k, _, _ in self._EPISODE_KEYS))
         head = (C.byref(self.b), _ptr(self.sys_dev), C.byref(self.sys), _ptr(self.obs), C.byref(pol), K, T, C.byref(eps))
         if input_stats:
             n_slabs = int(self.lib.carl_brax_policy_stats_slabs(C.byref(self.b), C.byref(self.sys), C.byref(pol), T))
             if n_slabs < 0:
                 raise ValueError("evaluate_episodes: this batch and model have no closed-loop launch shape")
-            shape = (n_slabs, 2, _lib.POLICY_MAX_IN)
-            partial = res.get("input_partial")
-            if partial is None:
-                partial = res["input_partial"] = torch.empty(shape, dtype=torch.float64, device=self.device)
-            if (partial.device != self.device or partial.dtype != torch.float64 or not partial.is_contiguous()
-                    or tuple(partial.shape) != shape):
-                raise ValueError(f"evaluate_episodes output 'input_partial' must be a contiguous torch.float64 "
-                                 f"{list(shape)} tensor on {self.device}")
-            st = _lib.PolicyStats(_ptr(partial), n_slabs)
+            st = self._policy_input_partial("evaluate_episodes", res, n_slabs)
             with torch.cuda.device(self.device):
                 _lib.check(self.lib.carl_brax_evaluate_policy_stats(*head, C.byref(st), self._stream()))
             return res

@@ -17,6 +17,7 @@ import numpy as np
 import torch
 
 from carl_amd import _lib
+from carl_amd._tensors import is_exact, is_rows, row_layout
 
 _FAMILY_BY_NAME = {
     "cartpole": _lib.CARTPOLE, "pendulum": _lib.PENDULUM, "acrobot": _lib.ACROBOT,
@@ -538,12 +539,10 @@ class LaneEngine:
         ``{"advantage", "return"}`` ``[T, N]`` float32 (``out``: buffers of the same layout to write into).  The rule is
         SB3's ``RolloutBuffer.compute_returns_and_advantage`` with ``boot_value`` as the timeout bootstrap; a finished
         step (either flag) cuts the recurrence.  No host synchronisation."""
-        T, N = (int(v) for v in reward.shape)
-        P = int(reward.stride(0)) if T > 1 else N
+        T, N, P = row_layout(reward)
 
         def rows(name, t, dtypes):
-            if t.dtype not in dtypes or t.device != self.device or tuple(t.shape) != (T, N) or (
-                    N > 1 and t.stride(1) != 1) or (T > 1 and t.stride(0) != P):
+            if not is_rows(t, self.device, dtypes, T, N, P):
                 raise ValueError(f"gae '{name}': needs {dtypes[0]} [{T}, {N}] rows of pitch {P} on {self.device}, got "
                                  f"{t.dtype} {tuple(t.shape)} strides {tuple(t.stride())}")
             return t
@@ -555,8 +554,7 @@ class LaneEngine:
         rows("truncated", truncated, u8)
         if boot_value is not None:
             rows("boot_value", boot_value, f32)
-        if last_value.dtype != torch.float32 or last_value.device != self.device or tuple(last_value.shape) != (N,) or (
-                N > 1 and last_value.stride(0) != 1):
+        if not is_exact(last_value, self.device, torch.float32, (N,)):
             raise ValueError(f"gae 'last_value': needs a contiguous float32 [{N}] tensor on {self.device}")
         res = {} if out is None else out
         for k in ("advantage", "return"):
@@ -572,6 +570,142 @@ class LaneEngine:
             _lib.check(self.lib.carl_gae(C.byref(g), self._stream()))
         return res
 
+    # ------------------------------------------------------------------ closed loop: the front end both engines share
+    # What an engine brings to ``rollout_policy`` / ``evaluate_policy`` / ``evaluate_episodes``: its policy check, the rules
+    # only it has, its checks of the summary's dtypes and of ``"action"``, and its C calls.
+    # (key, dtype, per-episode rows) of an evaluate_policy / evaluate_episodes result
+    _EPISODE_KEYS = (("episodes", torch.int32, False), ("steps", torch.int32, False), ("return", torch.float32, True),
+                     ("length", torch.int32, True), ("context_id", torch.int32, True), ("terminated", torch.uint8, True))
+    _SUMMARY_KEYS = (("episodes", torch.int32), ("return_sum", torch.float32), ("length_sum", torch.int32))
+
+    def alloc_policy_summary(self) -> dict:
+        """Per-lane totals of a summary-mode ``rollout_policy``: ``episodes`` / ``length_sum`` int32, ``return_sum``
+        float32, ``[N]`` each."""
+        return {k: torch.zeros(self.n, dtype=dt, device=self.device) for k, dt in self._SUMMARY_KEYS}
+
+    def alloc_policy_episodes(self, n_episodes: int) -> dict:
+        """Output buffers of ``evaluate_policy`` (a Brax engine: ``evaluate_episodes``): ``episodes`` / ``steps`` int32
+        ``[N]``; ``return`` float32, ``length`` / ``context_id`` int32, ``terminated`` uint8, ``[n_episodes, N]`` each.
+        The launch writes every element."""
+        K = int(n_episodes)
+        if K < 1:
+            raise ValueError(f"n_episodes {K} < 1")
+        return {k: torch.empty((K, self.n) if rows else (self.n,), dtype=dt, device=self.device)
+                for k, dt, rows in self._EPISODE_KEYS}
+
+    def _check_value_net(self, policy, value_net) -> None:
+        """ValueError unless ``value_net`` is a critic the valued launch can run next to ``policy``: a value head, the same
+        family, inputs and set layout, and a shift | scale | clip section equal to the actor's bit for bit (the critic
+        reads the actor's transformed inputs; with equal sections the critic's packed block alone defines V)."""
+        if getattr(value_net, "head", None) != "value":
+            raise ValueError("value_net must be an MLPPolicy built with head='value'")
+        if policy.head != "policy":
+            raise ValueError("the acting policy must have head='policy'")
+        if value_net.family != policy.family or value_net.obs_dim != policy.obs_dim:
+            raise ValueError(f"value_net was built for family {value_net.family}, the policy for family {policy.family}")
+        if list(value_net.ctx_rows) != list(policy.ctx_rows):
+            raise ValueError(f"value_net reads context rows {value_net.ctx_rows}, the policy {policy.ctx_rows}: the critic "
+                             "sees the actor's inputs")
+        if value_net.n_sets != policy.n_sets or value_net.lanes_per_set != policy.lanes_per_set:
+            raise ValueError(f"value_net has {value_net.n_sets} weight sets of {value_net.lanes_per_set} lanes, the policy "
+                             f"{policy.n_sets} of {policy.lanes_per_set}: one set layout for both")
+        a, c = policy.transform_section(), value_net.transform_section()
+        if not np.array_equal(np.ascontiguousarray(a).view(np.int32), np.ascontiguousarray(c).view(np.int32)):
+            raise ValueError("value_net's input_shift / input_scale / input_clip must equal the policy's bit for bit: the "
+                             "critic reads the actor's transformed inputs")
+
+    def _policy_keywords(self, policy, mode: str, deterministic: bool, log_prob: bool, value_net, bootstrap_truncated: bool,
+                         gae) -> tuple:
+        """The keyword rules of ``rollout_policy``, either engine's -> (whether the launch stores log-probabilities,
+        ``gae`` as floats)"""
+        if mode not in ("transitions", "summary"):
+            raise ValueError(f"mode {mode!r}: 'transitions' or 'summary'")
+        if gae is not None and value_net is None:
+            raise ValueError("gae=(gamma, lam) needs value_net: advantages are computed from the critic's values")
+        if value_net is not None:
+            if mode == "summary":
+                raise ValueError("value_net: transitions mode only (mode='summary' stores nothing per step)")
+            self._check_value_net(policy, value_net)
+            if bootstrap_truncated and not self.auto_reset:
+                raise ValueError("bootstrap_truncated=True needs auto_reset=True: without it no terminal observation is "
+                                 "kept apart from the next one (pass bootstrap_truncated=False)")
+            if gae is not None:
+                gamma, lam = (float(v) for v in gae)
+                gae = (gamma, lam)
+            log_prob = log_prob or not deterministic  # (a sampled launch with a critic always stores the log-probabilities)
+        if log_prob and deterministic:
+            raise ValueError("log_prob=True: sampled launches only (deterministic=False)")
+        if log_prob and mode == "summary":
+            raise ValueError("log_prob=True: transitions mode only (a summary launch stores nothing per step)")
+        if mode == "summary" and not self.auto_reset:
+            raise ValueError("mode='summary' needs auto_reset=True: without it a finished lane reports done on every later "
+                             "step, and the totals would count its episode on each of them")
+        return log_prob, gae
+
+    def _policy_summary(self, res: dict):
+        """the ``carl_policy_summary_t`` over a checked summary dict, by reference"""
+        return C.byref(_lib.PolicySummary(*(_ptr(res[k]) for k, _ in self._SUMMARY_KEYS)))
+
+    def _policy_columns(self, out: dict, keys, T: int, dtype=torch.float32) -> None:
+        """Each of ``out[keys]`` a ``[>= T, N]`` ``dtype`` column in rows of ``out``'s pitch (``_out_pitch``: a Brax
+        engine's rows are dense) on this device: allocated where absent, ValueError otherwise (every dtype before any row
+        layout; a buffer elsewhere is told where it must be, which ``_check_rows``' message does not say)."""
+        P = self._out_pitch(out)
+        for k in keys:
+            if k not in out:
+                out[k] = torch.empty((T, P), dtype=dtype, device=self.device)[:, : self.n]
+            elif out[k].dtype != dtype:
+                raise ValueError(f"rollout_policy '{k}' buffer must be {dtype}")
+        for k in keys:
+            if out[k].device != self.device:
+                raise ValueError(f"rollout_policy '{k}' buffer must be on {self.device}")
+        self._check_rows("rollout_policy", out, keys, P, T)
+
+    def _policy_last_value(self, out: dict) -> torch.Tensor:
+        """``out["last_value"]``, float32 ``[N]``: allocated where absent, checked otherwise"""
+        if "last_value" not in out:
+            out["last_value"] = torch.empty(self.n, dtype=torch.float32, device=self.device)
+        if not is_exact(out["last_value"], self.device, torch.float32, (self.n,)):
+            raise ValueError(f"rollout_policy 'last_value' must be a contiguous float32 [{self.n}] tensor on {self.device}")
+        return out["last_value"]
+
+    def _policy_gae(self, out: dict, T: int, gae: tuple, bootstrap_truncated: bool) -> None:
+        """``out["advantage"]`` / ``out["return"]`` from one ``gae`` launch of a valued launch's own columns"""
+        res = self.gae(out["reward"][:T], out["value"][:T], out["terminated"][:T], out["truncated"][:T], out["last_value"],
+                       *gae, boot_value=out["boot_value"][:T] if bootstrap_truncated else None,
+                       out={k: out[k] for k in ("advantage", "return") if k in out} or None)
+        out["advantage"], out["return"] = res["advantage"], res["return"]
+
+    def _policy_episodes(self, who: str, n_episodes: int, max_steps: int, out: dict | None) -> tuple:
+        """The checks ``evaluate_policy`` and ``evaluate_episodes`` (``who``) share -> (K, T, the result dict, its
+        ``carl_policy_episodes_t``)"""
+        if not self.auto_reset:
+            raise ValueError(f"{who} needs auto_reset=True: without it a finished lane reports done on every later step")
+        K, T = int(n_episodes), int(max_steps)
+        if K < 1:
+            raise ValueError(f"n_episodes {K} < 1")
+        if T < 0:
+            raise ValueError(f"max_steps {T} < 0")
+        if K * self.n >= 1 << 31:
+            raise ValueError(f"{K} episodes x {self.n} lanes: more than 2^31 - 1 records")
+        res = self.alloc_policy_episodes(K) if out is None else out
+        for k, dt, rows in self._EPISODE_KEYS:
+            shape = (K, self.n) if rows else (self.n,)
+            if not is_exact(res.get(k), self.device, dt, shape):
+                raise ValueError(f"{who} output '{k}' must be a contiguous {dt} {list(shape)} tensor on {self.device}")
+        return K, T, res, _lib.PolicyEpisodes(*(_ptr(res[k]) for k, _, _ in self._EPISODE_KEYS))
+
+    def _policy_input_partial(self, who: str, res: dict, n_slabs: int) -> "_lib.PolicyStats":
+        """``res["input_partial"]``, float64 ``[n_slabs, 2, 32]``: allocated where absent, checked otherwise -> the
+        ``carl_policy_stats_t`` over it"""
+        shape = (n_slabs, 2, _lib.POLICY_MAX_IN)
+        if res.get("input_partial") is None:
+            res["input_partial"] = torch.empty(shape, dtype=torch.float64, device=self.device)
+        if not is_exact(res["input_partial"], self.device, torch.float64, shape):
+            raise ValueError(f"{who} output 'input_partial' must be a contiguous torch.float64 {list(shape)} tensor on "
+                             f"{self.device}")
+        return _lib.PolicyStats(_ptr(res["input_partial"]), n_slabs)
+
     # ------------------------------------------------------------------ the PPO update (carl_amd/ppo.py)
     # One set of argument checks for both engines.  What an engine brings: its C entry points (``_c_context_trace``,
     # ``_c_ppo_workspace_floats``, ``_c_ppo_grad``), its policy check (``_ppo_check_policy``), the trailing shape of its
@@ -585,21 +719,18 @@ class LaneEngine:
         ``truncated`` rows (``alloc_rollout``-style views or dense; uint8 or bool).  The selector's walk is replayed with
         this engine's selector, stride, seed, lane offset and auto-reset setting, so those must be what the launch ran
         under.  ``out``: an int32 buffer of the flags' row layout to write into.  One launch, no host synchronisation."""
-        T, N = (int(v) for v in terminated.shape)
-        P = int(terminated.stride(0)) if T > 1 else N
+        T, N, P = row_layout(terminated)
         if N != self.n or P < N:
             raise ValueError(f"context_trace: flag rows of {N} lanes (pitch {P}) for an engine of {self.n}")
         for name, t in (("terminated", terminated), ("truncated", truncated)):
-            if t.dtype not in (torch.uint8, torch.bool) or t.device != self.device or tuple(t.shape) != (T, N) or (
-                    N > 1 and t.stride(1) != 1) or (T > 1 and t.stride(0) != P):
+            if not is_rows(t, self.device, (torch.uint8, torch.bool), T, N, P):
                 raise ValueError(f"context_trace '{name}': needs uint8 [{T}, {N}] rows of pitch {P} on {self.device}")
         for name, t in (("ctx_idx0", ctx_idx0), ("episode0", episode0)):
-            if t.dtype != torch.int32 or t.device != self.device or tuple(t.shape) != (N,) or not t.is_contiguous():
+            if not is_exact(t, self.device, torch.int32, (N,)):
                 raise ValueError(f"context_trace '{name}': needs a contiguous int32 [{N}] tensor on {self.device}")
         if out is None:
             out = torch.empty((T, P), dtype=torch.int32, device=self.device)[:, :N]
-        elif out.dtype != torch.int32 or out.device != self.device or tuple(out.shape) != (T, N) or (
-                N > 1 and out.stride(1) != 1) or (T > 1 and out.stride(0) != P):
+        elif not is_rows(out, self.device, (torch.int32,), T, N, P):
             raise ValueError(f"context_trace 'out': needs int32 [{T}, {N}] rows of pitch {P} on {self.device}")
         with torch.cuda.device(self.device):
             _lib.check(self._c_context_trace(_ptr(ctx_idx0), _ptr(episode0), _ptr(terminated), _ptr(truncated), T,
@@ -611,18 +742,17 @@ class LaneEngine:
         rows' pitch)."""
         act = buf["action"]
         tail = self._ppo_action_tail()
+        f32, i32 = torch.float32, torch.int32
+        adt = i32 if self.info.action_is_discrete else f32
         if tail:  # [T, N, n_act]: dense rows
             if act.dim() != 3 or tuple(act.shape[2:]) != tail or not act.is_contiguous():
                 raise ValueError(f"{who} 'action': needs a contiguous float32 [T, {self.n}, {tail[0]}] tensor on {self.device}")
             T, N = int(act.shape[0]), int(act.shape[1])
             P = N
         else:
-            T, N = (int(v) for v in act.shape)
-            P = int(act.stride(0)) if T > 1 else N
+            T, N, P = row_layout(act)
         if N != self.n:
             raise ValueError(f"{who}: a buffer of {N} lanes for an engine of {self.n}")
-        f32, i32 = torch.float32, torch.int32
-        adt = i32 if self.info.action_is_discrete else f32
         cols = {"action": (act, adt), "log_prob": (buf["log_prob"], f32), "advantage": (buf["advantage"], f32),
                 "return": (buf["return"], f32), "context_id": (context_id, i32)}
         if tail:  # (its shape is checked above)
@@ -630,27 +760,30 @@ class LaneEngine:
                 raise ValueError(f"{who} 'action': needs a contiguous float32 [T, {self.n}, {tail[0]}] tensor on {self.device}")
             del cols["action"]
         for k, (t, dt) in cols.items():
-            if t.dtype != dt or t.device != self.device or t.shape[0] < T or tuple(t.shape[1:]) != (N,) or (
-                    N > 1 and t.stride(1) != 1) or (T > 1 and t.stride(0) != P):
+            if not is_rows(t, self.device, (dt,), T, N, P, at_least=True):
                 raise ValueError(f"{who} '{k}': needs {dt} [{T}, {N}] rows of pitch {P} on {self.device}")
-        obs = buf["obs"]
-        if obs.dtype != f32 or obs.device != self.device or obs.shape[0] < T or tuple(obs.shape[1:]) != (N, self.D) or any(
-                sz > 1 and st != w for sz, st, w in zip(obs.shape, obs.stride(), (P * self.D, self.D, 1))):
-            raise ValueError(f"{who} 'obs': needs float32 [{T}, {N}, {self.D}] rows of pitch {P} on {self.device}")
-        if obs0.dtype != f32 or obs0.device != self.device or tuple(obs0.shape) != (N, self.D) or not obs0.is_contiguous():
-            raise ValueError(f"{who} 'obs0': needs a contiguous float32 [{N}, {self.D}] tensor on {self.device}")
+        self._ppo_observations(who, buf["obs"], obs0, T, N, P)
         return T, N, P
 
-    def _ppo_batch(self, T: int, N: int, P: int, buf: dict, obs0: torch.Tensor, context_id: torch.Tensor) -> "_lib.PpoBatch":
+    def _ppo_observations(self, who: str, obs: torch.Tensor, obs0: torch.Tensor, T: int, N: int, P: int) -> None:
+        """The checks of a buffer's ``obs`` (``[>= T, N, D]`` rows of pitch ``P``) and of ``obs0``"""
+        if not is_rows(obs, self.device, (torch.float32,), T, N, P, (self.D,), at_least=True):
+            raise ValueError(f"{who} 'obs': needs float32 [{T}, {N}, {self.D}] rows of pitch {P} on {self.device}")
+        if not is_exact(obs0, self.device, torch.float32, (N, self.D)):
+            raise ValueError(f"{who} 'obs0': needs a contiguous float32 [{N}, {self.D}] tensor on {self.device}")
+
+    def _ppo_batch(self, T: int, N: int, P: int, buf: dict, obs0: torch.Tensor, context_id: torch.Tensor,
+                   columns: bool = True) -> "_lib.PpoBatch":
         """The ``carl_ppo_batch_t`` of a buffer ``_ppo_buffer`` has checked, with everything but ``n_samples``, the
-        coefficients, ``idx`` and ``adv_norm``."""
-        act, obs = buf["action"], buf["obs"]
+        coefficients, ``idx`` and ``adv_norm``.  ``columns=False`` (``ppo_input_stats``, which checks and reads the
+        observations alone): the action's dtype and the four per-step columns stay zero / NULL."""
         pb = _lib.PpoBatch()
         pb.family, pb.n_lanes, pb.n_steps, pb.row_pitch, pb.obs_dim = self.family, N, T, (P if P != N else 0), self.D
         pb.n_contexts, pb.ctx_stride = int(self.b.n_contexts), int(self.b.ctx_stride)
-        pb.action_dtype = _lib.ACTION_I32 if self.info.action_is_discrete else _lib.ACTION_F32
-        pb.obs0, pb.obs, pb.context_id, pb.ctx_table = _ptr(obs0), _ptr(obs), _ptr(context_id), _ptr(self.ctx_table)
-        pb.action, pb.log_prob, pb.advantage, pb.ret = _ptr(act), _ptr(buf["log_prob"]), _ptr(buf["advantage"]), _ptr(buf["return"])
+        pb.obs0, pb.obs, pb.context_id, pb.ctx_table = _ptr(obs0), _ptr(buf["obs"]), _ptr(context_id), _ptr(self.ctx_table)
+        if columns:
+            pb.action_dtype = _lib.ACTION_I32 if self.info.action_is_discrete else _lib.ACTION_F32
+            pb.action, pb.log_prob, pb.advantage, pb.ret = (_ptr(buf[k]) for k in ("action", "log_prob", "advantage", "return"))
         return pb
 
     def ppo_workspace(self, policy, value_net, n_samples: int) -> torch.Tensor:
@@ -677,11 +810,10 @@ class LaneEngine:
         (host-built or ``on_device``).  No host synchronisation."""
         self._ppo_check_policy(policy)
         T, N, P = self._ppo_buffer("ppo_grad", buf, obs0, context_id)
-        f32, i32 = torch.float32, torch.int32
-        if idx is not None and (idx.dtype != i32 or idx.device != self.device or idx.dim() != 1 or not idx.is_contiguous()):
+        f32 = torch.float32
+        if idx is not None and not is_exact(idx, self.device, torch.int32, (None,)):
             raise ValueError(f"ppo_grad 'idx': needs a contiguous int32 [M] tensor on {self.device}")
-        if adv_norm is not None and (adv_norm.dtype != f32 or adv_norm.device != self.device or adv_norm.numel() != 2
-                                     or not adv_norm.is_contiguous()):
+        if adv_norm is not None and not is_exact(adv_norm, self.device, f32, 2):
             raise ValueError(f"ppo_grad 'adv_norm': needs a contiguous float32 [2] tensor on {self.device}")
         M = T * N if idx is None else int(idx.numel())
         res = {} if out is None else out
@@ -695,8 +827,7 @@ class LaneEngine:
         for k, size in want.items():
             if k not in res:
                 res[k] = torch.empty(size, dtype=f32, device=self.device)
-            t = res[k]
-            if t.dtype != f32 or t.device != self.device or t.numel() != size or not t.is_contiguous():
+            if not is_exact(res[k], self.device, f32, size):
                 raise ValueError(f"ppo_grad output '{k}': needs a contiguous float32 [{size}] tensor on {self.device}")
         pol = policy.struct(self.n, policy.device_params(self.device).data_ptr())
         crit = value_net.struct(self.n, value_net.device_params(self.device).data_ptr())
@@ -724,43 +855,34 @@ class LaneEngine:
         policy=policy)`` merges (``out``: such a dict to write into).  ``policy``: the one-set policy the collection ran
         (its shift centres the sums).  No host synchronisation."""
         self._ppo_check_policy(policy)
-        f32, i32 = torch.float32, torch.int32
+        i32 = torch.int32
         if context_id.dim() != 2:
             raise ValueError(f"ppo_input_stats 'context_id': needs int32 [T, {self.n}] rows on {self.device}")
-        T, N = (int(v) for v in context_id.shape)
-        P = N if self._ppo_action_tail() or T == 1 else int(context_id.stride(0))
+        T, N, P = row_layout(context_id)
+        if self._ppo_action_tail():
+            P = N
         if N != self.n or T < 1:
             raise ValueError(f"ppo_input_stats: a buffer of {T} steps x {N} lanes for an engine of {self.n}")
-        if context_id.dtype != i32 or context_id.device != self.device or (N > 1 and context_id.stride(1) != 1) or (
-                T > 1 and context_id.stride(0) != P) or P < N:
+        if not is_rows(context_id, self.device, (i32,), T, N, P) or P < N:
             raise ValueError(f"ppo_input_stats 'context_id': needs int32 [{T}, {N}] rows of pitch {P} on {self.device}")
-        obs = buf["obs"]
-        if obs.dtype != f32 or obs.device != self.device or obs.shape[0] < T or tuple(obs.shape[1:]) != (N, self.D) or any(
-                sz > 1 and st != w for sz, st, w in zip(obs.shape, obs.stride(), (P * self.D, self.D, 1))):
-            raise ValueError(f"ppo_input_stats 'obs': needs float32 [{T}, {N}, {self.D}] rows of pitch {P} on {self.device}")
-        if obs0.dtype != f32 or obs0.device != self.device or tuple(obs0.shape) != (N, self.D) or not obs0.is_contiguous():
-            raise ValueError(f"ppo_input_stats 'obs0': needs a contiguous float32 [{N}, {self.D}] tensor on {self.device}")
+        self._ppo_observations("ppo_input_stats", buf["obs"], obs0, T, N, P)
         slabs = int(self.lib.carl_ppo_input_stats_slabs(N, T))
         res = {} if out is None else out
         if "input_partial" not in res:
             res["input_partial"] = torch.empty((slabs, 2, _lib.POLICY_MAX_IN), dtype=torch.float64, device=self.device)
         if "steps" not in res:
             res["steps"] = torch.full((N,), T, dtype=i32, device=self.device)
-        part, steps = res["input_partial"], res["steps"]
-        if (part.dtype != torch.float64 or part.device != self.device or part.dim() != 3 or part.shape[0] < slabs
-                or tuple(part.shape[1:]) != (2, _lib.POLICY_MAX_IN) or not part.is_contiguous()):
+        part = res["input_partial"]
+        if not is_exact(part, self.device, torch.float64, (None, 2, _lib.POLICY_MAX_IN)) or part.shape[0] < slabs:
             raise ValueError(f"ppo_input_stats 'input_partial': needs a contiguous float64 [>= {slabs}, 2, "
                              f"{_lib.POLICY_MAX_IN}] tensor on {self.device}")
-        if steps.dtype != i32 or steps.device != self.device or tuple(steps.shape) != (N,) or not steps.is_contiguous():
+        if not is_exact(res["steps"], self.device, i32, (N,)):
             raise ValueError(f"ppo_input_stats 'steps': needs a contiguous int32 [{N}] tensor on {self.device} (filled with T)")
         if part.shape[0] != slabs:
             res["input_partial"] = part = part[:slabs]  # (the merge adds every slab of the tensor it is given)
         pol = policy.struct(self.n, policy.device_params(self.device).data_ptr())
-        pb = _lib.PpoBatch()
-        pb.family, pb.n_lanes, pb.n_steps, pb.row_pitch, pb.obs_dim = self.family, N, T, (P if P != N else 0), self.D
-        pb.n_contexts, pb.ctx_stride = int(self.b.n_contexts), int(self.b.ctx_stride)
+        pb = self._ppo_batch(T, N, P, buf, obs0, context_id, columns=False)
         pb.n_samples = T * N
-        pb.obs0, pb.obs, pb.context_id, pb.ctx_table = _ptr(obs0), _ptr(obs), _ptr(context_id), _ptr(self.ctx_table)
         st = _lib.PolicyStats(part.data_ptr(), slabs)
         with torch.cuda.device(self.device):
             _lib.check(self._c_ppo_input_stats(C.byref(pb), C.byref(pol), C.byref(st)))
@@ -773,32 +895,28 @@ class LaneEngine:
         finished step: VecNormalize's order) and written back.  Returns ``{"return_partial" [slabs, 2] float64}`` -- each
         workgroup's sums of the returns and of their squares -- and, with ``ret_rows=True``, ``"ret_rows"`` ``[T, N]``:
         the return after each step's reward (rows of the reward's pitch).  No host synchronisation."""
-        T, N = (int(v) for v in reward.shape)
-        P = int(reward.stride(0)) if T > 1 else N
+        T, N, P = row_layout(reward)
         if N != self.n or P < N or T < 1:
             raise ValueError(f"ppo_return_stats: reward rows of {T} steps x {N} lanes (pitch {P}) for an engine of {self.n}")
         for name, t, dts in (("reward", reward, (torch.float32,)), ("terminated", terminated, (torch.uint8, torch.bool)),
                              ("truncated", truncated, (torch.uint8, torch.bool))):
-            if t.dtype not in dts or t.device != self.device or tuple(t.shape) != (T, N) or (
-                    N > 1 and t.stride(1) != 1) or (T > 1 and t.stride(0) != P):
+            if not is_rows(t, self.device, dts, T, N, P):
                 raise ValueError(f"ppo_return_stats '{name}': needs {dts[0]} [{T}, {N}] rows of pitch {P} on {self.device}")
-        if ret.dtype != torch.float32 or ret.device != self.device or tuple(ret.shape) != (N,) or not ret.is_contiguous():
+        if not is_exact(ret, self.device, torch.float32, (N,)):
             raise ValueError(f"ppo_return_stats 'ret': needs a contiguous float32 [{N}] tensor on {self.device}")
         slabs = int(self.lib.carl_ppo_return_stats_slabs(N))
         res = {} if out is None else out
         if "return_partial" not in res:
             res["return_partial"] = torch.empty((slabs, 2), dtype=torch.float64, device=self.device)
         part = res["return_partial"]
-        if (part.dtype != torch.float64 or part.device != self.device or tuple(part.shape) != (slabs, 2)
-                or not part.is_contiguous()):
+        if not is_exact(part, self.device, torch.float64, (slabs, 2)):
             raise ValueError(f"ppo_return_stats 'return_partial': needs a contiguous float64 [{slabs}, 2] tensor on {self.device}")
         rows = None
         if ret_rows:
             if "ret_rows" not in res:
                 res["ret_rows"] = torch.empty((T, P), dtype=torch.float32, device=self.device)[:, :N]
             rows = res["ret_rows"]
-            if rows.dtype != torch.float32 or rows.device != self.device or tuple(rows.shape) != (T, N) or (
-                    N > 1 and rows.stride(1) != 1) or (T > 1 and rows.stride(0) != P):
+            if not is_rows(rows, self.device, (torch.float32,), T, N, P):
                 raise ValueError(f"ppo_return_stats 'ret_rows': needs float32 [{T}, {N}] rows of pitch {P} on {self.device}")
         rs = _lib.PpoReturnStats()
         rs.n_lanes, rs.n_steps, rs.row_pitch, rs.gamma = N, T, (P if P != N else 0), float(gamma)
@@ -814,16 +932,14 @@ class LaneEngine:
         float64 [1], "m2" float64 [1]}`` (device tensors, all zero before the first merge) by Chan's rule and write
         ``1 / sqrt(m2 / count + eps)`` to ``scale`` (a float32 ``[1]`` device tensor, allocated when None), which is
         returned (include/carl_amd.h: carl_ppo_return_merge).  No host synchronisation."""
-        if (partial.dtype != torch.float64 or partial.device != self.device or partial.dim() != 2 or partial.shape[1] != 2
-                or not partial.is_contiguous()):
+        if not is_exact(partial, self.device, torch.float64, (None, 2)):
             raise ValueError(f"ppo_return_merge 'partial': needs a contiguous float64 [slabs, 2] tensor on {self.device}")
         for k, dt in (("count", torch.int64), ("mean", torch.float64), ("m2", torch.float64)):
-            t = running[k]
-            if t.dtype != dt or t.device != self.device or t.numel() != 1:
+            if not is_exact(running[k], self.device, dt, 1):
                 raise ValueError(f"ppo_return_merge running['{k}']: needs a {dt} [1] tensor on {self.device}")
         if scale is None:
             scale = torch.empty(1, dtype=torch.float32, device=self.device)
-        if scale.dtype != torch.float32 or scale.device != self.device or scale.numel() != 1:
+        if not is_exact(scale, self.device, torch.float32, 1):
             raise ValueError(f"ppo_return_merge 'scale': needs a float32 [1] tensor on {self.device}")
         run = _lib.PolicyRunningStats(_ptr(running["count"]), _ptr(running["mean"]), _ptr(running["m2"]))
         with torch.cuda.device(self.device):
@@ -832,6 +948,19 @@ class LaneEngine:
         return scale
 
     # ------------------------------------------------------------------ PPO's minibatch step (carl_amd/ppo.py: fused_step)
+    def _advantage_storage(self, who: str, advantage: torch.Tensor) -> int:
+        """The elements an ``advantage`` argument spans from its first: float32 ``[T, N]`` rows of any one pitch, or a
+        contiguous 1-D storage (``ppo_adv_stats``, ``ppo_adv_stats_sets``: messages begin with ``who``)"""
+        if (advantage.dtype != torch.float32 or advantage.device != self.device or advantage.dim() not in (1, 2)
+                or advantage.numel() < 1 or (advantage.dim() == 1 and not advantage.is_contiguous())):
+            raise ValueError(f"{who} 'advantage': needs float32 [T, N] rows or a contiguous float32 [n] tensor on {self.device}")
+        if advantage.dim() == 1:
+            return int(advantage.numel())
+        T, N, P = row_layout(advantage)
+        if (N > 1 and advantage.stride(1) != 1) or P < N:
+            raise ValueError(f"{who} 'advantage': needs float32 [{T}, {N}] rows of one pitch on {self.device}")
+        return (T - 1) * P + N
+
     def ppo_adv_stats(self, advantage: torch.Tensor, idx: torch.Tensor, batch_size: int, eps: float = 1e-8,
                       out: torch.Tensor | None = None) -> torch.Tensor:
         """The advantage mean and ``1 / (std + eps)`` of every minibatch of an epoch in one launch (include/carl_amd.h:
@@ -839,20 +968,9 @@ class LaneEngine:
         1-D float32 storage; ``idx``: int32 ``[n_total]`` flat indices into it, the epoch's minibatches of ``batch_size``
         samples in order (the last may be shorter).  Returns float32 ``[ceil(n_total / batch_size), 2]``: row ``k`` is
         ``ppo_grad``'s ``adv_norm`` for minibatch ``k`` (``out``: such a tensor to write into).  No host synchronisation."""
-        f32, i32 = torch.float32, torch.int32
-        if advantage.dtype != f32 or advantage.device != self.device or advantage.dim() not in (1, 2) or advantage.numel() < 1:
-            raise ValueError(f"ppo_adv_stats 'advantage': needs float32 [T, N] rows or a contiguous float32 [n] tensor on {self.device}")
-        if advantage.dim() == 1:
-            if not advantage.is_contiguous():
-                raise ValueError(f"ppo_adv_stats 'advantage': needs float32 [T, N] rows or a contiguous float32 [n] tensor on {self.device}")
-            storage = int(advantage.numel())
-        else:
-            T, N = (int(v) for v in advantage.shape)
-            P = int(advantage.stride(0)) if T > 1 else N
-            if (N > 1 and advantage.stride(1) != 1) or P < N:
-                raise ValueError(f"ppo_adv_stats 'advantage': needs float32 [{T}, {N}] rows of one pitch on {self.device}")
-            storage = (T - 1) * P + N
-        if idx.dtype != i32 or idx.device != self.device or idx.dim() != 1 or not idx.is_contiguous() or idx.numel() < 1:
+        f32 = torch.float32
+        storage = self._advantage_storage("ppo_adv_stats", advantage)
+        if not is_exact(idx, self.device, torch.int32, (None,)) or idx.numel() < 1:
             raise ValueError(f"ppo_adv_stats 'idx': needs a contiguous int32 [n_total >= 1] tensor on {self.device}")
         n_total, batch_size = int(idx.numel()), int(batch_size)
         rows = int(self.lib.carl_ppo_adv_stats_rows(n_total, batch_size))
@@ -860,7 +978,7 @@ class LaneEngine:
             raise ValueError(f"ppo_adv_stats: batch_size {batch_size} < 1")
         if out is None:
             out = torch.empty((rows, 2), dtype=f32, device=self.device)
-        if out.dtype != f32 or out.device != self.device or tuple(out.shape) != (rows, 2) or not out.is_contiguous():
+        if not is_exact(out, self.device, f32, (rows, 2)):
             raise ValueError(f"ppo_adv_stats 'out': needs a contiguous float32 [{rows}, 2] tensor on {self.device}")
         a = _lib.PpoAdvStats(_ptr(advantage), _ptr(idx), _ptr(out), storage, n_total, batch_size, float(eps))
         with torch.cuda.device(self.device):
@@ -871,16 +989,57 @@ class LaneEngine:
         """Fresh state for ``adam_step`` over ``params``: ``{"m", "v"}`` zero tensors like each parameter, ``"step"`` int64
         ``[1]`` = 0, ``"beta_pow"`` float64 ``[2]`` = (1, 1), on the device.  ``n_sets``: the state of a population for
         ``adam_step_sets`` instead -- every parameter ``[n_sets, n_i]``, ``"step"`` ``[n_sets]``, ``"beta_pow"`` ``[n_sets, 2]``."""
-        if n_sets is None:
-            return {"m": [torch.zeros_like(p) for p in params], "v": [torch.zeros_like(p) for p in params],
-                    "step": torch.zeros(1, dtype=torch.int64, device=self.device),
-                    "beta_pow": torch.ones(2, dtype=torch.float64, device=self.device)}
-        n_sets = int(n_sets)
-        if n_sets < 1 or any(p.dim() < 1 or p.shape[0] != n_sets for p in params):
-            raise ValueError(f"adam_state: n_sets {n_sets} needs every parameter as [{n_sets}, n] rows")
+        lead = ()
+        if n_sets is not None:
+            lead = (int(n_sets),)
+            if lead[0] < 1 or any(p.dim() < 1 or p.shape[0] != lead[0] for p in params):
+                raise ValueError(f"adam_state: n_sets {lead[0]} needs every parameter as [{lead[0]}, n] rows")
         return {"m": [torch.zeros_like(p) for p in params], "v": [torch.zeros_like(p) for p in params],
-                "step": torch.zeros(n_sets, dtype=torch.int64, device=self.device),
-                "beta_pow": torch.ones((n_sets, 2), dtype=torch.float64, device=self.device)}
+                "step": torch.zeros(lead or 1, dtype=torch.int64, device=self.device),
+                "beta_pow": torch.ones(lead + (2,), dtype=torch.float64, device=self.device)}
+
+    def _adam_args(self, who: str, params, grads, state: dict, norm_out, betas, eps: float, sets: bool) -> tuple:
+        """``(carl_adam_t, n_sets)`` of ``adam_step`` (tensors of any shape, ``n`` elements each; ``n_sets`` None) or, with
+        ``sets``, of ``adam_step_sets`` (``[n_sets, n]`` rows), the tensors checked; ``lr`` and ``max_grad_norm`` are
+        the caller's."""
+        f32, i64, f64, dev = torch.float32, torch.int64, torch.float64, self.device
+        k = len(params)
+        if not 1 <= k <= _lib.ADAM_MAX_TENSORS:
+            raise ValueError(f"{who}: {k} tensors, the launch takes 1 to {_lib.ADAM_MAX_TENSORS}")
+        if len(grads) != k or len(state["m"]) != k or len(state["v"]) != k:
+            raise ValueError(f"{who}: {k} parameters need {k} gradients and {k} entries of state['m'] / state['v']")
+        n_sets = None
+        if sets:
+            if params[0].dim() < 1 or params[0].shape[0] < 1:
+                raise ValueError(f"{who} params[0]: needs [P, n] rows")
+            n_sets = int(params[0].shape[0])
+        a = _lib.Adam()
+        a.n_tensors = k
+        for i in range(k):
+            if sets and (params[i].dim() < 1 or params[i].shape[0] != n_sets):
+                raise ValueError(f"{who} params[{i}]: needs [{n_sets}, n] rows, one per member")
+            n = int(params[i].numel()) // (n_sets or 1)
+            for name, t in (("params", params[i]), ("grads", grads[i]), ("state['m']", state["m"][i]),
+                            ("state['v']", state["v"][i])):
+                if not is_exact(t, dev, f32, n * (n_sets or 1)) or (sets and (t.dim() < 1 or t.shape[0] != n_sets)):
+                    raise ValueError(f"{who} {name}[{i}]: needs a contiguous float32 " + (
+                        f"[{n_sets}, {n}] tensor" if sets else f"tensor of {n} elements") + f" on {dev}")
+            a.n[i], a.param[i], a.grad[i] = n, _ptr(params[i]), _ptr(grads[i])
+            a.m[i], a.v[i] = _ptr(state["m"][i]), _ptr(state["v"][i])
+        step, bp = state["step"], state["beta_pow"]
+        if sets:
+            if not is_exact(step, dev, i64, (n_sets,)):
+                raise ValueError(f"{who} state['step']: needs a contiguous int64 [{n_sets}] tensor on {dev}")
+        elif not is_exact(step, dev, i64, 1):
+            raise ValueError(f"{who} state['step']: needs an int64 [1] tensor on {dev}")
+        pair, pair_text = ((n_sets, 2), f"[{n_sets}, 2]") if sets else (2, "[2]")
+        if not is_exact(bp, dev, f64, pair):
+            raise ValueError(f"{who} state['beta_pow']: needs a contiguous float64 {pair_text} tensor on {dev}")
+        if norm_out is not None and not is_exact(norm_out, dev, f64, pair):
+            raise ValueError(f"{who} 'norm_out': needs a contiguous float64 {pair_text} tensor on {dev}")
+        a.beta1, a.beta2, a.eps = float(betas[0]), float(betas[1]), float(eps)
+        a.step, a.beta_pow, a.norm_out = _ptr(step), _ptr(bp), _ptr(norm_out)
+        return a, n_sets
 
     def adam_step(self, params: Sequence[torch.Tensor], grads: Sequence[torch.Tensor], state: dict, lr: float,
                   betas=(0.9, 0.999), eps: float = 1e-5, max_grad_norm: float | None = None,
@@ -889,40 +1048,14 @@ class LaneEngine:
         carl_adam_step): up to 4 contiguous float32 device tensors, ``grads[i]`` with as many elements as ``params[i]``.
         ``state``: ``adam_state(params)``'s dict, advanced in place.  ``max_grad_norm=None``: no clip.  ``norm_out``: a
         float64 ``[2]`` device tensor that receives the norm before the clip and the coefficient.  No host synchronisation."""
-        f32 = torch.float32
-        k = len(params)
-        if not 1 <= k <= _lib.ADAM_MAX_TENSORS:
-            raise ValueError(f"adam_step: {k} tensors, the launch takes 1 to {_lib.ADAM_MAX_TENSORS}")
-        if len(grads) != k or len(state["m"]) != k or len(state["v"]) != k:
-            raise ValueError(f"adam_step: {k} parameters need {k} gradients and {k} entries of state['m'] / state['v']")
-        a = _lib.Adam()
-        a.n_tensors = k
-        for i in range(k):
-            n = int(params[i].numel())
-            for name, t in (("params", params[i]), ("grads", grads[i]), ("state['m']", state["m"][i]),
-                            ("state['v']", state["v"][i])):
-                if t.dtype != f32 or t.device != self.device or t.numel() != n or not t.is_contiguous():
-                    raise ValueError(f"adam_step {name}[{i}]: needs a contiguous float32 tensor of {n} elements on {self.device}")
-            a.n[i], a.param[i], a.grad[i] = n, _ptr(params[i]), _ptr(grads[i])
-            a.m[i], a.v[i] = _ptr(state["m"][i]), _ptr(state["v"][i])
-        step, bp = state["step"], state["beta_pow"]
-        if step.dtype != torch.int64 or step.device != self.device or step.numel() != 1:
-            raise ValueError(f"adam_step state['step']: needs an int64 [1] tensor on {self.device}")
-        if bp.dtype != torch.float64 or bp.device != self.device or bp.numel() != 2 or not bp.is_contiguous():
-            raise ValueError(f"adam_step state['beta_pow']: needs a contiguous float64 [2] tensor on {self.device}")
-        if norm_out is not None and (norm_out.dtype != torch.float64 or norm_out.device != self.device
-                                     or norm_out.numel() != 2 or not norm_out.is_contiguous()):
-            raise ValueError(f"adam_step 'norm_out': needs a contiguous float64 [2] tensor on {self.device}")
-        a.lr, a.beta1, a.beta2, a.eps = float(lr), float(betas[0]), float(betas[1]), float(eps)
-        a.max_grad_norm = float("inf") if max_grad_norm is None else float(max_grad_norm)
-        a.step, a.beta_pow, a.norm_out = _ptr(step), _ptr(bp), _ptr(norm_out)
+        a, _ = self._adam_args("adam_step", params, grads, state, norm_out, betas, eps, sets=False)
+        a.lr, a.max_grad_norm = float(lr), float("inf") if max_grad_norm is None else float(max_grad_norm)
         with torch.cuda.device(self.device):
             _lib.check(self.lib.carl_adam_step(C.byref(a), self._stream()))
 
     # ------------------------------------------------------------------ a population's minibatch step (carl_amd/population.py)
     def _check_hyper(self, who: str, hyper: torch.Tensor, n_sets: int) -> None:
-        if (not isinstance(hyper, torch.Tensor) or hyper.dtype != torch.float64 or hyper.device != self.device
-                or tuple(hyper.shape) != (n_sets, _lib.PPO_HYPER) or not hyper.is_contiguous()):
+        if not is_exact(hyper, self.device, torch.float64, (n_sets, _lib.PPO_HYPER)):
             raise ValueError(f"{who} 'hyper': needs a contiguous float64 [{n_sets}, {_lib.PPO_HYPER}] tensor on {self.device} "
                              f"(columns {', '.join(_lib.PPO_HYPER_NAMES)})")
 
@@ -934,18 +1067,7 @@ class LaneEngine:
         (the last may be shorter).  Returns float32 ``[P, ceil(n_total / batch_size), 2]``: row ``(s, k)`` is bit-equal to
         ``ppo_adv_stats`` on row ``s`` (``out``: such a tensor to write into).  No host synchronisation."""
         f32, i32 = torch.float32, torch.int32
-        if advantage.dtype != f32 or advantage.device != self.device or advantage.dim() not in (1, 2) or advantage.numel() < 1:
-            raise ValueError(f"ppo_adv_stats_sets 'advantage': needs float32 [T, N] rows or a contiguous float32 [n] tensor on {self.device}")
-        if advantage.dim() == 1:
-            if not advantage.is_contiguous():
-                raise ValueError(f"ppo_adv_stats_sets 'advantage': needs float32 [T, N] rows or a contiguous float32 [n] tensor on {self.device}")
-            storage = int(advantage.numel())
-        else:
-            T, N = (int(v) for v in advantage.shape)
-            P = int(advantage.stride(0)) if T > 1 else N
-            if (N > 1 and advantage.stride(1) != 1) or P < N:
-                raise ValueError(f"ppo_adv_stats_sets 'advantage': needs float32 [{T}, {N}] rows of one pitch on {self.device}")
-            storage = (T - 1) * P + N
+        storage = self._advantage_storage("ppo_adv_stats_sets", advantage)
         if (idx.dtype != i32 or idx.device != self.device or idx.dim() != 2 or idx.shape[0] < 1 or idx.shape[1] < 1
                 or (idx.shape[1] > 1 and idx.stride(1) != 1) or (idx.shape[0] > 1 and idx.stride(0) < idx.shape[1])):
             raise ValueError(f"ppo_adv_stats_sets 'idx': needs int32 [P >= 1, n_total >= 1] rows of unit stride on {self.device}")
@@ -956,7 +1078,7 @@ class LaneEngine:
             raise ValueError(f"ppo_adv_stats_sets: batch_size {batch_size} < 1")
         if out is None:
             out = torch.empty((n_sets, rows, 2), dtype=f32, device=self.device)
-        if out.dtype != f32 or out.device != self.device or tuple(out.shape) != (n_sets, rows, 2) or not out.is_contiguous():
+        if not is_exact(out, self.device, f32, (n_sets, rows, 2)):
             raise ValueError(f"ppo_adv_stats_sets 'out': needs a contiguous float32 [{n_sets}, {rows}, 2] tensor on {self.device}")
         a = _lib.PpoAdvStats(_ptr(advantage), _ptr(idx), _ptr(out), storage, n_total, batch_size, float(eps))
         with torch.cuda.device(self.device):
@@ -971,40 +1093,9 @@ class LaneEngine:
         tensor; member ``s`` steps with its ``lr`` and clips by its ``max_grad_norm`` (``+inf``: no clip) -- values the host
         cannot see: finite and ``>= 0`` is the caller's to guarantee.  ``norm_out``: a float64 ``[P, 2]`` device tensor.
         Member ``s`` is bit-equal to ``adam_step`` on its rows.  No host synchronisation."""
-        f32 = torch.float32
-        k = len(params)
-        if not 1 <= k <= _lib.ADAM_MAX_TENSORS:
-            raise ValueError(f"adam_step_sets: {k} tensors, the launch takes 1 to {_lib.ADAM_MAX_TENSORS}")
-        if len(grads) != k or len(state["m"]) != k or len(state["v"]) != k:
-            raise ValueError(f"adam_step_sets: {k} parameters need {k} gradients and {k} entries of state['m'] / state['v']")
-        if params[0].dim() < 1 or params[0].shape[0] < 1:
-            raise ValueError("adam_step_sets params[0]: needs [P, n] rows")
-        n_sets = int(params[0].shape[0])
-        a = _lib.Adam()
-        a.n_tensors = k
-        for i in range(k):
-            shape = tuple(params[i].shape)
-            if len(shape) < 1 or shape[0] != n_sets:
-                raise ValueError(f"adam_step_sets params[{i}]: needs [{n_sets}, n] rows, one per member")
-            n = int(params[i].numel()) // n_sets
-            for name, t in (("params", params[i]), ("grads", grads[i]), ("state['m']", state["m"][i]),
-                            ("state['v']", state["v"][i])):
-                if t.dtype != f32 or t.device != self.device or t.numel() != n * n_sets or not t.is_contiguous() or (
-                        t.dim() < 1 or t.shape[0] != n_sets):
-                    raise ValueError(f"adam_step_sets {name}[{i}]: needs a contiguous float32 [{n_sets}, {n}] tensor on {self.device}")
-            a.n[i], a.param[i], a.grad[i] = n, _ptr(params[i]), _ptr(grads[i])
-            a.m[i], a.v[i] = _ptr(state["m"][i]), _ptr(state["v"][i])
-        step, bp = state["step"], state["beta_pow"]
-        if step.dtype != torch.int64 or step.device != self.device or tuple(step.shape) != (n_sets,) or not step.is_contiguous():
-            raise ValueError(f"adam_step_sets state['step']: needs a contiguous int64 [{n_sets}] tensor on {self.device}")
-        if bp.dtype != torch.float64 or bp.device != self.device or tuple(bp.shape) != (n_sets, 2) or not bp.is_contiguous():
-            raise ValueError(f"adam_step_sets state['beta_pow']: needs a contiguous float64 [{n_sets}, 2] tensor on {self.device}")
-        if norm_out is not None and (norm_out.dtype != torch.float64 or norm_out.device != self.device
-                                     or tuple(norm_out.shape) != (n_sets, 2) or not norm_out.is_contiguous()):
-            raise ValueError(f"adam_step_sets 'norm_out': needs a contiguous float64 [{n_sets}, 2] tensor on {self.device}")
+        a, n_sets = self._adam_args("adam_step_sets", params, grads, state, norm_out, betas, eps, sets=True)
         self._check_hyper("adam_step_sets", hyper, n_sets)
-        a.lr, a.beta1, a.beta2, a.eps, a.max_grad_norm = 0.0, float(betas[0]), float(betas[1]), float(eps), float("inf")
-        a.step, a.beta_pow, a.norm_out = _ptr(step), _ptr(bp), _ptr(norm_out)
+        a.lr, a.max_grad_norm = 0.0, float("inf")
         with torch.cuda.device(self.device):
             _lib.check(self.lib.carl_adam_step_sets(C.byref(a), n_sets, _ptr(hyper), self._stream()))
 
@@ -1165,12 +1256,6 @@ class VecEngine(LaneEngine):
         return buf
 
     # ------------------------------------------------------------------ closed loop (carl_amd/policy.py)
-    def alloc_policy_summary(self) -> dict:
-        """Per-lane totals of a summary-mode ``rollout_policy``: ``episodes`` / ``length_sum`` int32, ``return_sum``
-        float32, ``[N]`` each."""
-        z = lambda dt: torch.zeros(self.n, dtype=dt, device=self.device)  # noqa: E731
-        return {"episodes": z(torch.int32), "return_sum": z(torch.float32), "length_sum": z(torch.int32)}
-
     def _sampling(self, policy, deterministic: bool, sample_seed: int, log_prob: torch.Tensor | None = None):
         """the ``carl_policy_sampling_t`` of a sampled launch (include/carl_amd.h), None for a deterministic one"""
         if deterministic:
@@ -1264,8 +1349,7 @@ class VecEngine(LaneEngine):
         for k, shape in want.items():
             if k not in res:
                 res[k] = torch.empty(shape, dtype=f32, device=self.device)
-            t = res[k]
-            if t.dtype != f32 or t.device != self.device or tuple(t.shape) != shape or not t.is_contiguous():
+            if not is_exact(res[k], self.device, f32, shape):
                 raise ValueError(f"ppo_grad_sets output '{k}': needs a contiguous float32 {list(shape)} tensor on {self.device}")
         pol = policy.struct(self.n, policy.device_params(self.device).data_ptr())
         crit = value_net.struct(self.n, value_net.device_params(self.device).data_ptr())
@@ -1286,17 +1370,6 @@ class VecEngine(LaneEngine):
         """One closed-loop C call ``fn(batch, *args, stream)`` on the current stream, its error code raised."""
         with torch.cuda.device(self.device):
             _lib.check(fn(self._b_ref, *args, self._stream()))
-
-    def _policy_columns(self, out: dict, keys, T: int, dtype=torch.float32) -> None:
-        """Each of ``out[keys]`` a ``[>= T, N]`` ``dtype`` column in rows of ``out``'s pitch on this device: allocated
-        where absent, ValueError otherwise (every dtype before any row layout)."""
-        P = self._out_pitch(out)
-        for k in keys:
-            if k not in out:
-                out[k] = torch.empty((T, P), dtype=dtype, device=self.device)[:, : self.n]
-            elif out[k].dtype != dtype:
-                raise ValueError(f"rollout_policy '{k}' buffer must be {dtype}")
-        self._check_rows("rollout_policy", out, keys, P, T, self.device)
 
     def rollout_policy(self, policy, n_steps: int, out: dict | None = None, mode: str = "transitions",
                        final_obs: bool = False, deterministic: bool = True, sample_seed: int = 0,
@@ -1325,25 +1398,14 @@ class VecEngine(LaneEngine):
         ``gae=(gamma, lam)`` adds ``"advantage"`` and ``"return"`` ``[T, N]`` from one ``carl_gae`` launch on the same
         stream (``VecEngine.gae`` of the launch's own columns)."""
         _check_policy_family(self, policy)
-        if gae is not None and value_net is None:
-            raise ValueError("gae=(gamma, lam) needs value_net: advantages are computed from the critic's values")
-        if value_net is not None:
-            if mode == "summary":
-                raise ValueError("value_net: transitions mode only (mode='summary' stores nothing per step)")
-            self._check_value_net(policy, value_net)
-            if bootstrap_truncated and not self.auto_reset:
-                raise ValueError("bootstrap_truncated=True needs auto_reset=True: without it no terminal observation is "
-                                 "kept apart from the next one (pass bootstrap_truncated=False)")
-            if gae is not None:
-                gamma, lam = (float(v) for v in gae)
-        if mode == "summary" and not self.auto_reset:
-            raise ValueError("mode='summary' needs auto_reset=True: without it a finished lane reports done on every later "
-                             "step, and the totals would count its episode on each of them")
+        if final_obs and mode == "summary":
+            raise ValueError("final_obs: transitions mode only (a summary launch stores nothing per step)")
+        # (named by its class: test_policy_sampling.py drives this method on a stand-in ``self`` without the helpers)
+        log_prob, gae = LaneEngine._policy_keywords(self, policy, mode, deterministic, log_prob, value_net,
+                                                    bootstrap_truncated, gae)
         T = int(n_steps)
         params = policy.device_params(self.device)
         pol = policy.struct(self.n, params.data_ptr())
-        if log_prob and deterministic:
-            raise ValueError("log_prob=True: sampled launches only (deterministic=False)")
 
         def launch(smp, io, summ):  # the deterministic entry point or its sampled twin
             if smp is None:
@@ -1352,25 +1414,16 @@ class VecEngine(LaneEngine):
                 self._policy_call(self.lib.carl_rollout_policy_sampled, C.byref(pol), C.byref(smp), io, T, summ)
 
         if mode == "summary":
-            if final_obs:
-                raise ValueError("final_obs: transitions mode only (a summary launch stores nothing per step)")
-            if log_prob:
-                raise ValueError("log_prob=True: transitions mode only (a summary launch stores nothing per step)")
             res = self.alloc_policy_summary() if out is None else out
-            for k in ("episodes", "return_sum", "length_sum"):
+            for k, _ in self._SUMMARY_KEYS:  # (any 4-byte element type is taken here; the Brax engine wants the exact ones)
                 t = res[k]
                 if t.device != self.device or not t.is_contiguous() or t.numel() != self.n or t.element_size() != 4:
                     raise ValueError(f"summary output '{k}' must be a contiguous 4-byte [{self.n}] tensor on {self.device}")
-            summ = _lib.PolicySummary(_ptr(res["episodes"]), _ptr(res["return_sum"]), _ptr(res["length_sum"]))
-            launch(self._sampling(policy, deterministic, sample_seed), None, C.byref(summ))
+            launch(self._sampling(policy, deterministic, sample_seed), None, self._policy_summary(res))
             return res
-        if mode != "transitions":
-            raise ValueError(f"mode {mode!r}: 'transitions' or 'summary'")
         if out is None:
             out = self.alloc_rollout(T, final_obs=final_obs)
             self._policy_columns(out, ("action",), T, torch.int32 if self.info.action_is_discrete else torch.float32)
-        if value_net is not None and not deterministic:
-            log_prob = True  # (a sampled launch with a critic always stores the log-probabilities)
         io = self._rollout_io(None, None, out, T)
         if log_prob:
             self._policy_columns(out, ("log_prob",), T)
@@ -1379,56 +1432,15 @@ class VecEngine(LaneEngine):
             launch(smp, C.byref(io), None)
             return out
         self._policy_columns(out, ("value", "boot_value") if bootstrap_truncated else ("value",), T)
-        if "last_value" not in out:
-            out["last_value"] = torch.empty(self.n, dtype=torch.float32, device=self.device)
-        lv = out["last_value"]
-        if lv.dtype != torch.float32 or lv.device != self.device or tuple(lv.shape) != (self.n,) or not lv.is_contiguous():
-            raise ValueError(f"rollout_policy 'last_value' must be a contiguous float32 [{self.n}] tensor on {self.device}")
+        lv = self._policy_last_value(out)
         cparams = value_net.device_params(self.device)
         crit = value_net.struct(self.n, cparams.data_ptr())
         vout = _lib.PolicyValue(_ptr(out["value"]), _ptr(lv), _ptr(out["boot_value"]) if bootstrap_truncated else None)
         self._policy_call(self.lib.carl_rollout_policy_valued, C.byref(pol), C.byref(crit),
                           None if smp is None else C.byref(smp), C.byref(io), T, None, C.byref(vout))
         if gae is not None:
-            res = self.gae(out["reward"][:T], out["value"][:T], out["terminated"][:T], out["truncated"][:T], lv, gamma,
-                           lam, boot_value=out["boot_value"][:T] if bootstrap_truncated else None,
-                           out={k: out[k] for k in ("advantage", "return") if k in out} or None)
-            out["advantage"], out["return"] = res["advantage"], res["return"]
+            self._policy_gae(out, T, gae, bootstrap_truncated)
         return out
-
-    def _check_value_net(self, policy, value_net) -> None:
-        """ValueError unless ``value_net`` is a critic the valued launch can run next to ``policy``: a value head, the same
-        family, inputs and set layout, and a shift | scale | clip section equal to the actor's bit for bit (the critic
-        reads the actor's transformed inputs; with equal sections the critic's packed block alone defines V)."""
-        if getattr(value_net, "head", None) != "value":
-            raise ValueError("value_net must be an MLPPolicy built with head='value'")
-        if policy.head != "policy":
-            raise ValueError("the acting policy must have head='policy'")
-        if value_net.family != policy.family or value_net.obs_dim != policy.obs_dim:
-            raise ValueError(f"value_net was built for family {value_net.family}, the policy for family {policy.family}")
-        if list(value_net.ctx_rows) != list(policy.ctx_rows):
-            raise ValueError(f"value_net reads context rows {value_net.ctx_rows}, the policy {policy.ctx_rows}: the critic "
-                             "sees the actor's inputs")
-        if value_net.n_sets != policy.n_sets or value_net.lanes_per_set != policy.lanes_per_set:
-            raise ValueError(f"value_net has {value_net.n_sets} weight sets of {value_net.lanes_per_set} lanes, the policy "
-                             f"{policy.n_sets} of {policy.lanes_per_set}: one set layout for both")
-        a, c = policy.transform_section(), value_net.transform_section()
-        if not np.array_equal(np.ascontiguousarray(a).view(np.int32), np.ascontiguousarray(c).view(np.int32)):
-            raise ValueError("value_net's input_shift / input_scale / input_clip must equal the policy's bit for bit: the "
-                             "critic reads the actor's transformed inputs")
-
-    # (key, dtype, per-episode rows) of an evaluate_policy result
-    _EPISODE_KEYS =(("episodes", torch.int32, False), ("steps", torch.int32, False), ("return", torch.float32, True),
-                     ("length", torch.int32, True), ("context_id", torch.int32, True), ("terminated", torch.uint8, True))
-
-    def alloc_policy_episodes(self, n_episodes: int) -> dict:
-        """Output buffers of ``evaluate_policy``: ``episodes`` / ``steps`` int32 ``[N]``; ``return`` float32, ``length`` /
-        ``context_id`` int32, ``terminated`` uint8, ``[n_episodes, N]`` each.  The launch writes every element."""
-        K = int(n_episodes)
-        if K < 1:
-            raise ValueError(f"n_episodes {K} < 1")
-        return {k: torch.empty((K, self.n) if rows else (self.n,), dtype=dt, device=self.device)
-                for k, dt, rows in self._EPISODE_KEYS}
 
     def evaluate_policy(self, policy, n_episodes: int, max_steps: int, out: dict | None = None,
                         deterministic: bool = True, sample_seed: int = 0, input_stats: bool = False) -> dict:
@@ -1448,39 +1460,13 @@ class VecEngine(LaneEngine):
         sums of an earlier launch are never merged beside this launch's ``steps``).  Records and engine state are the
         same bits either way."""
         _check_policy_family(self, policy)
-        if not self.auto_reset:
-            raise ValueError("evaluate_policy needs auto_reset=True: without it a finished lane reports done on every "
-                             "later step")
-        K, T = int(n_episodes), int(max_steps)
-        if K < 1:
-            raise ValueError(f"n_episodes {K} < 1")
-        if T < 0:
-            raise ValueError(f"max_steps {T} < 0")
-        if K * self.n >= 1 << 31:
-            raise ValueError(f"{K} episodes x {self.n} lanes: more than 2^31 - 1 records")
-        res = self.alloc_policy_episodes(K) if out is None else out
-        for k, dt, rows in self._EPISODE_KEYS:
-            t = res.get(k)
-            shape = (K, self.n) if rows else (self.n,)
-            if t is None or t.device != self.device or t.dtype != dt or tuple(t.shape) != shape or not t.is_contiguous():
-                raise ValueError(f"evaluate_policy output '{k}' must be a contiguous {dt} {list(shape)} tensor on "
-                                 f"{self.device}")
+        K, T, res, eps = self._policy_episodes("evaluate_policy", n_episodes, max_steps, out)
         params = policy.device_params(self.device)
         pol = policy.struct(self.n, params.data_ptr())
-        eps = _lib.PolicyEpisodes(*(_ptr(res[k]) for k, _, _ in self._EPISODE_KEYS))
         smp = self._sampling(policy, deterministic, sample_seed)
         tail = (K, T, C.byref(eps))
         if input_stats:
-            n_wg = int(self.lib.carl_policy_stats_workgroups(self.n))
-            partial = res.get("input_partial")
-            if partial is None:
-                partial = res["input_partial"] = torch.empty((n_wg, 2, _lib.POLICY_MAX_IN), dtype=torch.float64,
-                                                             device=self.device)
-            if (partial.device != self.device or partial.dtype != torch.float64 or not partial.is_contiguous()
-                    or tuple(partial.shape) != (n_wg, 2, _lib.POLICY_MAX_IN)):
-                raise ValueError(f"evaluate_policy output 'input_partial' must be a contiguous torch.float64 "
-                                 f"[{n_wg}, 2, {_lib.POLICY_MAX_IN}] tensor on {self.device}")
-            st = _lib.PolicyStats(_ptr(partial), n_wg)
+            st = self._policy_input_partial("evaluate_policy", res, int(self.lib.carl_policy_stats_workgroups(self.n)))
             self._policy_call(self.lib.carl_evaluate_policy_stats, C.byref(pol), None if smp is None else C.byref(smp),
                               *tail, C.byref(st))
             return res

@@ -45,6 +45,7 @@ from typing import Callable
 import torch
 
 from carl_amd import _lib
+from carl_amd._tensors import is_exact
 from carl_amd.brax_policy import BraxMLPPolicy, _brax_engine_of
 from carl_amd.policy import InputStats, MLPPolicy, _engine_of
 
@@ -223,8 +224,7 @@ class EvolutionStrategy:
                 res = eng.evaluate_policy(self.population, n_episodes, max_steps, **kw)
         fitness = set_fitness(res, self.n_sets)
         weight = self._shape(fitness)
-        if (not isinstance(weight, torch.Tensor) or weight.dtype != torch.float32 or weight.device != eng.device
-                or tuple(weight.shape) != (self.n_pairs,)):
+        if not is_exact(weight, eng.device, torch.float32, (self.n_pairs,), contiguous=False):
             raise ValueError(f"fitness_shaping must return a float32 [{self.n_pairs}] tensor on {eng.device}")
         weight = weight.contiguous()
         grad = torch.empty(self.n_noisy, dtype=torch.float32, device=eng.device)

@@ -49,6 +49,7 @@ import numpy as np
 import torch
 
 from carl_amd import _lib
+from carl_amd._tensors import is_exact
 
 _ACTIVATIONS = {"identity": _lib.POLICY_IDENTITY, "tanh": _lib.POLICY_TANH, "relu": _lib.POLICY_RELU}
 
@@ -450,9 +451,7 @@ class InputStats:
             raise ValueError("InputStats.update: the policy's shape is not the template's")
         n_blocks = 0
         if block is not None:
-            if (not isinstance(block, torch.Tensor) or block.dtype != torch.float32 or block.device != self.device
-                    or not block.is_contiguous() or block.numel() % S or block.dim() not in (1, 2)
-                    or (block.dim() == 2 and block.shape[1] != S) or (block.dim() == 1 and block.numel() != S)):
+            if not (is_exact(block, self.device, torch.float32, (S,)) or is_exact(block, self.device, torch.float32, (None, S))):
                 raise ValueError(f"InputStats.update: the block must be a contiguous float32 [{S}] or [n, {S}] tensor on "
                                  f"{self.device}")
             n_blocks = block.numel() // S

@@ -40,6 +40,7 @@ from typing import Sequence
 import torch
 
 from carl_amd import _lib
+from carl_amd._tensors import is_exact
 from carl_amd.brax_policy import BraxMLPPolicy
 from carl_amd.policy import MLPPolicy, _engine_of
 from carl_amd.ppo import _ResidentPolicy, _resident
@@ -186,8 +187,7 @@ class PopulationPPO:
         sections it compares are those of construction and are not moved (``src`` is not known on the host) -- read a
         member's current transform from ``member(i)``, not from them."""
         dev = self.engine.device
-        if (not isinstance(src, torch.Tensor) or src.dtype != torch.int64 or src.device != dev
-                or tuple(src.shape) != (self.n_sets,)):
+        if not is_exact(src, dev, torch.int64, (self.n_sets,), contiguous=False):
             raise ValueError(f"copy_members 'src': needs an int64 [{self.n_sets}] tensor on {dev}")
         st = self.adam_state
         for t in [*self._opt_params, *st["m"], *st["v"], st["step"], st["beta_pow"], self.hyper]:
